@@ -18,9 +18,14 @@ N > 1 (torch.distributed.run, one rank per GPU): STRONG scaling of the same geno
 its own contigs, and the only collective is the final gather of the merged call records to rank 0 (one fixed-size all_gather per step,
 RCCL), inside the timed region. No data-path collective.
 
-Legs reported beside the headline at N = 1: `chr22_cigar_path` (BASELINE configs[1], last round's headline configuration),
-`chr1_cnv` (configs[2]: chr1 alone, all passes, with the window / Viterbi kernel times), `from_file` (one contig from a real BGZF BAM),
-`cpu_baseline` (the CPU restatement on the same 24 contigs, one contig per thread as the reference schedules them, on a stated sample).
+A plain run stages the genome, warms up, times the K steps and prints the line (headline, stage and kernel times of the timed steps,
+roofline). --full adds, at N = 1, the legs that take runs of their own: `no_split_overlap` (the same steps without the split overlap),
+`chr22_cigar_path` (BASELINE configs[1], an earlier round's headline configuration), `chr1_cnv` (configs[2]: chr1 alone, all passes, with the
+window / Viterbi kernel times), `from_file` / `from_file_wgs` (from real BGZF BAMs), `hifi_wgs` (configs[4]) and `cpu_baseline` (the CPU
+restatement on the same 24 contigs, one contig per thread as the reference schedules them, on a stated sample).
+
+--dump-outputs DIR writes what the last timed step returned as float64 .npy files: the merged call records field by field with their
+contig ids (`calls_*.npy`, gathered to rank 0 at N > 1) and rank 0's per-contig statistics (`contig_*.npy`).
 """
 import argparse
 import hashlib
@@ -41,6 +46,8 @@ GRCH38 = [248956422, 242193529, 198295559, 190214555, 181538259, 170805979, 1593
 NAMES = ["chr%d" % i for i in range(1, 23)] + ["chrX", "chrY"]
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured streaming copy)
 REC_I32 = 12                   # one merged call record = 48 B (host.CALL_DTYPE)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together; larger outputs are cut to a fixed, seeded sample of rows
+CONTIG_DUMP_FIELDS = ("n_signatures", "n_del", "n_ins", "depth_sum", "depth_nonzero", "min_pts", "mean_cov", "n_calls")   # (not the timings)
 
 
 def seed_of(config, contig):
@@ -103,6 +110,25 @@ def call_digest(tid, calls):
     return h.hexdigest()
 
 
+def dump_outputs(out_dir, tid, calls, contig_tid, per):
+    """--dump-outputs: one float64 .npy per field of the merged call records (+ their contig ids) and per per-contig statistic. Every field
+    is an integer below 2**53 or a double, so float64 holds it exactly."""
+    arrays = {"calls_tid": tid}
+    arrays.update({"calls_" + f: calls[f] for f in calls.dtype.names})
+    rows = len(tid)
+    row_bytes = 8 * len(arrays)
+    contig = {"contig_tid": np.asarray(contig_tid)}
+    contig.update({"contig_" + f: np.array([getattr(p, f) for p in per]) for f in CONTIG_DUMP_FIELDS})
+    budget = DUMP_MAX_BYTES - 8 * len(contig) * len(per) - 256 * (len(arrays) + len(contig))      # (256 B: room for each file's .npy header)
+    if rows * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(rows, budget // row_bytes, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    arrays.update(contig)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     t_start = time.perf_counter()
     ap = argparse.ArgumentParser()
@@ -118,11 +144,15 @@ def main():
     ap.add_argument("--lanes", type=int, default=3, help="contigs in flight per GPU during the CIGAR pass (contexts sharing a gate)")
     ap.add_argument("--host-threads", type=int, default=0, help="host threads of the split-read / copy-number passes (0 = hardware)")
     ap.add_argument("--gen-threads", type=int, default=0, help="threads of the generator (0 = the CPU share of this rank, at most 32)")
+    ap.add_argument("--gen-ahead", type=int, default=3, help="contigs generated at once while staging (each with --gen-threads; the same inputs at any value)")
     ap.add_argument("--no-split-overlap", action="store_true", help="run the split-read pass's first half after the CIGAR pass instead of beside it (A/B: the big kernels "
                     "then have the device to themselves)")
     ap.add_argument("--background", action="store_true", help="the caller's context at the LOWEST stream priority (csvgpu_create_background): the split pass's ordering "
                     "kernels then only fill the gaps of the CIGAR pass — measured: they no longer stretch the big kernels (depth 0.50 of peak instead of 0.48) but "
                     "finish 3.5 ms after the pass, 37.1 ms per step against 35.8")
+    ap.add_argument("--full", action="store_true", help="also the legs and the CPU baseline at N = 1 (a plain run is the headline only); the --no-* options "
+                    "below leave parts of them out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="headline only (no chr22 / chr1 / from-file legs)")
     ap.add_argument("--no-from-file", action="store_true")
@@ -133,6 +163,9 @@ def main():
                     "call set of the sharded run is byte-identical (rehearsals / tests; costs rank 0 the whole staging)")
     ap.add_argument("--dump-calls", default="", help="rank 0: write the gathered merged calls (npy: tid + CALL_DTYPE) here")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    legs = args.full and not args.no_legs
 
     import torch
     import contextsv_amd as cs
@@ -192,33 +225,47 @@ def main():
         c.set_gate(gate)
 
     def stage(contig_ids, keep_sample, tech=tech, depth=args.depth, config_id=config_id):
-        """Generate, upload and free one contig at a time -> (Genome, per-contig info, CPU-baseline samples)."""
+        """Generate, upload and free one contig at a time, in contig order -> (Genome, per-contig info, CPU-baseline samples). Up to
+        --gen-ahead contigs are generated at once beside the uploads (the generator's single-threaded merge is most of its time); a contig's
+        reads depend on its seed and gen_threads only."""
+        from concurrent.futures import ThreadPoolExecutor
+
+        def gen(k):
+            t0 = time.perf_counter()
+            syn = host.SynthShard(seed_of(config_id, k), lens[k], depth, tech, gen_threads)
+            return syn, time.perf_counter() - t0
+
         g = host.Genome()
         info, samples = [], []
         t_gen = t_up = 0.0
         h2d = 0
-        for k in contig_ids:
-            t0 = time.perf_counter()
-            syn = host.SynthShard(seed_of(config_id, k), lens[k], depth, tech, gen_threads)
-            t1 = time.perf_counter()
-            g.add_synth(ctx, NAMES[k], k, syn, snp_seed=seed_of(config_id, k), with_snps=True)
-            t2 = time.perf_counter()
-            r = syn.reads
-            info.append({"contig": NAMES[k], "tid": k, "len": lens[k], "reads": int(r.n_reads), "cigar_ops": int(r.n_cigar)})
-            h2d += r.cigar.nbytes + r.pos.nbytes + r.flag.nbytes + r.mapq.nbytes + r.cigar_off.nbytes
-            if keep_sample:
-                n = max(1, int(r.n_reads * args.cpu_sample_frac))
-                m = int(r.cigar_off[n])
-                sub = cs.Reads.__new__(cs.Reads)
-                sub.pos, sub.flag, sub.mapq, sub.tid = r.pos[:n].copy(), r.flag[:n].copy(), r.mapq[:n].copy(), None
-                sub.cigar_off, sub.cigar = r.cigar_off[: n + 1].copy(), r.cigar[:m].copy()
-                samples.append((NAMES[k], sub, syn.depth_len, int(r.n_reads)))
-            syn.free()
-            t_gen += t1 - t0
-            t_up += t2 - t1
-        return g, info, samples, {"synth_s": round(t_gen, 2), "upload_s": round(t_up, 2), "h2d_bytes": int(h2d)}
+        t_stage = time.perf_counter()
+        ahead = max(1, args.gen_ahead)
+        with ThreadPoolExecutor(max_workers=ahead) as ex:
+            pending = [ex.submit(gen, k) for k in contig_ids[:ahead]]
+            for i, k in enumerate(contig_ids):
+                syn, dt = pending.pop(0).result()
+                if i + ahead < len(contig_ids):
+                    pending.append(ex.submit(gen, contig_ids[i + ahead]))
+                t1 = time.perf_counter()
+                g.add_synth(ctx, NAMES[k], k, syn, snp_seed=seed_of(config_id, k), with_snps=True)
+                t2 = time.perf_counter()
+                r = syn.reads
+                info.append({"contig": NAMES[k], "tid": k, "len": lens[k], "reads": int(r.n_reads), "cigar_ops": int(r.n_cigar)})
+                h2d += r.cigar.nbytes + r.pos.nbytes + r.flag.nbytes + r.mapq.nbytes + r.cigar_off.nbytes
+                if keep_sample:
+                    n = max(1, int(r.n_reads * args.cpu_sample_frac))
+                    m = int(r.cigar_off[n])
+                    sub = cs.Reads.__new__(cs.Reads)
+                    sub.pos, sub.flag, sub.mapq, sub.tid = r.pos[:n].copy(), r.flag[:n].copy(), r.mapq[:n].copy(), None
+                    sub.cigar_off, sub.cigar = r.cigar_off[: n + 1].copy(), r.cigar[:m].copy()
+                    samples.append((NAMES[k], sub, syn.depth_len, int(r.n_reads)))
+                syn.free()
+                t_gen += dt
+                t_up += t2 - t1
+        return g, info, samples, {"synth_s": round(t_gen, 2), "upload_s": round(t_up, 2), "h2d_bytes": int(h2d), "wall_s": round(time.perf_counter() - t_stage, 2)}
 
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = world == 1 and args.full and not args.no_cpu_baseline
     genome, info, samples, staging = stage(mine, want_cpu)
     reads_mine = sum(i["reads"] for i in info)
     ops_mine = sum(i["cigar_ops"] for i in info)
@@ -304,6 +351,13 @@ def main():
             np.savez(args.dump_calls, tid=np.concatenate([np.full(len(gathered[k]), k, np.int32) for k in ks]), calls=np.concatenate([gathered[k] for k in ks]))
         else:
             np.savez(args.dump_calls, tid=tid, calls=calls)
+    if rank == 0 and args.dump_outputs:
+        if world > 1:
+            ks = sorted(gathered)
+            d_tid, d_calls = np.concatenate([np.full(len(gathered[k]), k, np.int32) for k in ks]), np.concatenate([gathered[k] for k in ks])
+        else:
+            d_tid, d_calls = tid, calls
+        dump_outputs(args.dump_outputs, d_tid, d_calls, [i["tid"] for i in info], per)
 
     if rank == 0:
         K = args.steps
@@ -375,7 +429,7 @@ def main():
         }
         if verify:
             out["verify"] = verify
-        if world == 1 and not args.no_legs and lane_ctx and not args.no_split_overlap:
+        if world == 1 and legs and lane_ctx and not args.no_split_overlap:
             # A/B of the one overlap that costs the big kernels something: the same steps with the split pass's first half AFTER the CIGAR pass
             for c in lane_ctx:
                 c.timing_enable(3); c.timing_reset()
@@ -399,7 +453,7 @@ def main():
                                        "roofline_frac": (alg_bytes[dominant] / (d_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if d_ms > 0 else None,
                                        "note": "the split-read pass's ordering kernels after the CIGAR pass instead of beside it: the big kernels have the device to "
                                                "themselves (plus the lanes' own small kernels), the step is longer"}
-        if world == 1 and not args.no_legs:
+        if world == 1 and legs:
             out["chr1_cnv"] = leg_chr1(cs, host, ctx, lane_ctx, genome, info, hmm, args)
             # the same kernel with the device to itself (the chr1 leg runs one contig on one context: nothing beside the scan / depth pair)
             alone = out["chr1_cnv"].get("depth_GBps" if dominant == "depth" else "cigar_scan_GBps")
@@ -415,7 +469,7 @@ def main():
                     genome.free()                                                # (the resident genome's host mirror + HBM are not needed any more; HiFi leg staged its own)
                     genome = host.Genome()
                     out["from_file_wgs"] = from_file_wgs(cs, host, ctx, args, lens, config_id, gen_threads)
-        if world == 1 and not args.no_legs and tech == 0 and not args.no_hifi_leg:
+        if world == 1 and legs and tech == 0 and not args.no_hifi_leg:
             out["hifi_wgs"] = leg_hifi_wgs(stage, ctx, lane_ctx, hmm, args, n_contigs, cap)
         if want_cpu:
             out["cpu_baseline"] = cpu_baseline(samples, args, reads_all)

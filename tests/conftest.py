@@ -21,12 +21,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref():
-    """The reference's own dbscan.cpp / dbscan1d.cpp / kc.cpp (oracle/_ref); skipped when not built."""
+    """The reference's own dbscan.cpp / dbscan1d.cpp / kc.cpp (oracle/_ref) where it is built; otherwise its answers recorded for the
+    inputs the tests generate (tests/golden/ref_answers.npz), which fail any input they do not hold."""
     import oracle_lib
-    lib = oracle_lib.load_ref()
-    if lib is None:
-        pytest.skip("oracle/_ref/libcsvref.so not built (needs /root/reference at build time)")
-    return lib
+    return oracle_lib.load_ref_or_recorded()
 
 
 @pytest.fixture(scope="session")

@@ -3,6 +3,10 @@
 /root/reference/src/{dbscan,dbscan1d,kc}.cpp compiled unmodified by oracle/Makefile). Run in the build
 container only (needs /root/reference); the JSON files are committed and are what the GPU box and the
 CPU suite check against. Inputs are seeded; expected outputs are whatever the reference code returns.
+Also writes tests/golden/ref_answers.npz: the reference code's answers to every call the tests that check against it make
+(tests/test_oracle_golden.py, test_oracle_windowed.py, test_gpu_ref_sweep.py, through the `ref` fixture), which that fixture
+gives them where oracle/_ref is not built. The tests' own bodies are run to record them; the device side of the GPU tests is
+answered by the reference code here, so no GPU is needed.
 
     python tests/golden/make_golden.py
 """
@@ -57,6 +61,40 @@ def main():
     json.dump({"source": "reference src/kc.cpp pdf_normal / cdf_normal via oracle/_ref (17 significant digits)", "values": vals},
               open(os.path.join(HERE, "kc_normal.json"), "w"))
     print("golden vectors written:", [f for f in os.listdir(HERE) if f.endswith(".json")])
+    record_ref_answers(ref)
+
+
+class _DeviceFromRef:
+    """the Context calls of tests/test_gpu_ref_sweep.py, answered by the reference code (their answers must equal it to pass)"""
+
+    def __init__(self, ref):
+        self.ref = ref
+
+    def dbscan_iv(self, s, e, eps, min_pts):
+        return self.ref.dbscan_iv(s, e, eps, min_pts)
+
+    def dbscan_1d(self, p, off, eps, min_pts):
+        assert len(off) == 2
+        return self.ref.dbscan_1d(p, eps, min_pts)
+
+    def dbscan_iv_batch(self, s, e, off, eps, min_pts):
+        return np.concatenate([self.ref.dbscan_iv(s[off[k]: off[k + 1]], e[off[k]: off[k + 1]], eps, min_pts) for k in range(len(off) - 1)])
+
+
+def record_ref_answers(ref):
+    import test_gpu_ref_sweep as t_gpu
+    import test_oracle_golden as t_golden
+    import test_oracle_windowed as t_windowed
+    rec = oracle_lib.RecordingRef(ref)
+    orc = oracle_lib.load_oracle()
+    dev = _DeviceFromRef(ref)
+    t_golden.test_oracle_vs_reference_live(orc, rec)
+    t_windowed.test_windowed_labeller_vs_reference_code_live(orc, rec)
+    t_gpu.test_interval_dbscan_vs_reference_code(dev, rec)
+    t_gpu.test_dbscan1d_vs_reference_code(dev, rec)
+    t_gpu.test_interval_dbscan_batch_against_reference(dev, rec)
+    rec.save(oracle_lib.REF_ANSWERS)
+    print("reference answers written:", len(rec.answers), "calls,", os.path.getsize(oracle_lib.REF_ANSWERS), "bytes")
 
 
 if __name__ == "__main__":

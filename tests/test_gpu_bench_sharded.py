@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +31,7 @@ COMMON = ["--steps", "2", "--warmup", "1", "--scale", "0.004", "--gen-threads", 
 
 
 def test_bench_single_rank_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *COMMON, "--cpu-sample-frac", "0.5"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *COMMON, "--full", "--cpu-sample-frac", "0.5"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["unit"] == "reads/s" and j["value"] > 0 and j["config"]["contigs"] == 24
@@ -40,6 +41,35 @@ def test_bench_single_rank_line():
     assert j["chr1_cnv"]["value"] > 0 and j["chr22_cigar_path"]["value"] > 0
     st = j["stage_ms_per_step_rank0"]
     assert st["ms_cigar"] > 0 and st["ms_total"] >= st["ms_cigar"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) is the headline only; --dump-outputs writes the last timed step's merged calls as float64 .npy files, field
+    for field the records --dump-calls writes, and the same files on a second run with the same arguments."""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *COMMON, "--steps", "3", "--dump-outputs", str(d),
+                            "--dump-calls", str(tmp_path / f"calls{i}.npz")], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        runs.append((_line(r.stdout), d))
+    j, d = runs[0]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "reads/s" and j["higher_is_better"] is True and j["dtype"] == "u32"
+    for leg in ("cpu_baseline", "chr1_cnv", "chr22_cigar_path", "from_file", "from_file_wgs", "hifi_wgs", "no_split_overlap"):
+        assert leg not in j
+    raw = np.load(tmp_path / "calls0.npz")
+    calls = raw["calls"]
+    assert len(calls) == j["config"]["merged_calls"] > 50
+    assert np.array_equal(np.load(d / "calls_tid.npy"), raw["tid"].astype(np.float64))
+    for f in calls.dtype.names:
+        a = np.load(d / f"calls_{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, calls[f].astype(np.float64), equal_nan=True), f
+    assert np.array_equal(np.load(d / "contig_tid.npy"), np.arange(24, dtype=np.float64))
+    assert np.load(d / "contig_n_signatures.npy").sum() == j["config"]["signatures"]
+    names = sorted(p.name for p in d.iterdir())
+    assert names == sorted(p.name for p in runs[1][1].iterdir())
+    for n in names:
+        assert np.array_equal(np.load(d / n), np.load(runs[1][1] / n), equal_nan=True), n
 
 
 @pytest.mark.parametrize("ranks", [2, 4])

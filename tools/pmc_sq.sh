@@ -5,7 +5,7 @@ set -e
 OUT=$(realpath "$1"); mkdir -p "$OUT"
 REPO=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-ARGS="$REPO/bench.py --lanes 1 --no-two-lanes --no-cpu-baseline --no-from-file --steps 20 --warmup 2"
+ARGS="$REPO/bench.py --full --lanes 1 --no-two-lanes --no-cpu-baseline --no-from-file --steps 20 --warmup 2"
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_WAVES" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY" \

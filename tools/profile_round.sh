@@ -10,7 +10,7 @@ REPO=$(pwd)
 WL=""; KEY="wgs"; LEGS=""
 if [ "$2" = "hifi" ]; then WL="--tech hifi --depth 60"; KEY="hifi_wgs"; LEGS="--no-legs --no-cpu-baseline"; fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 "$REPO/bench.py" --steps 20 --warmup 5 $WL $LEGS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -n 5 "$OUT/bench.err"; exit 1; }
+timeout -k 10 500 python3 "$REPO/bench.py" --full --steps 20 --warmup 5 $WL $LEGS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -n 5 "$OUT/bench.err"; exit 1; }
 echo "bench done"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$REPO/bench.py" --steps 5 --warmup 1 --no-legs --no-cpu-baseline $WL > "$OUT/stats.log" 2>&1 || { echo "stats pass failed"; tail -n 5 "$OUT/stats.log"; exit 1; }
 echo "stats done"
