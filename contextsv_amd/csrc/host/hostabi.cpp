@@ -677,7 +677,9 @@ void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n
 
 // One step: SVCaller::runResident over every staged contig. passes: bit 0 split-read pass, bit 1 CIGAR copy-number pass, bit 2 the two
 // final merges, bit 3 keep the qname map's order on the host (umap_order.h) instead of csvgpu_split_order,
-// bit 4 do not run the split pass's first half beside the CIGAR pass. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
+// bit 4 do not run the split pass's first half beside the CIGAR pass; the RunSchedule (no result depends on it): bits 5-6 early_batches
+// (0 timed, 1 none, 2 all at once, 3 every three), bit 7 no split chain beside the pass, bit 8 the two-call split order, bits 16-30
+// prepare_delay_ms. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
 int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *const *lane_ctxs, const csv_hmm *hmm, double eps, double min_pts_pct,
                        int sample_size, uint32_t min_cnv, int passes, int host_threads, csvhost_call *out, int32_t *out_tid, uint64_t cap, uint64_t *n_out,
                        csvhost_stage_times *times, csvhost_chr_stats *stats)
@@ -695,6 +697,10 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         P.host_threads = host_threads;
         P.split_order_on_device = (passes & 8) == 0;
         P.overlap_split_prepare = (passes & 16) == 0;
+        P.schedule.early_batches = (RunSchedule::EarlyBatches)((passes >> 5) & 3);
+        P.schedule.split_beside_pass = (passes & 128) == 0;
+        P.schedule.split_order_self = (passes & 256) == 0;
+        P.schedule.prepare_delay_ms = (passes >> 16) & 0x7fff;
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);
         // the call map of a genome is 3e4 records with strings in them: it is torn down beside whatever the caller does next — the next run,

@@ -311,10 +311,10 @@ void SVCaller::processResidentChromosomesPipelined(const std::vector<csv_shard *
         cv.notify_all();
         for (auto &t : workers) pool.wait(t);
     };
-    // The scan + depth pair of the next shard (CSV_JOBS_AHEAD of them: 1) is queued ahead of the shard whose results are being fetched. More
-    // than one ahead was measured and is no better (25.7 / 26.7 ms per genome step with one, 26.4 / 26.9 with three): the gaps between the
-    // big kernels were not a starved gate but a lane's stream sharing the gate's hardware queue — see csvgpu_gate_open.
-    static const size_t kAhead = [] { const char *e = getenv("CSV_JOBS_AHEAD"); const int v = e && *e ? atoi(e) : 1; return (size_t)std::min(std::max(v, 1), 8); }();
+    // The scan + depth pair of the next shard is queued ahead of the shard whose results are being fetched. More than one ahead was measured
+    // and is no better (25.7 / 26.7 ms per genome step with one, 26.4 / 26.9 with three): the gaps between the big kernels were not a starved
+    // gate but a lane's stream sharing the gate's hardware queue — see csvgpu_gate_open.
+    constexpr size_t kAhead = 1;
     std::deque<csv_job *> ahead;                          // jobs whose scan + depth pass is already queued, oldest first
     size_t next_begin = 0;
     auto begin_one = [&] {
@@ -454,19 +454,18 @@ struct ShardIntervals : IntervalSource {
 };
 
 // the iteration order of the reference's per-chromosome qname map from the device (csvgpu_split_order): shard_of[c] is the resident
-// shard of split-pass contig c (its query-name hashes were attached when it was staged)
+// shard of split-pass contig c (its query-name hashes were attached when it was staged). self_ok = false: a complete run takes the two-call
+// form too (RunSchedule::split_order_self)
 struct ShardOrderSource : SplitOrderSource {
-    ShardOrderSource(csv_ctx *ctx, std::vector<csv_shard *> shard_of) : ctx(ctx), shard_of(std::move(shard_of)) {}
+    ShardOrderSource(csv_ctx *ctx, std::vector<csv_shard *> shard_of, bool self_ok) : ctx(ctx), shard_of(std::move(shard_of)), self_ok(self_ok) {}
     void begin(const std::vector<size_t> &which, int min_mapq, bool complete) const override
     {
         pending.clear();
         if (which.empty() || which.size() > 32) return;                           // (more than one batch: the one-call form below)
-        { const char *e = getenv("CSV_SPLIT_ONE_CALL"); if (e && *e && *e != '0') return; }      // (A/B: no head start)
         std::vector<csv_shard *> sh(which.size());
         for (size_t k = 0; k < which.size(); k++) sh[k] = shard_of[which[k]];
         // every contig of the run in this one call: the supplementary hashes are the shards' own and the whole order is queued now
-        const char *e = getenv("CSV_SPLIT_NO_SELF");                                 // (A/B, tests: wait for the collected hashes)
-        pending_self = complete && !(e && *e && *e != '0');
+        pending_self = complete && self_ok;
         check(ctx, pending_self ? csvgpu_split_order_begin_self(ctx, (int)sh.size(), sh.data(), (uint8_t)min_mapq)
                                 : csvgpu_split_order_begin(ctx, (int)sh.size(), sh.data(), (uint8_t)min_mapq), "split-read order (begin)");
         pending = which; pending_mapq = min_mapq;
@@ -508,6 +507,7 @@ struct ShardOrderSource : SplitOrderSource {
     }
     csv_ctx *ctx;
     std::vector<csv_shard *> shard_of;
+    bool self_ok;
     mutable std::vector<size_t> pending;          // the contigs csvgpu_split_order_begin was called for, until _finish
     mutable int pending_mapq = 0;
     mutable bool pending_self = false;            // ... by csvgpu_split_order_begin_self: _finish takes no hashes
@@ -525,23 +525,275 @@ struct SVCaller::SplitSetup {
     SplitParams sp;
     std::unique_ptr<SplitPass> pass;
     double ms_prepare = 0.0;
-    std::exception_ptr err;
 };
 
 namespace {
 struct EmptySnps : SNPSource {
     void query(uint32_t, uint32_t, std::vector<uint32_t> &, std::unordered_map<uint32_t, double> &, std::unordered_map<uint32_t, double> &) const override {}
 };
-}  // namespace
 
-namespace {
 struct VectorSource : ContigSource {
     explicit VectorSource(const std::vector<ChromosomeInput> &v) : v(v) {}
     bool next(ChromosomeInput &out) override { if (i >= v.size()) return false; out = v[i++]; return true; }
     const std::vector<ChromosomeInput> &v;
     size_t i = 0;
 };
+
+using CallMap = std::unordered_map<std::string, std::vector<SVCall>>;
+
+CNVCaller makeCnv(csv_ctx *ctx, const RunParams &P)
+{
+    CNVCaller cn(ctx);
+    cn.sample_size = P.sample_size; cn.min_cnv_length = P.min_cnv_length; cn.host_threads = P.host_threads;
+    return cn;
+}
+
+struct ThreadContext {                                  // this thread's context for the host passes' clustering calls, while in scope
+    explicit ThreadContext(csv_ctx *c) { csvhost::set_thread_context(c); }
+    ~ThreadContext() { csvhost::set_thread_context(nullptr); }
+};
+
+// The contigs of a run as the passes behind the CIGAR merge see them: resident data, mean coverage and CIGAR calls (the lanes' result
+// vectors during the CIGAR pass, the call map behind it). Its steps are what the run does with a set of contigs behind their CIGAR
+// copy-number predictions (sv_caller.cpp:885-927 of the reference): split-read signatures -> their copy-number predictions -> mergeSVs of
+// the split calls -> concatenation -> final mergeSVs. Nothing in them reaches across contigs (supplementary records on another contig only
+// answer tid tests, :352-354), so any partition of the contigs gives the same calls: an early batch takes every step inside the CIGAR pass
+// (splitChain), the split chain beside the pass the first two, finishRun whatever is left behind the pass.
+struct RunContigs {
+    RunContigs(const std::vector<ResidentContig> &contigs, const CHMM &hmm, const RunParams &P)
+        : contigs(contigs), hmm(hmm), P(P), mean_cov(contigs.size(), 0.0), calls(contigs.size(), nullptr)
+    {
+        for (size_t i = 0; i < contigs.size(); i++) index_of[contigs[i].name] = i;
+    }
+    const std::vector<ResidentContig> &contigs;
+    const CHMM &hmm;
+    const RunParams &P;
+    std::unordered_map<std::string, size_t> index_of;
+    std::vector<double> mean_cov;                       // per contig
+    std::vector<std::vector<SVCall> *> calls;           // per contig: its CIGAR calls
+
+    // the copy-number job of contig i over `v` (its CIGAR or its split-read calls)
+    CNVCaller::ContigJob job(size_t i, std::vector<SVCall> &v) const
+    {
+        static const EmptySnps no_snps;
+        CNVCaller::ContigJob j;
+        j.chr = contigs[i].name; j.calls = &v; j.mean_chr_cov = mean_cov[i]; j.shard = contigs[i].shard;
+        j.snps = contigs[i].snps ? contigs[i].snps : (const SNPSource *)&no_snps; j.depth_len = contigs[i].depth_len;
+        return j;
+    }
+    // the jobs of the contigs of `m` that have calls and are not in `skip`, in the map's own order (the reference walks its map)
+    std::vector<CNVCaller::ContigJob> jobs(CallMap &m, const std::vector<char> *skip = nullptr) const
+    {
+        std::vector<CNVCaller::ContigJob> out;
+        for (auto &entry : m) {
+            if (entry.second.empty()) continue;
+            const size_t i = index_of.at(entry.first);
+            if (skip && (*skip)[i]) continue;
+            out.push_back(job(i, entry.second));
+        }
+        return out;
+    }
+    // split-read signatures of the contigs `idx` (their scans are over: the alignment intervals exist)
+    CallMap findSplit(SplitPass &pass, const std::vector<int> &block_of, const std::vector<size_t> &idx) const
+    {
+        std::vector<size_t> blocks;
+        for (size_t i : idx) if (block_of[i] >= 0) blocks.push_back((size_t)block_of[i]);
+        CallMap split;
+        pass.finishFor(blocks, split);
+        return split;
+    }
+    void predictSplit(const CNVCaller &cn, CallMap &split) const { std::vector<CNVCaller::ContigJob> j = jobs(split); cn.runSplitReadCopyNumberPredictionsAll(j, hmm); }
+    void mergeSplit(CallMap &split) const
+    {
+        std::vector<std::vector<SVCall> *> sets;
+        for (auto &entry : split) sets.push_back(&entry.second);
+        if (P.merge_split_svs) mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
+    }
+    // the split calls behind each contig's CIGAR calls; -> how many
+    size_t appendSplit(const CallMap &split) const
+    {
+        size_t k = 0;
+        for (const auto &entry : split) {
+            k += entry.second.size();
+            std::vector<SVCall> &dst = *calls[index_of.at(entry.first)];
+            dst.insert(dst.end(), entry.second.begin(), entry.second.end());
+        }
+        return k;
+    }
+    void mergeFinal(const std::vector<size_t> &idx) const
+    {
+        std::vector<std::vector<SVCall> *> sets;
+        for (size_t i : idx) sets.push_back(calls[i]);
+        if (P.merge_final_svs) mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
+    }
+    // every step for the contigs `idx`, whose CIGAR copy-number predictions are made; -> the number of split-read calls
+    size_t splitChain(SplitPass &pass, const std::vector<int> &block_of, const std::vector<size_t> &idx, const CNVCaller &cn) const
+    {
+        CallMap split = findSplit(pass, block_of, idx);
+        predictSplit(cn, split);
+        mergeSplit(split);
+        const size_t k = appendSplit(split);
+        mergeFinal(idx);
+        return k;
+    }
+};
 }  // namespace
+
+// runResident's work beside the CIGAR pass. With lanes, the caller's own context is idle during the pass, and the first half of the
+// split-read pass needs nothing the pass produces (flags, name hashes -> the qname map's iteration order): a task runs it there, on another
+// thread (prepare). When it is done the pass is a little over half way, and the task goes on with
+//  - early batches: the CIGAR copy-number predictions of the contigs whose calls are final by then, and every later step of the run for
+//    them (RunContigs::splitChain), in place on the lanes' result vectors; another batch whenever a few more contigs are merged. What is
+//    left when the pass ends is done behind it;
+//  - then, or instead (a rank with few contigs, or short reads: a first half as long as the pass, takes no batch), the split chain beside
+//    the pass: it needs the scans' alignment intervals and, for its copy-number pass, the depth maps and mean coverages — all there when a
+//    contig's device chain is over, before its host merge. The task runs it for every contig that went through no early batch, beside the
+//    rest of the pass and the CIGAR copy-number pass; finishRun meets it in front of the split chain.
+// Which of these the task does is decided by timing, within what RunSchedule allows; the calls never depend on it.
+struct SVCaller::PassOverlap {
+    PassOverlap(SVCaller &caller, std::vector<ResidentContig> &contigs, const std::vector<csv_ctx *> &lane_ctxs, const CHMM &hmm, const RunParams &P)
+        : ctx(caller.ctx), P(P), R(contigs, hmm, P), n(contigs.size()),
+          task(P.split_svs && P.cigar_svs && n && lane_ctxs.size() > 1 && P.overlap_split_prepare),
+          early(task && P.cigar_cn && !P.save_cnv && P.schedule.early_batches != RunSchedule::EarlyBatches::None),
+          forced(P.schedule.early_batches == RunSchedule::EarlyBatches::AllAtOnce || P.schedule.early_batches == RunSchedule::EarlyBatches::EveryThree),
+          beside(task && !P.save_cnv && !forced && P.schedule.split_beside_pass),
+          side_ctx(lane_ctxs.size() > 1 ? lane_ctxs[0] : nullptr), finished(n, 0)
+    {
+        if (P.split_svs) split = caller.makeSplitSetup(contigs, P);
+        if (task) ticket = csvhost::WorkerThreads::instance().start([this] { work(); });
+    }
+    ~PassOverlap() { { std::lock_guard<std::mutex> l(mu); pass_over = true; } wait(); }     // (also when the pass throws: the task refers to the run's frame)
+
+    // from the lanes (any thread): contig i's device chain is over (its depth map, alignment intervals and statistics are final) / its calls are final
+    void deviceDone(size_t i, const ChrStats &st) { R.mean_cov[i] = st.mean_chr_cov; std::lock_guard<std::mutex> l(mu); device_done.push_back(i); }
+    void merged(size_t i, std::vector<SVCall> &calls) { R.calls[i] = &calls; std::lock_guard<std::mutex> l(mu); merged_.push_back(i); }
+    // The CIGAR pass has returned: the task takes no batch any more (early batches work on the lanes' vectors in place: they must be over
+    // before those move). The run goes on without waiting for a task still inside prepare() — the CIGAR copy-number pass needs nothing of
+    // it — or running the split chain beside the pass, and meets it in front of the split chain (join). Any other task is over on return.
+    // (With save_cnv the copy-number passes run on the caller's context, which a task still running would use: the run waits.)
+    void passOver()
+    {
+        bool later;
+        { std::lock_guard<std::mutex> l(mu); pass_over = true; later = ticket && (!prepare_over || split_only) && !forced && !P.save_cnv; }
+        if (!later) join();
+    }
+    void join() { wait(); if (err) std::rethrow_exception(err); }
+
+    csv_ctx *const ctx;
+    const RunParams &P;
+    RunContigs R;
+    const size_t n;
+    // what does not depend on timing, decided once: whether the task starts; whether it may take early batches; whether the schedule forces
+    // them (tests: no split chain beside the pass and no late join then); whether it may run the split chain beside the pass
+    const bool task, early, forced, beside;
+    csv_ctx *const side_ctx;                           // a lane's context, idle behind the pass (finishRun's CIGAR copy-number pass)
+    std::unique_ptr<SplitSetup> split;
+    // read by finishRun after join()
+    std::vector<char> finished;                        // per contig: every step of the run made in an early batch (its calls are final)
+    size_t regions = 0, n_split_calls = 0;             // of the early batches
+    CallMap pre_split;                                 // the split chain beside the pass: the split-read calls, copy-number predictions made ...
+    bool pre_ready = false;                            // ... of every contig that went through no early batch
+
+private:
+    void wait() { if (ticket) { csvhost::WorkerThreads::instance().wait(ticket); ticket = nullptr; } }
+    void work()
+    {
+        prepare();
+        bool late;                                     // prepare() outlasted the CIGAR pass (short reads): the run has gone on without waiting
+        { std::lock_guard<std::mutex> l(mu); prepare_over = true; late = pass_over && !forced; }
+        if (err) return;
+        try {
+            if (late) {
+                if (beside) splitBesidePass();
+                return;
+            }
+            if (early) earlyBatches();
+            if (beside && takeSplitOnly()) splitBesidePass();
+        } catch (...) { err = std::current_exception(); }
+    }
+    void prepare()
+    {
+        const double t0 = now_ms();
+        if (P.schedule.prepare_delay_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(P.schedule.prepare_delay_ms));
+        try { split->pass->prepare(); } catch (...) { err = std::current_exception(); }
+        split->ms_prepare = now_ms() - t0;
+    }
+    // One batch now (a little over half the genome is merged), then another whenever a few more contigs are: what is left for the end of the
+    // pass is the last contigs' share. The pass's end ends the loop; whatever was not taken here is done behind the pass.
+    void earlyBatches()
+    {
+        const RunSchedule::EarlyBatches mode = P.schedule.early_batches;
+        if (mode == RunSchedule::EarlyBatches::AllAtOnce)               // every contig through this path, whatever the timing
+            for (int spin = 0; spin < 200000; spin++) {
+                { std::lock_guard<std::mutex> l(mu); if (merged_.size() >= n) break; }
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+            }
+        size_t taken = 0;
+        for (bool first = true;; first = false) {
+            std::vector<size_t> batch;
+            bool over;
+            size_t unmerged;
+            { std::lock_guard<std::mutex> l(mu); batch.assign(merged_.begin() + (std::ptrdiff_t)taken, merged_.end()); over = pass_over; unmerged = n - merged_.size(); }
+            // (a batch takes a few milliseconds beside the pass: with fewer than eight contigs still to come the pass could be over first and
+            // the run would wait for the batch — those go with the rest; a rank with a handful of contigs never takes one)
+            if (mode == RunSchedule::EarlyBatches::Timed && unmerged < 8) return;
+            if (mode == RunSchedule::EarlyBatches::EveryThree && first && batch.size() < 3 && !over) { std::this_thread::sleep_for(std::chrono::microseconds(100)); continue; }
+            if (!first && over) return;
+            if (!first && batch.size() < 3) { std::this_thread::sleep_for(std::chrono::microseconds(100)); continue; }
+            taken += batch.size();
+            takeBatch(batch);
+            if (mode == RunSchedule::EarlyBatches::AllAtOnce) return;
+        }
+    }
+    void takeBatch(const std::vector<size_t> &batch)
+    {
+        std::vector<CNVCaller::ContigJob> jobs;
+        for (size_t i : batch) if (!R.calls[i]->empty()) jobs.push_back(R.job(i, *R.calls[i]));
+        csvhost::TraceScope tr(jobs.empty() ? "cn: early batch (nothing merged yet)" : "cn: early batch");
+        ThreadContext tc(ctx);
+        const CNVCaller cn = makeCnv(ctx, P);
+        if (!jobs.empty()) regions += cn.runCIGARCopyNumberPredictionAll(jobs, R.hmm);
+        csvhost::TraceScope tr2("run: early split chain + merges");
+        n_split_calls += R.splitChain(*split->pass, split->block_of, batch, cn);
+        for (size_t i : batch) finished[i] = 1;
+    }
+    // the task takes no (more) early batches: the split chain beside the pass, unless the pass is over already
+    bool takeSplitOnly() { std::lock_guard<std::mutex> l(mu); split_only = !pass_over; return split_only; }
+    // whatever is ready goes now, the rest as it comes (a rank of six contigs has two ready when the first half is over and the last one when
+    // the pass ends: what runs behind the pass is that one's chain, not all six)
+    void splitBesidePass()
+    {
+        size_t taken = 0;
+        for (;;) {
+            std::vector<size_t> ready;
+            bool over;
+            { std::lock_guard<std::mutex> l(mu); ready.assign(device_done.begin() + (std::ptrdiff_t)taken, device_done.end()); over = pass_over; }
+            if (ready.empty()) {
+                if (taken >= n || over) break;                           // (over with contigs missing: the pass failed)
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+                continue;
+            }
+            taken += ready.size();
+            csvhost::TraceScope tr("run: split chain beside the pass");
+            std::vector<size_t> todo;                                    // (a contig that went through an early batch has its split calls merged in)
+            for (size_t i : ready) if (!finished[i] && split->block_of[i] >= 0) todo.push_back(i);
+            if (todo.empty()) continue;
+            ThreadContext tc(ctx);
+            CallMap part = R.findSplit(*split->pass, split->block_of, todo);
+            R.predictSplit(makeCnv(ctx, P), part);
+            for (auto &entry : part) pre_split[entry.first] = std::move(entry.second);
+        }
+        pre_ready = taken >= n;
+    }
+
+    std::mutex mu;                                     // guards what follows
+    std::vector<size_t> device_done, merged_;          // contigs, in the order the lanes reported them
+    bool pass_over = false;                            // the CIGAR pass has returned: no batch may be taken any more
+    bool prepare_over = false;                         // the task is past prepare()
+    bool split_only = false;                           // the task runs the split chain beside the pass; the run meets it in front of the split chain
+    std::exception_ptr err;
+    csvhost::WorkerThreads::Ticket ticket = nullptr;
+};
 
 void SVCaller::run(const std::vector<ChromosomeInput> &contigs, const CHMM &hmm, const RunParams &P,
                    std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls)
@@ -607,18 +859,14 @@ void SVCaller::run(ContigSource &source, const CHMM &hmm, const RunParams &P,
     free_all();
 }
 
-namespace {
-bool env_on(const char *name) { const char *e = getenv(name); return e && *e && *e != '0'; }       // (set, not empty, not "0")
-}  // namespace
-
 void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const std::vector<csv_ctx *> &lane_ctxs, const CHMM &hmm, const RunParams &P,
                            std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, std::vector<ChrStats> *stats_out, RunStageTimes *times)
 {
     csvhost::set_context(ctx);
     const double t_begin = now_ms();
     RunStageTimes T;
-    // The caller's own context works on another thread while the lanes run the CIGAR pass (split-read prepare, csvgpu_split_order, the early
-    // copy-number batches): a context is one arena + one stream + one set of timers and belongs to one thread at a time.
+    // The caller's own context works on another thread while the lanes run the CIGAR pass (PassOverlap): a context is one arena + one stream
+    // + one set of timers and belongs to one thread at a time.
     for (csv_ctx *lc : lane_ctxs)
         if (lc == ctx) throw std::invalid_argument("runResident: the caller's context must not be one of the lanes (each lane needs a context of its own)");
     for (size_t a = 0; a < lane_ctxs.size(); a++)
@@ -649,229 +897,7 @@ void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const 
             load[l] += (double)std::max<uint64_t>(contigs[i].split.n, contigs[i].depth_len / 400);
         }
     }
-    // The first half of the split-read pass needs nothing the CIGAR pass produces (flags, name hashes -> the qname map's iteration order):
-    // with lanes, this caller's own context is idle during the CIGAR pass, so that half runs beside it on another thread. When it is done
-    // the pass is a little over half way: the same thread then makes the CIGAR copy-number predictions of the contigs whose calls are
-    // final by then (own context, the host pool nobody else uses during the pass), and only the rest waits for the end of the pass.
-    struct EarlyCn {
-        std::mutex mu;
-        std::vector<std::pair<size_t, size_t>> merged;     // (lane, k) in the order the merge threads finished them
-        std::vector<char> done, finished;                  // per contig: CIGAR copy-number predictions made; every stage of the run made
-        size_t n_split_calls = 0;
-        std::exception_ptr err;
-        size_t regions = 0;
-        bool pass_over = false;                            // (under mu) the CIGAR pass has returned: the task stops taking batches
-        bool prepare_over = false;                         // (under mu) the task is past prepare()
-        // A rank with few contigs (or short reads: a first half as long as the pass) takes no batch of the kind above. Its split chain needs the
-        // scans' alignment intervals and, for its copy-number pass, the depth maps and mean coverages — all there when the contigs' device chains
-        // are over, before their host merges: the task runs it for ALL contigs then, beside the rest of the pass and the CIGAR copy-number pass.
-        std::vector<std::pair<size_t, size_t>> device_done; // (under mu) (lane, k) of the contigs whose device chain is over, in that order
-        bool split_only = false;                           // (under mu) the task has decided to do that; the run meets it in front of the split chain
-        bool main_joins_later = false;                     // (under mu, set with pass_over) the run has gone on without waiting for the task
-        bool pre_ready = false;                            // pre_split holds every contig's split-read calls (read after the join)
-        std::unordered_map<std::string, std::vector<SVCall>> pre_split;
-    } early;
-    early.done.assign(n, 0);
-    early.finished.assign(n, 0);
-    size_t n_lane_contigs = 0;
-    for (size_t l = 0; l < L; l++) n_lane_contigs += which[l].size();
-    const bool early_cn = P.cigar_svs && P.cigar_cn && P.split_svs && !P.save_cnv && n && lane_ctxs.size() > 1 && P.overlap_split_prepare && !env_on("CSV_NO_EARLY_CN");
-    std::unique_ptr<SplitSetup> split;
-    csvhost::WorkerThreads::Ticket split_task = nullptr;
-    const bool forced_batches = env_on("CSV_EARLY_CN_WAIT_ALL") || env_on("CSV_EARLY_SMALL_BATCHES");       // (tests)
-    if (P.split_svs) {
-        split = makeSplitSetup(contigs, P);
-        if (P.cigar_svs && n && lane_ctxs.size() > 1 && P.overlap_split_prepare) {
-            SplitSetup *S = split.get();
-            split_task = csvhost::WorkerThreads::instance().start([&, S, forced_batches] {
-                const double t0 = now_ms();
-                if (const char *e = getenv("CSV_TEST_PREPARE_DELAY_MS")) std::this_thread::sleep_for(std::chrono::milliseconds(atoi(e)));      // (tests: a first half that outlasts the pass)
-                try { S->pass->prepare(); } catch (...) { S->err = std::current_exception(); }
-                S->ms_prepare = now_ms() - t0;
-                if (S->err) { std::lock_guard<std::mutex> l(early.mu); early.prepare_over = true; return; }
-                // the split chain + its copy-number pass for every contig, on this thread and the caller's context (see EarlyCn::split_only)
-                auto split_only_batch = [&] {
-                    try {
-                        static const EmptySnps no_snps;
-                        // whatever is ready goes now, the rest as it comes (a rank of six contigs has two ready when the first half is over and
-                        // the last one when the pass ends: what runs behind the pass is that one's chain, not all six)
-                        size_t taken_b = 0;
-                        for (;;) {
-                            std::vector<std::pair<size_t, size_t>> snap;
-                            bool over;
-                            { std::lock_guard<std::mutex> l(early.mu); snap.assign(early.device_done.begin() + (std::ptrdiff_t)taken_b, early.device_done.end()); over = early.pass_over; }
-                            if (snap.empty()) {
-                                if (taken_b >= n_lane_contigs || over) break;          // (over with contigs missing: the pass failed)
-                                std::this_thread::sleep_for(std::chrono::microseconds(50));
-                                continue;
-                            }
-                            taken_b += snap.size();
-                            csvhost::TraceScope tr("run: split chain beside the pass");
-                            csvhost::set_thread_context(ctx);
-                            std::vector<size_t> blocks;
-                            std::unordered_map<std::string, std::pair<size_t, size_t>> lane_of;
-                            for (const auto &lk : snap) {
-                                if (early.finished[which[lk.first][lk.second]]) continue;      // (went through an early batch: its split calls are merged in)
-                                const int b = S->block_of[which[lk.first][lk.second]];
-                                if (b >= 0) blocks.push_back((size_t)b);
-                                lane_of[contigs[which[lk.first][lk.second]].name] = lk;
-                            }
-                            if (blocks.empty()) { csvhost::set_thread_context(nullptr); continue; }
-                            std::unordered_map<std::string, std::vector<SVCall>> part;
-                            S->pass->finishFor(blocks, part);
-                            std::vector<CNVCaller::ContigJob> sj;
-                            for (auto &entry : part) {
-                                if (entry.second.empty()) continue;
-                                const auto lk = lane_of.at(entry.first);
-                                const size_t i = which[lk.first][lk.second];
-                                CNVCaller::ContigJob j;
-                                j.chr = entry.first; j.calls = &entry.second; j.mean_chr_cov = lane_stats[lk.first][lk.second].mean_chr_cov; j.shard = contigs[i].shard;
-                                j.snps = contigs[i].snps ? contigs[i].snps : (const SNPSource *)&no_snps; j.depth_len = contigs[i].depth_len;
-                                sj.push_back(j);
-                            }
-                            CNVCaller cn(ctx);
-                            cn.sample_size = P.sample_size; cn.min_cnv_length = P.min_cnv_length; cn.host_threads = P.host_threads;
-                            cn.runSplitReadCopyNumberPredictionsAll(sj, hmm);
-                            for (auto &entry : part) early.pre_split[entry.first] = std::move(entry.second);
-                            csvhost::set_thread_context(nullptr);
-                        }
-                        early.pre_ready = taken_b >= n_lane_contigs;
-                    } catch (...) { early.err = std::current_exception(); csvhost::set_thread_context(nullptr); }
-                };
-                const bool can_split_only = !P.save_cnv && !forced_batches && !env_on("CSV_NO_SPLIT_BESIDE_PASS");
-                {   // prepare() outlasted the CIGAR pass (short reads): the run has gone on without waiting and no batch of the first kind may be taken any more
-                    std::unique_lock<std::mutex> l(early.mu);
-                    early.prepare_over = true;
-                    if (early.pass_over && !forced_batches) {
-                        const bool go = early.main_joins_later && can_split_only;
-                        l.unlock();
-                        if (go) split_only_batch();
-                        return;
-                    }
-                }
-                if (!early_cn) {
-                    bool go = false;
-                    { std::lock_guard<std::mutex> l(early.mu); if (can_split_only && !early.pass_over) { early.split_only = true; go = true; } }
-                    if (go) split_only_batch();
-                    return;
-                }
-                try {
-                    if (env_on("CSV_EARLY_CN_WAIT_ALL")) {                      // tests: every contig through this path, whatever the timing
-                        for (int spin = 0; spin < 200000; spin++) {
-                            { std::lock_guard<std::mutex> l(early.mu); if (early.merged.size() >= n_lane_contigs) break; }
-                            std::this_thread::sleep_for(std::chrono::microseconds(50));
-                        }
-                    }
-                    // One batch now (a little over half the genome is merged), then another whenever a few more contigs are: what is left
-                    // for the end of the pass is the last contigs' share. The pass's end (`pass_over`) ends the loop; whatever was not
-                    // taken here is done behind the pass as before.
-                    size_t taken = 0;
-                    for (bool first = true;; first = false) {
-                        std::vector<std::pair<size_t, size_t>> snap;
-                        bool over;
-                        size_t unmerged;
-                        { std::lock_guard<std::mutex> l(early.mu); snap.assign(early.merged.begin() + (std::ptrdiff_t)taken, early.merged.end()); over = early.pass_over;
-                          unmerged = n_lane_contigs - early.merged.size(); }
-                        // (a batch takes a few milliseconds beside the pass: with fewer than eight contigs still to come the pass could be
-                        // over first and the run would wait for the batch — those go with the rest, behind the pass; a rank with a handful of
-                        // contigs never takes one)
-                        // (CSV_EARLY_SMALL_BATCHES: tests — a batch whenever three more contigs are merged, down to the last one)
-                        const bool small_batches = env_on("CSV_EARLY_SMALL_BATCHES");
-                        if (unmerged < 8 && !env_on("CSV_EARLY_CN_WAIT_ALL") && !small_batches) {
-                            if (can_split_only) {                                       // no (more) batches of this kind: the split chain alone, for every contig that went through none
-                                bool go = false;
-                                { std::lock_guard<std::mutex> l(early.mu); if (!early.pass_over) { early.split_only = true; go = true; } }
-                                if (go) split_only_batch();
-                            }
-                            break;
-                        }
-                        if (small_batches && first && snap.size() < 3 && !over) { std::this_thread::sleep_for(std::chrono::microseconds(100)); continue; }
-                        if (!first && (over || snap.size() < 3)) {
-                            if (over) break;
-                            std::this_thread::sleep_for(std::chrono::microseconds(100));
-                            continue;
-                        }
-                        taken += snap.size();
-                        static const EmptySnps no_snps;
-                        std::vector<CNVCaller::ContigJob> jobs;
-                        for (const auto &lk : snap) {
-                            const size_t i = which[lk.first][lk.second];
-                            std::vector<SVCall> &v = lane_calls[lk.first][lk.second];
-                            if (v.empty()) continue;
-                            CNVCaller::ContigJob j;
-                            j.chr = contigs[i].name; j.calls = &v; j.mean_chr_cov = lane_stats[lk.first][lk.second].mean_chr_cov; j.shard = contigs[i].shard;
-                            j.snps = contigs[i].snps ? contigs[i].snps : (const SNPSource *)&no_snps; j.depth_len = contigs[i].depth_len;
-                            jobs.push_back(j);
-                        }
-                        csvhost::TraceScope tr(jobs.empty() ? "cn: early batch (nothing merged yet)" : "cn: early batch");
-                        if (!jobs.empty()) {
-                            csvhost::set_thread_context(ctx);
-                            CNVCaller cn(ctx);
-                            cn.sample_size = P.sample_size; cn.min_cnv_length = P.min_cnv_length; cn.host_threads = P.host_threads;
-                            early.regions += cn.runCIGARCopyNumberPredictionAll(jobs, hmm);
-                            csvhost::set_thread_context(nullptr);
-                        }
-                        for (const auto &lk : snap) early.done[which[lk.first][lk.second]] = 1;
-                        // ... and everything else the run does with these contigs (:885-927): nothing in it reaches across contigs, so the
-                        // same functions run on this batch's contigs now and on the rest behind the pass
-                        if (!env_on("CSV_NO_EARLY_SPLIT")) {
-                            csvhost::TraceScope tr2("run: early split chain + merges");
-                            csvhost::set_thread_context(ctx);
-                            std::vector<size_t> blocks;                                // (merged => scanned: their alignment intervals exist)
-                            for (const auto &lk : snap) { const int b = S->block_of[which[lk.first][lk.second]]; if (b >= 0) blocks.push_back((size_t)b); }
-                            std::unordered_map<std::string, std::vector<SVCall>> split_calls;
-                            S->pass->finishFor(blocks, split_calls);
-                            std::unordered_map<std::string, std::pair<size_t, size_t>> lane_of;     // contig name -> (lane, k)
-                            for (const auto &lk : snap) lane_of[contigs[which[lk.first][lk.second]].name] = lk;
-                            {
-                                std::vector<CNVCaller::ContigJob> sj;
-                                for (auto &entry : split_calls) {
-                                    if (entry.second.empty()) continue;
-                                    const auto lk = lane_of.at(entry.first);
-                                    const size_t i = which[lk.first][lk.second];
-                                    CNVCaller::ContigJob j;
-                                    j.chr = entry.first; j.calls = &entry.second; j.mean_chr_cov = lane_stats[lk.first][lk.second].mean_chr_cov; j.shard = contigs[i].shard;
-                                    j.snps = contigs[i].snps ? contigs[i].snps : (const SNPSource *)&no_snps; j.depth_len = contigs[i].depth_len;
-                                    sj.push_back(j);
-                                }
-                                CNVCaller cn(ctx);
-                                cn.sample_size = P.sample_size; cn.min_cnv_length = P.min_cnv_length; cn.host_threads = P.host_threads;
-                                cn.runSplitReadCopyNumberPredictionsAll(sj, hmm);
-                            }
-                            if (P.merge_split_svs) {
-                                std::vector<std::vector<SVCall> *> sets;
-                                for (auto &entry : split_calls) sets.push_back(&entry.second);
-                                mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
-                            }
-                            for (auto &entry : split_calls) {
-                                const auto lk = lane_of.at(entry.first);
-                                early.n_split_calls += entry.second.size();
-                                std::vector<SVCall> &dst = lane_calls[lk.first][lk.second];
-                                dst.insert(dst.end(), entry.second.begin(), entry.second.end());
-                            }
-                            if (P.merge_final_svs) {
-                                std::vector<std::vector<SVCall> *> sets;
-                                for (const auto &lk : snap) sets.push_back(&lane_calls[lk.first][lk.second]);
-                                mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
-                            }
-                            for (const auto &lk : snap) early.finished[which[lk.first][lk.second]] = 1;
-                            csvhost::set_thread_context(nullptr);
-                        }
-                        if (env_on("CSV_EARLY_CN_WAIT_ALL") || env_on("CSV_EARLY_ONE_BATCH")) break;
-                    }
-                } catch (...) { early.err = std::current_exception(); csvhost::set_thread_context(nullptr); }
-            });
-        }
-    }
-    struct JoinSplit {                                                  // the task refers to this frame: never leave it with the task running
-        csvhost::WorkerThreads::Ticket &t;
-        ~JoinSplit() { if (t) { csvhost::WorkerThreads::instance().wait(t); t = nullptr; } }
-    } join_split{split_task};
-    struct EndPass {                                                    // (declared after join_split: runs before it, also when the pass throws)
-        EarlyCn &e;
-        ~EndPass() { std::lock_guard<std::mutex> l(e.mu); e.pass_over = true; }
-    } end_pass{early};
-    bool join_later = false;
+    PassOverlap overlap(*this, contigs, lane_ctxs, hmm, P);
     if (P.cigar_svs && n) {
         csvhost::TraceScope tr_pass("run: CIGAR pass");
         if (L == 1) {
@@ -880,20 +906,13 @@ void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const 
             one.min_mapq = min_mapq; one.min_oplen = min_oplen;
             one.processResidentChromosomesPipelined(lanes[0].shards, lanes[0].seqs, P.dbscan_epsilon, P.dbscan_min_pts_pct, lane_calls[0], lane_stats[0]);
         } else {
-            std::function<void(size_t, size_t)> note;
-            if (early_cn) note = [&early](size_t l, size_t k) { std::lock_guard<std::mutex> g(early.mu); early.merged.emplace_back(l, k); };
-            std::function<void(size_t, size_t)> dev_note;
-            if (split_task) dev_note = [&early](size_t l, size_t k) { std::lock_guard<std::mutex> g(early.mu); early.device_done.emplace_back(l, k); };
-            processResidentLanes(lanes, nullptr, P.dbscan_epsilon, P.dbscan_min_pts_pct, lane_calls, lane_stats, note, min_mapq, min_oplen, dev_note);
+            std::function<void(size_t, size_t)> on_merged, on_device;
+            if (overlap.early) on_merged = [&](size_t l, size_t k) { overlap.merged(which[l][k], lane_calls[l][k]); };
+            if (overlap.task) on_device = [&](size_t l, size_t k) { overlap.deviceDone(which[l][k], lane_stats[l][k]); };
+            processResidentLanes(lanes, nullptr, P.dbscan_epsilon, P.dbscan_min_pts_pct, lane_calls, lane_stats, on_merged, min_mapq, min_oplen, on_device);
         }
         T.ms_cigar = now_ms() - t_begin;
-        // (the early copy-number batch works on lane_calls in place: it must be over before they move. A task still inside prepare()
-        // takes no batch after the pass: the run goes on — the CIGAR copy-number pass needs nothing of prepare() — and meets the task in
-        // front of the split chain.)
-        { std::lock_guard<std::mutex> l(early.mu); early.pass_over = true;
-          join_later = split_task && (!early.prepare_over || early.split_only) && !forced_batches && !env_on("CSV_NO_LATE_JOIN");
-          early.main_joins_later = join_later; }
-        if (split_task && !join_later) { csvhost::WorkerThreads::instance().wait(split_task); split_task = nullptr; }
+        overlap.passOver();
         for (size_t l = 0; l < L; l++)
             for (size_t k = 0; k < which[l].size(); k++) { per[which[l][k]] = std::move(lane_calls[l][k]); stats[which[l][k]] = lane_stats[l][k]; }
     } else T.ms_cigar = now_ms() - t_begin;
@@ -901,16 +920,9 @@ void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const 
         T.n_signatures += stats[i].n_signatures; T.n_cigar_calls += per[i].size(); T.n_reads += contigs[i].split.n;
         whole_genome_sv_calls[contigs[i].name] = std::move(per[i]);
     }
-    const std::function<void()> join = [&] {
-        if (split_task) { csvhost::WorkerThreads::instance().wait(split_task); split_task = nullptr; }
-        if (split && split->err) std::rethrow_exception(split->err);
-        if (early.err) std::rethrow_exception(early.err);
-    };
-    if (!join_later) join();
-    T.n_cigar_cn_regions += early.regions;                                  // (a task joined later has taken no batch)
-    T.n_split_calls += early.n_split_calls;
-    finishRun(contigs, stats, hmm, P, whole_genome_sv_calls, T, split.get(), lane_ctxs.size() > 1 ? lane_ctxs[0] : nullptr, early_cn ? &early.done : nullptr,
-              early_cn ? &early.finished : nullptr, join_later ? &join : nullptr, &early.pre_split, &early.pre_ready);
+    T.n_cigar_cn_regions += overlap.regions;                           // (a task the run meets later takes no batch after the pass)
+    T.n_split_calls += overlap.n_split_calls;
+    finishRun(contigs, stats, hmm, P, whole_genome_sv_calls, T, &overlap);
     T.ms_total = now_ms() - t_begin;
     if (stats_out) *stats_out = stats;
     if (times) *times = T;
@@ -932,7 +944,7 @@ std::unique_ptr<SVCaller::SplitSetup> SVCaller::makeSplitSetup(std::vector<Resid
         shard_of.push_back(c.shard);
     }
     S->sp.min_mapq = min_mapq; S->sp.threads = P.host_threads;
-    S->dev_order.reset(new ShardOrderSource(ctx, shard_of));
+    S->dev_order.reset(new ShardOrderSource(ctx, shard_of, P.schedule.split_order_self));
     S->intervals.reset(new ShardIntervals(ctx, shard_of));
     S->sp.intervals = S->intervals.get();
     if (P.split_order_on_device) S->sp.device_order = S->dev_order.get();          // only contigs staged with unique_names take it
@@ -941,21 +953,17 @@ std::unique_ptr<SVCaller::SplitSetup> SVCaller::makeSplitSetup(std::vector<Resid
 }
 
 void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector<ChrStats> &stats, const CHMM &hmm, const RunParams &P,
-                         std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, RunStageTimes &T, SplitSetup *split, csv_ctx *side_ctx,
-                         const std::vector<char> *cigar_cn_done, const std::vector<char> *finished, const std::function<void()> *before_split,
-                         std::unordered_map<std::string, std::vector<SVCall>> *pre_split, const bool *pre_split_ready)
+                         std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, RunStageTimes &T, PassOverlap *overlap)
 {
-    const EmptySnps no_snps;
     csvhost::WorkerThreads::Ticket teardown = nullptr;
     struct JoinTeardown {
         csvhost::WorkerThreads::Ticket &t;
         ~JoinTeardown() { if (t) csvhost::WorkerThreads::instance().wait(t); }
     } join_teardown{teardown};
-    std::unordered_map<std::string, size_t> index_of;
-    std::vector<std::string> names;
-    for (size_t i = 0; i < contigs.size(); i++) { index_of[contigs[i].name] = i; names.push_back(contigs[i].name); }
-    CNVCaller cnv(ctx);
-    cnv.sample_size = P.sample_size; cnv.min_cnv_length = P.min_cnv_length; cnv.host_threads = P.host_threads;
+    RunContigs R(contigs, hmm, P);
+    for (size_t i = 0; i < contigs.size(); i++) { R.mean_cov[i] = stats[i].mean_chr_cov; R.calls[i] = &whole_genome_sv_calls[contigs[i].name]; }
+    const std::vector<char> *finished = overlap ? &overlap->finished : nullptr;     // (every step made while the CIGAR pass was still running)
+    CNVCaller cnv = makeCnv(ctx, P);
     if (P.save_cnv && !P.vcf.output_dir.empty()) {                                 // main.cpp:109-118
         cnv.save_cnv_data = true;
         cnv.cnv_output_file = P.vcf.output_dir + "/CNVCalls.json";
@@ -963,22 +971,10 @@ void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector
         printMessage("Saving CNV data to: " + cnv.cnv_output_file);
     }
     double t0 = now_ms();
-    auto cn_jobs = [&](std::unordered_map<std::string, std::vector<SVCall>> &m, const std::vector<char> *skip = nullptr) {
-        std::vector<CNVCaller::ContigJob> jobs;
-        for (auto &entry : m) {                                                      // the map's own order, as the reference walks it
-            if (entry.second.empty()) continue;
-            const size_t i = index_of.at(entry.first);
-            if (skip && (*skip)[i]) continue;                                            // (predicted while the CIGAR pass was still running)
-            CNVCaller::ContigJob j;
-            j.chr = entry.first; j.calls = &entry.second; j.mean_chr_cov = stats[i].mean_chr_cov; j.shard = contigs[i].shard;
-            j.snps = contigs[i].snps ? contigs[i].snps : (const SNPSource *)&no_snps; j.depth_len = contigs[i].depth_len;
-            jobs.push_back(j);
-        }
-        return jobs;
-    };
     // The CIGAR copy-number pass (:865-881) and the split-read chain (:885-917) do not depend on each other: with a second context
     // at hand (`side_ctx`: a lane's, idle by now) the former runs on another thread — its own context, its own host pool — while
     // this thread goes on with the latter; they meet in front of the final merge.
+    csv_ctx *side_ctx = overlap ? overlap->side_ctx : nullptr;
     csvhost::WorkerThreads::Ticket cn_task = nullptr;
     std::exception_ptr cn_err;
     struct JoinCn {
@@ -989,20 +985,17 @@ void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector
         printMessage("Running copy number predictions on CIGAR SVs...");
         if (side_ctx && side_ctx != ctx && P.split_svs && !cnv.save_cnv_data) {
             cn_task = csvhost::WorkerThreads::instance().start([&, t0] {
+                csvhost::HostPool::second_pool_flag() = true;
                 try {
-                    csvhost::HostPool::second_pool_flag() = true;
-                    csvhost::set_thread_context(side_ctx);
-                    CNVCaller side(side_ctx);
-                    side.sample_size = cnv.sample_size; side.min_cnv_length = cnv.min_cnv_length; side.host_threads = cnv.host_threads;
-                    std::vector<CNVCaller::ContigJob> jobs = cn_jobs(whole_genome_sv_calls, cigar_cn_done);
-                    T.n_cigar_cn_regions += side.runCIGARCopyNumberPredictionAll(jobs, hmm);
+                    ThreadContext tc(side_ctx);
+                    std::vector<CNVCaller::ContigJob> jobs = R.jobs(whole_genome_sv_calls, finished);
+                    T.n_cigar_cn_regions += makeCnv(side_ctx, P).runCIGARCopyNumberPredictionAll(jobs, hmm);
                 } catch (...) { cn_err = std::current_exception(); }
-                csvhost::set_thread_context(nullptr);
                 csvhost::HostPool::second_pool_flag() = false;
                 T.ms_cigar_cn = now_ms() - t0;
             });
         } else {
-            std::vector<CNVCaller::ContigJob> jobs = cn_jobs(whole_genome_sv_calls, cigar_cn_done);
+            std::vector<CNVCaller::ContigJob> jobs = R.jobs(whole_genome_sv_calls, finished);
             T.n_cigar_cn_regions += cnv.runCIGARCopyNumberPredictionAll(jobs, hmm);
             T.ms_cigar_cn = now_ms() - t0;
         }
@@ -1010,12 +1003,13 @@ void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector
     if (P.split_svs) {                                                             // :885-917
         t0 = now_ms();
         std::unique_ptr<SplitSetup> own;
+        SplitSetup *split = overlap ? overlap->split.get() : nullptr;
         if (!split) { own = makeSplitSetup(contigs, P); split = own.get(); }
         T.ms_split_fetch = 0.0;
-        std::unordered_map<std::string, std::vector<SVCall>> split_calls;
-        if (before_split) (*before_split)();                                       // (prepare() still running on its thread: meet it here)
-        const bool pre = pre_split && pre_split_ready && *pre_split_ready;         // (the split chain and its copy-number pass ran beside the CIGAR pass)
-        if (pre) split_calls = std::move(*pre_split);
+        if (overlap) overlap->join();                                              // (prepare() or the split chain still running beside the pass: meet it here)
+        const bool pre = overlap && overlap->pre_ready;                            // (the split chain and its copy-number pass ran beside the CIGAR pass)
+        CallMap split_calls;
+        if (pre) split_calls = std::move(overlap->pre_split);
         else split->pass->finish(split_calls);                                     // (runs prepare() first when nobody has)
         T.ms_split_prepare = split->ms_prepare;
         {   // the pass's working set (1e5 small vectors for a genome) is torn down beside the next stages, not between them
@@ -1024,37 +1018,24 @@ void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector
         }
         T.ms_split = now_ms() - t0;
         t0 = now_ms();
-        if (!pre) {
-            std::vector<CNVCaller::ContigJob> jobs = cn_jobs(split_calls);
-            cnv.runSplitReadCopyNumberPredictionsAll(jobs, hmm);
-        }
+        if (!pre) R.predictSplit(cnv, split_calls);
         T.ms_split_cn = now_ms() - t0;
         t0 = now_ms();
-        if (P.merge_split_svs) {
-            std::vector<std::vector<SVCall> *> sets;
-            for (auto &entry : split_calls) sets.push_back(&entry.second);
-            mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
-        }
+        R.mergeSplit(split_calls);
         if (cn_task) { csvhost::WorkerThreads::instance().wait(cn_task); cn_task = nullptr; }          // the CIGAR calls are final from here on
         if (cn_err) std::rethrow_exception(cn_err);
-        for (auto &entry : split_calls) {
-            T.n_split_calls += entry.second.size();
-            std::vector<SVCall> &dst = whole_genome_sv_calls[entry.first];
-            dst.insert(dst.end(), entry.second.begin(), entry.second.end());
-        }
+        T.n_split_calls += R.appendSplit(split_calls);
         T.ms_merge_split = now_ms() - t0;
     }
     if (cn_task) { csvhost::WorkerThreads::instance().wait(cn_task); cn_task = nullptr; }
     if (cn_err) std::rethrow_exception(cn_err);
     t0 = now_ms();
-    if (P.merge_final_svs) {                                                                                 // :919-927
-        std::vector<std::vector<SVCall> *> sets;
-        for (auto &entry : whole_genome_sv_calls) {
-            if (finished && (*finished)[index_of.at(entry.first)]) continue;                                 // (merged while the CIGAR pass was still running)
-            sets.push_back(&entry.second);
-        }
-        mergeSVsMany(sets, 0.1, 2, true, P.host_threads);
+    std::vector<size_t> rest;                                                      // :919-927, the map's own order
+    for (const auto &entry : whole_genome_sv_calls) {
+        const size_t i = R.index_of.at(entry.first);
+        if (!(finished && (*finished)[i])) rest.push_back(i);
     }
+    R.mergeFinal(rest);
     T.ms_merge_final = now_ms() - t0;
     if (cnv.save_cnv_data) CNVCaller::closeJSON(cnv.cnv_output_file);                                       // :929-931
     uint32_t total = 0;

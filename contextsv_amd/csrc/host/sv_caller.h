@@ -80,6 +80,19 @@ struct RunStageTimes {
     uint64_t n_reads = 0, n_signatures = 0, n_cigar_calls = 0, n_cigar_cn_regions = 0, n_split_calls = 0, n_final_calls = 0;
 };
 
+// How runResident schedules its work around the CIGAR pass. Results never depend on these fields: the defaults are the production
+// schedule, and the others exist so that tests can force each branch that timing otherwise decides.
+struct RunSchedule {
+    // The copy-number predictions and every later step of the contigs merged so far, in batches inside the CIGAR pass (with lanes):
+    // Timed — one when the split pass's first half is done, another whenever three more contigs are merged, while eight or more are still
+    // to come; None; AllAtOnce — one batch of every contig, once all are merged; EveryThree — whenever three more are merged, to the last.
+    enum class EarlyBatches { Timed, None, AllAtOnce, EveryThree };
+    EarlyBatches early_batches = EarlyBatches::Timed;
+    bool split_beside_pass = true;          // contigs that go through no early batch get their split chain beside the pass (false: behind it)
+    bool split_order_self = true;           // a run's split order in one call when it holds every contig (false: _begin + the collected hashes)
+    int prepare_delay_ms = 0;               // the split pass's first half starts this much later (makes it outlast the CIGAR pass)
+};
+
 struct RunParams {
     double dbscan_epsilon = 0.1;            // --eps          (input_data.cpp:18-37)
     double dbscan_min_pts_pct = 0.1;        // --min-pts-pct
@@ -96,6 +109,7 @@ struct RunParams {
     std::string ethnicity;                  // --eth: AF_<eth> instead of AF
     const ReferenceGenome *ref_genome = nullptr;   // with vcf.output_dir set: write <output_dir>/output.vcf at the end (sv_caller.cpp:943-945)
     VCFOptions vcf;
+    RunSchedule schedule;
 };
 
 struct BamRunStats {
@@ -185,17 +199,13 @@ public:
 
 private:
     csv_ctx *ctx;
-    // everything of run() behind the CIGAR pass: CIGAR copy-number predictions, split-read signatures + their predictions, the two
-    // final merges, the VCF (sv_caller.cpp:865-945). stats[i] belongs to contigs[i].
     struct SplitSetup;
+    struct PassOverlap;                      // runResident's work beside the CIGAR pass
     std::unique_ptr<SplitSetup> makeSplitSetup(std::vector<ResidentContig> &contigs, const RunParams &P);
+    // everything of run() behind the CIGAR pass: CIGAR copy-number predictions, split-read signatures + their predictions, the two
+    // final merges, the VCF (sv_caller.cpp:865-945). stats[i] belongs to contigs[i]; `overlap`: what was done beside the pass (or null).
     void finishRun(std::vector<ResidentContig> &contigs, const std::vector<ChrStats> &stats, const CHMM &hmm, const RunParams &P,
-                   std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, RunStageTimes &T, SplitSetup *split = nullptr,
-                   csv_ctx *side_ctx = nullptr, const std::vector<char> *cigar_cn_done = nullptr /* per contig: CIGAR copy-number predictions already made */,
-                   const std::vector<char> *finished = nullptr /* per contig: every stage already made (its entry of the call map is final) */,
-                   const std::function<void()> *before_split = nullptr /* called in front of the split chain: joins a prepare() still running */,
-                   std::unordered_map<std::string, std::vector<SVCall>> *pre_split = nullptr, const bool *pre_split_ready = nullptr
-                   /* (read after before_split) the split-read calls of every contig, copy-number predictions made: the chain ran beside the CIGAR pass */);
+                   std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, RunStageTimes &T, PassOverlap *overlap = nullptr);
     struct DeviceOut {                       // what the device chain of one shard hands to the host merge: page-locked result buffers
         csv_ctx *ctx = nullptr;
         csv_sig *sig = nullptr;

@@ -243,6 +243,9 @@ class SynthShard:
             self.h = None
 
 
+_EARLY_BATCHES = {"timed": 0, "none": 1, "all": 2, "every3": 3}          # RunSchedule::EarlyBatches
+
+
 class Genome:
     """A staged genome: contigs resident in HBM + the small host arrays of the host-side passes; run() = SVCaller::runResident
     (one step of the whole-genome benchmark). Contigs are added through a Context (they may use different contexts of one GPU)."""
@@ -276,9 +279,18 @@ class Genome:
         return {"n_reads": nr.value, "n_cigar": nc.value, "depth_len": dl.value, "global_tid": gt.value, "shard": sh.value}
 
     def run(self, ctx: Context, hmm, lanes=None, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, merges=True,
-            host_threads=0, capacity: int = 1 << 20, host_split_order: bool = False, overlap_split: bool = True, copy: bool = True):
+            host_threads=0, capacity: int = 1 << 20, host_split_order: bool = False, overlap_split: bool = True, copy: bool = True,
+            early_batches: str = "timed", split_beside_pass: bool = True, split_order_self: bool = True, prepare_delay_ms: int = 0):
         """-> (calls[CALL_DTYPE], global tid per call, stage_times, per-contig chr_stats list). copy=False: the two arrays are views of buffers
-        the genome owns (two sets, used alternately) and stay valid until the run after the next one."""
+        the genome owns (two sets, used alternately) and stay valid until the run after the next one. early_batches ("timed" | "none" | "all" |
+        "every3"), split_beside_pass, split_order_self and prepare_delay_ms are RunParams::schedule: no result depends on them, they force
+        the branches that timing otherwise decides."""
+        if early_batches not in _EARLY_BATCHES:
+            raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {early_batches!r}")
+        if not 0 <= int(prepare_delay_ms) < 1 << 15:
+            raise ValueError(f"prepare_delay_ms must be in [0, 32767], not {prepare_delay_ms!r}")
+        passes = int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4) | \
+            (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(prepare_delay_ms) << 16)
         n = len(self)
         if getattr(self, "_cap", 0) < capacity:              # result buffers live with the genome (tens of megabytes of page faults per call otherwise)
             self._bufs = [(np.empty(capacity, CALL_DTYPE), np.empty(capacity, np.int32)) for _ in range(2)]
@@ -290,9 +302,8 @@ class Genome:
         cs = (chr_stats * max(n, 1))()
         lanes = lanes or []
         lp = (C.c_void_p * max(len(lanes), 1))(*[c.h for c in lanes])
-        _check(load().csvhost_genome_run(self.h, ctx.h, len(lanes), lp, C.byref(hmm), eps, min_pts_pct, sample_size, min_cnv,
-                                         int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4), host_threads, out.ctypes.data, tid.ctypes.data, capacity,
-                                         C.byref(k), C.byref(st), cs))
+        _check(load().csvhost_genome_run(self.h, ctx.h, len(lanes), lp, C.byref(hmm), eps, min_pts_pct, sample_size, min_cnv, passes, host_threads,
+                                         out.ctypes.data, tid.ctypes.data, capacity, C.byref(k), C.byref(st), cs))
         if k.value > capacity:
             raise RuntimeError("Genome.run: capacity too small")
         if copy:

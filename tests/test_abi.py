@@ -47,13 +47,22 @@ def test_no_cpu_fallback_without_device():
         host.merge_svs(host.make_calls([1, 2], [100, 101], [0, 0]), 0.1, 2, False)
 
 
+# environment switches that once steered SVCaller::runResident; the run's shape is RunParams::schedule now
+RETIRED_HOST_SWITCHES = ("CSV_NO_EARLY_CN", "CSV_EARLY_CN_WAIT_ALL", "CSV_EARLY_SMALL_BATCHES", "CSV_NO_SPLIT_BESIDE_PASS", "CSV_SPLIT_NO_SELF",
+                         "CSV_TEST_PREPARE_DELAY_MS", "CSV_NO_EARLY_SPLIT", "CSV_NO_LATE_JOIN", "CSV_EARLY_ONE_BATCH", "CSV_SPLIT_ONE_CALL",
+                         "CSV_JOBS_AHEAD")
+
+
 def test_product_package_does_not_touch_the_oracle():
     pkg = os.path.join(ROOT, "contextsv_amd")
+    host_src = os.path.join(pkg, "csrc", "host")
     for dp, _, files in os.walk(pkg):
         for f in files:
             if f.endswith((".py", ".cpp", ".h", ".hpp", ".hip")) or f == "Makefile":
                 txt = open(os.path.join(dp, f), errors="ignore").read()
                 assert "libcsvoracle" not in txt and "oracle_lib" not in txt and "csv_oracle" not in txt, os.path.join(dp, f)
+                if os.path.abspath(dp).startswith(host_src):
+                    assert not [s for s in RETIRED_HOST_SWITCHES if s in txt], os.path.join(dp, f)
 
 
 def test_testhooks_build_exports_the_same_abi_plus_the_hook():

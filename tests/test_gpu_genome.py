@@ -54,14 +54,8 @@ def test_resident_run_equals_uploading_run(ctx):
         # With lanes, the CIGAR copy-number predictions of the contigs that are merged when the split pass's first half is done are made
         # during the CIGAR pass, in place (SVCaller::runResident). Which contigs those are depends on timing: none of them, all of them
         # (the task waits for every merge), and whatever it happens to be must give the same calls.
-        import os
-        for env in ({"CSV_NO_EARLY_CN": "1"}, {"CSV_EARLY_CN_WAIT_ALL": "1"}):
-            os.environ.update(env)
-            try:
-                got4, tid4, st4, _ = g.run(ctx, hmm, lanes=lanes)
-            finally:
-                for k in env:
-                    del os.environ[k]
+        for early in ("none", "all"):
+            got4, tid4, st4, _ = g.run(ctx, hmm, lanes=lanes, early_batches=early)
             assert np.array_equal(tid4, ref_tid) and st4.n_cigar_cn_regions == st3.n_cigar_cn_regions
             _same(got4, ref_calls)
     finally:
@@ -124,8 +118,8 @@ def test_early_batches_inside_the_pass_give_the_same_calls(ctx):
     """The production path of the 24-contig step: with eight or more contigs still to come, the copy-number predictions, the split-read
     chain and the merges of the contigs merged so far are made in batches INSIDE the CIGAR pass (SVCaller::runResident). Fourteen small
     contigs through three lanes: the default run (batch sizes depend on timing), batches of three down to the last contig
-    (CSV_EARLY_SMALL_BATCHES), one batch of everything (CSV_EARLY_CN_WAIT_ALL), no early batch at all (CSV_NO_EARLY_CN), no split overlap,
-    and the run without lanes must give the same records."""
+    (early_batches="every3"), one batch of everything ("all"), no early batch at all ("none"), no split overlap, and the run without lanes
+    must give the same records."""
     import os
     hmm = make_hmm(**WGS_HMM)
     host.set_context(ctx)
@@ -137,21 +131,21 @@ def test_early_batches_inside_the_pass_give_the_same_calls(ctx):
             c.set_gate(gate)
         ref, ref_tid, st0, _ = g.run(ctx, hmm)                                     # no lanes: nothing early
         assert len(ref) > 20 and st0.n_cigar_cn_regions > 0 and st0.n_split_calls > 0
-        for env, kw in (({}, {}), ({"CSV_EARLY_SMALL_BATCHES": "1"}, {}), ({"CSV_EARLY_CN_WAIT_ALL": "1"}, {}), ({"CSV_NO_EARLY_CN": "1"}, {}),
-                        ({"CSV_NO_EARLY_SPLIT": "1", "CSV_EARLY_SMALL_BATCHES": "1"}, {}), ({}, {"overlap_split": False}),
+        for env, kw in (({}, {}), ({}, {"early_batches": "every3"}), ({}, {"early_batches": "all"}), ({}, {"early_batches": "none"}),
+                        ({}, {"overlap_split": False}),
                         # the split order in two calls with the caller's supplementary hashes instead of queued whole (csvgpu_split_order_begin_self);
-                        # the three-launch radix passes instead of the onesweep ones; a late split-read first half joined behind the pass
-                        ({"CSV_SPLIT_NO_SELF": "1"}, {}), ({"CSV_SORT_ONESWEEP": "0"}, {}), ({"CSV_NO_LATE_JOIN": "1", "CSV_SPLIT_NO_SELF": "1"}, {}),
-                        # the split-read first half made to outlast the CIGAR pass: joined in front of the split chain / behind the pass
-                        ({"CSV_TEST_PREPARE_DELAY_MS": "40"}, {}), ({"CSV_TEST_PREPARE_DELAY_MS": "40", "CSV_NO_LATE_JOIN": "1"}, {}),
+                        # the three-launch radix passes instead of the onesweep ones (libcsvgpu's own switch)
+                        ({}, {"split_order_self": False}), ({"CSV_SORT_ONESWEEP": "0"}, {}),
+                        # the split-read first half made to outlast the CIGAR pass: joined in front of the split chain
+                        ({}, {"prepare_delay_ms": 40}),
                         # without / with the split chain of all contigs beside the pass (what a run that takes no early batch does by default)
-                        ({"CSV_NO_SPLIT_BESIDE_PASS": "1"}, {}), ({"CSV_NO_SPLIT_BESIDE_PASS": "1", "CSV_TEST_PREPARE_DELAY_MS": "40"}, {}),
-                        ({"CSV_NO_EARLY_CN": "1", "CSV_NO_SPLIT_BESIDE_PASS": "1"}, {})):
+                        ({}, {"split_beside_pass": False}), ({}, {"split_beside_pass": False, "prepare_delay_ms": 40}),
+                        ({}, {"early_batches": "none", "split_beside_pass": False})):
             os.environ.update(env)
             try:
                 for _ in range(2):
                     got, tid, st, _ = g.run(ctx, hmm, lanes=lanes, **kw)
-                    assert np.array_equal(tid, ref_tid), env
+                    assert np.array_equal(tid, ref_tid), (env, kw)
                     _same(got, ref)
                     assert st.n_cigar_cn_regions == st0.n_cigar_cn_regions and st.n_split_calls == st0.n_split_calls
             finally:
