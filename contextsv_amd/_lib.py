@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CSVGPU_LIB: another build of the same library (tests: lib/libcsvgpu_testhooks.so, which also exports the allocation-failure hook)
 LIB_PATH = os.environ.get("CSVGPU_LIB") or os.path.join(_HERE, "lib", "libcsvgpu.so")
-ABI_VERSION = 3          # include/csvgpu.h CSVGPU_ABI_VERSION
+ABI_VERSION = 4          # include/csvgpu.h CSVGPU_ABI_VERSION
 
 CSV_OK, CSV_EINVAL, CSV_ENODEV, CSV_ENOMEM, CSV_EHIP, CSV_ECAPACITY = 0, -1, -2, -3, -4, -5
 STATUS_NAMES = {0: "CSV_OK", -1: "CSV_EINVAL", -2: "CSV_ENODEV", -3: "CSV_ENOMEM", -4: "CSV_EHIP", -5: "CSV_ECAPACITY"}
@@ -49,6 +49,11 @@ class csv_chr_result(C.Structure):
                 ("depth", C.c_void_p), ("ref_end", C.c_void_p), ("q_start", C.c_void_p), ("q_end", C.c_void_p)]
 
 
+class csv_tuning(C.Structure):
+    _fields_ = [("scan_form", C.c_int32), ("split_tail", C.c_int32), ("sort_three_launch", C.c_int32), ("dbscan_all_pairs", C.c_int32),
+                ("split_chain_only", C.c_int32)]
+
+
 # every symbol include/csvgpu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 ABI = {
@@ -61,6 +66,7 @@ ABI = {
     "csvgpu_timing_enable": (C.c_int, [_P, C.c_int]),
     "csvgpu_timing_reset": (C.c_int, [_P]),
     "csvgpu_timing_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "csvgpu_set_tuning": (C.c_int, [_P, C.POINTER(csv_tuning)]),
     "csvgpu_cigar_scan": (C.c_int, [_P, C.POINTER(csv_reads), C.c_uint32, C.c_uint32, C.c_uint8, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_aln_intervals": (C.c_int, [_P, C.POINTER(csv_reads), _P, _P, _P]),
     "csvgpu_depth": (C.c_int, [_P, C.POINTER(csv_reads), C.c_uint32, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

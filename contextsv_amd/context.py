@@ -99,6 +99,14 @@ class Context:
     def set_gate(self, gate: "Gate | None"):
         self._check(self.lib.csvgpu_set_gate(self.h, gate.h if gate is not None else None))
 
+    def set_tuning(self, scan_form: int | None = None, split_tail: int | None = None, sort_three_launch: bool = False,
+                   dbscan_all_pairs: bool = False, split_chain_only: bool = False):
+        """csvgpu_set_tuning: which of several kernels with the same result this context launches from now on (csv_tuning in csvgpu.h).
+        scan_form 0..3 / split_tail 0..3 force a value, None leaves the choice to the library; no argument at all = the defaults."""
+        t = _lib.csv_tuning(-1 if scan_form is None else scan_form, -1 if split_tail is None else split_tail, int(sort_three_launch),
+                            int(dbscan_all_pairs), int(split_chain_only))
+        self._check(self.lib.csvgpu_set_tuning(self.h, C.byref(t)))
+
     __del__ = close
 
     def __enter__(self):

@@ -73,6 +73,7 @@ struct csv_ctx {
     size_t       job_pin_next = 0;
     uint32_t     job_pin_busy = 0;          // bit i: slot i belongs to a job between begin and end / abort
     struct csv_split_state *split_state = nullptr;   // between csvgpu_split_order_begin and _finish
+    csv_tuning   tuning = CSV_TUNING_DEFAULTS;      // csvgpu_set_tuning
 };
 
 struct csv_shard {
@@ -93,7 +94,7 @@ struct csv_shard {
     uint64_t *counters = nullptr;  // device scalars (see ScanCounters) + bucket tables + the depth tiles' candidate ranges, zeroed together per chromosome
     uint64_t *tile_range = nullptr;   // inside `counters`
     uint64_t *scan_split = nullptr;   // the scan's work split for this device's grid (launch_scan_split, once per shard)
-    int       form = 0;               // SCAN_FORM_*: chosen from the mean CIGAR words per read when the shard is created
+    int       form = 0;               // SCAN_FORM_*: the creating context's forced form, or chosen from the mean CIGAR words per read, when the shard is created
     void     *depth_items = nullptr;  // depth_items_bytes(depth_len): the depth tiles' work lists (depth.hip)
     uint64_t *qhash = nullptr;        // [n_reads] std::hash<std::string> of every record's query name (csvgpu_shard_set_qname_hash), or null
     size_t    counters_bytes = 0;
@@ -161,8 +162,8 @@ struct ScanExtras {
     int       type_pos = -1, bucket_shift = 0;
 };
 // Forms of the scan (and of the depth pass's walk): a wave per read (long reads), or groups of 16 / 8 lanes per read (short reads)
-enum { SCAN_FORM_WAVE = 0, SCAN_FORM_ROWS16 = 1, SCAN_FORM_ROWS8 = 2, SCAN_FORM_LANES = 3 };      // (LANES: the scan walks a read per lane; the depth walk takes groups of 16)
-int scan_form_for(uint64_t n_reads, uint64_t n_cigar);          // by mean CIGAR words per read
+enum { SCAN_FORM_WAVE = CSV_FORM_WAVE, SCAN_FORM_ROWS16 = CSV_FORM_ROWS16, SCAN_FORM_ROWS8 = CSV_FORM_ROWS8, SCAN_FORM_LANES = CSV_FORM_LANES };      // (LANES: the scan walks a read per lane; the depth walk takes groups of 16)
+int scan_form_for(uint64_t n_reads, uint64_t n_cigar);          // by mean CIGAR words per read: SCAN_FORM_WAVE or SCAN_FORM_ROWS16
 void launch_cigar_scan(hipStream_t s, int n_cu, const csv_reads &d, uint32_t depth_len, uint32_t min_oplen,
                        uint32_t min_mapq, int emit, csv_sig *sig_out, uint64_t sig_cap,
                        int32_t *ref_end, int32_t *q_start, int32_t *q_end, uint32_t *ckpt, ScanCounters *cnt, const ScanExtras &extras = ScanExtras(),
@@ -197,9 +198,11 @@ void launch_depth_lookup(hipStream_t s, const uint32_t *depth, uint32_t depth_le
 // sort.hip
 size_t radix_sort_tmp_bytes(uint64_t n);
 // stable LSD sort of (key,val) pairs by key bits [0,key_bits). Both buffer pairs are clobbered; returns 1 when the
-// result is in keys_out/vals_out, 0 when it is in keys_in/vals_in (even number of passes).
+// result is in keys_out/vals_out, 0 when it is in keys_in/vals_in (even number of passes). onesweep: one launch per pass where n and
+// key_bits allow it, else (and with onesweep == false) histogram, table scan and scatter per pass — the same order bit for bit.
 int  launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out,
-                           uint64_t n, int key_bits, void *tmp);
+                           uint64_t n, int key_bits, void *tmp, bool onesweep);
+// (onesweep passes only: the other passes size their table from a count the host knows)
 int  launch_radix_sort_u64_devn(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out, uint64_t n_bound,
                                 const uint32_t *n_dev, int key_bits, void *tmp);
 // bucket ordering: BK_N most-significant-digit buckets + one wave ranking each bucket; see sort.hip
@@ -229,7 +232,7 @@ void launch_dbscan_iv_sorted(hipStream_t s, const uint32_t *start, const uint32_
 // many small sets (caller order, at most DBSCAN_IV_SMALL_MAX points each: larger segments are skipped) in one launch, one workgroup per set
 constexpr uint32_t DBSCAN_IV_SMALL_MAX = 2048;
 void launch_dbscan_iv_small_batched(hipStream_t s, const uint32_t *start, const uint32_t *end, const uint64_t *seg_off, uint64_t n_seg, double eps,
-                                    int min_pts, int32_t *labels);
+                                    int min_pts, int32_t *labels, bool all_pairs /* the kernel that tests every pair instead of the start-ordered one: same labels */);
 // splitorder.hip — the node order of the reference's per-chromosome qname hash map, all contigs of a batch per launch
 constexpr uint32_t SO_MAX_CONTIGS = 32;
 struct SplitOrderTab {                       // passed to the kernels by value
@@ -265,7 +268,7 @@ struct SplitSmallHost {
 };
 void launch_so_small_epochs(hipStream_t s, const SplitSmallHost &h, const uint64_t *node_hash, uint32_t *list);
 // the last epochs for the survivors only (splitorder.hip): level j = the contig's last epoch minus j
-constexpr uint32_t SO_TAIL_MAX = 3;
+constexpr uint32_t SO_TAIL_MAX = CSV_TAIL_MAX;
 struct SplitTailHost {
     uint32_t A = 0, D = 0;
     int      wv = 0, wa = 0;

@@ -213,20 +213,16 @@ static int check_reads_dev(csv_ctx *ctx, const csv_reads *r)
     return CSV_OK;
 }
 
-// The waits of the per-chromosome pipeline last a fraction of a millisecond: polling for up to a millisecond before blocking
+// The waits of the per-chromosome pipeline last a fraction of a millisecond: polling for up to 100 us before blocking
 // saves the tens of microseconds a blocked thread takes to be woken, during which the device has nothing queued.
-static std::chrono::microseconds spin_limit()
-{
-    static const int us = [] { const char *e = getenv("CSV_SPIN_US"); return e && *e ? atoi(e) : 100; }();
-    return std::chrono::microseconds(us);
-}
+constexpr std::chrono::microseconds kSpinLimit(100);
 static hipError_t wait_stream(hipStream_t s)
 {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
         const hipError_t e = hipStreamQuery(s);
         if (e != hipErrorNotReady) return e;
-        if (std::chrono::steady_clock::now() - t0 > spin_limit()) return hipStreamSynchronize(s);
+        if (std::chrono::steady_clock::now() - t0 > kSpinLimit) return hipStreamSynchronize(s);
     }
 }
 static hipError_t wait_event(hipEvent_t ev)
@@ -235,9 +231,17 @@ static hipError_t wait_event(hipEvent_t ev)
     for (;;) {
         const hipError_t e = hipEventQuery(ev);
         if (e != hipErrorNotReady) return e;
-        if (std::chrono::steady_clock::now() - t0 > spin_limit()) return hipEventSynchronize(ev);
+        if (std::chrono::steady_clock::now() - t0 > kSpinLimit) return hipEventSynchronize(ev);
     }
 }
+
+// The scan form of a shard created, or a host-pointer call made, on this context: the forced one (csv_tuning), behind scan_form_for's guard.
+static int scan_form(const csv_ctx *ctx, uint64_t n_reads, uint64_t n_cigar)
+{
+    const int by_rule = scan_form_for(n_reads, n_cigar);
+    return (ctx->tuning.scan_form == CSV_FORM_AUTO || n_cigar >= 0xffffffffull) ? by_rule : ctx->tuning.scan_form;
+}
+static bool onesweep(const csv_ctx *ctx) { return !ctx->tuning.sort_three_launch; }
 
 static int read_counters(csv_ctx *ctx, const ScanCounters *d_cnt, ScanCounters &h)
 {
@@ -305,7 +309,7 @@ static void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, u
     const KeyLayout kl = key_layout(depth_len, overflow != 0, with_type);
     const int type_pos = kl.type_pos, key_bits = kl.key_bits;
     launch_sig_make_keys(ctx->stream, sig_raw, n, 0, type_pos, w.k0, w.v0);
-    const int in_out = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, key_bits, w.tmp);
+    const int in_out = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, key_bits, w.tmp, onesweep(ctx));
     launch_sig_fix_ties_gather(ctx->stream, sig_raw, in_out ? w.k1 : w.k0, in_out ? w.v1 : w.v0, n, sig_sorted, start_out, end_out);
 }
 
@@ -338,7 +342,7 @@ static int depth_chain(csv_ctx *ctx, Arena &a, const csv_reads &d, const int32_t
         uint32_t *pos_g = (uint32_t *)arena_alloc(a, n * 4), *end_g = (uint32_t *)arena_alloc(a, n * 4);
         if (!sortws_carve(a, n, w) || !pos_g || !end_g) { ctx->err = "arena exhausted (depth/unsorted)"; return CSV_ENOMEM; }
         launch_iota_keys_i32(ctx->stream, d.pos, n, w.k0, w.v0);
-        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp);
+        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp, onesweep(ctx));
         const uint32_t *perm = io ? w.v1 : w.v0;
         launch_gather_u32(ctx->stream, (const uint32_t *)d.pos, perm, n, pos_g);
         launch_gather_u32(ctx->stream, (const uint32_t *)ref_end, perm, n, end_g);
@@ -381,7 +385,7 @@ static int dbscan_iv_chain(csv_ctx *ctx, Arena &a, const uint32_t *d_start, cons
     {
         TimerScope ts(ctx, CSV_K_SORT);
         launch_iota_keys_u32(ctx->stream, d_start, n, w.k0, w.v0);
-        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp);
+        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp, onesweep(ctx));
         perm = io ? w.v1 : w.v0;
         launch_gather_u32(ctx->stream, d_start, perm, n, s_s);
         launch_gather_u32(ctx->stream, d_end, perm, n, e_s);
@@ -425,9 +429,7 @@ static csv_ctx *create_ctx(int device_ordinal, void *stream, int low_priority)
     else {
         int least = 0, greatest = 0;
         if (low_priority) (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const char *pe = getenv("CSV_BG_PRIORITY");                    // experiments: "high" turns the background context into a foreground one
-        const int prio = (pe && pe[0] == 'h') ? greatest : least;
-        const hipError_t se = low_priority ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+        const hipError_t se = low_priority ? hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
         if (se != hipSuccess) { g_create_err = "hipStreamCreate failed"; delete ctx; return nullptr; }
         ctx->own_stream = true;
     }
@@ -460,6 +462,20 @@ int csvgpu_synchronize(csv_ctx *ctx)
 {
     if (!ctx) return CSV_EINVAL;
     CSV_HIP(ctx, wait_stream(ctx->stream));
+    return CSV_OK;
+}
+
+int csvgpu_set_tuning(csv_ctx *ctx, const csv_tuning *t)
+{
+    if (!ctx) return CSV_EINVAL;
+    if (ctx->job_pin_busy || ctx->split_state) { ctx->err = "set_tuning: a job or a split order is open on this context"; return CSV_EINVAL; }
+    const csv_tuning defaults = CSV_TUNING_DEFAULTS;
+    if (!t) t = &defaults;
+    if (t->scan_form < CSV_FORM_AUTO || t->scan_form > CSV_FORM_LANES) { ctx->err = "set_tuning: scan_form must be CSV_FORM_AUTO or one of the four forms"; return CSV_EINVAL; }
+    if (t->split_tail < CSV_TAIL_AUTO || t->split_tail > CSV_TAIL_MAX) { ctx->err = "set_tuning: split_tail must be CSV_TAIL_AUTO or 0..CSV_TAIL_MAX"; return CSV_EINVAL; }
+    for (int32_t flag : {t->sort_three_launch, t->dbscan_all_pairs, t->split_chain_only})
+        if (flag != 0 && flag != 1) { ctx->err = "set_tuning: sort_three_launch, dbscan_all_pairs and split_chain_only must be 0 or 1"; return CSV_EINVAL; }
+    ctx->tuning = *t;
     return CSV_OK;
 }
 
@@ -503,7 +519,7 @@ int csvgpu_cigar_scan(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, 
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, min_oplen, min_mapq, 1, sig_raw, cap, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt,
-                          scan_extras(dr.cnt, depth_len, false, nullptr), nullptr, scan_form_for(reads->n_reads, reads->n_cigar));
+                          scan_extras(dr.cnt, depth_len, false, nullptr), nullptr, scan_form(ctx, reads->n_reads, reads->n_cigar));
     }
     ScanCounters h;
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
@@ -533,7 +549,7 @@ int csvgpu_aln_intervals(csv_ctx *ctx, const csv_reads *reads, int32_t *ref_end,
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, 0, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
-                          scan_form_for(reads->n_reads, reads->n_cigar));
+                          scan_form(ctx, reads->n_reads, reads->n_cigar));
     }
     const uint64_t n = reads->n_reads;
     if (n) {
@@ -558,13 +574,13 @@ int csvgpu_depth(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, uint3
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
-                          scan_form_for(reads->n_reads, reads->n_cigar));
+                          scan_form(ctx, reads->n_reads, reads->n_cigar));
     }
     ScanCounters h;
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
     if ((rc = arena_reserve(ctx, ctx->work, depth_chain_bytes(reads->n_reads, depth_len)))) return rc;
     if ((rc = depth_chain(ctx, ctx->work, dr.d, dr.ref_end, dr.ckpt, h.unsorted != 0, depth_len, d_depth, dr.cnt, nullptr, 0, nullptr,
-                          scan_form_for(reads->n_reads, reads->n_cigar)))) return rc;
+                          scan_form(ctx, reads->n_reads, reads->n_cigar)))) return rc;
     if (depth && depth_len) CSV_HIP(ctx, hipMemcpyAsync(depth, d_depth, (size_t)depth_len * 4, hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
     if (sum) *sum = h.depth_sum;
@@ -642,7 +658,7 @@ int csvgpu_dbscan_iv_batch(csv_ctx *ctx, const uint32_t *start, const uint32_t *
     CSV_HIP(ctx, hipMemcpyAsync(doff, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, st));
     {
         TimerScope ts(ctx, CSV_K_DBSCAN);
-        launch_dbscan_iv_small_batched(st, ds, de, doff, n_seg, eps, min_pts, dl);
+        launch_dbscan_iv_small_batched(st, ds, de, doff, n_seg, eps, min_pts, dl, ctx->tuning.dbscan_all_pairs != 0);
     }
     if (max_len > DBSCAN_IV_SMALL_MAX) {                     // the few sets that do not fit a workgroup's LDS: windowed path, one at a time
         CSV_HIP(ctx, wait_stream(st));                       // (that path reads its sortedness flag back through the same page-locked block)
@@ -693,7 +709,7 @@ int csvgpu_dbscan_1d_dev(csv_ctx *ctx, const int32_t *d_pts, const uint64_t *d_s
         if (n > max_seg_len) { ctx->err = "dbscan1d: max_seg_len smaller than a segment"; return CSV_EINVAL; }
         TimerScope ts(ctx, CSV_K_DBSCAN1D);
         launch_iota_keys_i32(ctx->stream, d_pts + off[s], n, w.k0, w.v0);
-        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp);
+        const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp, onesweep(ctx));
         const uint32_t *perm = io ? w.v1 : w.v0;
         launch_gather_u32(ctx->stream, (const uint32_t *)(d_pts + off[s]), perm, n, ks);   // points in sorted order
         launch_dbscan_1d_big(ctx->stream, (const int32_t *)ks, perm, n, eps, min_pts, d_labels + off[s], tmp);
@@ -873,7 +889,7 @@ static csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh)
     sh->tile_range = (uint64_t *)((char *)sh->counters + align_up(kCntBytes, 256));
     ok &= hipMalloc((void **)&sh->ckpt, ckpt_bytes(sh->d.n_cigar)) == hipSuccess;
     ok &= hipMalloc(&sh->depth_items, depth_items_bytes(sh->depth_len) + 16) == hipSuccess;
-    sh->form = scan_form_for(sh->d.n_reads, sh->d.n_cigar);
+    sh->form = scan_form(ctx, sh->d.n_reads, sh->d.n_cigar);
     ok &= hipMalloc((void **)&sh->scan_split, scan_split_bytes(ctx->n_cu, sh->d.n_reads, sh->form) + 16) == hipSuccess;
     sh->sig_cap = std::max<uint64_t>(1u << 18, n * 2);
     ok &= hipMalloc((void **)&sh->sig_raw, sh->sig_cap * sizeof(csv_sig)) == hipSuccess;
@@ -1220,8 +1236,7 @@ static int split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
     {
         const uint64_t ratio = n_supp_hint > 0 ? n_nodes / (uint64_t)n_supp_hint : (n_nodes >= 4096 ? 64 : 1);
         while (D < (int)SO_TAIL_MAX && (ratio >> (2 * (D + 1))) >= 1) D++;
-        const char *e = getenv("CSV_SPLIT_TAIL");
-        if (e && *e) D = std::min<int>(std::max(atoi(e), 0), (int)SO_TAIL_MAX);
+        if (ctx->tuning.split_tail != CSV_TAIL_AUTO) D = ctx->tuning.split_tail;
     }
     SplitTailHost &th = st->th;
     th.A = (uint32_t)n_contigs; th.wv = std::max(1, bits_of(n_nodes)); th.wa = std::max(1, bits_of((uint64_t)n_contigs - 1));
@@ -1284,8 +1299,7 @@ static int split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
     {
         SplitSmallHost sm;
         while (n_small < first_node.size() && n_small < SO_SMALL_EPOCHS && buckets[n_small] <= SO_SMALL_B) n_small++;
-        const char *e = getenv("CSV_SPLIT_SMALL");
-        if (e && *e && atoi(e) == 0) n_small = 0;                               // (A/B and tests: every epoch through the chain's sorts)
+        if (ctx->tuning.split_chain_only) n_small = 0;                          // (A/B and tests: every epoch through the chain's sorts)
         sm.A = (uint32_t)n_contigs; sm.n_epochs = (uint32_t)n_small;
         bool any = false;
         for (int c = 0; c <= n_contigs; c++) sm.nbase[c] = th.nbase[c];
@@ -1320,14 +1334,14 @@ static int split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
         CSV_HIP(ctx, hipMemsetAsync(minT, 0xff, (size_t)e.A * B * 4, s));
         launch_so_mint(s, e, M, B, node_hash, list, minT);
         launch_so_keys(s, e, M, B, wbits, node_hash, list, minT, w.k0, w.v0);
-        const int io = launch_radix_sort_u64(s, w.k0, w.v0, w.k1, w.v1, M, key_bits, w.tmp);
+        const int io = launch_radix_sort_u64(s, w.k0, w.v0, w.k1, w.v1, M, key_bits, w.tmp, onesweep(ctx));
         launch_so_setlist(s, e, M, io ? w.v1 : w.v0, list);
     }
     if (D > 0) launch_st_inverse(s, th, (uint32_t)n_nodes, D - 1, list, st->prevrank);
     if (self) {
         // everything else too: the hashes sorted (64-bit keys, the values are not used), the survivors-only levels with the set sizes read on
         // the device, the survivors copied to the page-locked block — _finish only waits
-        const int io = launch_radix_sort_u64(s, st->d_supp, w.v0, w.k1, w.v1, n_supp_self, 64, w.tmp);
+        const int io = launch_radix_sort_u64(s, st->d_supp, w.v0, w.k1, w.v1, n_supp_self, 64, w.tmp, onesweep(ctx));
         if (io != 0) { ctx->err = "split_order: unexpected sort parity"; return CSV_EHIP; }
         if ((rc = split_order_tail(ctx, st.get(), st->d_supp, n_supp_self, true))) return rc;
         st->self_bound = std::min<uint64_t>(n_supp_self, n_nodes);
@@ -1385,7 +1399,7 @@ static int split_order_tail(csv_ctx *ctx, csv_split_state *st, const uint64_t *d
         launch_st_mint(s, th, j, st->set[j + 1], n, n_dev, st->node_hash, st->prevrank, st->minT);
         launch_st_keys(s, th, j, st->set[j + 1], n, n_dev, st->node_hash, st->prevrank, st->minT, w.k0, w.v0);
         const int io = devn ? launch_radix_sort_u64_devn(s, w.k0, w.v0, w.k1, w.v1, n, n_dev, key_bits, w.tmp)
-                            : launch_radix_sort_u64(s, w.k0, w.v0, w.k1, w.v1, n, key_bits, w.tmp);
+                            : launch_radix_sort_u64(s, w.k0, w.v0, w.k1, w.v1, n, key_bits, w.tmp, onesweep(ctx));
         if (io < 0) { ctx->err = "split_order: set too large for the queued sort"; return CSV_EINVAL; }
         const uint32_t *sorted = (devn || n > 1) ? (io ? w.v1 : w.v0) : w.v0;
         if (j > 0) launch_st_rank(s, sorted, n, n_dev, st->prevrank);

@@ -644,13 +644,11 @@ __global__ __launch_bounds__(IVS_THREADS) void dbscan_iv_small_sorted_kernel(con
 }
 
 void launch_dbscan_iv_small_batched(hipStream_t s, const uint32_t *start, const uint32_t *end, const uint64_t *seg_off, uint64_t n_seg, double eps,
-                                    int min_pts, int32_t *labels)
+                                    int min_pts, int32_t *labels, bool all_pairs)
 {
     if (n_seg == 0) return;
     const unsigned grid = (unsigned)std::min<uint64_t>(n_seg, 8192);
-    const char *be = getenv("CSV_DBSCAN_SMALL_BRUTE");                         // (A/B, tests: all pairs)
-    const bool brute = be && *be && *be != '0';
-    if (brute) hipLaunchKernelGGL(dbscan_iv_small_kernel, dim3(grid), dim3(IVS_THREADS), 0, s, start, end, seg_off, n_seg, eps, min_pts, labels);
+    if (all_pairs) hipLaunchKernelGGL(dbscan_iv_small_kernel, dim3(grid), dim3(IVS_THREADS), 0, s, start, end, seg_off, n_seg, eps, min_pts, labels);
     else hipLaunchKernelGGL(dbscan_iv_small_sorted_kernel, dim3(grid), dim3(IVS_THREADS), 0, s, start, end, seg_off, n_seg, eps, min_pts, labels);
 }
 

@@ -314,9 +314,7 @@ extern "C" void csvgpu_debug_depth_phase(unsigned long long *out, int reset)
 // every chunk load is one unconditional 16-byte load per lane.
 // GL: lanes that walk one item together — 64 (a wave per item, the stream of 1 KiB chunks below: long reads) or 16 / 8 (short reads:
 // a (tile, read) item of a HiFi shard is 40 words, and a whole wave per item left 5 lanes in 6 idle; 64-word windows, see scan.hip).
-// WPL (wave-per-item walk only): CIGAR words per lane and chunk visit — 4 (1 KiB chunks, six in flight) or 8 (2 KiB chunks, three in flight: the
-// per-visit bookkeeping, the wave scan and the span update once per 512 words instead of once per 256).
-template <bool PADDED, int GL, int WPL = 4>
+template <bool PADDED, int GL>
 __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
     uint64_t n_reads, uint64_t n_cigar, const int32_t *__restrict__ pos, const uint16_t *__restrict__ flag,
     const uint64_t *__restrict__ cigar_off, const uint32_t *__restrict__ cigar, int vec_ok, int dvec_ok,
@@ -463,8 +461,9 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                 for (int k = 0; k < GW; k++) ww[k] = wn[k];
             }
         } else if (n_items) {
-            constexpr int NS = WPL == 8 ? 3 : DEPTH_PF + 1;                            // ring slots (chunks in flight)
-            constexpr uint32_t CW = (uint32_t)WPL * WAVE;                            // words per chunk
+            constexpr int WPL = 4;                                                   // CIGAR words per lane and chunk visit (one 16-byte load)
+            constexpr int NS = DEPTH_PF + 1;                                         // ring slots (chunks in flight)
+            constexpr uint32_t CW = (uint32_t)WPL * WAVE;                            // words per chunk (1 KiB)
             uint32_t w[NS][WPL];
             uint32_t m_o0[NS], m_nrem[NS], m_c0rel[NS];
             int32_t m_start[NS];
@@ -484,7 +483,7 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                         f_nrem = uniform32(d.y);
                         f_start = (int32_t)uniform32(d.w);
                         const uint32_t pk = uniform32(d.z);
-                        f_n = WPL == 4 ? pk >> 6 : (f_nrem + CW - 1) / CW; f_c0rel = pk & 63u; f_c = 0;
+                        f_n = pk >> 6; f_c0rel = pk & 63u; f_c = 0;
                         if (lane == 0) nxt_v = atomicAdd(&next_item, 1u);
                     } else f_done = true;
                 }
@@ -499,24 +498,15 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                     // lanes whose words all lie behind the item's last word repeat the last lane that has one: no cache line is fetched
                     // for them, and the load stays unconditional (the consumer masks those words anyway)
                     const uint32_t lw = min((uint32_t)lane * WPL, (f_nrem - 1u - f_off) & ~(uint32_t)(WPL - 1));
-#pragma unroll
-                    for (int q = 0; q < WPL; q += 4) {
-                        const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + lw + q);
-                        w[j][q] = v.x; w[j][q + 1] = v.y; w[j][q + 2] = v.z; w[j][q + 3] = v.w;
-                    }
+                    const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + lw);
+                    w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
                 } else if (vec_ok && f_addr + CW <= n_cigar) {
-#pragma unroll
-                    for (int q = 0; q < WPL; q += 4) {
-                        const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + (uint64_t)lane * WPL + q);
-                        w[j][q] = v.x; w[j][q + 1] = v.y; w[j][q + 2] = v.z; w[j][q + 3] = v.w;
-                    }
+                    const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + (uint64_t)lane * WPL);
+                    w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
                 } else {
-#pragma unroll
-                    for (int q = 0; q < WPL; q += 4) {
-                        uint32_t t4[4];
-                        depth_load4(cigar, n_cigar, vec_ok, f_addr + (uint64_t)lane * WPL + q, t4);
-                        w[j][q] = t4[0]; w[j][q + 1] = t4[1]; w[j][q + 2] = t4[2]; w[j][q + 3] = t4[3];
-                    }
+                    uint32_t t4[4];
+                    depth_load4(cigar, n_cigar, vec_ok, f_addr + (uint64_t)lane * WPL, t4);
+                    w[j][0] = t4[0]; w[j][1] = t4[1]; w[j][2] = t4[2]; w[j][3] = t4[3];
                 }
             };
 #pragma unroll
@@ -711,13 +701,7 @@ void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, 
                        vec_ok, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it)
     if (form == SCAN_FORM_ROWS16 || form == SCAN_FORM_LANES) { if (padded) CSV_TILE_LAUNCH(true, 16); else CSV_TILE_LAUNCH(false, 16); }
     else if (form == SCAN_FORM_ROWS8) { if (padded) CSV_TILE_LAUNCH(true, 8); else CSV_TILE_LAUNCH(false, 8); }
-    else {
-        static const int wpl = [] { const char *e = getenv("CSV_DEPTH_WPL"); return e && atoi(e) == 8 ? 8 : 4; }();
-        if (wpl == 8 && cigar_pad_words >= 8 * WAVE) {
-            hipLaunchKernelGGL((depth_tile_kernel<true, WAVE, 8>), dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off, d.cigar,
-                               vec_ok, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it);
-        } else if (padded) CSV_TILE_LAUNCH(true, WAVE); else CSV_TILE_LAUNCH(false, WAVE);
-    }
+    else { if (padded) CSV_TILE_LAUNCH(true, WAVE); else CSV_TILE_LAUNCH(false, WAVE); }
 #undef CSV_TILE_LAUNCH
 }
 

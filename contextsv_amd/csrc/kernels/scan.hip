@@ -997,13 +997,10 @@ __global__ __launch_bounds__(256) void scan_split_kernel(const uint64_t *__restr
 }
 
 // Which form of the scan (and of the depth pass's walk) suits a shard: reads of a few dozen ops (HiFi) are walked by groups of lanes,
-// several reads per wave; long reads (ONT: ~1 200 ops) by a wave each. CSV_SCAN_FORM = 0 / 1 / 2 / 3 overrides (experiments, tests).
+// several reads per wave; long reads (ONT: ~1 200 ops) by a wave each.
 int scan_form_for(uint64_t n_reads, uint64_t n_cigar)
 {
-    const char *e = getenv("CSV_SCAN_FORM");
-    const int forced = e && *e ? atoi(e) : -1;
-    if (n_cigar >= 0xffffffffull) return SCAN_FORM_WAVE;          // the short-read form indexes words in 32 bits
-    if (forced >= 0 && forced <= 3) return forced;
+    if (n_cigar >= 0xffffffffull) return SCAN_FORM_WAVE;          // the short-read forms index words in 32 bits
     return (n_reads && n_cigar / n_reads < 192) ? SCAN_FORM_ROWS16 : SCAN_FORM_WAVE;
 }
 

@@ -360,13 +360,6 @@ static uint64_t os_wg_tiles_max(uint64_t n)       // workgroup tiles of the larg
 }
 static size_t os_tmp_bytes(uint64_t n) { return 256 + align_up((size_t)OS_MAX_PASSES * RS_BINS * 4, 256) + (size_t)OS_MAX_PASSES * os_wg_tiles_max(n) * RS_BINS * 4; }
 
-static bool onesweep_on()
-{
-    const char *e = getenv("CSV_SORT_ONESWEEP");                                  // "0": the three-launch passes (A/B, tests)
-    return !(e && *e == '0');
-}
-
-
 // [0, 256): tile counters (one per pass) and the error flag; digit totals of every pass; status words of every pass
 static void launch_onesweep(hipStream_t s, uint64_t *ki, uint32_t *vi, uint64_t *ko, uint32_t *vo, uint64_t n, const uint32_t *n_dev, int passes, unsigned grid,
                             uint32_t n_tiles, int rounds, void *tmp)
@@ -408,7 +401,7 @@ size_t radix_sort_tmp_bytes(uint64_t n)
 }
 
 int launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out,
-                          uint64_t n, int key_bits, void *tmp)
+                          uint64_t n, int key_bits, void *tmp, bool onesweep)
 {
     if (n <= 1 || key_bits <= 0) return 0;
     const int rounds = rs_rounds_for(n);
@@ -421,7 +414,7 @@ int launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, u
     const int passes = (key_bits + RS_BITS - 1) / RS_BITS;
     uint64_t *ki = keys_in, *ko = keys_out;
     uint32_t *vi = vals_in, *vo = vals_out;
-    if (onesweep_on() && n < (1ull << 30) && passes <= OS_MAX_PASSES && grid + 1 <= os_wg_tiles_max(n)) {
+    if (onesweep && n < (1ull << 30) && passes <= OS_MAX_PASSES && grid + 1 <= os_wg_tiles_max(n)) {
         launch_onesweep(s, ki, vi, ko, vo, n, nullptr, passes, grid, n_tiles, rounds, tmp);
         return (passes & 1) ? 1 : 0;
     }

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CSVGPU_ABI_VERSION 3   /* 3: csvgpu_split_order_begin_self; 2: CSV_K_SPLIT_ORDER, csvgpu_split_order_begin / _finish, the job / gate / batch entry points; the test hook left the product library */
+#define CSVGPU_ABI_VERSION 4   /* 4: csv_tuning, csvgpu_set_tuning (the library reads no environment variable); 3: csvgpu_split_order_begin_self; 2: CSV_K_SPLIT_ORDER, csvgpu_split_order_begin / _finish, the job / gate / batch entry points; the test hook left the product library */
 
 typedef struct csv_ctx csv_ctx;
 
@@ -126,6 +126,31 @@ int         csvgpu_synchronize(csv_ctx *ctx);
 int         csvgpu_timing_enable(csv_ctx *ctx, int on);
 int         csvgpu_timing_reset(csv_ctx *ctx);
 int         csvgpu_timing_get(csv_ctx *ctx, int kernel_id, double *total_ms, uint64_t *launches);
+
+/* Which of several kernels that compute the SAME result a context launches (tests and A/B measurements: no value changes an output).
+ * A new context holds CSV_TUNING_DEFAULTS. */
+enum { CSV_FORM_AUTO = -1, CSV_FORM_WAVE = 0, CSV_FORM_ROWS16 = 1, CSV_FORM_ROWS8 = 2, CSV_FORM_LANES = 3 };
+#define CSV_TAIL_AUTO (-1)
+#define CSV_TAIL_MAX  3
+typedef struct csv_tuning {
+    int32_t scan_form;          /* how the CIGAR scan and the depth walk take a read: CSV_FORM_AUTO = from the shard's mean CIGAR words per read
+                                 * (a wave per long read, 16 lanes per short one), or one of the four forms forced. A shard of 2^32 - 1 words or more is
+                                 * always walked by waves. */
+    int32_t split_tail;         /* split order: how many of every contig's last epochs are ordered for the survivors only, 0 (the full chain of sorts)
+                                 * .. CSV_TAIL_MAX; CSV_TAIL_AUTO = from the nodes per supplementary record. Orders too large for the
+                                 * survivors' keys take the full chain whatever is set. */
+    int32_t sort_three_launch;  /* radix sorts: 0 = onesweep passes (one launch per pass) where the sort's size allows them, 1 = histogram, scan and scatter
+                                 * launches per pass. Sorts whose key count is still on the device when they are queued (csvgpu_split_order_begin_self)
+                                 * are onesweep passes either way. */
+    int32_t dbscan_all_pairs;   /* interval DBSCAN of small sets (csvgpu_dbscan_iv_batch): 0 = the kernel that meets the pairs in start order, 1 = all pairs */
+    int32_t split_chain_only;   /* split order: 0 = the first epochs in one launch (nodes and buckets in LDS), 1 = through the chain's sorts like the rest */
+} csv_tuning;
+#define CSV_TUNING_DEFAULTS { CSV_FORM_AUTO, CSV_TAIL_AUTO, 0, 0, 0 }
+/* Replace the context's record (t == NULL: the defaults); it applies to everything started on this context afterwards. CSV_EINVAL, the record
+ * unchanged: a field out of range, a job open on the context (csvgpu_chr_job_begin without its _end / _abort) or a split order between _begin
+ * and _finish. A resident shard keeps the scan form of the context that created it (csvgpu_shard_upload / _wrap_dev), on whichever context it is
+ * run later; the host-pointer entry points take the form of the context they are called on. */
+int         csvgpu_set_tuning(csv_ctx *ctx, const csv_tuning *t);
 
 /* ------------------------------------------------------------------------------------------ */
 /* host-pointer entry points (the seams of SURVEY.md §8b)                                       */

@@ -24,14 +24,18 @@ def test_header_symbols_exported():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/csvgpu.h but not exported"
     assert sorted(_lib.ABI) == names, "ctypes table and header disagree"
-    assert lib.csvgpu_abi_version() == _lib.ABI_VERSION == 3
+    assert lib.csvgpu_abi_version() == _lib.ABI_VERSION == 4
     assert not hasattr(lib, "csvgpu_test_fail_next_alloc"), "the allocation-failure hook must not be in the product library"
+    assert "csvgpu_set_tuning" in names and _lib.ABI["csvgpu_set_tuning"][1][1]._type_ is _lib.csv_tuning
 
 
 def test_struct_layouts_match_header():
     from contextsv_amd import _lib
     assert C.sizeof(_lib.csv_reads) == 64 and C.sizeof(_lib.csv_hmm) == 8 * (36 + 6 + 6 + 6 + 1 + 5 + 5 + 1)
     assert _lib.SIG_DTYPE.itemsize == 16 and C.sizeof(_lib.csv_chr_result) == 8 * 4 + 4 + 4 + 8 + 8 * 8
+    text = open(os.path.join(ROOT, "include", "csvgpu.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct csv_tuning \{(.*?)\} csv_tuning;", text, flags=re.S).group(1), flags=re.S)
+    assert re.findall(r"int32_t\s+(\w+);", body) == [f for f, _ in _lib.csv_tuning._fields_] and C.sizeof(_lib.csv_tuning) == 4 * 5
 
 
 def test_no_cpu_fallback_without_device():
@@ -51,6 +55,21 @@ def test_no_cpu_fallback_without_device():
 RETIRED_HOST_SWITCHES = ("CSV_NO_EARLY_CN", "CSV_EARLY_CN_WAIT_ALL", "CSV_EARLY_SMALL_BATCHES", "CSV_NO_SPLIT_BESIDE_PASS", "CSV_SPLIT_NO_SELF",
                          "CSV_TEST_PREPARE_DELAY_MS", "CSV_NO_EARLY_SPLIT", "CSV_NO_LATE_JOIN", "CSV_EARLY_ONE_BATCH", "CSV_SPLIT_ONE_CALL",
                          "CSV_JOBS_AHEAD")
+
+
+# switches of the device library that csv_tuning (csvgpu_set_tuning) replaced or that were retired: it reads no environment variable
+RETIRED_DEVICE_SWITCHES = ("CSV_SCAN_FORM", "CSV_SORT_ONESWEEP", "CSV_DBSCAN_SMALL_BRUTE", "CSV_SPLIT_TAIL", "CSV_SPLIT_SMALL", "CSV_DEPTH_WPL",
+                           "CSV_SPIN_US", "CSV_BG_PRIORITY")
+
+
+def test_device_library_reads_no_environment():
+    csrc = os.path.join(ROOT, "contextsv_amd", "csrc")
+    files = [os.path.join(csrc, f) for f in ("csvgpu.hip", "common.hpp", "devutil.hpp")]
+    files += [os.path.join(csrc, "kernels", f) for f in sorted(os.listdir(os.path.join(csrc, "kernels")))]
+    assert len(files) >= 10
+    for f in files:
+        txt = open(f, errors="ignore").read()
+        assert "getenv" not in txt and not [s for s in RETIRED_DEVICE_SWITCHES if s in txt], f
 
 
 def test_product_package_does_not_touch_the_oracle():

@@ -1,14 +1,13 @@
 """The forms of the scan and of the depth walk (a wave per read; groups of 16 or 8 lanes per read; a lane per read: scan.hip, depth.hip) on the same
 shards, each against the oracle: signatures, alignment intervals, depth map, sums. The form is normally chosen per shard from the mean
-CIGAR words per read; CSV_SCAN_FORM forces it (read when a shard is created / a host-pointer entry point is called). Both instances of
+CIGAR words per read; csv_tuning::scan_form forces it (taken when a shard is created / a host-pointer entry point is called). Both instances of
 every kernel are covered: host-pointer entry points stage an UNPADDED copy (bounds-checked loads), resident shards are padded."""
-import os
-
 import numpy as np
 import pytest
 
 import synth_small as ss
 from contextsv_amd import Reads, host
+from contextsv_amd._lib import ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +15,10 @@ M, I, D, N, S, H, P, EQ, X = range(9)
 
 
 @pytest.fixture(params=[0, 1, 2, 3], ids=["wave", "rows16", "rows8", "lanes"])
-def form(request):
-    old = os.environ.get("CSV_SCAN_FORM")
-    os.environ["CSV_SCAN_FORM"] = str(request.param)
+def form(request, ctx):
+    ctx.set_tuning(scan_form=request.param)
     yield request.param
-    if old is None:
-        del os.environ["CSV_SCAN_FORM"]
-    else:
-        os.environ["CSV_SCAN_FORM"] = old
+    ctx.set_tuning()
 
 
 def _check(ctx, oracle, reads, depth_len, min_oplen=50, min_mapq=20):
@@ -109,10 +104,75 @@ def test_forms_on_generated_shards(ctx, oracle, form, tech, chr_len, depth):
 
 def test_form_is_chosen_from_the_read_length(ctx, oracle):
     """Default choice (no override): a HiFi-shaped shard and an ONT-shaped shard both equal the oracle (whatever form each took)."""
-    os.environ.pop("CSV_SCAN_FORM", None)
+    ctx.set_tuning()
     for tech, depth in ((1, 40.0), (0, 15.0)):
         syn = host.SynthShard(seed=0x5EED0000 + 277 + tech, chr_len=800_000, depth=depth, tech=tech, threads=4)
         try:
             _check(ctx, oracle, syn.reads, syn.depth_len)
         finally:
             syn.free()
+
+
+def test_tuning_is_per_context_and_checked(ctx):
+    """csvgpu_set_tuning: a field out of range, and a call while a job or a split order is open on the context, are CSV_EINVAL and leave the
+    record and the context as they were; two contexts of one process with different forced forms give the same signatures, intervals and
+    depth on the same reads (a shard takes the form of the context that uploads it)."""
+    import ctypes as C
+
+    from contextsv_amd import Context, CsvError, _lib
+    reads, depth_len = ss.random_shard(11, n_reads=600, mean_ops=25, chr_len=50_000, big_frac=0.2)
+    exp = ctx.cigar_scan(reads, depth_len)
+    assert len(exp) > 0
+    for bad in (dict(scan_form=4), dict(scan_form=-2), dict(split_tail=4), dict(split_tail=-2)):
+        with pytest.raises(CsvError) as ei:
+            ctx.set_tuning(**bad)
+        assert ei.value.status == _lib.CSV_EINVAL, bad
+    for field in ("sort_three_launch", "dbscan_all_pairs", "split_chain_only"):
+        t = _lib.csv_tuning(-1, -1, 0, 0, 0)
+        setattr(t, field, 2)
+        assert ctx.lib.csvgpu_set_tuning(ctx.h, C.byref(t)) == _lib.CSV_EINVAL, field
+    sh = ctx.upload(reads, depth_len)
+    try:
+        job = ctx.lib.csvgpu_chr_job_begin(ctx.h, sh.h, 50, 20, 0.1)
+        assert job
+        try:
+            with pytest.raises(CsvError) as ei:
+                ctx.set_tuning(scan_form=3)
+            assert ei.value.status == _lib.CSV_EINVAL
+        finally:
+            assert ctx.lib.csvgpu_chr_job_abort(ctx.h, job) == 0
+        sh.set_qname_hash(np.arange(1, reads.n_reads + 1, dtype=np.uint64))
+        hs = (C.c_void_p * 1)(sh.h)
+        assert ctx.lib.csvgpu_split_order_begin(ctx.h, 1, hs, 20) == 0
+        try:
+            assert ctx.lib.csvgpu_set_tuning(ctx.h, None) == _lib.CSV_EINVAL
+        finally:
+            out, off = np.zeros(reads.n_reads, np.uint32), np.zeros(2, np.uint64)
+            assert ctx.lib.csvgpu_split_order_finish(ctx.h, None, 0, ptr(out), len(out), ptr(off)) == 0
+        ctx.set_tuning()                                    # nothing open any more: accepted
+        got = ctx.cigar_scan(reads, depth_len)              # the refused calls changed nothing: still usable, still the default form's answer
+        assert np.array_equal(got, exp)
+    finally:
+        sh.free()
+    others = [Context(0) for _ in range(2)]
+    try:
+        others[0].set_tuning(scan_form=0)
+        others[1].set_tuning(scan_form=3, sort_three_launch=True)
+        for c in others:
+            assert np.array_equal(c.cigar_scan(reads, depth_len), exp)
+            for g, e in zip(c.aln_intervals(reads), ctx.aln_intervals(reads)):
+                assert np.array_equal(g, e)
+            d, s, nz = c.depth(reads, depth_len)
+            d0, s0, nz0 = ctx.depth(reads, depth_len)
+            assert np.array_equal(d, d0) and (s, nz) == (s0, nz0)
+            shc = c.upload(reads, depth_len)
+            try:
+                res = shc.pipeline(eps=0.1, min_pts_pct=0.1)
+                out = shc.fetch(res)
+                kind = exp["qpos_kind"] & 3
+                assert np.array_equal(out["sig_del"], exp[kind == 1]) and np.array_equal(out["sig_ins"], exp[kind != 1])
+            finally:
+                shc.free()
+    finally:
+        for c in others:
+            c.close()

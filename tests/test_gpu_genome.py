@@ -120,7 +120,6 @@ def test_early_batches_inside_the_pass_give_the_same_calls(ctx):
     contigs through three lanes: the default run (batch sizes depend on timing), batches of three down to the last contig
     (early_batches="every3"), one batch of everything ("all"), no early batch at all ("none"), no split overlap, and the run without lanes
     must give the same records."""
-    import os
     hmm = make_hmm(**WGS_HMM)
     host.set_context(ctx)
     g = _many_small(ctx)
@@ -131,26 +130,29 @@ def test_early_batches_inside_the_pass_give_the_same_calls(ctx):
             c.set_gate(gate)
         ref, ref_tid, st0, _ = g.run(ctx, hmm)                                     # no lanes: nothing early
         assert len(ref) > 20 and st0.n_cigar_cn_regions > 0 and st0.n_split_calls > 0
-        for env, kw in (({}, {}), ({}, {"early_batches": "every3"}), ({}, {"early_batches": "all"}), ({}, {"early_batches": "none"}),
-                        ({}, {"overlap_split": False}),
-                        # the split order in two calls with the caller's supplementary hashes instead of queued whole (csvgpu_split_order_begin_self);
-                        # the three-launch radix passes instead of the onesweep ones (libcsvgpu's own switch)
-                        ({}, {"split_order_self": False}), ({"CSV_SORT_ONESWEEP": "0"}, {}),
-                        # the split-read first half made to outlast the CIGAR pass: joined in front of the split chain
-                        ({}, {"prepare_delay_ms": 40}),
-                        # without / with the split chain of all contigs beside the pass (what a run that takes no early batch does by default)
-                        ({}, {"split_beside_pass": False}), ({}, {"split_beside_pass": False, "prepare_delay_ms": 40}),
-                        ({}, {"early_batches": "none", "split_beside_pass": False})):
-            os.environ.update(env)
-            try:
-                for _ in range(2):
-                    got, tid, st, _ = g.run(ctx, hmm, lanes=lanes, **kw)
-                    assert np.array_equal(tid, ref_tid), (env, kw)
-                    _same(got, ref)
-                    assert st.n_cigar_cn_regions == st0.n_cigar_cn_regions and st.n_split_calls == st0.n_split_calls
-            finally:
-                for k in env:
-                    del os.environ[k]
+        def check(**kw):
+            for _ in range(2):
+                got, tid, st, _ = g.run(ctx, hmm, lanes=lanes, **kw)
+                assert np.array_equal(tid, ref_tid), kw
+                _same(got, ref)
+                assert st.n_cigar_cn_regions == st0.n_cigar_cn_regions and st.n_split_calls == st0.n_split_calls
+
+        for kw in ({}, {"early_batches": "every3"}, {"early_batches": "all"}, {"early_batches": "none"}, {"overlap_split": False},
+                   # the split order in two calls with the caller's supplementary hashes instead of queued whole (csvgpu_split_order_begin_self)
+                   {"split_order_self": False},
+                   # the split-read first half made to outlast the CIGAR pass: joined in front of the split chain
+                   {"prepare_delay_ms": 40},
+                   # without / with the split chain of all contigs beside the pass (what a run that takes no early batch does by default)
+                   {"split_beside_pass": False}, {"split_beside_pass": False, "prepare_delay_ms": 40},
+                   {"early_batches": "none", "split_beside_pass": False}):
+            check(**kw)
+        # the three-launch radix passes instead of the onesweep ones (csv_tuning, on the caller's context and on every lane)
+        for c in [ctx] + lanes:
+            c.set_tuning(sort_three_launch=True)
+        try:
+            check()
+        finally:
+            ctx.set_tuning()
     finally:
         for c in lanes:
             c.set_gate(None)

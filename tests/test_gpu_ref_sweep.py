@@ -50,10 +50,9 @@ def test_interval_dbscan_batch_against_reference(ctx, ref):
 
 
 def test_interval_dbscan_batch_sorted_equals_all_pairs(ctx):
-    """The small-set kernel meets every neighbour pair once in start order; CSV_DBSCAN_SMALL_BRUTE=1 selects the all-pairs kernel it replaced
+    """The small-set kernel meets every neighbour pair once in start order; csv_tuning::dbscan_all_pairs selects the all-pairs kernel it replaced
     (itself pinned against the reference above). Same labels on nested piles, duplicates, zero-length intervals, and on coordinates beyond
     2^31 (the predicate compares as int, like the reference's arithmetic: the start order has to be the signed one)."""
-    import os
     rng = np.random.default_rng(123)
     sets = []
     for it in range(60):
@@ -78,10 +77,10 @@ def test_interval_dbscan_batch_sorted_equals_all_pairs(ctx):
     S = np.concatenate([s for s, _ in sets]); E = np.concatenate([e for _, e in sets])
     for eps, min_pts in ((0.1, 2), (0.25, 4), (0.0, 1), (0.999, 2)):
         got = ctx.dbscan_iv_batch(S, E, off, eps, min_pts)
-        os.environ["CSV_DBSCAN_SMALL_BRUTE"] = "1"
+        ctx.set_tuning(dbscan_all_pairs=True)
         try:
             exp = ctx.dbscan_iv_batch(S, E, off, eps, min_pts)
         finally:
-            del os.environ["CSV_DBSCAN_SMALL_BRUTE"]
+            ctx.set_tuning()
         bad = np.flatnonzero(got != exp)
         assert len(bad) == 0, (eps, min_pts, int(np.searchsorted(off, bad[0], side="right") - 1), bad[:5])

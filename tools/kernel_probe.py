@@ -4,7 +4,7 @@ digest of everything the pair writes (signatures as a sorted set, ref_end / q_st
 the labels) — the A/B tool for kernel experiments: a changed kernel must print the same digest as the committed build
 (tools/probes/kernel_probe_digests.json; --record rewrites it).
 
-    python tools/kernel_probe.py [--contig 22|1] [--tech ont|hifi] [--depth 30] [--steps 20] [--record]
+    python tools/kernel_probe.py [--contig 22|1] [--tech ont|hifi] [--depth 30] [--steps 20] [--scan-form 0|1|2|3] [--record]
 """
 import argparse, hashlib, json, os, sys, time
 import numpy as np
@@ -21,6 +21,7 @@ def main():
     ap.add_argument("--depth", type=float, default=30.0)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--scan-form", type=int, default=None, help="force a form of the scan / depth walk (csv_tuning::scan_form); default: by read length")
     ap.add_argument("--record", action="store_true")
     args = ap.parse_args()
     import contextsv_amd as cs
@@ -31,6 +32,7 @@ def main():
     reads, depth_len = syn.reads, syn.depth_len
     n_reads, n_cigar = reads.n_reads, reads.n_cigar
     ctx = cs.Context(0)
+    ctx.set_tuning(scan_form=args.scan_form)
     sh = ctx.upload(reads, depth_len)
     ctx.synchronize()
     syn.free()
