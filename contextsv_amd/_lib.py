@@ -19,8 +19,8 @@ ABI_VERSION = 4          # include/csvgpu.h CSVGPU_ABI_VERSION
 CSV_OK, CSV_EINVAL, CSV_ENODEV, CSV_ENOMEM, CSV_EHIP, CSV_ECAPACITY = 0, -1, -2, -3, -4, -5
 STATUS_NAMES = {0: "CSV_OK", -1: "CSV_EINVAL", -2: "CSV_ENODEV", -3: "CSV_ENOMEM", -4: "CSV_EHIP", -5: "CSV_ECAPACITY"}
 
-K_CIGAR_SCAN, K_DEPTH, K_SORT, K_DBSCAN, K_DBSCAN1D, K_WINDOW, K_VITERBI, K_MISC, K_SPLIT_ORDER, K_COUNT = range(10)
-KERNEL_NAMES = ["cigar_scan", "depth", "sort", "dbscan", "dbscan1d", "window", "viterbi", "misc", "split_order"]
+K_CIGAR_SCAN, K_DEPTH, K_SORT, K_DBSCAN, K_DBSCAN1D, K_WINDOW, K_VITERBI, K_MISC, K_SPLIT_ORDER, K_SPLIT_GROUPS, K_COUNT = range(11)
+KERNEL_NAMES = ["cigar_scan", "depth", "sort", "dbscan", "dbscan1d", "window", "viterbi", "misc", "split_order", "split_groups"]
 
 SIG_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("read", "<u4"), ("qpos_kind", "<u4")])
 KIND_INS, KIND_DEL, KIND_CLIP = 0, 1, 2
@@ -98,6 +98,7 @@ ABI = {
     "csvgpu_split_order_begin": (C.c_int, [_P, C.c_int, _P, C.c_uint8]),
     "csvgpu_split_order_begin_self": (C.c_int, [_P, C.c_int, _P, C.c_uint8]),
     "csvgpu_split_order_finish": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P]),
+    "csvgpu_split_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

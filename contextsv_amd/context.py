@@ -239,6 +239,27 @@ class Context:
         self._check(rc)
         return [out[int(off[k]): int(off[k + 1])].copy() for k in range(n)]
 
+    def split_groups(self, start, end, seg_off, capacity: int | None = None):
+        """csvgpu_split_groups: the overlap groups (more than one member) of every segment, members of a segment given in the iteration
+        order of its qname map as closed intervals -> (seg_group_off, group_off, members), members = indices within the segment in
+        findOverlaps' traversal order. capacity None: sized from the input and retried once on CSV_ECAPACITY; given: CsvError when too small."""
+        start = np.ascontiguousarray(start, np.int32)
+        end = np.ascontiguousarray(end, np.int32)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        n_seg = len(seg_off) - 1
+        if n_seg < 0 or len(start) != len(end) or (n_seg >= 0 and len(seg_off) and int(seg_off[-1]) != len(start)):
+            raise ValueError("split_groups: seg_off must have n_seg + 1 entries and end at the number of members")
+        cap = capacity if capacity is not None else max(1024, 2 * len(start))
+        sgo = np.zeros(n_seg + 1, np.uint64)
+        go = np.zeros(len(start) + 1, np.uint64)
+        mem = np.zeros(max(cap, 1), np.uint32)
+        n = C.c_uint64(cap)
+        rc = self.lib.csvgpu_split_groups(self.h, ptr(start), ptr(end), ptr(seg_off), n_seg, ptr(sgo), ptr(go), ptr(mem), C.byref(n))
+        if rc == _lib.CSV_ECAPACITY and capacity is None:
+            return self.split_groups(start, end, seg_off, capacity=int(n.value))
+        self._check(rc)
+        return sgo, go[: int(sgo[n_seg]) + 1].copy(), mem[: int(n.value)].copy()
+
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):
         self._check(self.lib.csvgpu_synchronize(self.h))

@@ -205,6 +205,9 @@ int  launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, 
 // (onesweep passes only: the other passes size their table from a count the host knows)
 int  launch_radix_sort_u64_devn(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out, uint64_t n_bound,
                                 const uint32_t *n_dev, int key_bits, void *tmp);
+// The word (device memory inside `tmp`) that a one-launch pass sets when its bounded look-back gave up — the order is then wrong and the caller
+// must fail (CSV_EHIP); nullptr when the sort with these arguments takes the three-launch passes, which cannot give up.
+const uint32_t *radix_sort_gave_up(const void *tmp, uint64_t n, int key_bits, bool onesweep);
 // bucket ordering: BK_N most-significant-digit buckets + one wave ranking each bucket; see sort.hip
 constexpr uint32_t BK_BITS = 14, BK_N = 1u << BK_BITS, BK_LOCAL_MAX = 2048;
 // (the bucket counts come from the scan: ScanExtras::bucket_hist)
@@ -291,6 +294,29 @@ void launch_st_rank(hipStream_t s, const uint32_t *vals, uint32_t n, const uint3
 void launch_st_emit(hipStream_t s, const SplitTailHost &h, const uint32_t *vals, uint32_t n, const uint32_t *n_dev, const uint8_t *is_surv, const uint32_t *node_rec,
                     csv_split_survivor *out, uint64_t cap, unsigned long long *count);
 void launch_so_supp(hipStream_t s, const SplitOrderTab &tab, uint32_t n_blocks, uint32_t min_mapq, uint64_t *supp_hash, unsigned int *count);
+// splitgroups.hip — the overlap groups that the split order seeds (interval tree + greedy seeding of the reference), all segments of a call per launch
+struct SplitGroupsWs {                       // device arrays of one call, n = members of the call
+    int32_t  *ss, *se;                       // [n] start / end by position in the (segment, start, rank) order
+    uint32_t *sid, *posof, *plo, *lp1;       // [n] position -> member, member -> position, position -> first position of its segment, L + 1
+    uint32_t *blk_min_id;                    // [n / 64 + 1] smallest member index of every 64 positions
+    int32_t  *blk_max_end;                   // [n / 64 + 1] largest end
+    uint8_t  *head;                          // [n] the position starts a connected component
+    int32_t  *pm;                            // [n] running maximum of the ends inside a component (written for components too large for LDS only)
+    uint32_t *cstart, *cend, *seed_of_group; // [n] by seed: its component; by group: its seed
+    uint64_t *group_off, *seg_group_off;     // [n + 1], [n_seg + 1]
+    uint64_t *res;                           // total members, groups, error word
+    // zeroed together before the chain:
+    uint32_t *hist, *cnt, *keep;             // [n + 1] link histogram -> its exclusive sum; group sizes -> member offsets; kept flags -> group numbers
+    uint8_t  *state;                         // [n] seeds' scratch of components too large for LDS
+    unsigned long long *total;
+    uint32_t *err;
+};
+void launch_sg_keys(hipStream_t s, const int32_t *start, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, uint64_t *keys, uint32_t *vals);
+void launch_sg_links(hipStream_t s, const SplitGroupsWs &w, const uint64_t *keys, const uint32_t *vals, const int32_t *start, const int32_t *end,
+                     const uint64_t *seg_off, uint32_t n);
+void launch_sg_seeds(hipStream_t s, const SplitGroupsWs &w, uint32_t n);
+void launch_sg_offsets(hipStream_t s, const SplitGroupsWs &w, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, const uint32_t *sort_err);
+void launch_sg_fill(hipStream_t s, const SplitGroupsWs &w, uint32_t n_groups, int pre_bits, uint64_t *keys, uint32_t *vals);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

@@ -1508,6 +1508,132 @@ int csvgpu_split_order(csv_ctx *ctx, int n_contigs, csv_shard *const *shards, ui
     return rc;
 }
 
+// The overlap groups that the order seeds (kernels/splitgroups.hip). One wait sizes the answer (members, groups, error word); the second is the
+// answer's own copy. Everything in front of the first wait is queued without the host looking at the device.
+int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint64_t *seg_group_off,
+                        uint64_t *group_off, uint32_t *members, uint64_t *n_members)
+{
+    if (!ctx) return CSV_EINVAL;
+    if (!seg_off || !seg_group_off || !group_off || !n_members) { ctx->err = "split_groups: null array"; return CSV_EINVAL; }
+    if (ctx->split_state) { ctx->err = "split_groups: a split order is pending on this context"; return CSV_EINVAL; }
+    if (n_seg >= 0xffffffffull) { ctx->err = "split_groups: too many segments"; return CSV_EINVAL; }
+    uint64_t max_len = 0;
+    for (uint64_t c = 0; c < n_seg; c++) {
+        if (seg_off[c + 1] < seg_off[c]) { ctx->err = "split_groups: seg_off not ascending"; return CSV_EINVAL; }
+        max_len = std::max(max_len, seg_off[c + 1] - seg_off[c]);
+    }
+    const uint64_t n64 = seg_off[n_seg] - seg_off[0];
+    if (seg_off[0] != 0) { ctx->err = "split_groups: seg_off[0] must be 0"; return CSV_EINVAL; }
+    if (n64 >= 0xffffffffull) { ctx->err = "split_groups: more than 2^32 - 1 members"; return CSV_EINVAL; }
+    const uint64_t capacity = *n_members;
+    if (n64 && (!start || !end)) { ctx->err = "split_groups: null array"; return CSV_EINVAL; }
+    if (capacity && !members) { ctx->err = "split_groups: null members with a capacity"; return CSV_EINVAL; }
+    for (uint64_t i = 0; i < n64; i++) if (end[i] < start[i]) { ctx->err = "split_groups: end < start"; return CSV_EINVAL; }
+    const uint32_t n = (uint32_t)n64;
+    *n_members = 0;
+    if (n == 0 || max_len < 2) {                             // no segment can hold a group of two
+        for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
+        group_off[0] = 0;
+        return CSV_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    const size_t n4 = align_up(((size_t)n + 1) * 4, 256), nb = align_up((size_t)n / 64 * 4 + 4, 256), n1 = align_up((size_t)n, 256);
+    const size_t segb = align_up((n_seg + 1) * 8, 256);
+    const size_t zero_bytes = 3 * n4 + n1 + 256;             // hist, cnt, keep, state, total + err
+    const size_t need = 2 * n4 + segb                        /* start, end, seg_off */
+                        + sortws_bytes(n)
+                        + 10 * n4 + 2 * nb + n1              /* ss se sid posof plo lp1 cstart cend seed_of_group pm; block summaries; head */
+                        + align_up(((size_t)n + 1) * 8, 256) + segb + 256   /* group_off, seg_group_off, res */
+                        + zero_bytes + exclusive_sum_tmp_bytes((uint64_t)n + 1) + 16 * 256;
+    if ((rc = arena_reserve(ctx, ctx->arena, need))) return rc;
+    Arena &A = ctx->arena;
+    int32_t *d_start = (int32_t *)arena_alloc(A, (size_t)n * 4), *d_end = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    SortWs sw;
+    const bool sort_ok = sortws_carve(A, n, sw);
+    SplitGroupsWs w;
+    w.ss = (int32_t *)arena_alloc(A, (size_t)n * 4); w.se = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    w.sid = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.posof = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.plo = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.lp1 = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.cstart = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.cend = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.seed_of_group = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.pm = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    w.blk_min_id = (uint32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4); w.blk_max_end = (int32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4);
+    w.head = (uint8_t *)arena_alloc(A, n);
+    w.group_off = (uint64_t *)arena_alloc(A, ((size_t)n + 1) * 8); w.seg_group_off = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    w.res = (uint64_t *)arena_alloc(A, 256);
+    char *zero = (char *)arena_alloc(A, zero_bytes);
+    void *es_tmp = arena_alloc(A, exclusive_sum_tmp_bytes((uint64_t)n + 1));
+    if (!d_start || !d_end || !d_seg || !sort_ok || !w.seed_of_group || !w.pm || !w.blk_max_end || !w.head || !w.seg_group_off || !w.res || !zero || !es_tmp) {
+        ctx->err = "arena exhausted (split_groups)"; return CSV_ENOMEM;
+    }
+    w.hist = (uint32_t *)zero; w.cnt = (uint32_t *)(zero + n4); w.keep = (uint32_t *)(zero + 2 * n4);
+    w.state = (uint8_t *)(zero + 3 * n4);
+    w.total = (unsigned long long *)(zero + 3 * n4 + n1); w.err = (uint32_t *)(zero + 3 * n4 + n1 + 64);
+
+    if ((rc = ensure_pinned(ctx, 2 * PinStage::need((size_t)n * 4) + PinStage::need((n_seg + 1) * 8) + 4096))) return rc;
+    PinStage pin(ctx);
+    CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    volatile uint64_t *h_res = (volatile uint64_t *)((char *)ctx->pinned + pin.used);
+    const int key_bits = 32 + bits_of(n_seg - 1);
+    const bool one_launch = onesweep(ctx);
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
+        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
+        launch_sg_keys(s, d_start, d_seg, n_seg, n, sw.k0, sw.v0);
+        const int io = launch_radix_sort_u64(s, sw.k0, sw.v0, sw.k1, sw.v1, n, key_bits, sw.tmp, one_launch);
+        launch_sg_links(s, w, io ? sw.k1 : sw.k0, io ? sw.v1 : sw.v0, d_start, d_end, d_seg, n);
+        launch_exclusive_sum_u32(s, w.hist, (uint64_t)n + 1, es_tmp);
+        launch_sg_seeds(s, w, n);
+        launch_exclusive_sum_u32(s, w.cnt, (uint64_t)n + 1, es_tmp);
+        launch_exclusive_sum_u32(s, w.keep, (uint64_t)n + 1, es_tmp);
+        launch_sg_offsets(s, w, d_seg, n_seg, n, radix_sort_gave_up(sw.tmp, n, key_bits, one_launch));
+        CSV_HIP(ctx, hipMemcpyAsync((void *)h_res, w.res, 24, hipMemcpyDeviceToHost, s));
+    }
+    CSV_HIP(ctx, wait_stream(s));
+    const uint64_t total = h_res[0], n_groups = h_res[1], bad = h_res[2];
+    if (bad) { ctx->err = "split_groups: a bounded device loop gave up (radix look-back or seeding rounds)"; return CSV_EHIP; }
+    if (n_groups > n || total < 2 * n_groups) { ctx->err = "split_groups: counts out of range"; return CSV_EHIP; }
+    *n_members = total;
+    if (total > capacity) { ctx->err = "split_groups: members capacity too small"; return CSV_ECAPACITY; }
+    if (total >= 0xffffffffull) { ctx->err = "split_groups: more than 2^32 - 1 entries in the answer"; *n_members = 0; return CSV_EINVAL; }
+    if (n_groups == 0) {
+        for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
+        group_off[0] = 0;
+        return CSV_OK;
+    }
+    // ---- the members: (group ‖ pre) keys, one stable sort for every group of the call -----------------------------------------------------
+    if ((rc = arena_reserve(ctx, ctx->work, sortws_bytes(total) + 1024))) return rc;
+    SortWs fw;
+    if (!sortws_carve(ctx->work, total, fw)) { ctx->err = "arena exhausted (split_groups fill)"; return CSV_ENOMEM; }
+    const int pre_bits = std::max(1, bits_of(max_len - 1)), fill_bits = pre_bits + bits_of(n_groups - 1);
+    constexpr size_t kPinnedOutMax = (size_t)64 << 20;       // larger answers are copied straight into the caller's array
+    const bool members_pinned = total * 4 <= kPinnedOutMax;
+    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need((n_groups + 1) * 8) + (members_pinned ? PinStage::need(total * 4) : 0) + 4096))) return rc;
+    PinStage out(ctx);
+    uint32_t *h_sort_err = (uint32_t *)out.in(nullptr, 0);
+    out.used += 256;
+    *h_sort_err = 0;
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
+        launch_sg_fill(s, w, (uint32_t)n_groups, pre_bits, fw.k0, fw.v0);
+        const int io = launch_radix_sort_u64(s, fw.k0, fw.v0, fw.k1, fw.v1, total, fill_bits, fw.tmp, one_launch);
+        const uint32_t *d_members = io ? fw.v1 : fw.v0;
+        if (const uint32_t *flag = radix_sort_gave_up(fw.tmp, total, fill_bits, one_launch)) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, flag, 4, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(out.out(seg_group_off, (n_seg + 1) * 8), w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(out.out(group_off, (n_groups + 1) * 8), w.group_off, (n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (members_pinned) CSV_HIP(ctx, hipMemcpyAsync(out.out(members, total * 4), d_members, total * 4, hipMemcpyDeviceToHost, s));
+        else CSV_HIP(ctx, hipMemcpyAsync(members, d_members, total * 4, hipMemcpyDeviceToHost, s));
+    }
+    CSV_HIP(ctx, wait_stream(s));
+    if (*h_sort_err) { ctx->err = "split_groups: a radix pass's look-back gave up"; *n_members = 0; return CSV_EHIP; }
+    out.finish();
+    return CSV_OK;
+}
+
 int csvgpu_window_log2_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *region_start, const uint32_t *region_end,
                                 const int32_t *sample_size, const uint64_t *win_off, uint64_t n_regions, double mean_cov,
                                 double *log2_cov, uint32_t *win_start, uint32_t *win_end)

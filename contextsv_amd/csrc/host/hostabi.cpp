@@ -320,9 +320,10 @@ int csvhost_process_resident_lanes(int n_lanes, csv_ctx *const *ctxs, csv_shard 
 struct csvhost_split_call { uint32_t start, end; int32_t sv_type, cluster_size, aln_offset; uint32_t aln_flags; int32_t tid; };
 
 // records in file order; qname = "r<qname_id>". Output sorted by contig id, each contig's calls in the reference's order.
-int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
-                             const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
-                             int min_mapq, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
+// device_groups != 0: the overlap groups come from csvgpu_split_groups on `ctx` (SplitParams::device_groups) instead of the host tree.
+int csvhost_split_signatures_opts(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
+                                  const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
+                                  int min_mapq, int device_groups, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
 {
     GUARD({
         csvhost::set_context(ctx);
@@ -334,6 +335,8 @@ int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const
             qn[i] = "r" + std::to_string(qname_id[i]);
         }
         SplitParams p; p.min_mapq = min_mapq;
+        std::unique_ptr<SplitGroupSource> dev_groups;
+        if (device_groups) { dev_groups = makeDeviceGroupSource(ctx); p.device_groups = dev_groups.get(); }
         std::unordered_map<std::string, std::vector<SVCall>> calls;
         findSplitSVSignatures(rec, qn, targets, p, calls);
         uint64_t k = 0;
@@ -347,6 +350,34 @@ int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const
         }
         *n_out = k;
     })
+}
+
+int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
+                             const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
+                             int min_mapq, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
+{
+    return csvhost_split_signatures_opts(ctx, n, tid, pos, flag, mapq, ref_end, q_start, q_end, qname_id, n_targets, min_mapq, 0, out, cap, n_out);
+}
+
+// The outputs of csvgpu_split_groups computed by the host's interval tree (the path without SplitParams::device_groups); needs no GPU.
+// seg_group_off [n_seg + 1]; group_off [seg_off[n_seg] + 1] (entries 0 .. seg_group_off[n_seg] written); *n_members: in capacity, out count
+// required; -5 (CSV_ECAPACITY) when members[] is too small, -1 (CSV_EINVAL) on end < start or descending offsets.
+int csvhost_split_groups_host(const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint64_t *seg_group_off,
+                              uint64_t *group_off, uint32_t *members, uint64_t *n_members)
+{
+    try {
+        std::vector<uint64_t> sgo, go;
+        std::vector<uint32_t> mem;
+        splitGroupsHost(start, end, seg_off, n_seg, sgo, go, mem);
+        const uint64_t cap = *n_members;
+        *n_members = mem.size();
+        if (mem.size() > cap) { g_err = "split_groups_host: members capacity too small"; return CSV_ECAPACITY; }
+        std::copy(sgo.begin(), sgo.end(), seg_group_off);
+        std::copy(go.begin(), go.end(), group_off);
+        std::copy(mem.begin(), mem.end(), members);
+        return 0;
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return CSV_EINVAL;
+    } catch (const std::exception &e) { g_err = e.what(); return -100; }
 }
 
 // std::hash<std::string> of n '\n'-joined names (what the staging code attaches to a shard as its query-name column)
@@ -677,7 +708,7 @@ void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n
 
 // One step: SVCaller::runResident over every staged contig. passes: bit 0 split-read pass, bit 1 CIGAR copy-number pass, bit 2 the two
 // final merges, bit 3 keep the qname map's order on the host (umap_order.h) instead of csvgpu_split_order,
-// bit 4 do not run the split pass's first half beside the CIGAR pass; the RunSchedule (no result depends on it): bits 5-6 early_batches
+// bit 4 do not run the split pass's first half beside the CIGAR pass; bit 9 the overlap groups from csvgpu_split_groups (split_groups_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
 // (0 timed, 1 none, 2 all at once, 3 every three), bit 7 no split chain beside the pass, bit 8 the two-call split order, bits 16-30
 // prepare_delay_ms. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
 int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *const *lane_ctxs, const csv_hmm *hmm, double eps, double min_pts_pct,
@@ -700,6 +731,7 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         P.schedule.early_batches = (RunSchedule::EarlyBatches)((passes >> 5) & 3);
         P.schedule.split_beside_pass = (passes & 128) == 0;
         P.schedule.split_order_self = (passes & 256) == 0;
+        P.split_groups_on_device = (passes & 512) != 0;
         P.schedule.prepare_delay_ms = (passes >> 16) & 0x7fff;
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);

@@ -129,6 +129,8 @@ struct ContigWork {
     std::vector<PrimaryAlignment> member;
     std::vector<uint32_t> member_slot, supp_slot;      // where member m's / supplementary reference q's record sits in its contig's `need` list (prepare())
     std::vector<SuppAlignment> member_supps;           // member m's: [member_supp_off[m - 1], member_supp_off[m]) (one array: 1e4 one-element vectors cost more than the pass's arithmetic)
+    std::vector<uint64_t> group_off;                   // the overlap groups between their synthesis and the point sets: [n_groups + 1] into group_mem
+    std::vector<uint32_t> group_mem;                   // members (indices into `member`) in findOverlaps' traversal order
     std::vector<Group> groups;
     size_t set_base = 0;                           // first of this contig's point sets in the genome-wide batch
     size_t n_primary = 0;
@@ -153,7 +155,11 @@ struct SplitPass::Impl {
     std::vector<std::vector<uint32_t>> dev_recs;
     std::vector<char> grouped, called;                  // per contig: intervals gathered and overlap groups built; calls made and handed out
     void gatherFor(const std::vector<size_t> &ids);
+    void membersOf(size_t c);
+    void hostGroupsOf(size_t c, bool trace);
+    void setsOf(size_t c);
     void groupsOf(size_t c, bool trace);
+    void groupsOnDevice(const std::vector<size_t> &ids);
     void finishEarly(const std::vector<size_t> &ids);
     void finishFor(const std::vector<size_t> &ids, std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
     Impl(const std::vector<SplitContig> &c, const std::vector<std::string> &t, const SplitParams &p) : contigs(c), target_names(t), params(p) {}
@@ -323,13 +329,12 @@ void SplitPass::Impl::gatherFor(const std::vector<size_t> &ids)
     }
 }
 
-// phase 2 for one contig: interval tree, overlap groups, the six point sets (:215-347)
-void SplitPass::Impl::groupsOf(size_t c, bool trace)
+// phase 2 for one contig in three parts: members (intervals -> PrimaryAlignment + supplementary records), overlap groups (:215-238), the six
+// point sets and the strand vote (:248-347)
+void SplitPass::Impl::membersOf(size_t c)
 {
         ContigWork &W = work[c];
         const SplitContig &C = *W.in;
-        const int primary_tid = C.tid;
-        std::unique_ptr<csvhost::TraceScope> t2(trace ? new csvhost::TraceScope("split: groups[0] members") : nullptr);
         W.member.reserve(W.member_rec.size());
         W.member_supps.reserve(W.member_supp_ref.size());
         // (the records' places in the gathered arrays were looked up by prepare(): no searches on this side of the CIGAR pass)
@@ -350,33 +355,52 @@ void SplitPass::Impl::groupsOf(size_t c, bool trace)
                 W.member_supps.push_back(SuppAlignment{S.tid, S.pos[r] + 1, at(SW, r, sr, 0), at(SW, r, sr, 1), at(SW, r, sr, 2), !(S.flag[r] & FLAG_REVERSE)});
             }
         }
+}
 
-        if (trace) t2.reset(new csvhost::TraceScope("split: groups[0] tree"));
-        // overlap groups (:215-238): direct overlaps of the first unprocessed read in iteration order, not transitive
-        IntervalTree tree;
-        tree.nodes.reserve(W.member.size());
-        for (size_t m = 0; m < W.member.size(); m++) tree.add(W.member[m], (uint32_t)m);
-        tree.build();
-        if (trace) t2.reset(new csvhost::TraceScope("split: groups[0] seeds"));
-        std::vector<std::vector<uint32_t>> primary_clusters;
-        {
-            std::vector<char> processed(W.member.size(), 0);
-            std::vector<int32_t> walk;
-            for (size_t m = 0; m < W.member.size(); m++) {
-                if (processed[m]) continue;
-                std::vector<uint32_t> group;
-                tree.overlaps(W.member[m], group, walk);
-                for (uint32_t q : group) processed[q] = 1;
-                if (group.size() > 1) primary_clusters.push_back(std::move(group));
-            }
-        }
-        if (trace) t2.reset(new csvhost::TraceScope("split: groups[0] sets"));
-        W.groups.assign(primary_clusters.size(), Group());
-        for (size_t g = 0; g < primary_clusters.size(); g++) {
+namespace {
+// overlap groups (:215-238) of one segment's members, given in iteration order: direct overlaps of the first unprocessed read, not transitive.
+// Appends the groups with more than one member to (off, mem); off ends with mem.size() before and after.
+void host_groups(const PrimaryAlignment *member, size_t n, std::vector<uint64_t> &off, std::vector<uint32_t> &mem, bool trace)
+{
+    std::unique_ptr<csvhost::TraceScope> t2(trace ? new csvhost::TraceScope("split: groups[0] tree") : nullptr);
+    IntervalTree tree;
+    tree.nodes.reserve(n);
+    for (size_t m = 0; m < n; m++) tree.add(member[m], (uint32_t)m);
+    tree.build();
+    if (trace) t2.reset(new csvhost::TraceScope("split: groups[0] seeds"));
+    std::vector<char> processed(n, 0);
+    std::vector<int32_t> walk;
+    for (size_t m = 0; m < n; m++) {
+        if (processed[m]) continue;
+        const size_t before = mem.size();
+        tree.overlaps(member[m], mem, walk);
+        for (size_t q = before; q < mem.size(); q++) processed[mem[q]] = 1;
+        if (mem.size() - before > 1) off.push_back(mem.size());
+        else mem.resize(before);
+    }
+}
+}  // namespace
+
+void SplitPass::Impl::hostGroupsOf(size_t c, bool trace)
+{
+        ContigWork &W = work[c];
+        W.group_off.assign(1, 0);
+        W.group_mem.clear();
+        host_groups(W.member.data(), W.member.size(), W.group_off, W.group_mem, trace);
+}
+
+void SplitPass::Impl::setsOf(size_t c)
+{
+        ContigWork &W = work[c];
+        const int primary_tid = W.in->tid;
+        const size_t n_groups = W.group_off.size() - 1;
+        W.groups.assign(n_groups, Group());
+        for (size_t g = 0; g < n_groups; g++) {
             Group &G = W.groups[g];
-            const auto &members = primary_clusters[g];
+            const uint32_t *members = W.group_mem.data() + W.group_off[g], *members_end = W.group_mem.data() + W.group_off[g + 1];
             int n_opposite = 0;
-            for (uint32_t q : members) {
+            for (const uint32_t *qp = members; qp != members_end; ++qp) {
+                const uint32_t q = *qp;
                 const PrimaryAlignment &p = W.member[q];
                 bool opposite = false;
                 for (size_t z = q ? W.member_supp_off[q - 1] : 0; z < W.member_supp_off[q]; z++) {
@@ -387,8 +411,9 @@ void SplitPass::Impl::groupsOf(size_t c, bool trace)
                 G.sets[0].push_back(p.start);
                 G.sets[1].push_back(p.end);
             }
-            G.inversion = (double)n_opposite / (double)(int)members.size() > 0.5;                   // :265
-            for (uint32_t q : members) {
+            G.inversion = (double)n_opposite / (double)(int)(members_end - members) > 0.5;            // :265
+            for (const uint32_t *qp = members; qp != members_end; ++qp) {
+                const uint32_t q = *qp;
                 const PrimaryAlignment &p = W.member[q];
                 for (size_t z = q ? W.member_supp_off[q - 1] : 0; z < W.member_supp_off[q]; z++) {
                     const SuppAlignment &s = W.member_supps[z];
@@ -405,6 +430,49 @@ void SplitPass::Impl::groupsOf(size_t c, bool trace)
                 }
             }
         }
+        W.group_off = {}; W.group_mem = {};
+}
+
+void SplitPass::Impl::groupsOf(size_t c, bool trace)
+{
+        std::unique_ptr<csvhost::TraceScope> t2(trace ? new csvhost::TraceScope("split: groups[0] members") : nullptr);
+        membersOf(c);
+        t2.reset();
+        hostGroupsOf(c, trace);
+        if (trace) t2.reset(new csvhost::TraceScope("split: groups[0] sets"));
+        setsOf(c);
+}
+
+// The same for several contigs with SplitParams::device_groups: members of all of them in parallel, ONE groups() call for the batch (segment k =
+// contig ids[k]'s members in iteration order), then the sets in parallel.
+void SplitPass::Impl::groupsOnDevice(const std::vector<size_t> &ids)
+{
+    if (ids.empty()) return;
+    std::unique_ptr<csvhost::TraceScope> t2(new csvhost::TraceScope("split: groups members"));
+    parallel_over(ids.size(), params.threads, [&](size_t k) { membersOf(ids[k]); });
+    std::vector<uint64_t> seg_off(ids.size() + 1, 0);
+    for (size_t k = 0; k < ids.size(); k++) seg_off[k + 1] = seg_off[k] + work[ids[k]].member.size();
+    std::vector<int32_t> start(seg_off.back()), end(seg_off.back());
+    parallel_over(ids.size(), params.threads, [&](size_t k) {
+        const ContigWork &W = work[ids[k]];
+        for (size_t m = 0; m < W.member.size(); m++) { start[seg_off[k] + m] = W.member[m].start; end[seg_off[k] + m] = W.member[m].end; }
+    });
+    t2.reset(new csvhost::TraceScope("split: groups on device"));
+    std::vector<uint64_t> seg_group_off, group_off;
+    std::vector<uint32_t> members;
+    params.device_groups->groups(start, end, seg_off, seg_group_off, group_off, members);
+    if (seg_group_off.size() != ids.size() + 1 || group_off.size() < seg_group_off.back() + 1 || members.size() < group_off[seg_group_off.back()])
+        throw std::runtime_error("findSplitSVSignatures: the group source returned tables of the wrong size");
+    t2.reset(new csvhost::TraceScope("split: groups sets"));
+    parallel_over(ids.size(), params.threads, [&](size_t k) {
+        ContigWork &W = work[ids[k]];
+        const uint64_t g0 = seg_group_off[k], g1 = seg_group_off[k + 1], m0 = group_off[g0];
+        W.group_off.resize(g1 - g0 + 1);
+        for (uint64_t g = g0; g <= g1; g++) W.group_off[g - g0] = group_off[g] - m0;
+        W.group_mem.assign(members.begin() + (std::ptrdiff_t)m0, members.begin() + (std::ptrdiff_t)group_off[g1]);
+        for (uint32_t q : W.group_mem) if (q >= W.member.size()) throw std::runtime_error("findSplitSVSignatures: a group member out of range");
+        setsOf(ids[k]);
+    });
 }
 
 // Contigs whose scan outputs exist already (the caller knows): their intervals and groups now, the rest in finish()
@@ -416,7 +484,8 @@ void SplitPass::Impl::finishEarly(const std::vector<size_t> &ids)
     csvhost::TraceScope tr("split: early gather + groups");
     gatherFor(todo);
     std::sort(todo.begin(), todo.end(), [&](size_t a, size_t b) { return work[a].member_rec.size() > work[b].member_rec.size(); });
-    parallel_over(todo.size(), params.threads, [&](size_t k) { groupsOf(todo[k], false); });
+    if (params.device_groups) groupsOnDevice(todo);
+    else parallel_over(todo.size(), params.threads, [&](size_t k) { groupsOf(todo[k], false); });
     for (size_t c : todo) grouped[c] = 1;
 }
 
@@ -439,7 +508,8 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
     tr.reset(new csvhost::TraceScope("split: interval gather"));
     gatherFor(rest);
     tr.reset(new csvhost::TraceScope("split: groups"));
-    parallel_over(rest.size(), params.threads, [&](size_t k) { groupsOf(rest[k], k == 0); });
+    if (params.device_groups) groupsOnDevice(rest);
+    else parallel_over(rest.size(), params.threads, [&](size_t k) { groupsOf(rest[k], k == 0); });
     for (size_t c : rest) grouped[c] = 1;
 
     // ---- the six DBSCAN1D(100, 5) fits of every group of every contig: ONE batched launch (:270-372) ------------------------------
@@ -570,4 +640,30 @@ void findSplitSVSignatures(const std::vector<SplitRecord> &records, const std::v
         contigs.push_back(c);
     }
     findSplitSVSignatures(contigs, target_names, params, sv_calls);
+}
+
+void splitGroupsHost(const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, std::vector<uint64_t> &seg_group_off,
+                     std::vector<uint64_t> &group_off, std::vector<uint32_t> &members)
+{
+    seg_group_off.assign(1, 0);
+    group_off.assign(1, 0);
+    members.clear();
+    std::vector<PrimaryAlignment> seg;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> mem;
+    for (uint64_t c = 0; c < n_seg; c++) {
+        if (seg_off[c + 1] < seg_off[c]) throw std::invalid_argument("splitGroupsHost: seg_off not ascending");
+        seg.clear();
+        for (uint64_t i = seg_off[c]; i < seg_off[c + 1]; i++) {
+            if (end[i] < start[i]) throw std::invalid_argument("splitGroupsHost: end < start");
+            seg.push_back(PrimaryAlignment{start[i], end[i], 0, 0, true, 0});
+        }
+        off.assign(1, 0);
+        mem.clear();
+        host_groups(seg.data(), seg.size(), off, mem, false);
+        const uint64_t base = members.size();
+        for (size_t g = 1; g < off.size(); g++) group_off.push_back(base + off[g]);
+        members.insert(members.end(), mem.begin(), mem.end());
+        seg_group_off.push_back(group_off.size() - 1);
+    }
 }

@@ -7,7 +7,9 @@
 // one batched launch for the whole genome (DBSCAN1D::fitBatch -> csvgpu_dbscan_1d). What stays here: the order-defining
 // steps (SURVEY §7 hard part 2) — the iteration order of the reference's qname-keyed unordered_map, replayed exactly by
 // umap_order.h instead of building 6e5 string-keyed nodes per chromosome; the (unbalanced) interval tree that order builds; the
-// overlap groups, medians and votes — one host thread per contig, contigs being independent.
+// overlap groups, medians and votes — one host thread per contig, contigs being independent. The tree and the groups can also come from
+// the device for a whole batch of contigs (SplitGroupSource below: csvgpu_split_groups, the same lists member for member); off unless
+// SplitParams::device_groups is set.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -54,6 +56,18 @@ struct SplitOrderSource {
     virtual void begin(const std::vector<size_t> &which, int min_mapq, bool complete) const { (void)which; (void)min_mapq; (void)complete; }
 };
 
+// The overlap groups of several contigs (the interval tree and the greedy seeding of sv_caller.cpp:215-238, :948-980), computed somewhere else
+// than on the host threads (the device: csvgpu_split_groups behind ShardGroupSource in sv_caller.cpp).
+struct SplitGroupSource {
+    virtual ~SplitGroupSource() = default;
+    // segment k = members [seg_off[k], seg_off[k+1]) of one contig in the iteration order of its qname map, each the closed interval
+    // [start, end] (pos + 1, bam_endpos). -> the groups with more than one member: segment k's are [seg_group_off[k], seg_group_off[k+1]) in seed
+    // order, group g's members are members[group_off[g] .. group_off[g+1]): indices WITHIN the segment, in findOverlaps' traversal order.
+    // One call per batch of contigs; asked from the thread that runs finishEarly / finishFor / finish.
+    virtual void groups(const std::vector<int32_t> &start, const std::vector<int32_t> &end, const std::vector<uint64_t> &seg_off,
+                        std::vector<uint64_t> &seg_group_off, std::vector<uint64_t> &group_off, std::vector<uint32_t> &members) const = 0;
+};
+
 struct SplitParams {
     int min_mapq = 20;        // sv_caller.h:72
     double eps = 100;         // DBSCAN1D(100, 5) at sv_caller.cpp:270
@@ -62,6 +76,7 @@ struct SplitParams {
     int max_length = 1000000; // :244
     const IntervalSource *intervals = nullptr;        // for contigs given without ref_end / q_start / q_end arrays
     const SplitOrderSource *device_order = nullptr;   // where contigs with unique_names get their iteration order from (nullptr: replayed on the host)
+    const SplitGroupSource *device_groups = nullptr;  // where the overlap groups come from (nullptr: the host's interval tree, one contig per host thread)
     int threads = 0;          // host threads over contigs (0: one per contig, at most the hardware's); the result does not depend on it
 };
 
@@ -113,3 +128,8 @@ private:
 void findSplitSVSignatures(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames,
                            const std::vector<std::string> &target_names, const SplitParams &params,
                            std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
+
+// The overlap groups of csvgpu_split_groups computed by the host's interval tree (the path SplitParams::device_groups == nullptr takes), same
+// outputs: seg_group_off [n_seg + 1], group_off [groups + 1], members. Throws std::invalid_argument on end < start or descending offsets.
+void splitGroupsHost(const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, std::vector<uint64_t> &seg_group_off,
+                     std::vector<uint64_t> &group_off, std::vector<uint32_t> &members);

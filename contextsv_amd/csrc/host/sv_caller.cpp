@@ -513,7 +513,33 @@ struct ShardOrderSource : SplitOrderSource {
     mutable bool pending_self = false;            // ... by csvgpu_split_order_begin_self: _finish takes no hashes
 };
 
+// the overlap groups from the device (csvgpu_split_groups), on the context that the same thread's interval gather (ShardIntervals) and DBSCAN1D
+// batch use: the split pass's calls come one after the other from one thread, and a context is one arena and one stream
+struct ShardGroupSource : SplitGroupSource {
+    explicit ShardGroupSource(csv_ctx *ctx) : ctx(ctx) {}
+    void groups(const std::vector<int32_t> &start, const std::vector<int32_t> &end, const std::vector<uint64_t> &seg_off, std::vector<uint64_t> &seg_group_off,
+                std::vector<uint64_t> &group_off, std::vector<uint32_t> &members) const override
+    {
+        const uint64_t n_seg = seg_off.size() - 1;
+        seg_group_off.assign(n_seg + 1, 0);
+        group_off.assign(start.size() + 1, 0);
+        members.resize(std::max<size_t>(start.size() * 2, 1024));            // (events of a few dozen reads: about one entry per member)
+        uint64_t n = members.size();
+        int rc = csvgpu_split_groups(ctx, start.data(), end.data(), seg_off.data(), n_seg, seg_group_off.data(), group_off.data(), members.data(), &n);
+        if (rc == CSV_ECAPACITY) {
+            members.resize(n);
+            rc = csvgpu_split_groups(ctx, start.data(), end.data(), seg_off.data(), n_seg, seg_group_off.data(), group_off.data(), members.data(), &n);
+        }
+        check(ctx, rc, "split-read overlap groups");
+        members.resize(n);
+        group_off.resize(seg_group_off[n_seg] + 1);
+    }
+    csv_ctx *ctx;
+};
+
 }  // namespace
+
+std::unique_ptr<SplitGroupSource> makeDeviceGroupSource(csv_ctx *ctx) { return std::unique_ptr<SplitGroupSource>(new ShardGroupSource(ctx)); }
 
 // what the split-read pass of a run works on (built once per run; prepare() may already be running while the CIGAR pass is on the device)
 struct SVCaller::SplitSetup {
@@ -522,6 +548,7 @@ struct SVCaller::SplitSetup {
     std::vector<std::string> names;
     std::unique_ptr<ShardOrderSource> dev_order;
     std::unique_ptr<ShardIntervals> intervals;
+    std::unique_ptr<ShardGroupSource> dev_groups;
     SplitParams sp;
     std::unique_ptr<SplitPass> pass;
     double ms_prepare = 0.0;
@@ -948,6 +975,8 @@ std::unique_ptr<SVCaller::SplitSetup> SVCaller::makeSplitSetup(std::vector<Resid
     S->intervals.reset(new ShardIntervals(ctx, shard_of));
     S->sp.intervals = S->intervals.get();
     if (P.split_order_on_device) S->sp.device_order = S->dev_order.get();          // only contigs staged with unique_names take it
+    S->dev_groups.reset(new ShardGroupSource(ctx));
+    if (P.split_groups_on_device) S->sp.device_groups = S->dev_groups.get();
     S->pass.reset(new SplitPass(S->blocks, S->names, S->sp));
     return S;
 }

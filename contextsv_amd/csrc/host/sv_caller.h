@@ -100,6 +100,8 @@ struct RunParams {
     uint32_t min_cnv_length = 2000;         // --min-cnv
     bool cigar_svs = true, cigar_cn = true, split_svs = true, merge_split_svs = true, merge_final_svs = true;   // sv_caller.cpp:749-753
     bool split_order_on_device = true;      // contigs staged with unique query-name hashes (SplitContig::unique_names) get the qname map's order from csvgpu_split_order
+    bool split_groups_on_device = false;    // the overlap groups of the split-read pass (interval tree + greedy seeding, sv_caller.cpp:215-238) from csvgpu_split_groups, one
+                                            // call per batch of contigs, instead of the host tree on one pool thread per contig; the calls do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it
@@ -117,6 +119,10 @@ struct BamRunStats {
     double ms_decode = 0.0;          // wall time spent waiting for decoded contigs (decode not hidden behind the device)
     double ms_total = 0.0;
 };
+
+// A SplitGroupSource that asks csvgpu_split_groups on `ctx` (SplitParams::device_groups); the caller keeps the context alive and uses it from the
+// thread that runs the split pass only.
+std::unique_ptr<SplitGroupSource> makeDeviceGroupSource(csv_ctx *ctx);
 
 class SVCaller {
 public:

@@ -400,6 +400,21 @@ size_t radix_sort_tmp_bytes(uint64_t n)
     return std::max(align_up(tab * sizeof(uint32_t), 256) + exclusive_sum_tmp_bytes(tab), os_tmp_bytes(n));
 }
 
+// whether launch_radix_sort_u64 takes the one-launch passes for this sort
+static bool rs_takes_onesweep(uint64_t n, int passes, unsigned grid, bool onesweep)
+{
+    return onesweep && n < (1ull << 30) && passes <= OS_MAX_PASSES && grid + 1 <= os_wg_tiles_max(n);
+}
+
+const uint32_t *radix_sort_gave_up(const void *tmp, uint64_t n, int key_bits, bool onesweep)
+{
+    if (n <= 1 || key_bits <= 0) return nullptr;
+    const uint64_t tile_keys = (uint64_t)rs_rounds_for(n) * WAVE;
+    const uint32_t n_tiles = (uint32_t)((n + tile_keys - 1) / tile_keys);
+    if (!rs_takes_onesweep(n, (key_bits + RS_BITS - 1) / RS_BITS, (n_tiles + RS_WAVES - 1) / RS_WAVES, onesweep)) return nullptr;
+    return (const uint32_t *)tmp + OS_MAX_PASSES;          // launch_onesweep: the pass counters, then the flag
+}
+
 int launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out,
                           uint64_t n, int key_bits, void *tmp, bool onesweep)
 {
@@ -414,7 +429,7 @@ int launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, u
     const int passes = (key_bits + RS_BITS - 1) / RS_BITS;
     uint64_t *ki = keys_in, *ko = keys_out;
     uint32_t *vi = vals_in, *vo = vals_out;
-    if (onesweep && n < (1ull << 30) && passes <= OS_MAX_PASSES && grid + 1 <= os_wg_tiles_max(n)) {
+    if (rs_takes_onesweep(n, passes, grid, onesweep)) {
         launch_onesweep(s, ki, vi, ko, vo, n, nullptr, passes, grid, n_tiles, rounds, tmp);
         return (passes & 1) ? 1 : 0;
     }

@@ -98,7 +98,8 @@ typedef enum csv_kernel_id {
     CSV_K_VITERBI    = 6,   /* emissions + Viterbi DP + backtrack */
     CSV_K_MISC       = 7,   /* memsets, small scans, partition */
     CSV_K_SPLIT_ORDER = 8,  /* hash-map node order of the split-read pass (compaction + per-epoch sorts + survivors) */
-    CSV_K_COUNT      = 9
+    CSV_K_SPLIT_GROUPS = 9, /* overlap groups of the split-read pass (member order, links, seeds, fill + its sorts) */
+    CSV_K_COUNT      = 10
 } csv_kernel_id;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -352,6 +353,22 @@ int csvgpu_split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
  * that are not in this call must use _begin and pass all hashes to _finish. */
 int csvgpu_split_order_begin_self(csv_ctx *ctx, int n_contigs, csv_shard *const *shards, uint8_t min_mapq);
 int csvgpu_split_order_finish(csv_ctx *ctx, const uint64_t *supp_hash, uint64_t n_supp, uint32_t *out_rec, uint64_t capacity, uint64_t *out_off);
+
+/* §8f-4, second half: replaces the interval tree and the greedy overlap groups of findSplitSVSignatures (sv_caller.cpp:215-238,
+ * insert :964-980, findOverlaps :948-962) for a batch of contigs. Segment c = members [seg_off[c], seg_off[c+1])
+ * in the iteration order of that contig's qname map (what csvgpu_split_order returns); member = closed interval
+ * [start, end] (start = pos + 1, end = bam_endpos). Output: the groups with more than one member, per segment in
+ * seed order; members[] holds indices WITHIN the segment, in findOverlaps' traversal order:
+ *   groups of segment c = [seg_group_off[c], seg_group_off[c+1]); members of group g = members[group_off[g] .. group_off[g+1]).
+ * Only group_off[0 .. seg_group_off[n_seg]] is written. Any int32_t coordinates are valid (no arithmetic is done on them).
+ * *n_members: in = capacity of members[] in entries, out = entries required. CSV_ECAPACITY when the capacity is too small (members shared
+ * between groups make the total quadratic in the worst case: k disjoint seeds under L long intervals give k * L entries); nothing but
+ * *n_members is then written. CSV_EINVAL: end < start anywhere, offsets not ascending, more than 2^32 - 1 members in the call or
+ * entries in the answer. Empty segments and n_seg == 0 are valid. */
+int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg,
+                        uint64_t *seg_group_off,   /* [n_seg + 1]: first group of each segment */
+                        uint64_t *group_off,       /* [seg_off[n_seg] + 1]: there are never more groups than members */
+                        uint32_t *members, uint64_t *n_members /* in: capacity of members[], out: count required */);
 
 /* csvgpu_window_log2 on the depth map that the last csvgpu_chr_pipeline_dev() left resident in `shard`
  * (region tables and outputs are host memory; the depth map never leaves HBM). */
