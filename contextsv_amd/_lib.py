@@ -19,11 +19,13 @@ ABI_VERSION = 4          # include/csvgpu.h CSVGPU_ABI_VERSION
 CSV_OK, CSV_EINVAL, CSV_ENODEV, CSV_ENOMEM, CSV_EHIP, CSV_ECAPACITY = 0, -1, -2, -3, -4, -5
 STATUS_NAMES = {0: "CSV_OK", -1: "CSV_EINVAL", -2: "CSV_ENODEV", -3: "CSV_ENOMEM", -4: "CSV_EHIP", -5: "CSV_ECAPACITY"}
 
-K_CIGAR_SCAN, K_DEPTH, K_SORT, K_DBSCAN, K_DBSCAN1D, K_WINDOW, K_VITERBI, K_MISC, K_SPLIT_ORDER, K_SPLIT_GROUPS, K_COUNT = range(11)
-KERNEL_NAMES = ["cigar_scan", "depth", "sort", "dbscan", "dbscan1d", "window", "viterbi", "misc", "split_order", "split_groups"]
+K_CIGAR_SCAN, K_DEPTH, K_SORT, K_DBSCAN, K_DBSCAN1D, K_WINDOW, K_VITERBI, K_MISC, K_SPLIT_ORDER, K_SPLIT_GROUPS, K_SPLIT_FITS, K_COUNT = range(12)
+KERNEL_NAMES = ["cigar_scan", "depth", "sort", "dbscan", "dbscan1d", "window", "viterbi", "misc", "split_order", "split_groups", "split_fits"]
 
 SIG_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("read", "<u4"), ("qpos_kind", "<u4")])
 KIND_INS, KIND_DEL, KIND_CLIP = 0, 1, 2
+# csv_split_fit: one overlap group's evidence (csvgpu_split_fits), 64 bytes
+SPLIT_FIT_DTYPE = np.dtype([("median", "<i4", (6,)), ("size", "<u4", (6,)), ("n_members", "<u4"), ("n_opposite", "<u4"), ("reserved", "<u4", (2,))])
 
 
 class CsvError(RuntimeError):
@@ -52,6 +54,12 @@ class csv_chr_result(C.Structure):
 class csv_tuning(C.Structure):
     _fields_ = [("scan_form", C.c_int32), ("split_tail", C.c_int32), ("sort_three_launch", C.c_int32), ("dbscan_all_pairs", C.c_int32),
                 ("split_chain_only", C.c_int32)]
+
+
+class csv_split_tables(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("n_supp", C.c_uint64), ("start", C.c_void_p), ("end", C.c_void_p), ("q_start", C.c_void_p),
+                ("q_end", C.c_void_p), ("reverse", C.c_void_p), ("supp_off", C.c_void_p), ("supp_start", C.c_void_p), ("supp_end", C.c_void_p),
+                ("supp_q_start", C.c_void_p), ("supp_q_end", C.c_void_p), ("supp_flags", C.c_void_p)]
 
 
 # every symbol include/csvgpu.h declares: name -> (restype, argtypes)
@@ -99,6 +107,8 @@ ABI = {
     "csvgpu_split_order_begin_self": (C.c_int, [_P, C.c_int, _P, C.c_uint8]),
     "csvgpu_split_order_finish": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P]),
     "csvgpu_split_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_split_fits": (C.c_int, [_P, C.POINTER(csv_split_tables), _P, C.c_uint64, _P, _P, _P, C.c_double, C.c_int32, _P]),
+    "csvgpu_split_groups_fits": (C.c_int, [_P, C.POINTER(csv_split_tables), _P, C.c_uint64, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

@@ -8,7 +8,51 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import SIG_DTYPE, CsvError, csv_chr_result, csv_hmm, csv_reads, ptr
+from ._lib import SIG_DTYPE, CsvError, csv_chr_result, csv_hmm, csv_reads, csv_split_tables, ptr
+
+
+@dataclass
+class SplitTables:
+    """The members of a batch of contigs (primary alignments that have a supplementary record, map iteration order per segment) and
+    their supplementary records (include/csvgpu.h csv_split_tables)."""
+    start: np.ndarray         # int32 [n_members]  pos + 1
+    end: np.ndarray           # int32 [n_members]  bam_endpos
+    q_start: np.ndarray
+    q_end: np.ndarray
+    reverse: np.ndarray       # uint8 [n_members]  1 = FLAG 0x10
+    supp_off: np.ndarray      # uint64 [n_members + 1]
+    supp_start: np.ndarray    # int32 [n_supp]
+    supp_end: np.ndarray
+    supp_q_start: np.ndarray
+    supp_q_end: np.ndarray
+    supp_flags: np.ndarray    # uint8 [n_supp]  bit 0 reverse strand, bit 1 on another tid than the primary
+
+    def __post_init__(self):
+        for f in ("start", "end", "q_start", "q_end", "supp_start", "supp_end", "supp_q_start", "supp_q_end"):
+            setattr(self, f, np.ascontiguousarray(getattr(self, f), dtype=np.int32))
+        self.reverse = np.ascontiguousarray(self.reverse, dtype=np.uint8)
+        self.supp_flags = np.ascontiguousarray(self.supp_flags, dtype=np.uint8)
+        self.supp_off = np.ascontiguousarray(self.supp_off, dtype=np.uint64)
+        n, k = len(self.start), len(self.supp_start)
+        if not (len(self.end) == n and len(self.q_start) == n and len(self.q_end) == n and len(self.reverse) == n and len(self.supp_off) == n + 1):
+            raise ValueError("SplitTables: member array lengths disagree")
+        if not (len(self.supp_end) == k and len(self.supp_q_start) == k and len(self.supp_q_end) == k and len(self.supp_flags) == k):
+            raise ValueError("SplitTables: supplementary array lengths disagree")
+
+    @property
+    def n_members(self) -> int:
+        return len(self.start)
+
+    @property
+    def n_supp(self) -> int:
+        return len(self.supp_start)
+
+    def c_struct(self) -> csv_split_tables:
+        t = csv_split_tables()
+        t.n_members, t.n_supp = self.n_members, self.n_supp
+        for f in ("start", "end", "q_start", "q_end", "reverse", "supp_off", "supp_start", "supp_end", "supp_q_start", "supp_q_end", "supp_flags"):
+            setattr(t, f, ptr(getattr(self, f)))
+        return t
 
 
 @dataclass
@@ -259,6 +303,30 @@ class Context:
             return self.split_groups(start, end, seg_off, capacity=int(n.value))
         self._check(rc)
         return sgo, go[: int(sgo[n_seg]) + 1].copy(), mem[: int(n.value)].copy()
+
+    def split_fits(self, tables, seg_off, groups=None, eps: float = 100.0, min_pts: int = 5):
+        """csvgpu_split_fits / csvgpu_split_groups_fits: the evidence the reference derives from every overlap group — strand vote, the six
+        point sets, their DBSCAN1D fits, the largest clusters and their medians — as one SPLIT_FIT_DTYPE record per group.
+        tables: SplitTables (members and their supplementary records, segment by segment); groups: (seg_group_off, group_off, members) as
+        split_groups or host.split_groups_host returns them, or None for the fused call, which computes the groups on the device and
+        leaves them there. -> (seg_group_off, fits)."""
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        n_seg = len(seg_off) - 1
+        if n_seg < 0:
+            raise ValueError("split_fits: seg_off must have n_seg + 1 entries")
+        t = tables.c_struct()
+        if groups is None:
+            sgo = np.zeros(n_seg + 1, np.uint64)
+            out = np.zeros(max(tables.n_members, 1), _lib.SPLIT_FIT_DTYPE)
+            n = C.c_uint64(0)
+            self._check(self.lib.csvgpu_split_groups_fits(self.h, C.byref(t), ptr(seg_off), n_seg, eps, min_pts, ptr(sgo), ptr(out), C.byref(n)))
+            return sgo, out[: int(n.value)].copy()
+        sgo, go, mem = (np.ascontiguousarray(groups[0], np.uint64), np.ascontiguousarray(groups[1], np.uint64), np.ascontiguousarray(groups[2], np.uint32))
+        if len(sgo) != n_seg + 1 or len(go) < int(sgo[n_seg]) + 1 or len(mem) < int(go[int(sgo[n_seg])]):
+            raise ValueError("split_fits: the group tables do not fit the segments")
+        out = np.zeros(max(int(sgo[n_seg]), 1), _lib.SPLIT_FIT_DTYPE)
+        self._check(self.lib.csvgpu_split_fits(self.h, C.byref(t), ptr(seg_off), n_seg, ptr(sgo), ptr(go), ptr(mem), eps, min_pts, ptr(out)))
+        return sgo, out[: int(sgo[n_seg])]
 
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):

@@ -317,6 +317,27 @@ void launch_sg_links(hipStream_t s, const SplitGroupsWs &w, const uint64_t *keys
 void launch_sg_seeds(hipStream_t s, const SplitGroupsWs &w, uint32_t n);
 void launch_sg_offsets(hipStream_t s, const SplitGroupsWs &w, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, const uint32_t *sort_err);
 void launch_sg_fill(hipStream_t s, const SplitGroupsWs &w, uint32_t n_groups, int pre_bits, uint64_t *keys, uint32_t *vals);
+// splitfits.hip — what the reference derives from an overlap group (point sets, DBSCAN1D fits, largest clusters, medians, strand vote)
+struct SplitFitsIn {                         // device arrays, passed to the kernels by value
+    const int32_t *start, *end, *q_start, *q_end;        // [n_members]
+    const uint8_t *reverse;
+    const uint64_t *supp_off;                            // [n_members + 1]
+    const int32_t *supp_start, *supp_end, *supp_q_start, *supp_q_end;   // [n_supp]
+    const uint8_t *supp_flags;
+    const uint64_t *seg_off, *seg_group_off;             // [n_seg + 1]
+    const uint64_t *group_off;                           // [n_groups + 1]
+    const uint32_t *members;                             // indices within the group's segment
+    uint64_t n_seg;
+    uint32_t n_groups;
+};
+// One wave per (group, set): out[g] complete for the sets of at most DBSCAN1D_MAX_SEG points; a larger set w = 6 g + set gets big_n[w] = its
+// size (0 otherwise) and adds itself to big_res[0] (sets) and big_res[1] (points). big_n and big_res zeroed by the caller.
+void launch_sf_fits(hipStream_t s, const SplitFitsIn &in, double eps, int min_pts, csv_split_fit *out, uint32_t *big_n, unsigned long long *big_res);
+// the points of ONE set, in the reference's order, to global memory (the sets too large for LDS)
+void launch_sf_big_points(hipStream_t s, const SplitFitsIn &in, uint32_t w, int32_t *pts);
+// largest cluster and median of one labelled set: pts_sorted / oid as launch_dbscan_1d_big takes them, labels by original index; sizes[n] zeroed
+void launch_sf_big_reduce(hipStream_t s, const int32_t *pts_sorted, const uint32_t *oid, const int32_t *labels, uint32_t n, uint32_t *sizes,
+                          csv_split_fit *rec, int set);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

@@ -1510,6 +1510,116 @@ int csvgpu_split_order(csv_ctx *ctx, int n_contigs, csv_shard *const *shards, ui
 
 // The overlap groups that the order seeds (kernels/splitgroups.hip). One wait sizes the answer (members, groups, error word); the second is the
 // answer's own copy. Everything in front of the first wait is queued without the host looking at the device.
+// The chain in three steps, so that csvgpu_split_groups_fits can leave the groups where they lie: sg_queue reserves ctx->arena (+ arena_extra for
+// the caller's own arrays, carved after it returns) and the page-locked block (+ pin_extra, continued at pin_used), stages the intervals and queues
+// everything up to the copy of the three result words; sg_wait waits and reads them; sg_fill_reserve reserves ctx->work (+ work_extra), sg_fill_launch
+// queues the member lists' sort.
+struct SgChain {
+    SplitGroupsWs w;
+    SortWs sw;
+    int32_t *d_start = nullptr, *d_end = nullptr;
+    uint64_t *d_seg = nullptr;
+    uint32_t n = 0;
+    uint64_t n_seg = 0, max_len = 0;
+    volatile uint64_t *h_res = nullptr;
+    size_t pin_used = 0;
+    uint64_t total = 0, n_groups = 0;
+    const uint32_t *d_members = nullptr;       // after sg_fill
+    const uint32_t *sort_flag = nullptr;       // the fill sort's gave-up word (device), or null
+};
+
+static int sg_queue(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, uint64_t max_len,
+                    size_t arena_extra, size_t pin_extra, SgChain &c)
+{
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    int rc;
+    c.n = n; c.n_seg = n_seg; c.max_len = max_len;
+    const size_t n4 = align_up(((size_t)n + 1) * 4, 256), nb = align_up((size_t)n / 64 * 4 + 4, 256), n1 = align_up((size_t)n, 256);
+    const size_t segb = align_up((n_seg + 1) * 8, 256);
+    const size_t zero_bytes = 3 * n4 + n1 + 256;             // hist, cnt, keep, state, total + err
+    const size_t need = 2 * n4 + segb                        /* start, end, seg_off */
+                        + sortws_bytes(n)
+                        + 10 * n4 + 2 * nb + n1              /* ss se sid posof plo lp1 cstart cend seed_of_group pm; block summaries; head */
+                        + align_up(((size_t)n + 1) * 8, 256) + segb + 256   /* group_off, seg_group_off, res */
+                        + zero_bytes + exclusive_sum_tmp_bytes((uint64_t)n + 1) + 16 * 256;
+    if ((rc = arena_reserve(ctx, ctx->arena, need + arena_extra))) return rc;
+    Arena &A = ctx->arena;
+    SplitGroupsWs &w = c.w;
+    SortWs &sw = c.sw;
+    int32_t *d_start = c.d_start = (int32_t *)arena_alloc(A, (size_t)n * 4), *d_end = c.d_end = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    uint64_t *d_seg = c.d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    const bool sort_ok = sortws_carve(A, n, sw);
+    w.ss = (int32_t *)arena_alloc(A, (size_t)n * 4); w.se = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    w.sid = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.posof = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.plo = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.lp1 = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.cstart = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.cend = (uint32_t *)arena_alloc(A, (size_t)n * 4);
+    w.seed_of_group = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.pm = (int32_t *)arena_alloc(A, (size_t)n * 4);
+    w.blk_min_id = (uint32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4); w.blk_max_end = (int32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4);
+    w.head = (uint8_t *)arena_alloc(A, n);
+    w.group_off = (uint64_t *)arena_alloc(A, ((size_t)n + 1) * 8); w.seg_group_off = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    w.res = (uint64_t *)arena_alloc(A, 256);
+    char *zero = (char *)arena_alloc(A, zero_bytes);
+    void *es_tmp = arena_alloc(A, exclusive_sum_tmp_bytes((uint64_t)n + 1));
+    if (!d_start || !d_end || !d_seg || !sort_ok || !w.seed_of_group || !w.pm || !w.blk_max_end || !w.head || !w.seg_group_off || !w.res || !zero || !es_tmp) {
+        ctx->err = "arena exhausted (split_groups)"; return CSV_ENOMEM;
+    }
+    w.hist = (uint32_t *)zero; w.cnt = (uint32_t *)(zero + n4); w.keep = (uint32_t *)(zero + 2 * n4);
+    w.state = (uint8_t *)(zero + 3 * n4);
+    w.total = (unsigned long long *)(zero + 3 * n4 + n1); w.err = (uint32_t *)(zero + 3 * n4 + n1 + 64);
+
+    if ((rc = ensure_pinned(ctx, 2 * PinStage::need((size_t)n * 4) + PinStage::need((n_seg + 1) * 8) + 4096 + pin_extra))) return rc;
+    PinStage pin(ctx);
+    CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    c.h_res = (volatile uint64_t *)((char *)ctx->pinned + pin.used);
+    c.pin_used = pin.used + 256;
+    const int key_bits = 32 + bits_of(n_seg - 1);
+    const bool one_launch = onesweep(ctx);
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
+        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
+        launch_sg_keys(s, d_start, d_seg, n_seg, n, sw.k0, sw.v0);
+        const int io = launch_radix_sort_u64(s, sw.k0, sw.v0, sw.k1, sw.v1, n, key_bits, sw.tmp, one_launch);
+        launch_sg_links(s, w, io ? sw.k1 : sw.k0, io ? sw.v1 : sw.v0, d_start, d_end, d_seg, n);
+        launch_exclusive_sum_u32(s, w.hist, (uint64_t)n + 1, es_tmp);
+        launch_sg_seeds(s, w, n);
+        launch_exclusive_sum_u32(s, w.cnt, (uint64_t)n + 1, es_tmp);
+        launch_exclusive_sum_u32(s, w.keep, (uint64_t)n + 1, es_tmp);
+        launch_sg_offsets(s, w, d_seg, n_seg, n, radix_sort_gave_up(sw.tmp, n, key_bits, one_launch));
+        CSV_HIP(ctx, hipMemcpyAsync((void *)c.h_res, w.res, 24, hipMemcpyDeviceToHost, s));
+    }
+    return CSV_OK;
+}
+
+static int sg_wait(csv_ctx *ctx, SgChain &c)
+{
+    CSV_HIP(ctx, wait_stream(ctx->stream));
+    c.total = c.h_res[0]; c.n_groups = c.h_res[1];
+    if (c.h_res[2]) { ctx->err = "split_groups: a bounded device loop gave up (radix look-back or seeding rounds)"; return CSV_EHIP; }
+    if (c.n_groups > c.n || c.total < 2 * c.n_groups) { ctx->err = "split_groups: counts out of range"; return CSV_EHIP; }
+    return CSV_OK;
+}
+
+// ---- the members: (group ‖ pre) keys, one stable sort for every group of the call ---------------------------------------------------------
+static int sg_fill_reserve(csv_ctx *ctx, SgChain &c, size_t work_extra, SortWs &fw)
+{
+    int rc;
+    if ((rc = arena_reserve(ctx, ctx->work, sortws_bytes(c.total) + 1024 + work_extra))) return rc;
+    if (!sortws_carve(ctx->work, c.total, fw)) { ctx->err = "arena exhausted (split_groups fill)"; return CSV_ENOMEM; }
+    return CSV_OK;
+}
+static void sg_fill_launch(csv_ctx *ctx, SgChain &c, SortWs &fw)
+{
+    const int pre_bits = std::max(1, bits_of(c.max_len - 1)), fill_bits = pre_bits + bits_of(c.n_groups - 1);
+    const bool one_launch = onesweep(ctx);
+    launch_sg_fill(ctx->stream, c.w, (uint32_t)c.n_groups, pre_bits, fw.k0, fw.v0);
+    const int io = launch_radix_sort_u64(ctx->stream, fw.k0, fw.v0, fw.k1, fw.v1, c.total, fill_bits, fw.tmp, one_launch);
+    c.d_members = io ? fw.v1 : fw.v0;
+    c.sort_flag = radix_sort_gave_up(fw.tmp, c.total, fill_bits, one_launch);
+}
+
 int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint64_t *seg_group_off,
                         uint64_t *group_off, uint32_t *members, uint64_t *n_members)
 {
@@ -1536,67 +1646,12 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
         group_off[0] = 0;
         return CSV_OK;
     }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
     int rc;
-    const size_t n4 = align_up(((size_t)n + 1) * 4, 256), nb = align_up((size_t)n / 64 * 4 + 4, 256), n1 = align_up((size_t)n, 256);
-    const size_t segb = align_up((n_seg + 1) * 8, 256);
-    const size_t zero_bytes = 3 * n4 + n1 + 256;             // hist, cnt, keep, state, total + err
-    const size_t need = 2 * n4 + segb                        /* start, end, seg_off */
-                        + sortws_bytes(n)
-                        + 10 * n4 + 2 * nb + n1              /* ss se sid posof plo lp1 cstart cend seed_of_group pm; block summaries; head */
-                        + align_up(((size_t)n + 1) * 8, 256) + segb + 256   /* group_off, seg_group_off, res */
-                        + zero_bytes + exclusive_sum_tmp_bytes((uint64_t)n + 1) + 16 * 256;
-    if ((rc = arena_reserve(ctx, ctx->arena, need))) return rc;
-    Arena &A = ctx->arena;
-    int32_t *d_start = (int32_t *)arena_alloc(A, (size_t)n * 4), *d_end = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    SortWs sw;
-    const bool sort_ok = sortws_carve(A, n, sw);
-    SplitGroupsWs w;
-    w.ss = (int32_t *)arena_alloc(A, (size_t)n * 4); w.se = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    w.sid = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.posof = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.plo = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.lp1 = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.cstart = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.cend = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.seed_of_group = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.pm = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    w.blk_min_id = (uint32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4); w.blk_max_end = (int32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4);
-    w.head = (uint8_t *)arena_alloc(A, n);
-    w.group_off = (uint64_t *)arena_alloc(A, ((size_t)n + 1) * 8); w.seg_group_off = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    w.res = (uint64_t *)arena_alloc(A, 256);
-    char *zero = (char *)arena_alloc(A, zero_bytes);
-    void *es_tmp = arena_alloc(A, exclusive_sum_tmp_bytes((uint64_t)n + 1));
-    if (!d_start || !d_end || !d_seg || !sort_ok || !w.seed_of_group || !w.pm || !w.blk_max_end || !w.head || !w.seg_group_off || !w.res || !zero || !es_tmp) {
-        ctx->err = "arena exhausted (split_groups)"; return CSV_ENOMEM;
-    }
-    w.hist = (uint32_t *)zero; w.cnt = (uint32_t *)(zero + n4); w.keep = (uint32_t *)(zero + 2 * n4);
-    w.state = (uint8_t *)(zero + 3 * n4);
-    w.total = (unsigned long long *)(zero + 3 * n4 + n1); w.err = (uint32_t *)(zero + 3 * n4 + n1 + 64);
-
-    if ((rc = ensure_pinned(ctx, 2 * PinStage::need((size_t)n * 4) + PinStage::need((n_seg + 1) * 8) + 4096))) return rc;
-    PinStage pin(ctx);
-    CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-    volatile uint64_t *h_res = (volatile uint64_t *)((char *)ctx->pinned + pin.used);
-    const int key_bits = 32 + bits_of(n_seg - 1);
-    const bool one_launch = onesweep(ctx);
-    {
-        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
-        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
-        launch_sg_keys(s, d_start, d_seg, n_seg, n, sw.k0, sw.v0);
-        const int io = launch_radix_sort_u64(s, sw.k0, sw.v0, sw.k1, sw.v1, n, key_bits, sw.tmp, one_launch);
-        launch_sg_links(s, w, io ? sw.k1 : sw.k0, io ? sw.v1 : sw.v0, d_start, d_end, d_seg, n);
-        launch_exclusive_sum_u32(s, w.hist, (uint64_t)n + 1, es_tmp);
-        launch_sg_seeds(s, w, n);
-        launch_exclusive_sum_u32(s, w.cnt, (uint64_t)n + 1, es_tmp);
-        launch_exclusive_sum_u32(s, w.keep, (uint64_t)n + 1, es_tmp);
-        launch_sg_offsets(s, w, d_seg, n_seg, n, radix_sort_gave_up(sw.tmp, n, key_bits, one_launch));
-        CSV_HIP(ctx, hipMemcpyAsync((void *)h_res, w.res, 24, hipMemcpyDeviceToHost, s));
-    }
-    CSV_HIP(ctx, wait_stream(s));
-    const uint64_t total = h_res[0], n_groups = h_res[1], bad = h_res[2];
-    if (bad) { ctx->err = "split_groups: a bounded device loop gave up (radix look-back or seeding rounds)"; return CSV_EHIP; }
-    if (n_groups > n || total < 2 * n_groups) { ctx->err = "split_groups: counts out of range"; return CSV_EHIP; }
+    SgChain ch;
+    if ((rc = sg_queue(ctx, start, end, seg_off, n_seg, n, max_len, 0, 0, ch))) return rc;
+    if ((rc = sg_wait(ctx, ch))) return rc;
+    hipStream_t s = ctx->stream;
+    const uint64_t total = ch.total, n_groups = ch.n_groups;
     *n_members = total;
     if (total > capacity) { ctx->err = "split_groups: members capacity too small"; return CSV_ECAPACITY; }
     if (total >= 0xffffffffull) { ctx->err = "split_groups: more than 2^32 - 1 entries in the answer"; *n_members = 0; return CSV_EINVAL; }
@@ -1605,11 +1660,8 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
         group_off[0] = 0;
         return CSV_OK;
     }
-    // ---- the members: (group ‖ pre) keys, one stable sort for every group of the call -----------------------------------------------------
-    if ((rc = arena_reserve(ctx, ctx->work, sortws_bytes(total) + 1024))) return rc;
     SortWs fw;
-    if (!sortws_carve(ctx->work, total, fw)) { ctx->err = "arena exhausted (split_groups fill)"; return CSV_ENOMEM; }
-    const int pre_bits = std::max(1, bits_of(max_len - 1)), fill_bits = pre_bits + bits_of(n_groups - 1);
+    if ((rc = sg_fill_reserve(ctx, ch, 0, fw))) return rc;
     constexpr size_t kPinnedOutMax = (size_t)64 << 20;       // larger answers are copied straight into the caller's array
     const bool members_pinned = total * 4 <= kPinnedOutMax;
     if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need((n_groups + 1) * 8) + (members_pinned ? PinStage::need(total * 4) : 0) + 4096))) return rc;
@@ -1619,19 +1671,287 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
     *h_sort_err = 0;
     {
         TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
-        launch_sg_fill(s, w, (uint32_t)n_groups, pre_bits, fw.k0, fw.v0);
-        const int io = launch_radix_sort_u64(s, fw.k0, fw.v0, fw.k1, fw.v1, total, fill_bits, fw.tmp, one_launch);
-        const uint32_t *d_members = io ? fw.v1 : fw.v0;
-        if (const uint32_t *flag = radix_sort_gave_up(fw.tmp, total, fill_bits, one_launch)) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, flag, 4, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(out.out(seg_group_off, (n_seg + 1) * 8), w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(out.out(group_off, (n_groups + 1) * 8), w.group_off, (n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (members_pinned) CSV_HIP(ctx, hipMemcpyAsync(out.out(members, total * 4), d_members, total * 4, hipMemcpyDeviceToHost, s));
-        else CSV_HIP(ctx, hipMemcpyAsync(members, d_members, total * 4, hipMemcpyDeviceToHost, s));
+        sg_fill_launch(ctx, ch, fw);
+        if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(out.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(out.out(group_off, (n_groups + 1) * 8), ch.w.group_off, (n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (members_pinned) CSV_HIP(ctx, hipMemcpyAsync(out.out(members, total * 4), ch.d_members, total * 4, hipMemcpyDeviceToHost, s));
+        else CSV_HIP(ctx, hipMemcpyAsync(members, ch.d_members, total * 4, hipMemcpyDeviceToHost, s));
     }
     CSV_HIP(ctx, wait_stream(s));
     if (*h_sort_err) { ctx->err = "split_groups: a radix pass's look-back gave up"; *n_members = 0; return CSV_EHIP; }
     out.finish();
     return CSV_OK;
+}
+
+// ---- the groups' evidence (kernels/splitfits.hip) ------------------------------------------------------------------------------------------
+// Everything the two entry points share: argument checks, the tables' way to the device, the launch with its one readback, and the sets too
+// large for LDS (materialised one by one, labelled by the large-segment path of csvgpu_dbscan_1d, reduced out of global memory).
+static int sf_check(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, double eps, int32_t min_pts, uint64_t &max_len)
+{
+    int rc = check_dbscan_args(ctx, eps, min_pts, false);
+    if (rc) return rc;
+    if (!t || !seg_off) { ctx->err = "split_fits: null array"; return CSV_EINVAL; }
+    if (ctx->split_state) { ctx->err = "split_fits: a split order is pending on this context"; return CSV_EINVAL; }
+    if (n_seg >= 0xffffffffull) { ctx->err = "split_fits: too many segments"; return CSV_EINVAL; }
+    if (seg_off[0] != 0) { ctx->err = "split_fits: seg_off[0] must be 0"; return CSV_EINVAL; }
+    max_len = 0;
+    for (uint64_t c = 0; c < n_seg; c++) {
+        if (seg_off[c + 1] < seg_off[c]) { ctx->err = "split_fits: seg_off not ascending"; return CSV_EINVAL; }
+        max_len = std::max(max_len, seg_off[c + 1] - seg_off[c]);
+    }
+    const uint64_t nm = t->n_members, ns = t->n_supp;
+    if (seg_off[n_seg] != nm) { ctx->err = "split_fits: seg_off does not end at the tables' member count"; return CSV_EINVAL; }
+    if (nm >= 0xffffffffull || ns >= 0xffffffffull) { ctx->err = "split_fits: more than 2^32 - 1 members or supplementary records"; return CSV_EINVAL; }
+    if (!t->supp_off || (nm && (!t->start || !t->end || !t->q_start || !t->q_end || !t->reverse)) ||
+        (ns && (!t->supp_start || !t->supp_end || !t->supp_q_start || !t->supp_q_end || !t->supp_flags))) { ctx->err = "split_fits: null array in the tables"; return CSV_EINVAL; }
+    if (t->supp_off[0] != 0 || t->supp_off[nm] != ns) { ctx->err = "split_fits: supp_off must run from 0 to n_supp"; return CSV_EINVAL; }
+    for (uint64_t m = 0; m < nm; m++) {
+        if (t->supp_off[m + 1] < t->supp_off[m]) { ctx->err = "split_fits: supp_off not ascending"; return CSV_EINVAL; }
+        if (t->start[m] < 0 || t->q_start[m] < 0 || t->q_end[m] < 0 || t->end[m] < t->start[m]) { ctx->err = "split_fits: a member's coordinate is negative or end < start"; return CSV_EINVAL; }
+    }
+    for (uint64_t z = 0; z < ns; z++) {
+        if (t->supp_flags[z] & 2u) continue;                 // another tid: only the flags are read
+        if (t->supp_start[z] < 0 || t->supp_q_start[z] < 0 || t->supp_q_end[z] < 0 || t->supp_end[z] < t->supp_start[z]) {
+            ctx->err = "split_fits: a supplementary record's coordinate is negative or end < start"; return CSV_EINVAL;
+        }
+    }
+    return CSV_OK;
+}
+
+static size_t sf_tables_bytes(uint64_t nm, uint64_t ns, bool with_start_end)      // (false: start / end are the chain's own copies)
+{
+    return (with_start_end ? 4 : 2) * align_up(nm * 4, 256) + align_up(nm, 256) + align_up((nm + 1) * 8, 256) + 4 * align_up(ns * 4, 256) + align_up(ns, 256) + 12 * 256;
+}
+// (page-locked bytes: the same slices, PinStage::need rounds like align_up(, 256))
+
+// start / end already on the device (the chain's copies): d_start, d_end given
+static int sf_upload(csv_ctx *ctx, Arena &A, PinStage &pin, const csv_split_tables *t, const int32_t *d_start, const int32_t *d_end, SplitFitsIn &in)
+{
+    const uint64_t nm = t->n_members, ns = t->n_supp;
+    hipStream_t s = ctx->stream;
+    bool room = true;
+    hipError_t err = hipSuccess;
+    auto up = [&](const void *src, size_t bytes) -> const void * {
+        void *d = arena_alloc(A, bytes);
+        if (!d) { room = false; return nullptr; }
+        if (bytes && err == hipSuccess) err = hipMemcpyAsync(d, pin.in(src, bytes), bytes, hipMemcpyHostToDevice, s);
+        return d;
+    };
+    in.start = d_start ? d_start : (const int32_t *)up(t->start, nm * 4);
+    in.end = d_end ? d_end : (const int32_t *)up(t->end, nm * 4);
+    in.q_start = (const int32_t *)up(t->q_start, nm * 4); in.q_end = (const int32_t *)up(t->q_end, nm * 4);
+    in.reverse = (const uint8_t *)up(t->reverse, nm);
+    in.supp_off = (const uint64_t *)up(t->supp_off, (nm + 1) * 8);
+    in.supp_start = (const int32_t *)up(t->supp_start, ns * 4); in.supp_end = (const int32_t *)up(t->supp_end, ns * 4);
+    in.supp_q_start = (const int32_t *)up(t->supp_q_start, ns * 4); in.supp_q_end = (const int32_t *)up(t->supp_q_end, ns * 4);
+    in.supp_flags = (const uint8_t *)up(t->supp_flags, ns);
+    if (!room) { ctx->err = "arena exhausted (split_fits tables)"; return CSV_ENOMEM; }
+    if (err != hipSuccess) { ctx->err = std::string("split_fits: copying the tables: ") + hipGetErrorString(err); return CSV_EHIP; }
+    return CSV_OK;
+}
+
+static size_t sf_big_bytes(uint64_t B)
+{
+    return B > DBSCAN1D_MAX_SEG ? sortws_bytes(B) + dbscan1d_big_tmp_bytes(B) + 4 * align_up(B * 4, 256) + 8 * 256 : 0;
+}
+static size_t sf_out_bytes(uint64_t n_groups) { return align_up(n_groups * sizeof(csv_split_fit), 256) + align_up(n_groups * 6 * 4, 256) + 4 * 256; }
+
+struct SfRun {
+    SplitFitsIn in;
+    Arena *A = nullptr;                        // holds sf_out_bytes(n_groups) + sf_big_bytes(B) for this run
+    uint64_t B = 0;                            // no set has more points
+    csv_split_fit *d_out = nullptr;
+    uint32_t *d_big_n = nullptr;
+    unsigned long long *d_res = nullptr;
+    volatile uint64_t *h_res = nullptr;        // sets and points beyond the LDS kernel
+};
+
+// the launch and the copies of the records and the two counters into the page-locked block; the caller adds its own copies and waits
+static int sf_queue(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, PinStage &pin, csv_split_fit *out)
+{
+    const uint64_t G = r.in.n_groups;
+    hipStream_t s = ctx->stream;
+    r.d_out = (csv_split_fit *)arena_alloc(*r.A, G * sizeof(csv_split_fit));
+    r.d_big_n = (uint32_t *)arena_alloc(*r.A, G * 6 * 4);
+    r.d_res = (unsigned long long *)arena_alloc(*r.A, 256);
+    if (!r.d_out || !r.d_big_n || !r.d_res) { ctx->err = "arena exhausted (split_fits)"; return CSV_ENOMEM; }
+    r.h_res = (volatile uint64_t *)pin.in(nullptr, 0);
+    pin.used += 256;
+    TimerScope ts(ctx, CSV_K_SPLIT_FITS);
+    CSV_HIP(ctx, hipMemsetAsync(r.d_big_n, 0, G * 6 * 4, s));
+    CSV_HIP(ctx, hipMemsetAsync(r.d_res, 0, 16, s));
+    launch_sf_fits(s, r.in, eps, min_pts, r.d_out, r.d_big_n, r.d_res);
+    CSV_HIP(ctx, hipMemcpyAsync((void *)r.h_res, r.d_res, 16, hipMemcpyDeviceToHost, s));
+    CSV_HIP(ctx, hipMemcpyAsync(pin.out(out, G * sizeof(csv_split_fit)), r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
+    return CSV_OK;
+}
+
+// after the wait, when r.h_res[0] sets were too large for LDS (the page-locked block is free again: its outputs have been taken)
+static int sf_big(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, csv_split_fit *out)
+{
+    const uint64_t n_big = r.h_res[0], G = r.in.n_groups, B = r.B;
+    hipStream_t s = ctx->stream;
+    int rc;
+    std::vector<uint32_t> big_n(G * 6);
+    CSV_HIP(ctx, hipMemcpyAsync(big_n.data(), r.d_big_n, G * 6 * 4, hipMemcpyDeviceToHost, s));
+    CSV_HIP(ctx, wait_stream(s));
+    if (B <= DBSCAN1D_MAX_SEG) { ctx->err = "split_fits: a set larger than its bound"; return CSV_EHIP; }
+    Arena &A = *r.A;
+    int32_t *pts = (int32_t *)arena_alloc(A, B * 4), *ks = (int32_t *)arena_alloc(A, B * 4), *labels = (int32_t *)arena_alloc(A, B * 4);
+    uint32_t *sizes = (uint32_t *)arena_alloc(A, B * 4);
+    void *tmp = arena_alloc(A, dbscan1d_big_tmp_bytes(B));
+    SortWs w;
+    if (!sortws_carve(A, B, w) || !pts || !ks || !labels || !sizes || !tmp) { ctx->err = "arena exhausted (split_fits, large sets)"; return CSV_ENOMEM; }
+    if ((rc = ensure_pinned(ctx, PinStage::need(G * sizeof(csv_split_fit)) + PinStage::need(n_big * 4) + 4096))) return rc;
+    PinStage pin(ctx);
+    uint32_t *h_flags = (uint32_t *)pin.in(nullptr, 0);
+    pin.used += PinStage::need(n_big * 4);
+    memset(h_flags, 0, n_big * 4);
+    const bool one_launch = onesweep(ctx);
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_FITS);
+        uint64_t k = 0;
+        for (uint64_t item = 0; item < G * 6; item++) {
+            const uint32_t n = big_n[item];
+            if (!n) continue;
+            if (n > B || n <= DBSCAN1D_MAX_SEG || k >= n_big) { ctx->err = "split_fits: large-set counts out of range"; return CSV_EHIP; }
+            launch_sf_big_points(s, r.in, (uint32_t)item, pts);
+            launch_iota_keys_i32(s, pts, n, w.k0, w.v0);
+            const int io = launch_radix_sort_u64(s, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp, one_launch);
+            const uint32_t *perm = io ? w.v1 : w.v0;
+            if (const uint32_t *flag = radix_sort_gave_up(w.tmp, n, 32, one_launch)) CSV_HIP(ctx, hipMemcpyAsync(h_flags + k, flag, 4, hipMemcpyDeviceToHost, s));
+            launch_gather_u32(s, (const uint32_t *)pts, perm, n, (uint32_t *)ks);
+            launch_dbscan_1d_big(s, ks, perm, n, eps, min_pts, labels, tmp);
+            CSV_HIP(ctx, hipMemsetAsync(sizes, 0, (size_t)n * 4, s));
+            launch_sf_big_reduce(s, ks, perm, labels, n, sizes, r.d_out + item / 6, (int)(item % 6));
+            k++;
+        }
+        CSV_HIP(ctx, hipMemcpyAsync(pin.out(out, G * sizeof(csv_split_fit)), r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
+    }
+    CSV_HIP(ctx, wait_stream(s));
+    for (uint64_t k = 0; k < n_big; k++) if (h_flags[k]) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
+    pin.finish();
+    return CSV_OK;
+}
+
+int csvgpu_split_fits(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, const uint64_t *seg_group_off,
+                      const uint64_t *group_off, const uint32_t *members, double eps, int32_t min_pts, csv_split_fit *out)
+{
+    if (!ctx) return CSV_EINVAL;
+    uint64_t max_len = 0;
+    int rc = sf_check(ctx, t, seg_off, n_seg, eps, min_pts, max_len);
+    if (rc) return rc;
+    if (!seg_group_off || !group_off) { ctx->err = "split_fits: null array"; return CSV_EINVAL; }
+    if (seg_group_off[0] != 0 || group_off[0] != 0) { ctx->err = "split_fits: group offsets must start at 0"; return CSV_EINVAL; }
+    for (uint64_t c = 0; c < n_seg; c++) if (seg_group_off[c + 1] < seg_group_off[c]) { ctx->err = "split_fits: seg_group_off not ascending"; return CSV_EINVAL; }
+    const uint64_t G = seg_group_off[n_seg];
+    if (G > t->n_members) { ctx->err = "split_fits: more groups than members"; return CSV_EINVAL; }
+    uint64_t max_group = 0;
+    for (uint64_t g = 0; g < G; g++) {
+        if (group_off[g + 1] < group_off[g]) { ctx->err = "split_fits: group_off not ascending"; return CSV_EINVAL; }
+        max_group = std::max(max_group, group_off[g + 1] - group_off[g]);
+    }
+    if (G == 0) return CSV_OK;
+    const uint64_t total = group_off[G];
+    if (total >= 0xffffffffull) { ctx->err = "split_fits: more than 2^32 - 1 entries in the groups"; return CSV_EINVAL; }
+    if (!out || (total && !members)) { ctx->err = "split_fits: null array"; return CSV_EINVAL; }
+    {   // members: inside their segment, and distinct within a group (a group is a set of reads; the large-set bound below counts on it)
+        std::vector<uint64_t> seen(max_len, 0);              // by member of the current segment: the last group (+ 1) that held it
+        for (uint64_t c = 0; c < n_seg; c++) {
+            const uint64_t len = seg_off[c + 1] - seg_off[c];
+            for (uint64_t g = seg_group_off[c]; g < seg_group_off[c + 1]; g++)
+                for (uint64_t q = group_off[g]; q < group_off[g + 1]; q++) {
+                    if (members[q] >= len) { ctx->err = "split_fits: a member index outside its segment"; return CSV_EINVAL; }
+                    if (seen[members[q]] == g + 1) { ctx->err = "split_fits: a member twice in one group"; return CSV_EINVAL; }
+                    seen[members[q]] = g + 1;
+                }
+        }
+    }
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    const uint64_t nm = t->n_members, ns = t->n_supp;
+    SfRun r;
+    r.B = std::max(max_group, ns);
+    const size_t segb = align_up((n_seg + 1) * 8, 256), gob = align_up((G + 1) * 8, 256), memb = align_up(total * 4, 256);
+    if ((rc = arena_reserve(ctx, ctx->arena, sf_tables_bytes(nm, ns, true) + 2 * segb + gob + memb + sf_out_bytes(G) + sf_big_bytes(r.B) + 1024))) return rc;
+    if ((rc = ensure_pinned(ctx, sf_tables_bytes(nm, ns, true) + 2 * segb + gob + memb + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
+    Arena &A = ctx->arena;
+    r.A = &A;
+    PinStage pin(ctx);
+    if ((rc = sf_upload(ctx, A, pin, t, nullptr, nullptr, r.in))) return rc;
+    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8), *d_sgo = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    uint64_t *d_go = (uint64_t *)arena_alloc(A, (G + 1) * 8);
+    uint32_t *d_mem = (uint32_t *)arena_alloc(A, total * 4);
+    if (!d_seg || !d_sgo || !d_go || !d_mem) { ctx->err = "arena exhausted (split_fits)"; return CSV_ENOMEM; }
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_sgo, pin.in(seg_group_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_go, pin.in(group_off, (G + 1) * 8), (G + 1) * 8, hipMemcpyHostToDevice, s));
+    if (total) CSV_HIP(ctx, hipMemcpyAsync(d_mem, pin.in(members, total * 4), total * 4, hipMemcpyHostToDevice, s));
+    r.in.seg_off = d_seg; r.in.seg_group_off = d_sgo; r.in.group_off = d_go; r.in.members = d_mem;
+    r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
+    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
+    CSV_HIP(ctx, wait_stream(s));
+    pin.finish();
+    if (r.h_res[0] == 0) return CSV_OK;
+    return sf_big(ctx, r, eps, min_pts, out);
+}
+
+int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, double eps, int32_t min_pts,
+                             uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups)
+{
+    if (!ctx) return CSV_EINVAL;
+    uint64_t max_len = 0;
+    int rc = sf_check(ctx, t, seg_off, n_seg, eps, min_pts, max_len);
+    if (rc) return rc;
+    if (!seg_group_off || !n_groups) { ctx->err = "split_fits: null array"; return CSV_EINVAL; }
+    const uint64_t nm = t->n_members, ns = t->n_supp;
+    if (nm && !out) { ctx->err = "split_fits: null array"; return CSV_EINVAL; }
+    *n_groups = 0;
+    if (nm == 0 || max_len < 2) {                            // no segment can hold a group of two
+        for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
+        return CSV_OK;
+    }
+    hipStream_t s = ctx->stream;
+    SgChain ch;
+    if ((rc = sg_queue(ctx, t->start, t->end, seg_off, n_seg, (uint32_t)nm, max_len, sf_tables_bytes(nm, ns, false), sf_tables_bytes(nm, ns, false), ch))) return rc;
+    SfRun r;
+    {   // the tables travel while the chain runs
+        PinStage pin(ctx);
+        pin.used = ch.pin_used;
+        if ((rc = sf_upload(ctx, ctx->arena, pin, t, ch.d_start, ch.d_end, r.in))) { (void)wait_stream(s); return rc; }
+    }
+    if ((rc = sg_wait(ctx, ch))) return rc;
+    const uint64_t G = ch.n_groups, total = ch.total;
+    if (total >= 0xffffffffull) { ctx->err = "split_fits: more than 2^32 - 1 entries in the groups"; return CSV_EINVAL; }
+    if (G == 0) {
+        for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
+        return CSV_OK;
+    }
+    r.B = std::max(std::min(total, max_len), ns);
+    SortWs fw;
+    if ((rc = sg_fill_reserve(ctx, ch, sf_out_bytes(G) + sf_big_bytes(r.B), fw))) return rc;
+    r.A = &ctx->work;
+    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
+    PinStage pin(ctx);
+    uint32_t *h_sort_err = (uint32_t *)pin.in(nullptr, 0);
+    pin.used += 256;
+    *h_sort_err = 0;
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
+        sg_fill_launch(ctx, ch, fw);
+        if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(pin.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
+    r.in.seg_off = ch.d_seg; r.in.seg_group_off = ch.w.seg_group_off; r.in.group_off = ch.w.group_off; r.in.members = ch.d_members;
+    r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
+    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
+    CSV_HIP(ctx, wait_stream(s));
+    if (*h_sort_err) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
+    pin.finish();
+    *n_groups = G;
+    if (r.h_res[0] == 0) return CSV_OK;
+    return sf_big(ctx, r, eps, min_pts, out);
 }
 
 int csvgpu_window_log2_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *region_start, const uint32_t *region_end,

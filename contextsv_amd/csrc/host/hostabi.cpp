@@ -321,9 +321,11 @@ struct csvhost_split_call { uint32_t start, end; int32_t sv_type, cluster_size, 
 
 // records in file order; qname = "r<qname_id>". Output sorted by contig id, each contig's calls in the reference's order.
 // device_groups != 0: the overlap groups come from csvgpu_split_groups on `ctx` (SplitParams::device_groups) instead of the host tree.
-int csvhost_split_signatures_opts(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
-                                  const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
-                                  int min_mapq, int device_groups, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
+// device_fits != 0: the groups' point sets, fits, largest clusters and medians come from csvgpu_split_fits (SplitParams::device_fits) — with both
+// set, groups and fits from csvgpu_split_groups_fits.
+int csvhost_split_signatures_dev(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
+                                 const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
+                                 int min_mapq, int device_groups, int device_fits, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
 {
     GUARD({
         csvhost::set_context(ctx);
@@ -337,6 +339,8 @@ int csvhost_split_signatures_opts(csv_ctx *ctx, uint64_t n, const int32_t *tid, 
         SplitParams p; p.min_mapq = min_mapq;
         std::unique_ptr<SplitGroupSource> dev_groups;
         if (device_groups) { dev_groups = makeDeviceGroupSource(ctx); p.device_groups = dev_groups.get(); }
+        std::unique_ptr<SplitFitSource> dev_fits;
+        if (device_fits) { dev_fits = makeDeviceFitSource(ctx); p.device_fits = dev_fits.get(); }
         std::unordered_map<std::string, std::vector<SVCall>> calls;
         findSplitSVSignatures(rec, qn, targets, p, calls);
         uint64_t k = 0;
@@ -350,6 +354,13 @@ int csvhost_split_signatures_opts(csv_ctx *ctx, uint64_t n, const int32_t *tid, 
         }
         *n_out = k;
     })
+}
+
+int csvhost_split_signatures_opts(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
+                                  const int32_t *ref_end, const int32_t *q_start, const int32_t *q_end, const uint32_t *qname_id, int n_targets,
+                                  int min_mapq, int device_groups, csvhost_split_call *out, uint64_t cap, uint64_t *n_out)
+{
+    return csvhost_split_signatures_dev(ctx, n, tid, pos, flag, mapq, ref_end, q_start, q_end, qname_id, n_targets, min_mapq, device_groups, 0, out, cap, n_out);
 }
 
 int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq,
@@ -375,6 +386,32 @@ int csvhost_split_groups_host(const int32_t *start, const int32_t *end, const ui
         std::copy(sgo.begin(), sgo.end(), seg_group_off);
         std::copy(go.begin(), go.end(), group_off);
         std::copy(mem.begin(), mem.end(), members);
+        return 0;
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return CSV_EINVAL;
+    } catch (const std::exception &e) { g_err = e.what(); return -100; }
+}
+
+// The records of csvgpu_split_fits by the host route (splitFitsHost: point sets and reductions on this thread, one csvgpu_dbscan_1d batch on `ctx`);
+// out[seg_group_off[n_seg]] records of 64 bytes (csv_split_fit). -1 (CSV_EINVAL) on tables that do not fit.
+int csvhost_split_fits_host(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, const uint64_t *seg_group_off, const uint64_t *group_off,
+                            const uint32_t *members, double eps, int min_pts, csv_split_fit *out)
+{
+    try {
+        csvhost::set_context(ctx);
+        static_assert(sizeof(SplitFit) == sizeof(csv_split_fit), "SplitFit is csv_split_fit");
+        SplitFitTables T;
+        const uint64_t nm = t->n_members, ns = t->n_supp;
+        T.start.assign(t->start, t->start + nm); T.end.assign(t->end, t->end + nm); T.q_start.assign(t->q_start, t->q_start + nm); T.q_end.assign(t->q_end, t->q_end + nm);
+        T.reverse.assign(t->reverse, t->reverse + nm); T.supp_off.assign(t->supp_off, t->supp_off + nm + 1);
+        T.supp_start.assign(t->supp_start, t->supp_start + ns); T.supp_end.assign(t->supp_end, t->supp_end + ns);
+        T.supp_q_start.assign(t->supp_q_start, t->supp_q_start + ns); T.supp_q_end.assign(t->supp_q_end, t->supp_q_end + ns);
+        T.supp_flags.assign(t->supp_flags, t->supp_flags + ns);
+        const uint64_t n_groups = seg_group_off[n_seg];
+        std::vector<uint64_t> so(seg_off, seg_off + n_seg + 1), sgo(seg_group_off, seg_group_off + n_seg + 1), go(group_off, group_off + n_groups + 1);
+        std::vector<uint32_t> mem(members, members + go[n_groups]);
+        std::vector<SplitFit> fits;
+        splitFitsHost(T, so, sgo, go, mem, eps, min_pts, fits);
+        if (!fits.empty()) memcpy(out, fits.data(), fits.size() * sizeof(SplitFit));
         return 0;
     } catch (const std::invalid_argument &e) { g_err = e.what(); return CSV_EINVAL;
     } catch (const std::exception &e) { g_err = e.what(); return -100; }
@@ -708,7 +745,8 @@ void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n
 
 // One step: SVCaller::runResident over every staged contig. passes: bit 0 split-read pass, bit 1 CIGAR copy-number pass, bit 2 the two
 // final merges, bit 3 keep the qname map's order on the host (umap_order.h) instead of csvgpu_split_order,
-// bit 4 do not run the split pass's first half beside the CIGAR pass; bit 9 the overlap groups from csvgpu_split_groups (split_groups_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
+// bit 4 do not run the split pass's first half beside the CIGAR pass; bit 9 the overlap groups from csvgpu_split_groups (split_groups_on_device), bit 10 the groups' fits from csvgpu_split_fits
+// (split_fits_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
 // (0 timed, 1 none, 2 all at once, 3 every three), bit 7 no split chain beside the pass, bit 8 the two-call split order, bits 16-30
 // prepare_delay_ms. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
 int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *const *lane_ctxs, const csv_hmm *hmm, double eps, double min_pts_pct,
@@ -732,6 +770,7 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         P.schedule.split_beside_pass = (passes & 128) == 0;
         P.schedule.split_order_self = (passes & 256) == 0;
         P.split_groups_on_device = (passes & 512) != 0;
+        P.split_fits_on_device = (passes & 1024) != 0;
         P.schedule.prepare_delay_ms = (passes >> 16) & 0x7fff;
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);

@@ -132,6 +132,8 @@ struct ContigWork {
     std::vector<uint64_t> group_off;                   // the overlap groups between their synthesis and the point sets: [n_groups + 1] into group_mem
     std::vector<uint32_t> group_mem;                   // members (indices into `member`) in findOverlaps' traversal order
     std::vector<Group> groups;
+    std::vector<SplitFit> fits;                        // with SplitParams::device_fits: one per group, instead of `groups`
+    bool have_fits = false;
     size_t set_base = 0;                           // first of this contig's point sets in the genome-wide batch
     size_t n_primary = 0;
     std::vector<SVCall> calls;
@@ -160,6 +162,8 @@ struct SplitPass::Impl {
     void setsOf(size_t c);
     void groupsOf(size_t c, bool trace);
     void groupsOnDevice(const std::vector<size_t> &ids);
+    void fitsOnDevice(const std::vector<size_t> &ids);
+    void groupWork(const std::vector<size_t> &ids, bool trace);
     void finishEarly(const std::vector<size_t> &ids);
     void finishFor(const std::vector<size_t> &ids, std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
     Impl(const std::vector<SplitContig> &c, const std::vector<std::string> &t, const SplitParams &p) : contigs(c), target_names(t), params(p) {}
@@ -475,6 +479,73 @@ void SplitPass::Impl::groupsOnDevice(const std::vector<size_t> &ids)
     });
 }
 
+// With SplitParams::device_fits: members of all contigs in parallel, their tables flattened (segment k = contig ids[k]), ONE fits() call for the batch —
+// on the groups of the host tree, or, with device_groups also set, on groups that the source computes itself and keeps — and the records kept per contig.
+// Neither setsOf nor the DBSCAN1D batch runs for these contigs.
+void SplitPass::Impl::fitsOnDevice(const std::vector<size_t> &ids)
+{
+    if (ids.empty()) return;
+    std::unique_ptr<csvhost::TraceScope> t2(new csvhost::TraceScope("split: fits members"));
+    const bool fused = params.device_groups != nullptr;
+    parallel_over(ids.size(), params.threads, [&](size_t k) { membersOf(ids[k]); if (!fused) hostGroupsOf(ids[k], false); });
+    std::vector<uint64_t> seg_off(ids.size() + 1, 0), supp_base(ids.size() + 1, 0), seg_group_off(ids.size() + 1, 0), mem_base(ids.size() + 1, 0);
+    for (size_t k = 0; k < ids.size(); k++) {
+        const ContigWork &W = work[ids[k]];
+        seg_off[k + 1] = seg_off[k] + W.member.size();
+        supp_base[k + 1] = supp_base[k] + W.member_supps.size();
+        if (!fused) { seg_group_off[k + 1] = seg_group_off[k] + (W.group_off.size() - 1); mem_base[k + 1] = mem_base[k] + W.group_mem.size(); }
+    }
+    SplitFitTables T;
+    const size_t nm = seg_off.back(), ns = supp_base.back();
+    T.start.resize(nm); T.end.resize(nm); T.q_start.resize(nm); T.q_end.resize(nm); T.reverse.resize(nm); T.supp_off.resize(nm + 1);
+    T.supp_start.resize(ns); T.supp_end.resize(ns); T.supp_q_start.resize(ns); T.supp_q_end.resize(ns); T.supp_flags.resize(ns);
+    std::vector<uint64_t> group_off(fused ? 0 : seg_group_off.back() + 1, 0);
+    std::vector<uint32_t> members(fused ? 0 : mem_base.back());
+    parallel_over(ids.size(), params.threads, [&](size_t k) {
+        const ContigWork &W = work[ids[k]];
+        const int primary_tid = W.in->tid;
+        for (size_t m = 0; m < W.member.size(); m++) {
+            const PrimaryAlignment &p = W.member[m];
+            const size_t at = seg_off[k] + m;
+            T.start[at] = p.start; T.end[at] = p.end; T.q_start[at] = p.query_start; T.q_end[at] = p.query_end; T.reverse[at] = p.strand ? 0 : 1;
+            T.supp_off[at] = supp_base[k] + (m ? W.member_supp_off[m - 1] : 0);
+        }
+        for (size_t z = 0; z < W.member_supps.size(); z++) {
+            const SuppAlignment &s = W.member_supps[z];
+            const size_t at = supp_base[k] + z;
+            T.supp_start[at] = s.start; T.supp_end[at] = s.end; T.supp_q_start[at] = s.query_start; T.supp_q_end[at] = s.query_end;
+            T.supp_flags[at] = (uint8_t)((s.strand ? 0 : 1) | (s.tid != primary_tid ? 2 : 0));
+        }
+        if (!fused) {
+            for (size_t g = 0; g + 1 < W.group_off.size(); g++) group_off[seg_group_off[k] + g + 1] = mem_base[k] + W.group_off[g + 1];
+            std::copy(W.group_mem.begin(), W.group_mem.end(), members.begin() + (std::ptrdiff_t)mem_base[k]);
+        }
+    });
+    T.supp_off[nm] = ns;
+    t2.reset(new csvhost::TraceScope("split: fits on device"));
+    std::vector<uint64_t> sgo;
+    std::vector<SplitFit> fits;
+    const SplitFitSource::Groups given{&seg_group_off, &group_off, &members};
+    params.device_fits->fits(T, seg_off, fused ? nullptr : &given, params.eps, params.min_pts, sgo, fits);
+    if (sgo.size() != ids.size() + 1 || fits.size() < sgo.back() || (!fused && sgo != seg_group_off))
+        throw std::runtime_error("findSplitSVSignatures: the fit source returned tables of the wrong size");
+    for (size_t k = 0; k < ids.size(); k++) {
+        ContigWork &W = work[ids[k]];
+        if (sgo[k + 1] < sgo[k]) throw std::runtime_error("findSplitSVSignatures: the fit source's group offsets descend");
+        W.fits.assign(fits.begin() + (std::ptrdiff_t)sgo[k], fits.begin() + (std::ptrdiff_t)sgo[k + 1]);
+        W.have_fits = true;
+        W.group_off = {}; W.group_mem = {};
+    }
+}
+
+// intervals gathered: the groups (and, with device_fits, everything up to the medians) of these contigs, by whichever route the parameters select
+void SplitPass::Impl::groupWork(const std::vector<size_t> &ids, bool trace)
+{
+    if (params.device_fits) fitsOnDevice(ids);
+    else if (params.device_groups) groupsOnDevice(ids);
+    else parallel_over(ids.size(), params.threads, [&](size_t k) { groupsOf(ids[k], trace && k == 0); });
+}
+
 // Contigs whose scan outputs exist already (the caller knows): their intervals and groups now, the rest in finish()
 void SplitPass::Impl::finishEarly(const std::vector<size_t> &ids)
 {
@@ -484,8 +555,7 @@ void SplitPass::Impl::finishEarly(const std::vector<size_t> &ids)
     csvhost::TraceScope tr("split: early gather + groups");
     gatherFor(todo);
     std::sort(todo.begin(), todo.end(), [&](size_t a, size_t b) { return work[a].member_rec.size() > work[b].member_rec.size(); });
-    if (params.device_groups) groupsOnDevice(todo);
-    else parallel_over(todo.size(), params.threads, [&](size_t k) { groupsOf(todo[k], false); });
+    groupWork(todo, false);
     for (size_t c : todo) grouped[c] = 1;
 }
 
@@ -508,8 +578,7 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
     tr.reset(new csvhost::TraceScope("split: interval gather"));
     gatherFor(rest);
     tr.reset(new csvhost::TraceScope("split: groups"));
-    if (params.device_groups) groupsOnDevice(rest);
-    else parallel_over(rest.size(), params.threads, [&](size_t k) { groupsOf(rest[k], k == 0); });
+    groupWork(rest, true);
     for (size_t c : rest) grouped[c] = 1;
 
     // ---- the six DBSCAN1D(100, 5) fits of every group of every contig: ONE batched launch (:270-372) ------------------------------
@@ -518,6 +587,7 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
     std::vector<uint64_t> flat_off{0};
     for (size_t c : todo) {
         ContigWork &W = work[c];
+        if (W.have_fits) continue;                             // (device_fits: sets, fits and medians came back as records)
         W.set_base = flat_off.size() - 1;
         for (Group &G : W.groups)
             for (int s = 0; s < 6; s++) { flat_pts.insert(flat_pts.end(), G.sets[s].begin(), G.sets[s].end()); flat_off.push_back(flat_pts.size()); }
@@ -525,33 +595,48 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
     if (!flat_pts.empty()) DBSCAN1D::fitBatchFlat(flat_pts, flat_off, params.eps, params.min_pts, flat_labels);
 
     // ---- phase 3: medians, SPLITDIST1 candidates, SPLIT dummies (:283-486), per contig --------------------------------------------
+    // Every group comes here as six (size of the largest cluster, its median) pairs and the strand vote: from the labels of the batch above
+    // (largest_cluster / sorted_median), or from the SplitFit records of params.device_fits.
     tr.reset(new csvhost::TraceScope("split: calls"));
     parallel_over(todo.size(), params.threads, [&](size_t k) {
         ContigWork &W = work[todo[k]];
         if (W.n_primary == 0) return;                        // no entry in primary_map for this tid
         std::vector<SVCall> &chr_sv_calls = W.calls;
         chr_sv_calls.reserve(1000);
-        for (size_t g = 0; g < W.groups.size(); g++) {
-            Group &G = W.groups[g];
-            std::vector<int> cl[6];
-            for (int s = 0; s < 6; s++) cl[s] = largest_cluster(G.sets[s], flat_labels.data() + flat_off[W.set_base + g * 6 + (size_t)s]);
-            std::vector<int> &p_start = cl[0], &p_end = cl[1], &s_start = cl[2], &s_end = cl[3], &read_d = cl[4], &ref_d = cl[5];
-            if (p_start.empty() && p_end.empty()) continue;                                          // :291-293
-            if (s_start.empty() && s_end.empty() && read_d.empty() && ref_d.empty()) continue;        // :375-377
+        const size_t n_groups = W.have_fits ? W.fits.size() : W.groups.size();
+        for (size_t g = 0; g < n_groups; g++) {
+            int size[6], median[6];
+            bool inversion;
+            if (W.have_fits) {
+                const SplitFit &F = W.fits[g];
+                for (int s = 0; s < 6; s++) { size[s] = (int)F.size[s]; median[s] = F.median[s]; }
+                inversion = (double)(int)F.n_opposite / (double)(int)F.n_members > 0.5;              // :265
+            } else {
+                Group &G = W.groups[g];
+                for (int s = 0; s < 6; s++) {
+                    std::vector<int> cl = largest_cluster(G.sets[s], flat_labels.data() + flat_off[W.set_base + g * 6 + (size_t)s]);
+                    size[s] = (int)cl.size();
+                    median[s] = cl.empty() ? 0 : sorted_median(cl);
+                }
+                inversion = G.inversion;
+            }
+            enum { P_START, P_END, S_START, S_END, READ_D, REF_D };
+            if (!size[P_START] && !size[P_END]) continue;                                            // :291-293
+            if (!size[S_START] && !size[S_END] && !size[READ_D] && !size[REF_D]) continue;            // :375-377
 
             std::vector<int> primary_positions, supp_positions;
             int primary_cluster_size = 0, supp_cluster_size = 0;
             bool primary_end = false, supp_end = false;
-            if (!p_start.empty()) { primary_positions.push_back(sorted_median(p_start)); primary_cluster_size = (int)p_start.size(); }
-            if (!p_end.empty()) { primary_positions.push_back(sorted_median(p_end)); primary_cluster_size = std::max(primary_cluster_size, (int)p_end.size()); primary_end = true; }
-            if (!s_start.empty()) { supp_positions.push_back(sorted_median(s_start)); supp_cluster_size = (int)s_start.size(); }
-            if (!s_end.empty()) { supp_positions.push_back(sorted_median(s_end)); supp_cluster_size = std::max(supp_cluster_size, (int)s_end.size()); supp_end = true; }
+            if (size[P_START]) { primary_positions.push_back(median[P_START]); primary_cluster_size = size[P_START]; }
+            if (size[P_END]) { primary_positions.push_back(median[P_END]); primary_cluster_size = std::max(primary_cluster_size, size[P_END]); primary_end = true; }
+            if (size[S_START]) { supp_positions.push_back(median[S_START]); supp_cluster_size = size[S_START]; }
+            if (size[S_END]) { supp_positions.push_back(median[S_END]); supp_cluster_size = std::max(supp_cluster_size, size[S_END]); supp_end = true; }
 
-            if (!read_d.empty() && !ref_d.empty()) {                                                  // :422-468
-                int read_distance = sorted_median(read_d);
+            if (size[READ_D] && size[REF_D]) {                                                        // :422-468
+                int read_distance = median[READ_D];
                 const bool primary_5p_most = read_distance > 0;
                 read_distance = std::abs(read_distance);
-                const int ref_distance = sorted_median(ref_d);
+                const int ref_distance = median[REF_D];
                 int sv_start = 0;
                 bool candidate = false;
                 if (primary_5p_most && primary_end) {
@@ -578,7 +663,7 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
             }
             // dummy call per (primary median, supplementary median) pair for the copy-number pass (:470-486)
             const int cluster_size = std::max(primary_cluster_size, supp_cluster_size);
-            const SVType sv_type = G.inversion ? SVType::INV : SVType::UNKNOWN;
+            const SVType sv_type = inversion ? SVType::INV : SVType::UNKNOWN;
             const std::string alt = (sv_type == SVType::INV) ? "<INV>" : ".";
             for (int primary_pos : primary_positions)
                 for (int supp_pos : supp_positions) {
@@ -666,4 +751,52 @@ void splitGroupsHost(const int32_t *start, const int32_t *end, const uint64_t *s
         members.insert(members.end(), mem.begin(), mem.end());
         seg_group_off.push_back(group_off.size() - 1);
     }
+}
+
+void splitFitsHost(const SplitFitTables &T, const std::vector<uint64_t> &seg_off, const std::vector<uint64_t> &seg_group_off, const std::vector<uint64_t> &group_off,
+                   const std::vector<uint32_t> &members, double eps, int min_pts, std::vector<SplitFit> &fits)
+{
+    const size_t n_seg = seg_off.size() - 1, n_groups = (size_t)seg_group_off.at(n_seg);
+    if (seg_group_off.size() != n_seg + 1 || group_off.size() < n_groups + 1 || members.size() < group_off[n_groups] || T.supp_off.size() != T.start.size() + 1)
+        throw std::invalid_argument("splitFitsHost: tables of the wrong size");
+    fits.assign(n_groups, SplitFit());
+    std::vector<int> flat_pts, flat_labels;
+    std::vector<uint64_t> flat_off{0};
+    std::vector<int> sets[6];
+    for (size_t c = 0; c < n_seg; c++)
+        for (uint64_t g = seg_group_off[c]; g < seg_group_off[c + 1]; g++) {
+            for (auto &v : sets) v.clear();
+            uint32_t n_opposite = 0;
+            for (uint64_t k = group_off[g]; k < group_off[g + 1]; k++) {
+                const uint64_t m = seg_off[c] + members[k];
+                if (m >= seg_off[c + 1]) throw std::invalid_argument("splitFitsHost: a group member out of range");
+                bool opposite = false;
+                sets[0].push_back(T.start[m]);
+                sets[1].push_back(T.end[m]);
+                for (uint64_t z = T.supp_off[m]; z < T.supp_off[m + 1]; z++) {
+                    const uint8_t f = T.supp_flags[z];
+                    if (f & 2) continue;
+                    sets[2].push_back(T.supp_start[z]);
+                    sets[3].push_back(T.supp_end[z]);
+                    if ((f & 1) != (T.reverse[m] & 1)) { opposite = true; continue; }
+                    int read_distance = std::max(0, std::max(T.supp_q_start[z], T.q_start[m]) - std::min(T.supp_q_end[z], T.q_end[m]));
+                    if (!(T.start[m] < T.supp_start[z])) read_distance = -read_distance;
+                    sets[4].push_back(read_distance);
+                    sets[5].push_back(std::max(0, std::max(T.supp_start[z], T.start[m]) - std::min(T.supp_end[z], T.end[m])));
+                }
+                n_opposite += opposite;
+            }
+            fits[g].n_members = (uint32_t)(group_off[g + 1] - group_off[g]);
+            fits[g].n_opposite = n_opposite;
+            for (auto &v : sets) { flat_pts.insert(flat_pts.end(), v.begin(), v.end()); flat_off.push_back(flat_pts.size()); }
+        }
+    if (!flat_pts.empty()) DBSCAN1D::fitBatchFlat(flat_pts, flat_off, eps, min_pts, flat_labels);
+    for (size_t g = 0; g < n_groups; g++)
+        for (size_t s = 0; s < 6; s++) {
+            const uint64_t a = flat_off[g * 6 + s], b = flat_off[g * 6 + s + 1];
+            std::vector<int> pts(flat_pts.begin() + (std::ptrdiff_t)a, flat_pts.begin() + (std::ptrdiff_t)b);
+            std::vector<int> cl = largest_cluster(pts, flat_labels.data() + a);
+            fits[g].size[s] = (uint32_t)cl.size();
+            fits[g].median[s] = cl.empty() ? 0 : sorted_median(cl);
+        }
 }

@@ -68,6 +68,31 @@ struct SplitGroupSource {
                         std::vector<uint64_t> &seg_group_off, std::vector<uint64_t> &group_off, std::vector<uint32_t> &members) const = 0;
 };
 
+// What the reference derives from every overlap group before it makes calls (sv_caller.cpp:248-416: strand vote, six point sets, six DBSCAN1D fits,
+// largest clusters, medians), computed somewhere else than on the host threads (the device: csvgpu_split_fits / csvgpu_split_groups_fits behind
+// ShardFitSource in sv_caller.cpp). The tables are csv_split_tables' arrays for a batch of contigs, the record is csv_split_fit.
+struct SplitFitTables {
+    std::vector<int32_t> start, end, q_start, q_end;      // [members]: pos + 1, bam_endpos, query_start, query_end; map iteration order per segment
+    std::vector<uint8_t> reverse;                         // [members]: 1 = FLAG 0x10
+    std::vector<uint64_t> supp_off;                       // [members + 1]
+    std::vector<int32_t> supp_start, supp_end, supp_q_start, supp_q_end;
+    std::vector<uint8_t> supp_flags;                      // bit 0 reverse strand, bit 1 on another tid than the primary
+};
+struct SplitFit {
+    int32_t  median[6];               // sets in the order of Group::sets (split_caller.cpp); sorted largest cluster [size / 2], 0 when there is none
+    uint32_t size[6];                 // points in the largest cluster
+    uint32_t n_members, n_opposite;   // the strand vote's two counts (:248-265)
+    uint32_t reserved[2];
+};
+struct SplitFitSource {
+    virtual ~SplitFitSource() = default;
+    // segment k = members [seg_off[k], seg_off[k+1]). groups given (seg_group_off / group_off / members as SplitGroupSource::groups returns them):
+    // their fits; groups == nullptr: the source computes the groups itself (the same ones) and returns their seg_group_off. fits[g] per group.
+    struct Groups { const std::vector<uint64_t> *seg_group_off, *group_off; const std::vector<uint32_t> *members; };
+    virtual void fits(const SplitFitTables &tables, const std::vector<uint64_t> &seg_off, const Groups *groups, double eps, int min_pts,
+                      std::vector<uint64_t> &seg_group_off, std::vector<SplitFit> &fits) const = 0;
+};
+
 struct SplitParams {
     int min_mapq = 20;        // sv_caller.h:72
     double eps = 100;         // DBSCAN1D(100, 5) at sv_caller.cpp:270
@@ -77,6 +102,8 @@ struct SplitParams {
     const IntervalSource *intervals = nullptr;        // for contigs given without ref_end / q_start / q_end arrays
     const SplitOrderSource *device_order = nullptr;   // where contigs with unique_names get their iteration order from (nullptr: replayed on the host)
     const SplitGroupSource *device_groups = nullptr;  // where the overlap groups come from (nullptr: the host's interval tree, one contig per host thread)
+    const SplitFitSource *device_fits = nullptr;      // where the groups' point sets, fits, largest clusters and medians come from (nullptr: setsOf + one DBSCAN1D batch + the host's
+                                                      // reductions); with device_groups also set the source computes the groups too and they never reach the host
     int threads = 0;          // host threads over contigs (0: one per contig, at most the hardware's); the result does not depend on it
 };
 
@@ -133,3 +160,9 @@ void findSplitSVSignatures(const std::vector<SplitRecord> &records, const std::v
 // outputs: seg_group_off [n_seg + 1], group_off [groups + 1], members. Throws std::invalid_argument on end < start or descending offsets.
 void splitGroupsHost(const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, std::vector<uint64_t> &seg_group_off,
                      std::vector<uint64_t> &group_off, std::vector<uint32_t> &members);
+
+// The records of csvgpu_split_fits by the route SplitParams::device_fits == nullptr takes — the six point sets of every group built on this thread, ONE
+// DBSCAN1D batch for all of them (csvgpu_dbscan_1d on the host mirror's context), largest clusters and medians on this thread: what tools/bench_split_fits.py
+// measures the device entry points against. Throws std::invalid_argument on tables that do not fit.
+void splitFitsHost(const SplitFitTables &tables, const std::vector<uint64_t> &seg_off, const std::vector<uint64_t> &seg_group_off,
+                   const std::vector<uint64_t> &group_off, const std::vector<uint32_t> &members, double eps, int min_pts, std::vector<SplitFit> &fits);

@@ -1,4 +1,5 @@
 #include "sv_caller.h"
+#include <cstddef>
 
 #include <deque>
 
@@ -537,9 +538,46 @@ struct ShardGroupSource : SplitGroupSource {
     csv_ctx *ctx;
 };
 
+// the groups' evidence from the device (csvgpu_split_fits on given groups, csvgpu_split_groups_fits when the device computes the groups too), on the same
+// context and from the same thread as the sources above
+static_assert(sizeof(SplitFit) == sizeof(csv_split_fit) && sizeof(SplitFit) == 64 && offsetof(SplitFit, median) == offsetof(csv_split_fit, median) &&
+              offsetof(SplitFit, size) == offsetof(csv_split_fit, size) && offsetof(SplitFit, n_members) == offsetof(csv_split_fit, n_members) &&
+              offsetof(SplitFit, n_opposite) == offsetof(csv_split_fit, n_opposite) && offsetof(SplitFit, reserved) == offsetof(csv_split_fit, reserved),
+              "SplitFit (split_caller.h, which does not see the C-ABI header) is csv_split_fit field for field");
+struct ShardFitSource : SplitFitSource {
+    explicit ShardFitSource(csv_ctx *ctx) : ctx(ctx) {}
+    void fits(const SplitFitTables &T, const std::vector<uint64_t> &seg_off, const Groups *groups, double eps, int min_pts,
+              std::vector<uint64_t> &seg_group_off, std::vector<SplitFit> &out) const override
+    {
+        const uint64_t n_seg = seg_off.size() - 1;
+        csv_split_tables t;
+        t.n_members = T.start.size(); t.n_supp = T.supp_start.size();
+        t.start = T.start.data(); t.end = T.end.data(); t.q_start = T.q_start.data(); t.q_end = T.q_end.data(); t.reverse = T.reverse.data();
+        t.supp_off = T.supp_off.data();
+        t.supp_start = T.supp_start.data(); t.supp_end = T.supp_end.data(); t.supp_q_start = T.supp_q_start.data(); t.supp_q_end = T.supp_q_end.data();
+        t.supp_flags = T.supp_flags.data();
+        if (groups) {
+            seg_group_off = *groups->seg_group_off;
+            out.assign(std::max<size_t>(seg_group_off.back(), 1), SplitFit());
+            check(ctx, csvgpu_split_fits(ctx, &t, seg_off.data(), n_seg, seg_group_off.data(), groups->group_off->data(), groups->members->data(), eps, min_pts,
+                                         (csv_split_fit *)out.data()), "split-read group fits");
+            out.resize(seg_group_off.back());
+            return;
+        }
+        seg_group_off.assign(n_seg + 1, 0);
+        out.assign(std::max<size_t>(T.start.size(), 1), SplitFit());
+        uint64_t n_groups = 0;
+        check(ctx, csvgpu_split_groups_fits(ctx, &t, seg_off.data(), n_seg, eps, min_pts, seg_group_off.data(), (csv_split_fit *)out.data(), &n_groups),
+              "split-read overlap groups and fits");
+        out.resize(n_groups);
+    }
+    csv_ctx *ctx;
+};
+
 }  // namespace
 
 std::unique_ptr<SplitGroupSource> makeDeviceGroupSource(csv_ctx *ctx) { return std::unique_ptr<SplitGroupSource>(new ShardGroupSource(ctx)); }
+std::unique_ptr<SplitFitSource> makeDeviceFitSource(csv_ctx *ctx) { return std::unique_ptr<SplitFitSource>(new ShardFitSource(ctx)); }
 
 // what the split-read pass of a run works on (built once per run; prepare() may already be running while the CIGAR pass is on the device)
 struct SVCaller::SplitSetup {
@@ -549,6 +587,7 @@ struct SVCaller::SplitSetup {
     std::unique_ptr<ShardOrderSource> dev_order;
     std::unique_ptr<ShardIntervals> intervals;
     std::unique_ptr<ShardGroupSource> dev_groups;
+    std::unique_ptr<ShardFitSource> dev_fits;
     SplitParams sp;
     std::unique_ptr<SplitPass> pass;
     double ms_prepare = 0.0;
@@ -977,6 +1016,8 @@ std::unique_ptr<SVCaller::SplitSetup> SVCaller::makeSplitSetup(std::vector<Resid
     if (P.split_order_on_device) S->sp.device_order = S->dev_order.get();          // only contigs staged with unique_names take it
     S->dev_groups.reset(new ShardGroupSource(ctx));
     if (P.split_groups_on_device) S->sp.device_groups = S->dev_groups.get();
+    S->dev_fits.reset(new ShardFitSource(ctx));
+    if (P.split_fits_on_device) S->sp.device_fits = S->dev_fits.get();
     S->pass.reset(new SplitPass(S->blocks, S->names, S->sp));
     return S;
 }

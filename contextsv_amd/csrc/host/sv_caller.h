@@ -102,6 +102,9 @@ struct RunParams {
     bool split_order_on_device = true;      // contigs staged with unique query-name hashes (SplitContig::unique_names) get the qname map's order from csvgpu_split_order
     bool split_groups_on_device = false;    // the overlap groups of the split-read pass (interval tree + greedy seeding, sv_caller.cpp:215-238) from csvgpu_split_groups, one
                                             // call per batch of contigs, instead of the host tree on one pool thread per contig; the calls do not depend on it
+    bool split_fits_on_device = false;      // what the split-read pass derives from every overlap group (point sets, DBSCAN1D fits, largest clusters, medians, strand vote;
+                                            // sv_caller.cpp:248-416) from csvgpu_split_fits — with split_groups_on_device from csvgpu_split_groups_fits, the groups then staying
+                                            // on the device — instead of the host's sets and one DBSCAN1D batch; the calls do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it
@@ -123,6 +126,8 @@ struct BamRunStats {
 // A SplitGroupSource that asks csvgpu_split_groups on `ctx` (SplitParams::device_groups); the caller keeps the context alive and uses it from the
 // thread that runs the split pass only.
 std::unique_ptr<SplitGroupSource> makeDeviceGroupSource(csv_ctx *ctx);
+// A SplitFitSource that asks csvgpu_split_fits / csvgpu_split_groups_fits on `ctx` (SplitParams::device_fits); same conditions.
+std::unique_ptr<SplitFitSource> makeDeviceFitSource(csv_ctx *ctx);
 
 class SVCaller {
 public:

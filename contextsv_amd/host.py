@@ -66,6 +66,8 @@ def load() -> C.CDLL:
                                           C.c_double, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint64]
     lib.csvhost_split_signatures.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_opts.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.csvhost_split_signatures_dev.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.csvhost_split_fits_host.argtypes = [_P, C.POINTER(_lib.csv_split_tables), _P, C.c_uint64, _P, _P, _P, C.c_double, C.c_int, _P]
     lib.csvhost_split_groups_host.argtypes = [_P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]
     lib.csvhost_run.argtypes = [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_lib.csv_hmm), C.c_double, C.c_double,
                                 C.c_int, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_char_p, C.c_char_p, _P, C.c_uint64, _P, C.c_int]
@@ -283,18 +285,21 @@ class Genome:
     def run(self, ctx: Context, hmm, lanes=None, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, merges=True,
             host_threads=0, capacity: int = 1 << 20, host_split_order: bool = False, overlap_split: bool = True, copy: bool = True,
             early_batches: str = "timed", split_beside_pass: bool = True, split_order_self: bool = True, prepare_delay_ms: int = 0,
-            split_groups_on_device: bool = False):
+            split_groups_on_device: bool = False, split_fits_on_device: bool = False):
         """-> (calls[CALL_DTYPE], global tid per call, stage_times, per-contig chr_stats list). copy=False: the two arrays are views of buffers
         the genome owns (two sets, used alternately) and stay valid until the run after the next one. early_batches ("timed" | "none" | "all" |
         "every3"), split_beside_pass, split_order_self and prepare_delay_ms are RunParams::schedule: no result depends on them, they force
         the branches that timing otherwise decides. split_groups_on_device: the split-read pass's overlap groups from csvgpu_split_groups (one
-        call per batch of contigs) instead of the host's interval tree; the calls are the same."""
+        call per batch of contigs) instead of the host's interval tree; the calls are the same. split_fits_on_device: what the pass derives from
+        every group (point sets, DBSCAN1D fits, largest clusters, medians, strand vote) from csvgpu_split_fits — with split_groups_on_device from
+        csvgpu_split_groups_fits, the groups then staying on the device — instead of the host's sets and one DBSCAN1D batch; the calls are the same."""
         if early_batches not in _EARLY_BATCHES:
             raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {early_batches!r}")
         if not 0 <= int(prepare_delay_ms) < 1 << 15:
             raise ValueError(f"prepare_delay_ms must be in [0, 32767], not {prepare_delay_ms!r}")
         passes = int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4) | \
-            (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(bool(split_groups_on_device)) << 9) | (int(prepare_delay_ms) << 16)
+            (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(bool(split_groups_on_device)) << 9) | \
+            (int(bool(split_fits_on_device)) << 10) | (int(prepare_delay_ms) << 16)
         n = len(self)
         if getattr(self, "_cap", 0) < capacity:              # result buffers live with the genome (tens of megabytes of page faults per call otherwise)
             self._bufs = [(np.empty(capacity, CALL_DTYPE), np.empty(capacity, np.int32)) for _ in range(2)]
@@ -454,18 +459,37 @@ SPLIT_CALL_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("sv_type", "<i4"
 
 
 def split_signatures(ctx: Context, tid, pos, flag, mapq, ref_end, q_start, q_end, qname_id, n_targets: int, min_mapq: int = 20,
-                     device_groups: bool = False) -> np.ndarray:
+                     device_groups: bool = False, device_fits: bool = False) -> np.ndarray:
     """findSplitSVSignatures mirror (qname of record i = "r<qname_id[i]>") -> calls sorted by contig id. device_groups: the overlap groups
-    from csvgpu_split_groups on `ctx` instead of the host's interval tree (same calls)."""
+    from csvgpu_split_groups on `ctx` instead of the host's interval tree (same calls). device_fits: the groups' point sets, DBSCAN1D fits,
+    largest clusters and medians from csvgpu_split_fits (with device_groups: groups and fits from csvgpu_split_groups_fits) instead of the
+    host's sets and one csvgpu_dbscan_1d batch (same calls)."""
     a = [np.ascontiguousarray(x, dt) for x, dt in ((tid, np.int32), (pos, np.int32), (flag, np.uint16), (mapq, np.uint8), (ref_end, np.int32),
                                                     (q_start, np.int32), (q_end, np.int32), (qname_id, np.uint32))]
     n = len(a[0])
     cap = 4 * n + 16
     out = np.zeros(cap, SPLIT_CALL_DTYPE)
     k = C.c_uint64(0)
-    _check(load().csvhost_split_signatures_opts(ctx.h, n, *[x.ctypes.data for x in a], n_targets, min_mapq, int(bool(device_groups)), out.ctypes.data, cap,
-                                                C.byref(k)))
+    _check(load().csvhost_split_signatures_dev(ctx.h, n, *[x.ctypes.data for x in a], n_targets, min_mapq, int(bool(device_groups)), int(bool(device_fits)),
+                                               out.ctypes.data, cap, C.byref(k)))
     return out[: k.value].copy()
+
+
+def split_fits_host(ctx: Context, tables, seg_off, groups, eps: float = 100.0, min_pts: int = 5):
+    """The records of Context.split_fits(tables, seg_off, groups) by the host route the split-read pass takes without device_fits: point sets,
+    largest clusters and medians on this thread, one csvgpu_dbscan_1d batch on `ctx` -> fits[SPLIT_FIT_DTYPE]."""
+    seg_off = np.ascontiguousarray(seg_off, np.uint64)
+    sgo, go, mem = (np.ascontiguousarray(groups[0], np.uint64), np.ascontiguousarray(groups[1], np.uint64), np.ascontiguousarray(groups[2], np.uint32))
+    n_seg = len(seg_off) - 1
+    if len(sgo) != n_seg + 1 or len(go) < int(sgo[n_seg]) + 1 or len(mem) < int(go[int(sgo[n_seg])]):
+        raise ValueError("split_fits_host: the group tables do not fit the segments")
+    out = np.zeros(max(int(sgo[n_seg]), 1), _lib.SPLIT_FIT_DTYPE)
+    t = tables.c_struct()
+    rc = load().csvhost_split_fits_host(ctx.h, C.byref(t), seg_off.ctypes.data, n_seg, sgo.ctypes.data, go.ctypes.data, mem.ctypes.data, eps, min_pts, out.ctypes.data)
+    if rc == _lib.CSV_EINVAL:
+        raise ValueError((load().csvhost_last_error() or b"").decode())
+    _check(rc)
+    return out[: int(sgo[n_seg])]
 
 
 def split_groups_host(start, end, seg_off):

@@ -99,7 +99,8 @@ typedef enum csv_kernel_id {
     CSV_K_MISC       = 7,   /* memsets, small scans, partition */
     CSV_K_SPLIT_ORDER = 8,  /* hash-map node order of the split-read pass (compaction + per-epoch sorts + survivors) */
     CSV_K_SPLIT_GROUPS = 9, /* overlap groups of the split-read pass (member order, links, seeds, fill + its sorts) */
-    CSV_K_COUNT      = 10
+    CSV_K_SPLIT_FITS = 10,  /* point sets, 1-D DBSCAN fits, largest clusters, medians and strand vote of the overlap groups */
+    CSV_K_COUNT      = 11
 } csv_kernel_id;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -369,6 +370,52 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
                         uint64_t *seg_group_off,   /* [n_seg + 1]: first group of each segment */
                         uint64_t *group_off,       /* [seg_off[n_seg] + 1]: there are never more groups than members */
                         uint32_t *members, uint64_t *n_members /* in: capacity of members[], out: count required */);
+
+/* §8f-4, third part: what the reference derives from every overlap group before it makes calls (sv_caller.cpp:248-416): the strand vote
+ * (:248-265), the six point sets (:270-347), their DBSCAN1D(eps, min_pts) fits, getLargestCluster (dbscan1d.cpp:72-90) and the medians
+ * of the largest clusters — on the device, one 64-byte record per group back.
+ * The members (primary alignments that have a supplementary record) and their supplementary records, host pointers, for a batch of
+ * contigs: segment c = members [seg_off[c], seg_off[c+1]), as in csvgpu_split_groups. */
+typedef struct csv_split_tables {
+    uint64_t n_members, n_supp;
+    const int32_t *start, *end, *q_start, *q_end;   /* [n_members]: pos + 1, bam_endpos, query_start, query_end of each member (a primary alignment), map iteration order per segment */
+    const uint8_t *reverse;                         /* [n_members]: 1 = FLAG 0x10 */
+    const uint64_t *supp_off;                       /* [n_members + 1]: member m's supplementary records, file order */
+    const int32_t *supp_start, *supp_end, *supp_q_start, *supp_q_end;   /* [n_supp] */
+    const uint8_t *supp_flags;                      /* [n_supp]: bit 0 reverse strand, bit 1 on another tid than the primary (then only the flags are read) */
+} csv_split_tables;
+/* Coordinates (of members, and of the supplementary records on the primary's tid) must lie in [0, 2^31 - 1] with end >= start
+ * (q_end may be below q_start); CSV_EINVAL otherwise, nothing reaching the device. Every int difference the reference forms to BUILD
+ * the sets (:322-345), and every distance of its DBSCAN1D (dbscan1d.cpp:68-70) on sets 0-3 and 5, is then free of overflow. Set 4 is
+ * NOT covered: it holds read distances of both signs, and the distance of two of them, |a - b| in int, overflows once they differ by
+ * more than 2^31 - 1 — query coordinates beyond 2^30, which no read has. The reference's own expression is undefined there, and so is
+ * the record's set-4 pair (nothing else of the record is affected). */
+
+/* One group's evidence. Sets: 0 primary starts, 1 primary ends, 2 supplementary starts, 3 supplementary ends, 4 signed read distances,
+ * 5 reference distances (sets 2, 3: the supplementary records on the primary's tid; 4, 5: those of them on the primary's strand).
+ * Points of a set are in the reference's order — members in the group's findOverlaps order, a member's supplementary records in supp_off
+ * order — which decides the cluster ids and so, among clusters of equal size, the largest (the lowest id). */
+typedef struct csv_split_fit {
+    int32_t  median[6];    /* sorted largest cluster [size / 2]; 0 when size == 0 */
+    uint32_t size[6];      /* points in the largest cluster (getLargestCluster, dbscan1d.cpp:72-90); 0 = none */
+    uint32_t n_members, n_opposite;   /* group size; members with a same-tid supplementary record on the other strand (sv_caller.cpp:248-265) */
+    uint32_t reserved[2];  /* 0 */
+} csv_split_fit;
+/* The inversion vote stays the caller's double expression: (double)n_opposite / (double)n_members > 0.5 (:265). */
+
+/* The fits of given groups — seg_group_off / group_off / members exactly as csvgpu_split_groups (or the host's tree) returns them;
+ * out[g] for g < seg_group_off[n_seg]. Requires eps >= 0 and min_pts >= 1 (as csvgpu_dbscan_1d). Sets of more than 512 points are
+ * solved by the large-segment path of csvgpu_dbscan_1d inside this call, with the same result. CSV_EINVAL: a null array, offsets not
+ * ascending or not ending at the tables' counts, a member index outside its segment or twice in one group, a coordinate out of range, a split order pending on
+ * the context. CSV_EHIP also when a bounded device loop (a radix pass's look-back) gave up. Empty segments and n_seg == 0 are valid. */
+int csvgpu_split_fits(csv_ctx *ctx, const csv_split_tables *tables, const uint64_t *seg_off, uint64_t n_seg, const uint64_t *seg_group_off,
+                      const uint64_t *group_off, const uint32_t *members, double eps, int32_t min_pts, csv_split_fit *out);
+/* csvgpu_split_groups and csvgpu_split_fits in one call: the groups are computed by the chain of csvgpu_split_groups from the tables'
+ * start / end and consumed where they lie — the member lists never reach the host, so there is no capacity to guess: the workspace is
+ * sized from the chain's one readback. seg_group_off[n_seg + 1] and *n_groups = seg_group_off[n_seg] are returned with the records;
+ * out has room for tables->n_members records (there are never more groups than members). */
+int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *tables, const uint64_t *seg_off, uint64_t n_seg, double eps, int32_t min_pts,
+                             uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups);
 
 /* csvgpu_window_log2 on the depth map that the last csvgpu_chr_pipeline_dev() left resident in `shard`
  * (region tables and outputs are host memory; the depth map never leaves HBM). */
