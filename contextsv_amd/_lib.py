@@ -62,6 +62,11 @@ class csv_split_tables(C.Structure):
                 ("supp_q_start", C.c_void_p), ("supp_q_end", C.c_void_p), ("supp_flags", C.c_void_p)]
 
 
+class csv_split_refs(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("n_supp", C.c_uint64), ("member_rec", C.c_void_p), ("supp_off", C.c_void_p), ("supp_rec", C.c_void_p),
+                ("supp_where", C.c_void_p)]
+
+
 # every symbol include/csvgpu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 ABI = {
@@ -109,6 +114,8 @@ ABI = {
     "csvgpu_split_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_split_fits": (C.c_int, [_P, C.POINTER(csv_split_tables), _P, C.c_uint64, _P, _P, _P, C.c_double, C.c_int32, _P]),
     "csvgpu_split_groups_fits": (C.c_int, [_P, C.POINTER(csv_split_tables), _P, C.c_uint64, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_split_tables_resident": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.POINTER(csv_split_tables)]),
+    "csvgpu_split_resident_fits": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import SIG_DTYPE, CsvError, csv_chr_result, csv_hmm, csv_reads, csv_split_tables, ptr
+from ._lib import SIG_DTYPE, CsvError, csv_chr_result, csv_hmm, csv_reads, csv_split_refs, csv_split_tables, ptr
 
 
 @dataclass
@@ -304,6 +304,41 @@ class Context:
         self._check(rc)
         return sgo, go[: int(sgo[n_seg]) + 1].copy(), mem[: int(n.value)].copy()
 
+    @staticmethod
+    def _split_refs_args(shards, refs, seg_off, what):
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        n_seg = len(seg_off) - 1
+        if n_seg < 0 or len(shards) != n_seg:
+            raise ValueError(what + ": seg_off must have one entry more than there are shards")
+        hs = (C.c_void_p * max(n_seg, 1))(*[s.h for s in shards])
+        return seg_off, n_seg, hs
+
+    def split_tables_resident(self, shards, refs, seg_off) -> "SplitTables":
+        """csvgpu_split_tables_resident: the SplitTables of record references (SplitRefs) into resident shards — segment c = members
+        [seg_off[c], seg_off[c + 1]) of shards[c], on which the pipeline has run — built on the device and copied back."""
+        seg_off, n_seg, hs = self._split_refs_args(shards, refs, seg_off, "split_tables_resident")
+        nm, ns = refs.n_members, refs.n_supp
+        i32 = lambda n: np.zeros(n, np.int32)
+        out = SplitTables(i32(nm), i32(nm), i32(nm), i32(nm), np.zeros(nm, np.uint8), np.zeros(nm + 1, np.uint64), i32(ns), i32(ns), i32(ns), i32(ns),
+                          np.zeros(ns, np.uint8))
+        t, f = out.c_struct(), refs.c_struct()
+        self._check(self.lib.csvgpu_split_tables_resident(self.h, n_seg, hs, C.byref(f), ptr(seg_off), C.byref(t)))
+        if (t.n_members, t.n_supp) != (nm, ns):
+            raise RuntimeError("split_tables_resident: the library returned other counts than the references hold")
+        return out
+
+    def split_resident_fits(self, shards, refs, seg_off, eps: float = 100.0, min_pts: int = 5):
+        """csvgpu_split_resident_fits: the tables of split_tables_resident built where the groups -> fits chain reads them, and that chain: what
+        split_fits(split_tables_resident(...), seg_off) returns, with nothing but the references going up and the records coming back.
+        -> (seg_group_off, fits)."""
+        seg_off, n_seg, hs = self._split_refs_args(shards, refs, seg_off, "split_resident_fits")
+        sgo = np.zeros(n_seg + 1, np.uint64)
+        out = np.zeros(max(refs.n_members, 1), _lib.SPLIT_FIT_DTYPE)
+        n = C.c_uint64(0)
+        f = refs.c_struct()
+        self._check(self.lib.csvgpu_split_resident_fits(self.h, n_seg, hs, C.byref(f), ptr(seg_off), eps, min_pts, ptr(sgo), ptr(out), C.byref(n)))
+        return sgo, out[: int(n.value)].copy()
+
     def split_fits(self, tables, seg_off, groups=None, eps: float = 100.0, min_pts: int = 5):
         """csvgpu_split_fits / csvgpu_split_groups_fits: the evidence the reference derives from every overlap group — strand vote, the six
         point sets, their DBSCAN1D fits, the largest clusters and their medians — as one SPLIT_FIT_DTYPE record per group.
@@ -378,6 +413,39 @@ class Context:
                 raise ValueError("wrap_device: tensors must be contiguous device tensors of the csv_reads element sizes")
         return self.wrap_device_ptrs(n, m, pos.data_ptr(), flag.data_ptr(), mapq.data_ptr(), cigar_off.data_ptr(), cigar.data_ptr(), depth_len,
                                      keep=(pos, flag, mapq, cigar_off, cigar))
+
+
+@dataclass
+class SplitRefs:
+    """Record references into resident shards from which the device builds SplitTables (include/csvgpu.h csv_split_refs): segment by segment,
+    every member and every supplementary entry as a record index in the segment's shard, or — an entry on another tid — as its flags byte."""
+    member_rec: np.ndarray    # uint32 [n_members]  record index in its segment's shard
+    supp_off: np.ndarray      # uint64 [n_members + 1]
+    supp_rec: np.ndarray      # uint32 [n_supp]  record index in the same shard (not read where supp_where != 0)
+    supp_where: np.ndarray    # uint8 [n_supp]  0 = same shard, 2 | reverse = on another tid
+
+    def __post_init__(self):
+        self.member_rec = np.ascontiguousarray(self.member_rec, dtype=np.uint32)
+        self.supp_off = np.ascontiguousarray(self.supp_off, dtype=np.uint64)
+        self.supp_rec = np.ascontiguousarray(self.supp_rec, dtype=np.uint32)
+        self.supp_where = np.ascontiguousarray(self.supp_where, dtype=np.uint8)
+        if len(self.supp_off) != len(self.member_rec) + 1 or len(self.supp_where) != len(self.supp_rec):
+            raise ValueError("SplitRefs: array lengths disagree")
+
+    @property
+    def n_members(self) -> int:
+        return len(self.member_rec)
+
+    @property
+    def n_supp(self) -> int:
+        return len(self.supp_rec)
+
+    def c_struct(self) -> csv_split_refs:
+        f = csv_split_refs()
+        f.n_members, f.n_supp = self.n_members, self.n_supp
+        for k in ("member_rec", "supp_off", "supp_rec", "supp_where"):
+            setattr(f, k, ptr(getattr(self, k)))
+        return f
 
 
 @dataclass

@@ -338,6 +338,28 @@ void launch_sf_big_points(hipStream_t s, const SplitFitsIn &in, uint32_t w, int3
 // largest cluster and median of one labelled set: pts_sorted / oid as launch_dbscan_1d_big takes them, labels by original index; sizes[n] zeroed
 void launch_sf_big_reduce(hipStream_t s, const int32_t *pts_sorted, const uint32_t *oid, const int32_t *labels, uint32_t n, uint32_t *sizes,
                           csv_split_fit *rec, int set);
+// splittables.hip — the tables SplitFitsIn points to, built from record references into resident shards (csvgpu_split_tables_resident / _resident_fits)
+struct SplitTabSeg { const int32_t *pos; const uint16_t *flag; const int32_t *ref_end, *q_start, *q_end; };   // one segment's shard arrays (device)
+struct SplitTablesIn {                       // device arrays, passed to the kernel by value
+    const SplitTabSeg *seg;                  // [n_seg]
+    const uint64_t *seg_off;                 // [n_seg + 1]
+    uint64_t n_seg;
+    const uint32_t *member_rec;              // [n_members]
+    const uint64_t *supp_off;                // [n_members + 1]
+    const uint32_t *supp_rec;                // [n_supp]
+    const uint8_t *supp_where;               // [n_supp]
+    uint32_t n_members, n_supp;
+};
+struct SplitTablesOut {
+    int32_t *start, *end, *q_start, *q_end;  // [n_members]
+    uint8_t *reverse;
+    int32_t *supp_start, *supp_end, *supp_q_start, *supp_q_end;   // [n_supp]
+    uint8_t *supp_flags;
+    uint32_t *err;                           // zeroed by the caller; err_bit is ORed in when a coordinate lies outside the fits' domain
+    uint32_t err_bit;
+};
+constexpr uint32_t ST_MAX_BLOCKS = 1024;     // of 256 threads; larger calls stride
+void launch_st_tables(hipStream_t s, const SplitTablesIn &in, const SplitTablesOut &out);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

@@ -1514,6 +1514,7 @@ int csvgpu_split_order(csv_ctx *ctx, int n_contigs, csv_shard *const *shards, ui
 // the caller's own arrays, carved after it returns) and the page-locked block (+ pin_extra, continued at pin_used), stages the intervals and queues
 // everything up to the copy of the three result words; sg_wait waits and reads them; sg_fill_reserve reserves ctx->work (+ work_extra), sg_fill_launch
 // queues the member lists' sort.
+constexpr uint32_t SG_ERR_DOMAIN = 2;             // in w.err: ORed in by an SgDeviceFill's kernel (the chain's own kernels OR in 1)
 struct SgChain {
     SplitGroupsWs w;
     SortWs sw;
@@ -1528,8 +1529,14 @@ struct SgChain {
     const uint32_t *sort_flag = nullptr;       // the fill sort's gave-up word (device), or null
 };
 
+// on_device: start / end are not the caller's but written on the device, into c.d_start / c.d_end, by what this function queues (it carves its own
+// arrays from ctx->arena and stages through `pin`, both sized by the extras); the chain then skips its upload — and the caller's host range check.
+// The chain's zeroed block (w.err with it) is cleared in front of the call: what it queues may OR SG_ERR_DOMAIN (the value 2) into *c.w.err, which
+// sg_wait reports as CSV_EINVAL.
+typedef int (*SgDeviceFill)(void *arg, SgChain &c, PinStage &pin);
+
 static int sg_queue(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, uint64_t max_len,
-                    size_t arena_extra, size_t pin_extra, SgChain &c)
+                    size_t arena_extra, size_t pin_extra, SgChain &c, SgDeviceFill on_device = nullptr, void *on_device_arg = nullptr)
 {
     (void)hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
@@ -1570,16 +1577,22 @@ static int sg_queue(csv_ctx *ctx, const int32_t *start, const int32_t *end, cons
 
     if ((rc = ensure_pinned(ctx, 2 * PinStage::need((size_t)n * 4) + PinStage::need((n_seg + 1) * 8) + 4096 + pin_extra))) return rc;
     PinStage pin(ctx);
-    CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (!on_device) {
+        CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    }
     CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    if (on_device) {
+        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
+        if ((rc = on_device(on_device_arg, c, pin))) return rc;
+    }
     c.h_res = (volatile uint64_t *)((char *)ctx->pinned + pin.used);
     c.pin_used = pin.used + 256;
     const int key_bits = 32 + bits_of(n_seg - 1);
     const bool one_launch = onesweep(ctx);
     {
         TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
-        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
+        if (!on_device) CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
         launch_sg_keys(s, d_start, d_seg, n_seg, n, sw.k0, sw.v0);
         const int io = launch_radix_sort_u64(s, sw.k0, sw.v0, sw.k1, sw.v1, n, key_bits, sw.tmp, one_launch);
         launch_sg_links(s, w, io ? sw.k1 : sw.k0, io ? sw.v1 : sw.v0, d_start, d_end, d_seg, n);
@@ -1597,6 +1610,7 @@ static int sg_wait(csv_ctx *ctx, SgChain &c)
 {
     CSV_HIP(ctx, wait_stream(ctx->stream));
     c.total = c.h_res[0]; c.n_groups = c.h_res[1];
+    if (c.h_res[2] & SG_ERR_DOMAIN) { ctx->err = "split_resident_fits: a coordinate of the shards is negative or end < start"; return CSV_EINVAL; }
     if (c.h_res[2]) { ctx->err = "split_groups: a bounded device loop gave up (radix look-back or seeding rounds)"; return CSV_EHIP; }
     if (c.n_groups > c.n || c.total < 2 * c.n_groups) { ctx->err = "split_groups: counts out of range"; return CSV_EHIP; }
     return CSV_OK;
@@ -1835,6 +1849,46 @@ static int sf_big(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, csv_split
     return CSV_OK;
 }
 
+// what the fused calls share behind the chain's queue (r.in's tables set): the one sizing readback, the member lists' sort, the fits' launch and
+// its records, the sets too large for LDS
+static int sgf_finish(csv_ctx *ctx, SgChain &ch, SfRun &r, uint64_t n_seg, uint64_t max_len, uint64_t ns, double eps, int32_t min_pts,
+                      uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups)
+{
+    int rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = sg_wait(ctx, ch))) return rc;
+    const uint64_t G = ch.n_groups, total = ch.total;
+    if (total >= 0xffffffffull) { ctx->err = "split_fits: more than 2^32 - 1 entries in the groups"; return CSV_EINVAL; }
+    if (G == 0) {
+        for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
+        return CSV_OK;
+    }
+    r.B = std::max(std::min(total, max_len), ns);
+    SortWs fw;
+    if ((rc = sg_fill_reserve(ctx, ch, sf_out_bytes(G) + sf_big_bytes(r.B), fw))) return rc;
+    r.A = &ctx->work;
+    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
+    PinStage pin(ctx);
+    uint32_t *h_sort_err = (uint32_t *)pin.in(nullptr, 0);
+    pin.used += 256;
+    *h_sort_err = 0;
+    {
+        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
+        sg_fill_launch(ctx, ch, fw);
+        if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(pin.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
+    r.in.seg_off = ch.d_seg; r.in.seg_group_off = ch.w.seg_group_off; r.in.group_off = ch.w.group_off; r.in.members = ch.d_members;
+    r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
+    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
+    CSV_HIP(ctx, wait_stream(s));
+    if (*h_sort_err) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
+    pin.finish();
+    *n_groups = G;
+    if (r.h_res[0] == 0) return CSV_OK;
+    return sf_big(ctx, r, eps, min_pts, out);
+}
+
 int csvgpu_split_fits(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, const uint64_t *seg_group_off,
                       const uint64_t *group_off, const uint32_t *members, double eps, int32_t min_pts, csv_split_fit *out)
 {
@@ -1921,37 +1975,185 @@ int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *t, const uint
         pin.used = ch.pin_used;
         if ((rc = sf_upload(ctx, ctx->arena, pin, t, ch.d_start, ch.d_end, r.in))) { (void)wait_stream(s); return rc; }
     }
-    if ((rc = sg_wait(ctx, ch))) return rc;
-    const uint64_t G = ch.n_groups, total = ch.total;
-    if (total >= 0xffffffffull) { ctx->err = "split_fits: more than 2^32 - 1 entries in the groups"; return CSV_EINVAL; }
-    if (G == 0) {
+    return sgf_finish(ctx, ch, r, n_seg, max_len, ns, eps, min_pts, seg_group_off, out, n_groups);
+}
+
+// ---- the tables from the resident shards (kernels/splittables.hip) ------------------------------------------------------------------------
+// What the two entry points share: the checks of the references (everything the kernel indexes with is bounded here), their way to the device
+// and the launch.
+static int sr_check(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *seg_off, uint64_t &max_len)
+{
+    if (!f || !seg_off || (n_seg && !shards)) { ctx->err = "split_tables_resident: null array"; return CSV_EINVAL; }
+    if (ctx->split_state) { ctx->err = "split_tables_resident: a split order is pending on this context"; return CSV_EINVAL; }
+    if (n_seg >= 0xffffffffull) { ctx->err = "split_tables_resident: too many segments"; return CSV_EINVAL; }
+    const uint64_t nm = f->n_members, ns = f->n_supp;
+    if (nm >= 0xffffffffull || ns >= 0xffffffffull) { ctx->err = "split_tables_resident: 2^32 - 1 or more members or supplementary entries"; return CSV_EINVAL; }
+    if (!f->supp_off || (nm && !f->member_rec) || (ns && (!f->supp_rec || !f->supp_where))) { ctx->err = "split_tables_resident: null array in the references"; return CSV_EINVAL; }
+    if (seg_off[0] != 0) { ctx->err = "split_tables_resident: seg_off[0] must be 0"; return CSV_EINVAL; }
+    max_len = 0;
+    for (uint64_t c = 0; c < n_seg; c++) {
+        if (seg_off[c + 1] < seg_off[c]) { ctx->err = "split_tables_resident: seg_off not ascending"; return CSV_EINVAL; }
+        max_len = std::max(max_len, seg_off[c + 1] - seg_off[c]);
+    }
+    if (seg_off[n_seg] != nm) { ctx->err = "split_tables_resident: seg_off does not end at the references' member count"; return CSV_EINVAL; }
+    if (f->supp_off[0] != 0 || f->supp_off[nm] != ns) { ctx->err = "split_tables_resident: supp_off must run from 0 to n_supp"; return CSV_EINVAL; }
+    for (uint64_t m = 0; m < nm; m++) if (f->supp_off[m + 1] < f->supp_off[m]) { ctx->err = "split_tables_resident: supp_off not ascending"; return CSV_EINVAL; }
+    for (uint64_t c = 0; c < n_seg; c++) {
+        const csv_shard *sh = shards[c];
+        if (!sh || (sh->d.n_reads && (!sh->d.pos || !sh->d.flag || !sh->ref_end || !sh->q_start || !sh->q_end))) { ctx->err = "split_tables_resident: null shard"; return CSV_EINVAL; }
+        const uint64_t n_reads = sh->d.n_reads;
+        for (uint64_t m = seg_off[c]; m < seg_off[c + 1]; m++) {
+            if (f->member_rec[m] >= n_reads) { ctx->err = "split_tables_resident: a member's record index beyond its shard"; return CSV_EINVAL; }
+            for (uint64_t z = f->supp_off[m]; z < f->supp_off[m + 1]; z++) {
+                const uint8_t w = f->supp_where[z];
+                if (w != 0 && w != 2 && w != 3) { ctx->err = "split_tables_resident: supp_where must be 0, 2 or 3"; return CSV_EINVAL; }
+                if (w == 0 && f->supp_rec[z] >= n_reads) { ctx->err = "split_tables_resident: a supplementary record index beyond its shard"; return CSV_EINVAL; }
+            }
+        }
+    }
+    return CSV_OK;
+}
+
+static size_t sr_refs_bytes(uint64_t n_seg, uint64_t nm, uint64_t ns)
+{
+    return align_up(n_seg * sizeof(SplitTabSeg), 256) + align_up(nm * 4, 256) + align_up((nm + 1) * 8, 256) + align_up(ns * 4, 256) + align_up(ns, 256) + 8 * 256;
+}
+
+// the references and the shard table up (through `pin`), the launch; d_seg: seg_off on the device. in.supp_off is what the fits read afterwards.
+static int sr_queue(csv_ctx *ctx, Arena &A, PinStage &pin, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *d_seg,
+                    SplitTablesIn &in, const SplitTablesOut &out)
+{
+    const uint64_t nm = f->n_members, ns = f->n_supp;
+    hipStream_t s = ctx->stream;
+    std::vector<SplitTabSeg> tab(n_seg);
+    for (uint64_t c = 0; c < n_seg; c++) { const csv_shard *sh = shards[c]; tab[c] = SplitTabSeg{sh->d.pos, sh->d.flag, sh->ref_end, sh->q_start, sh->q_end}; }
+    bool room = true;
+    hipError_t err = hipSuccess;
+    auto up = [&](const void *src, size_t bytes) -> const void * {
+        void *d = arena_alloc(A, bytes);
+        if (!d) { room = false; return nullptr; }
+        if (bytes && err == hipSuccess) err = hipMemcpyAsync(d, pin.in(src, bytes), bytes, hipMemcpyHostToDevice, s);
+        return d;
+    };
+    in.seg = (const SplitTabSeg *)up(tab.data(), n_seg * sizeof(SplitTabSeg));
+    in.seg_off = d_seg; in.n_seg = n_seg;
+    in.member_rec = (const uint32_t *)up(f->member_rec, nm * 4);
+    in.supp_off = (const uint64_t *)up(f->supp_off, (nm + 1) * 8);
+    in.supp_rec = (const uint32_t *)up(f->supp_rec, ns * 4);
+    in.supp_where = (const uint8_t *)up(f->supp_where, ns);
+    in.n_members = (uint32_t)nm; in.n_supp = (uint32_t)ns;
+    if (!room) { ctx->err = "arena exhausted (split_tables_resident)"; return CSV_ENOMEM; }
+    if (err != hipSuccess) { ctx->err = std::string("split_tables_resident: copying the references: ") + hipGetErrorString(err); return CSV_EHIP; }
+    TimerScope ts(ctx, CSV_K_MISC);
+    launch_st_tables(s, in, out);
+    return CSV_OK;
+}
+
+// the arrays of SplitTablesOut behind start / end (which the caller places)
+static bool sr_carve(Arena &A, uint64_t nm, uint64_t ns, SplitTablesOut &o)
+{
+    o.q_start = (int32_t *)arena_alloc(A, nm * 4); o.q_end = (int32_t *)arena_alloc(A, nm * 4); o.reverse = (uint8_t *)arena_alloc(A, nm);
+    o.supp_start = (int32_t *)arena_alloc(A, ns * 4); o.supp_end = (int32_t *)arena_alloc(A, ns * 4);
+    o.supp_q_start = (int32_t *)arena_alloc(A, ns * 4); o.supp_q_end = (int32_t *)arena_alloc(A, ns * 4); o.supp_flags = (uint8_t *)arena_alloc(A, ns);
+    return o.q_start && o.q_end && o.reverse && o.supp_start && o.supp_end && o.supp_q_start && o.supp_q_end && o.supp_flags;
+}
+
+int csvgpu_split_tables_resident(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *seg_off, csv_split_tables *t)
+{
+    if (!ctx) return CSV_EINVAL;
+    uint64_t max_len = 0;
+    int rc = sr_check(ctx, n_seg, shards, f, seg_off, max_len);
+    if (rc) return rc;
+    if (!t) { ctx->err = "split_tables_resident: null array"; return CSV_EINVAL; }
+    const uint64_t nm = f->n_members, ns = f->n_supp;
+    if (!t->supp_off || (nm && (!t->start || !t->end || !t->q_start || !t->q_end || !t->reverse)) ||
+        (ns && (!t->supp_start || !t->supp_end || !t->supp_q_start || !t->supp_q_end || !t->supp_flags))) { ctx->err = "split_tables_resident: null array in the tables"; return CSV_EINVAL; }
+    if (nm == 0) {
+        t->n_members = t->n_supp = 0;
+        ((uint64_t *)t->supp_off)[0] = 0;
+        return CSV_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    const size_t segb = align_up((n_seg + 1) * 8, 256);
+    if ((rc = arena_reserve(ctx, ctx->arena, sf_tables_bytes(nm, ns, true) + sr_refs_bytes(n_seg, nm, ns) + segb + 1024))) return rc;
+    if ((rc = ensure_pinned(ctx, sf_tables_bytes(nm, ns, true) + sr_refs_bytes(n_seg, nm, ns) + segb + 4096))) return rc;
+    Arena &A = ctx->arena;
+    PinStage pin(ctx);
+    SplitTablesOut o;
+    o.start = (int32_t *)arena_alloc(A, nm * 4); o.end = (int32_t *)arena_alloc(A, nm * 4);
+    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
+    o.err = (uint32_t *)arena_alloc(A, 256); o.err_bit = 1;
+    if (!sr_carve(A, nm, ns, o) || !o.start || !o.end || !d_seg || !o.err) { ctx->err = "arena exhausted (split_tables_resident)"; return CSV_ENOMEM; }
+    CSV_HIP(ctx, hipMemsetAsync(o.err, 0, 4, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    SplitTablesIn in;
+    if ((rc = sr_queue(ctx, A, pin, n_seg, shards, f, d_seg, in, o))) { (void)wait_stream(s); return rc; }
+    volatile uint32_t *h_err = (volatile uint32_t *)pin.in(nullptr, 0);
+    pin.used += 256;
+    CSV_HIP(ctx, hipMemcpyAsync((void *)h_err, o.err, 4, hipMemcpyDeviceToHost, s));
+    auto down = [&](const void *dst, const void *src, size_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(pin.out((void *)dst, bytes), src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    CSV_HIP(ctx, down(t->start, o.start, nm * 4)); CSV_HIP(ctx, down(t->end, o.end, nm * 4));
+    CSV_HIP(ctx, down(t->q_start, o.q_start, nm * 4)); CSV_HIP(ctx, down(t->q_end, o.q_end, nm * 4)); CSV_HIP(ctx, down(t->reverse, o.reverse, nm));
+    CSV_HIP(ctx, down(t->supp_start, o.supp_start, ns * 4)); CSV_HIP(ctx, down(t->supp_end, o.supp_end, ns * 4));
+    CSV_HIP(ctx, down(t->supp_q_start, o.supp_q_start, ns * 4)); CSV_HIP(ctx, down(t->supp_q_end, o.supp_q_end, ns * 4));
+    CSV_HIP(ctx, down(t->supp_flags, o.supp_flags, ns));
+    CSV_HIP(ctx, wait_stream(s));
+    if (*h_err) { ctx->err = "split_tables_resident: a coordinate of the shards is negative or end < start"; return CSV_EINVAL; }
+    pin.finish();
+    memcpy((void *)t->supp_off, f->supp_off, (nm + 1) * 8);
+    t->n_members = nm; t->n_supp = ns;
+    return CSV_OK;
+}
+
+namespace {
+struct SrFill {
+    csv_ctx *ctx; uint64_t n_seg; csv_shard *const *shards; const csv_split_refs *f;
+    SplitFitsIn *fits_in;
+    static int queue(void *arg, SgChain &c, PinStage &pin) { return ((SrFill *)arg)->run(c, pin); }
+    int run(SgChain &c, PinStage &pin)
+    {
+        const uint64_t nm = f->n_members, ns = f->n_supp;
+        SplitTablesOut o;
+        o.start = c.d_start; o.end = c.d_end;
+        o.err = c.w.err; o.err_bit = SG_ERR_DOMAIN;
+        if (!sr_carve(ctx->arena, nm, ns, o)) { ctx->err = "arena exhausted (split_resident_fits)"; return CSV_ENOMEM; }
+        SplitTablesIn in;
+        const int rc = sr_queue(ctx, ctx->arena, pin, n_seg, shards, f, c.d_seg, in, o);
+        if (rc) return rc;
+        SplitFitsIn &r = *fits_in;
+        r.start = o.start; r.end = o.end; r.q_start = o.q_start; r.q_end = o.q_end; r.reverse = o.reverse; r.supp_off = in.supp_off;
+        r.supp_start = o.supp_start; r.supp_end = o.supp_end; r.supp_q_start = o.supp_q_start; r.supp_q_end = o.supp_q_end; r.supp_flags = o.supp_flags;
+        return CSV_OK;
+    }
+};
+}  // namespace
+
+int csvgpu_split_resident_fits(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *seg_off, double eps,
+                               int32_t min_pts, uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups)
+{
+    if (!ctx) return CSV_EINVAL;
+    int rc = check_dbscan_args(ctx, eps, min_pts, false);
+    if (rc) return rc;
+    uint64_t max_len = 0;
+    if ((rc = sr_check(ctx, n_seg, shards, f, seg_off, max_len))) return rc;
+    if (!seg_group_off || !n_groups) { ctx->err = "split_resident_fits: null array"; return CSV_EINVAL; }
+    const uint64_t nm = f->n_members, ns = f->n_supp;
+    if (nm && !out) { ctx->err = "split_resident_fits: null array"; return CSV_EINVAL; }
+    *n_groups = 0;
+    if (nm == 0 || max_len < 2) {                            // no segment can hold a group of two
         for (uint64_t c = 0; c <= n_seg; c++) seg_group_off[c] = 0;
         return CSV_OK;
     }
-    r.B = std::max(std::min(total, max_len), ns);
-    SortWs fw;
-    if ((rc = sg_fill_reserve(ctx, ch, sf_out_bytes(G) + sf_big_bytes(r.B), fw))) return rc;
-    r.A = &ctx->work;
-    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
-    PinStage pin(ctx);
-    uint32_t *h_sort_err = (uint32_t *)pin.in(nullptr, 0);
-    pin.used += 256;
-    *h_sort_err = 0;
-    {
-        TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
-        sg_fill_launch(ctx, ch, fw);
-        if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(pin.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
-    }
-    r.in.seg_off = ch.d_seg; r.in.seg_group_off = ch.w.seg_group_off; r.in.group_off = ch.w.group_off; r.in.members = ch.d_members;
-    r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
-    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
-    CSV_HIP(ctx, wait_stream(s));
-    if (*h_sort_err) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
-    pin.finish();
-    *n_groups = G;
-    if (r.h_res[0] == 0) return CSV_OK;
-    return sf_big(ctx, r, eps, min_pts, out);
+    SgChain ch;
+    SfRun r;
+    SrFill fill;
+    fill.ctx = ctx; fill.n_seg = n_seg; fill.shards = shards; fill.f = f; fill.fits_in = &r.in;
+    const size_t extra = sf_tables_bytes(nm, ns, false) + sr_refs_bytes(n_seg, nm, ns);
+    if ((rc = sg_queue(ctx, nullptr, nullptr, seg_off, n_seg, (uint32_t)nm, max_len, extra, extra, ch, SrFill::queue, &fill))) { (void)wait_stream(ctx->stream); return rc; }
+    return sgf_finish(ctx, ch, r, n_seg, max_len, ns, eps, min_pts, seg_group_off, out, n_groups);
 }
 
 int csvgpu_window_log2_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *region_start, const uint32_t *region_end,

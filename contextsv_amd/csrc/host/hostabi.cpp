@@ -370,6 +370,40 @@ int csvhost_split_signatures(csv_ctx *ctx, uint64_t n, const int32_t *tid, const
     return csvhost_split_signatures_opts(ctx, n, tid, pos, flag, mapq, ref_end, q_start, q_end, qname_id, n_targets, min_mapq, 0, out, cap, n_out);
 }
 
+// The record references that SplitPass::prepare() computes (csv_split_refs' arrays, what SplitParams::device_tables is given), from the inputs of
+// csvhost_split_signatures without the intervals; needs no GPU. Segment t = tid t: seg_off [n_targets + 1]; record indices count within the tid's
+// records in file order (a contig uploaded as its own shard); supp_rec / supp_tid say which record an entry on another tid is (no device call reads
+// them). The member arrays have room for n entries (supp_off: n + 1), the entry arrays for `cap`; n_out[0] = members, n_out[1] = entries; -5 (CSV_ECAPACITY)
+// with only n_out written when there are more entries than `cap`.
+int csvhost_split_refs(uint64_t n, const int32_t *tid, const int32_t *pos, const uint16_t *flag, const uint8_t *mapq, const uint32_t *qname_id, int n_targets,
+                       int min_mapq, uint64_t *seg_off, uint32_t *member_rec, uint64_t *supp_off, uint32_t *supp_rec, uint8_t *supp_where, int32_t *supp_tid,
+                       uint64_t cap, uint64_t *n_out)
+{
+    try {
+        std::vector<SplitRecord> rec(n);
+        std::vector<std::string> qn(n);
+        for (uint64_t i = 0; i < n; i++) {
+            rec[i] = SplitRecord{tid[i], pos[i], flag[i], mapq[i], 0, 0, 0};
+            qn[i] = "r" + std::to_string(qname_id[i]);
+        }
+        SplitParams p; p.min_mapq = min_mapq;
+        SplitRefTables R;
+        std::vector<uint64_t> so;
+        splitReferences(rec, qn, (size_t)(n_targets > 0 ? n_targets : 0), p, R, so);
+        n_out[0] = R.member_rec.size(); n_out[1] = R.supp_rec.size();
+        if (R.member_rec.size() > n) { g_err = "split_refs: more members than records"; return -100; }
+        if (R.supp_rec.size() > cap) { g_err = "split_refs: entry capacity too small"; return CSV_ECAPACITY; }
+        std::copy(so.begin(), so.end(), seg_off);
+        std::copy(R.member_rec.begin(), R.member_rec.end(), member_rec);
+        std::copy(R.supp_off.begin(), R.supp_off.end(), supp_off);
+        std::copy(R.supp_rec.begin(), R.supp_rec.end(), supp_rec);
+        std::copy(R.supp_where.begin(), R.supp_where.end(), supp_where);
+        std::copy(R.supp_tid.begin(), R.supp_tid.end(), supp_tid);
+        return 0;
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return CSV_EINVAL;
+    } catch (const std::exception &e) { g_err = e.what(); return -100; }
+}
+
 // The outputs of csvgpu_split_groups computed by the host's interval tree (the path without SplitParams::device_groups); needs no GPU.
 // seg_group_off [n_seg + 1]; group_off [seg_off[n_seg] + 1] (entries 0 .. seg_group_off[n_seg] written); *n_members: in capacity, out count
 // required; -5 (CSV_ECAPACITY) when members[] is too small, -1 (CSV_EINVAL) on end < start or descending offsets.
@@ -746,7 +780,7 @@ void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n
 // One step: SVCaller::runResident over every staged contig. passes: bit 0 split-read pass, bit 1 CIGAR copy-number pass, bit 2 the two
 // final merges, bit 3 keep the qname map's order on the host (umap_order.h) instead of csvgpu_split_order,
 // bit 4 do not run the split pass's first half beside the CIGAR pass; bit 9 the overlap groups from csvgpu_split_groups (split_groups_on_device), bit 10 the groups' fits from csvgpu_split_fits
-// (split_fits_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
+// (split_fits_on_device), bit 11 the members' tables built on the device from the resident shards, groups and fits with them (split_tables_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
 // (0 timed, 1 none, 2 all at once, 3 every three), bit 7 no split chain beside the pass, bit 8 the two-call split order, bits 16-30
 // prepare_delay_ms. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
 int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *const *lane_ctxs, const csv_hmm *hmm, double eps, double min_pts_pct,
@@ -771,6 +805,7 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         P.schedule.split_order_self = (passes & 256) == 0;
         P.split_groups_on_device = (passes & 512) != 0;
         P.split_fits_on_device = (passes & 1024) != 0;
+        P.split_tables_on_device = (passes & 2048) != 0;
         P.schedule.prepare_delay_ms = (passes >> 16) & 0x7fff;
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);

@@ -163,6 +163,9 @@ struct SplitPass::Impl {
     void groupsOf(size_t c, bool trace);
     void groupsOnDevice(const std::vector<size_t> &ids);
     void fitsOnDevice(const std::vector<size_t> &ids);
+    bool byRefs(size_t c) const { return params.device_tables && !contigs[c].ref_end; }   // tables, groups and fits from record references (SplitParams::device_tables)
+    void refsOf(const std::vector<size_t> &ids, SplitRefTables &refs, std::vector<uint64_t> &seg_off) const;
+    void tablesOnDevice(const std::vector<size_t> &ids);
     void groupWork(const std::vector<size_t> &ids, bool trace);
     void finishEarly(const std::vector<size_t> &ids);
     void finishFor(const std::vector<size_t> &ids, std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
@@ -178,6 +181,7 @@ void SplitPass::prepare() { p->prepare(); prepared = true; }
 void SplitPass::finish(std::unordered_map<std::string, std::vector<SVCall>> &sv_calls) { if (!prepared) prepare(); p->finish(sv_calls); }
 void SplitPass::finishEarly(const std::vector<size_t> &contig_ids) { if (prepared) p->finishEarly(contig_ids); }
 void SplitPass::finishFor(const std::vector<size_t> &contig_ids, std::unordered_map<std::string, std::vector<SVCall>> &sv_calls) { if (!prepared) prepare(); p->finishFor(contig_ids, sv_calls); }
+void SplitPass::references(const std::vector<size_t> &contig_ids, SplitRefTables &refs, std::vector<uint64_t> &seg_off) { if (!prepared) prepare(); p->refsOf(contig_ids, refs, seg_off); }
 
 void findSplitSVSignatures(const std::vector<SplitContig> &contigs, const std::vector<std::string> &target_names, const SplitParams &params,
                            std::unordered_map<std::string, std::vector<SVCall>> &sv_calls)
@@ -290,7 +294,7 @@ void SplitPass::Impl::prepare()
     tr.reset(new csvhost::TraceScope("split: need lists"));
     parallel_over(work.size(), params.threads, [&](size_t c) {
         ContigWork &W = work[c];
-        if (W.in->ref_end) return;
+        if (W.in->ref_end || byRefs(c)) return;                                    // (by references: nothing of this contig is ever gathered)
         for (uint32_t r : W.member_rec) W.need.push_back(r);
         for (const SuppRef &sr : W.supps) W.need.push_back(sr.rec);
         std::sort(W.need.begin(), W.need.end());
@@ -298,6 +302,7 @@ void SplitPass::Impl::prepare()
     });
     parallel_over(work.size(), params.threads, [&](size_t c) {                     // (every contig's list is complete by now)
         ContigWork &W = work[c];
+        if (byRefs(c)) return;
         auto slot_of = [](const ContigWork &X, uint32_t rec) { return (uint32_t)(std::lower_bound(X.need.begin(), X.need.end(), rec) - X.need.begin()); };
         if (!W.in->ref_end) { W.member_slot.reserve(W.member_rec.size()); for (uint32_t r : W.member_rec) W.member_slot.push_back(slot_of(W, r)); }
         W.supp_slot.reserve(W.member_supp_ref.size());
@@ -538,9 +543,65 @@ void SplitPass::Impl::fitsOnDevice(const std::vector<size_t> &ids)
     }
 }
 
-// intervals gathered: the groups (and, with device_fits, everything up to the medians) of these contigs, by whichever route the parameters select
-void SplitPass::Impl::groupWork(const std::vector<size_t> &ids, bool trace)
+// The record references of these contigs (segment k = contig ids[k]): member_rec as prepare() left it, every supplementary entry as a record of the
+// member's own contig or as the flags byte of a record elsewhere. Needs no alignment intervals.
+void SplitPass::Impl::refsOf(const std::vector<size_t> &ids, SplitRefTables &R, std::vector<uint64_t> &seg_off) const
 {
+    seg_off.assign(ids.size() + 1, 0);
+    std::vector<uint64_t> supp_base(ids.size() + 1, 0);
+    for (size_t k = 0; k < ids.size(); k++) {
+        const ContigWork &W = work.at(ids[k]);
+        seg_off[k + 1] = seg_off[k] + W.member_rec.size();
+        supp_base[k + 1] = supp_base[k] + W.member_supp_ref.size();
+    }
+    const size_t nm = seg_off.back(), ns = supp_base.back();
+    R.member_rec.resize(nm); R.supp_off.resize(nm + 1); R.supp_rec.resize(ns); R.supp_where.resize(ns); R.supp_tid.resize(ns);
+    parallel_over(ids.size(), params.threads, [&](size_t k) {
+        const size_t c = ids[k];
+        const ContigWork &W = work[c];
+        std::copy(W.member_rec.begin(), W.member_rec.end(), R.member_rec.begin() + (std::ptrdiff_t)seg_off[k]);
+        for (size_t m = 0; m < W.member_rec.size(); m++) R.supp_off[seg_off[k] + m] = supp_base[k] + (m ? W.member_supp_off[m - 1] : 0);
+        for (size_t q = 0; q < W.member_supp_ref.size(); q++) {
+            const SplitContig &S = *work[W.member_supp_ref[q].first].in;
+            const uint32_t r = W.member_supp_ref[q].second;
+            const size_t at = supp_base[k] + q;
+            R.supp_rec[at] = r;
+            R.supp_where[at] = W.member_supp_ref[q].first == c ? 0 : (uint8_t)(2 | ((S.flag[r] & FLAG_REVERSE) ? 1 : 0));
+            R.supp_tid[at] = S.tid;
+        }
+    });
+    R.supp_off[nm] = ns;
+}
+
+// With SplitParams::device_tables, for contigs whose records lie in resident shards: ONE fits() call for the batch on nothing but the references —
+// no interval gather, no members, no flattening; the records kept per contig as fitsOnDevice keeps them.
+void SplitPass::Impl::tablesOnDevice(const std::vector<size_t> &ids)
+{
+    if (ids.empty()) return;
+    std::unique_ptr<csvhost::TraceScope> t2(new csvhost::TraceScope("split: references"));
+    SplitRefTables R;
+    std::vector<uint64_t> seg_off, sgo;
+    refsOf(ids, R, seg_off);
+    t2.reset(new csvhost::TraceScope("split: tables + fits on device"));
+    std::vector<SplitFit> fits;
+    params.device_tables->fits(ids, R, seg_off, params.eps, params.min_pts, sgo, fits);
+    if (sgo.size() != ids.size() + 1 || fits.size() < sgo.back())
+        throw std::runtime_error("findSplitSVSignatures: the table source returned tables of the wrong size");
+    for (size_t k = 0; k < ids.size(); k++) {
+        ContigWork &W = work[ids[k]];
+        if (sgo[k + 1] < sgo[k]) throw std::runtime_error("findSplitSVSignatures: the table source's group offsets descend");
+        W.fits.assign(fits.begin() + (std::ptrdiff_t)sgo[k], fits.begin() + (std::ptrdiff_t)sgo[k + 1]);
+        W.have_fits = true;
+    }
+}
+
+// intervals gathered: the groups (and, with device_fits, everything up to the medians) of these contigs, by whichever route the parameters select;
+// contigs that go by references (device_tables) need no intervals and take their own route
+void SplitPass::Impl::groupWork(const std::vector<size_t> &all, bool trace)
+{
+    std::vector<size_t> by_refs, ids;
+    for (size_t c : all) (byRefs(c) ? by_refs : ids).push_back(c);
+    tablesOnDevice(by_refs);
     if (params.device_fits) fitsOnDevice(ids);
     else if (params.device_groups) groupsOnDevice(ids);
     else parallel_over(ids.size(), params.threads, [&](size_t k) { groupsOf(ids[k], trace && k == 0); });
@@ -688,43 +749,72 @@ void SplitPass::Impl::finishFor(const std::vector<size_t> &ids, std::unordered_m
         called[c] = 1;
         if (W.n_primary == 0) continue;
         const std::string chr_name = target_names.at((size_t)W.in->tid);
-        printMessage("Processing chromosome " + chr_name + " with " + std::to_string(W.member.size()) + " primary alignments");
+        printMessage("Processing chromosome " + chr_name + " with " + std::to_string(W.member_rec.size()) + " primary alignments");
         printMessage(chr_name + ": Found " + std::to_string(W.calls.size()) + " SV candidates");
         sv_calls[chr_name] = std::move(W.calls);
     }
 }
 
+namespace {
+// records in file order (any mix of tids) regrouped by tid: file order kept inside a tid; tids in order of first appearance, which is file order for a
+// sorted BAM
+struct RecordBlocks {
+    struct Block { int32_t tid; std::vector<int32_t> pos, ref_end, q_start, q_end; std::vector<uint16_t> flag; std::vector<uint8_t> mapq;
+                   std::vector<uint64_t> qhash, name_off, file_idx; std::string names; };
+    std::vector<std::unique_ptr<Block>> blocks;
+    std::vector<SplitContig> contigs;
+    RecordBlocks(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames)
+    {
+        std::unordered_map<int32_t, size_t> at;
+        for (size_t i = 0; i < records.size(); i++) {
+            const SplitRecord &r = records[i];
+            auto it = at.find(r.tid);
+            if (it == at.end()) { it = at.emplace(r.tid, blocks.size()).first; blocks.emplace_back(new Block()); blocks.back()->tid = r.tid; blocks.back()->name_off.push_back(0); }
+            Block &b = *blocks[it->second];
+            b.pos.push_back(r.pos); b.ref_end.push_back(r.ref_end); b.q_start.push_back(r.q_start); b.q_end.push_back(r.q_end);
+            b.flag.push_back(r.flag); b.mapq.push_back(r.mapq);
+            b.qhash.push_back(csvhost::std_string_hash(qnames[i].data(), qnames[i].size()));
+            b.names += qnames[i];
+            b.file_idx.push_back(i);
+            b.name_off.push_back(b.names.size());
+        }
+        for (auto &bp : blocks) {
+            Block &b = *bp;
+            SplitContig c;
+            c.tid = b.tid; c.n = b.pos.size();
+            c.pos = b.pos.data(); c.flag = b.flag.data(); c.mapq = b.mapq.data(); c.ref_end = b.ref_end.data(); c.q_start = b.q_start.data(); c.q_end = b.q_end.data();
+            c.qhash = b.qhash.data(); c.name_bytes = b.names.data(); c.name_off = b.name_off.data(); c.file_idx = b.file_idx.data();
+            contigs.push_back(c);
+        }
+    }
+};
+}  // namespace
+
 void findSplitSVSignatures(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames,
                            const std::vector<std::string> &target_names, const SplitParams &params,
                            std::unordered_map<std::string, std::vector<SVCall>> &sv_calls)
 {
-    // regroup by tid (file order kept inside a tid; tids in order of first appearance, which is file order for a sorted BAM)
-    struct Block { int32_t tid; std::vector<int32_t> pos, ref_end, q_start, q_end; std::vector<uint16_t> flag; std::vector<uint8_t> mapq;
-                   std::vector<uint64_t> qhash, name_off, file_idx; std::string names; };
-    std::vector<std::unique_ptr<Block>> blocks;
-    std::unordered_map<int32_t, size_t> at;
-    for (size_t i = 0; i < records.size(); i++) {
-        const SplitRecord &r = records[i];
-        auto it = at.find(r.tid);
-        if (it == at.end()) { it = at.emplace(r.tid, blocks.size()).first; blocks.emplace_back(new Block()); blocks.back()->tid = r.tid; blocks.back()->name_off.push_back(0); }
-        Block &b = *blocks[it->second];
-        b.pos.push_back(r.pos); b.ref_end.push_back(r.ref_end); b.q_start.push_back(r.q_start); b.q_end.push_back(r.q_end);
-        b.flag.push_back(r.flag); b.mapq.push_back(r.mapq);
-        b.qhash.push_back(csvhost::std_string_hash(qnames[i].data(), qnames[i].size()));
-        b.names += qnames[i];
-        b.file_idx.push_back(i);
-        b.name_off.push_back(b.names.size());
+    RecordBlocks B(records, qnames);
+    findSplitSVSignatures(B.contigs, target_names, params, sv_calls);
+}
+
+void splitReferences(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames, size_t n_targets, const SplitParams &params,
+                     SplitRefTables &refs, std::vector<uint64_t> &seg_off)
+{
+    RecordBlocks B(records, qnames);
+    const std::vector<std::string> names(n_targets);
+    std::vector<size_t> ids;                               // by tid; a tid without records: an empty contig behind the blocks
+    std::vector<SplitContig> contigs = B.contigs;
+    for (size_t t = 0; t < n_targets; t++) {
+        size_t k = 0;
+        while (k < contigs.size() && (size_t)contigs[k].tid != t) k++;
+        if (k == contigs.size()) { SplitContig c; c.tid = (int32_t)t; contigs.push_back(c); }
+        ids.push_back(k);
     }
-    std::vector<SplitContig> contigs;
-    for (auto &bp : blocks) {
-        Block &b = *bp;
-        SplitContig c;
-        c.tid = b.tid; c.n = b.pos.size();
-        c.pos = b.pos.data(); c.flag = b.flag.data(); c.mapq = b.mapq.data(); c.ref_end = b.ref_end.data(); c.q_start = b.q_start.data(); c.q_end = b.q_end.data();
-        c.qhash = b.qhash.data(); c.name_bytes = b.names.data(); c.name_off = b.name_off.data(); c.file_idx = b.file_idx.data();
-        contigs.push_back(c);
-    }
-    findSplitSVSignatures(contigs, target_names, params, sv_calls);
+    for (const SplitContig &c : contigs) if (c.tid < 0 || (size_t)c.tid >= n_targets) throw std::invalid_argument("splitReferences: a tid outside the targets");
+    SplitPass pass(contigs, names, params);
+    pass.prepare();
+    pass.references(ids, refs, seg_off);
 }
 
 void splitGroupsHost(const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, std::vector<uint64_t> &seg_group_off,

@@ -93,6 +93,24 @@ struct SplitFitSource {
                       std::vector<uint64_t> &seg_group_off, std::vector<SplitFit> &fits) const = 0;
 };
 
+// The same evidence from record REFERENCES: for contigs whose records lie in resident shards (those served by an IntervalSource) nothing of the tables
+// has to be gathered, built or uploaded — the device builds them from the shards (csvgpu_split_resident_fits behind ShardTableSource in sv_caller.cpp).
+// csv_split_refs' arrays for a batch of contigs.
+struct SplitRefTables {
+    std::vector<uint32_t> member_rec;                     // [members]: the primary's record index in its contig, map iteration order per segment
+    std::vector<uint64_t> supp_off;                       // [members + 1]
+    std::vector<uint32_t> supp_rec;                       // [entries]: record index in ITS contig (read by the device only when supp_where == 0)
+    std::vector<uint8_t> supp_where;                      // [entries]: 0 = on the member's contig, else 2 | reverse strand
+    std::vector<int32_t> supp_tid;                        // [entries]: the entry's tid (for tests and tools; no source reads it)
+};
+struct SplitTableSource {
+    virtual ~SplitTableSource() = default;
+    // segment k = members [seg_off[k], seg_off[k+1]) of contig which[k] (index into the `contigs` vector). -> the groups' seg_group_off and fits[g] per group,
+    // as SplitFitSource::fits returns them without given groups. One call per batch; asked from the thread that runs finishEarly / finishFor / finish.
+    virtual void fits(const std::vector<size_t> &which, const SplitRefTables &refs, const std::vector<uint64_t> &seg_off, double eps, int min_pts,
+                      std::vector<uint64_t> &seg_group_off, std::vector<SplitFit> &fits) const = 0;
+};
+
 struct SplitParams {
     int min_mapq = 20;        // sv_caller.h:72
     double eps = 100;         // DBSCAN1D(100, 5) at sv_caller.cpp:270
@@ -104,6 +122,8 @@ struct SplitParams {
     const SplitGroupSource *device_groups = nullptr;  // where the overlap groups come from (nullptr: the host's interval tree, one contig per host thread)
     const SplitFitSource *device_fits = nullptr;      // where the groups' point sets, fits, largest clusters and medians come from (nullptr: setsOf + one DBSCAN1D batch + the host's
                                                       // reductions); with device_groups also set the source computes the groups too and they never reach the host
+    const SplitTableSource *device_tables = nullptr;  // contigs WITHOUT ref_end / q_start / q_end arrays (those `intervals` serves): tables, groups and fits from this source, given only
+                                                      // record references — no interval gather, no members, no flattening for them; contigs with arrays keep the routes above
     int threads = 0;          // host threads over contigs (0: one per contig, at most the hardware's); the result does not depend on it
 };
 
@@ -145,6 +165,9 @@ public:
     // finish() for a subset of the contigs (those of it not done yet): a contig's calls depend on nothing outside the contig, so any
     // partition of the contigs over calls gives the calls one finish() gives; finish() afterwards does what is left
     void finishFor(const std::vector<size_t> &contig_ids, std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
+    // after prepare(): the record references of these contigs' members and supplementary entries (what SplitParams::device_tables is given), segment k =
+    // contig contig_ids[k]
+    void references(const std::vector<size_t> &contig_ids, SplitRefTables &refs, std::vector<uint64_t> &seg_off);
 private:
     struct Impl;
     std::unique_ptr<Impl> p;
@@ -155,6 +178,11 @@ private:
 void findSplitSVSignatures(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames,
                            const std::vector<std::string> &target_names, const SplitParams &params,
                            std::unordered_map<std::string, std::vector<SVCall>> &sv_calls);
+
+// The references prepare() computes, from records in file order and their names: segment t = the members of tid t (t < n_targets), record indices counted
+// within the tid's records in file order (a contig uploaded as its own shard). Needs no alignment intervals and no device.
+void splitReferences(const std::vector<SplitRecord> &records, const std::vector<std::string> &qnames, size_t n_targets, const SplitParams &params,
+                     SplitRefTables &refs, std::vector<uint64_t> &seg_off);
 
 // The overlap groups of csvgpu_split_groups computed by the host's interval tree (the path SplitParams::device_groups == nullptr takes), same
 // outputs: seg_group_off [n_seg + 1], group_off [groups + 1], members. Throws std::invalid_argument on end < start or descending offsets.

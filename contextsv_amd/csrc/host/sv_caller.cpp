@@ -574,6 +574,29 @@ struct ShardFitSource : SplitFitSource {
     csv_ctx *ctx;
 };
 
+// tables, groups and fits from the device, given record references into the resident shards (csvgpu_split_resident_fits); shard_of[c] is the
+// resident shard of split-pass contig c, as for ShardIntervals, and the context and thread are theirs
+struct ShardTableSource : SplitTableSource {
+    ShardTableSource(csv_ctx *ctx, std::vector<csv_shard *> shard_of) : ctx(ctx), shard_of(std::move(shard_of)) {}
+    void fits(const std::vector<size_t> &which, const SplitRefTables &R, const std::vector<uint64_t> &seg_off, double eps, int min_pts,
+              std::vector<uint64_t> &seg_group_off, std::vector<SplitFit> &out) const override
+    {
+        std::vector<csv_shard *> sh(which.size());
+        for (size_t k = 0; k < which.size(); k++) sh[k] = shard_of.at(which[k]);
+        csv_split_refs f;
+        f.n_members = R.member_rec.size(); f.n_supp = R.supp_rec.size();
+        f.member_rec = R.member_rec.data(); f.supp_off = R.supp_off.data(); f.supp_rec = R.supp_rec.data(); f.supp_where = R.supp_where.data();
+        seg_group_off.assign(which.size() + 1, 0);
+        out.assign(std::max<size_t>(R.member_rec.size(), 1), SplitFit());
+        uint64_t n_groups = 0;
+        check(ctx, csvgpu_split_resident_fits(ctx, which.size(), sh.data(), &f, seg_off.data(), eps, min_pts, seg_group_off.data(), (csv_split_fit *)out.data(), &n_groups),
+              "split-read tables, overlap groups and fits");
+        out.resize(n_groups);
+    }
+    csv_ctx *ctx;
+    std::vector<csv_shard *> shard_of;
+};
+
 }  // namespace
 
 std::unique_ptr<SplitGroupSource> makeDeviceGroupSource(csv_ctx *ctx) { return std::unique_ptr<SplitGroupSource>(new ShardGroupSource(ctx)); }
@@ -588,6 +611,7 @@ struct SVCaller::SplitSetup {
     std::unique_ptr<ShardIntervals> intervals;
     std::unique_ptr<ShardGroupSource> dev_groups;
     std::unique_ptr<ShardFitSource> dev_fits;
+    std::unique_ptr<ShardTableSource> dev_tables;
     SplitParams sp;
     std::unique_ptr<SplitPass> pass;
     double ms_prepare = 0.0;
@@ -1018,6 +1042,8 @@ std::unique_ptr<SVCaller::SplitSetup> SVCaller::makeSplitSetup(std::vector<Resid
     if (P.split_groups_on_device) S->sp.device_groups = S->dev_groups.get();
     S->dev_fits.reset(new ShardFitSource(ctx));
     if (P.split_fits_on_device) S->sp.device_fits = S->dev_fits.get();
+    S->dev_tables.reset(new ShardTableSource(ctx, shard_of));
+    if (P.split_tables_on_device) S->sp.device_tables = S->dev_tables.get();
     S->pass.reset(new SplitPass(S->blocks, S->names, S->sp));
     return S;
 }

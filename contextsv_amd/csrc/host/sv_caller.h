@@ -105,6 +105,9 @@ struct RunParams {
     bool split_fits_on_device = false;      // what the split-read pass derives from every overlap group (point sets, DBSCAN1D fits, largest clusters, medians, strand vote;
                                             // sv_caller.cpp:248-416) from csvgpu_split_fits — with split_groups_on_device from csvgpu_split_groups_fits, the groups then staying
                                             // on the device — instead of the host's sets and one DBSCAN1D batch; the calls do not depend on it
+    bool split_tables_on_device = false;    // the members' and supplementary records' tables of the split-read pass built on the device from the resident shards
+                                            // (csvgpu_split_resident_fits): no interval gather, no members on the pool, no upload; groups and fits then come from the
+                                            // device too, whatever the two switches above say; the calls do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it

@@ -316,7 +316,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_seeds_kernel(const int32_t *__r
             }
             best = sg_wave_min_u64(next);
         }
-        if (best != SG_NONE && lane == 0) *err = 1u;                      // cannot happen; reported (CSV_EHIP), never silently wrong
+        if (best != SG_NONE && lane == 0) atomicOr(err, 1u);              // (the word is shared with the table kernel's domain bit) cannot happen; reported (CSV_EHIP), never silently wrong
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");            // this component's LDS reads before the next one's staging stores
         __builtin_amdgcn_wave_barrier();
     }
@@ -334,6 +334,8 @@ __global__ __launch_bounds__(SG_THREADS) void sg_offsets_kernel(const uint32_t *
         if (goff[t + 1] != g) { seed_of_group[g] = (uint32_t)t; group_off[g] = moff[t]; }
     } else if (t == n) {
         group_off[goff[n]] = *total;
+        // (both give-up flags are exactly 1 — sg_seeds ORs 1 into *err, a onesweep pass stores 1 —, so that the value 2 in this word stays the table
+        // kernel's domain bit, SG_ERR_DOMAIN in csvgpu.hip, which sg_wait tells apart)
         res[0] = *total; res[1] = goff[n]; res[2] = (uint64_t)(*err | (sort_err ? *sort_err : 0u));
     } else if (t - n - 1 <= n_seg) {
         const uint64_t c = t - n - 1;

@@ -68,6 +68,7 @@ def load() -> C.CDLL:
     lib.csvhost_split_signatures_opts.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_dev.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_fits_host.argtypes = [_P, C.POINTER(_lib.csv_split_tables), _P, C.c_uint64, _P, _P, _P, C.c_double, C.c_int, _P]
+    lib.csvhost_split_refs.argtypes = [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, _P]
     lib.csvhost_split_groups_host.argtypes = [_P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]
     lib.csvhost_run.argtypes = [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_lib.csv_hmm), C.c_double, C.c_double,
                                 C.c_int, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_char_p, C.c_char_p, _P, C.c_uint64, _P, C.c_int]
@@ -285,21 +286,24 @@ class Genome:
     def run(self, ctx: Context, hmm, lanes=None, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, merges=True,
             host_threads=0, capacity: int = 1 << 20, host_split_order: bool = False, overlap_split: bool = True, copy: bool = True,
             early_batches: str = "timed", split_beside_pass: bool = True, split_order_self: bool = True, prepare_delay_ms: int = 0,
-            split_groups_on_device: bool = False, split_fits_on_device: bool = False):
+            split_groups_on_device: bool = False, split_fits_on_device: bool = False, split_tables_on_device: bool = False):
         """-> (calls[CALL_DTYPE], global tid per call, stage_times, per-contig chr_stats list). copy=False: the two arrays are views of buffers
         the genome owns (two sets, used alternately) and stay valid until the run after the next one. early_batches ("timed" | "none" | "all" |
         "every3"), split_beside_pass, split_order_self and prepare_delay_ms are RunParams::schedule: no result depends on them, they force
         the branches that timing otherwise decides. split_groups_on_device: the split-read pass's overlap groups from csvgpu_split_groups (one
         call per batch of contigs) instead of the host's interval tree; the calls are the same. split_fits_on_device: what the pass derives from
         every group (point sets, DBSCAN1D fits, largest clusters, medians, strand vote) from csvgpu_split_fits — with split_groups_on_device from
-        csvgpu_split_groups_fits, the groups then staying on the device — instead of the host's sets and one DBSCAN1D batch; the calls are the same."""
+        csvgpu_split_groups_fits, the groups then staying on the device — instead of the host's sets and one DBSCAN1D batch; the calls are the same.
+        split_tables_on_device: the members' and supplementary records' tables built on the device from the resident shards and fed straight into
+        that chain (csvgpu_split_resident_fits): no interval gather, no members on the host, no upload; groups and fits then come from the device
+        whatever the two other switches say; the calls are the same."""
         if early_batches not in _EARLY_BATCHES:
             raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {early_batches!r}")
         if not 0 <= int(prepare_delay_ms) < 1 << 15:
             raise ValueError(f"prepare_delay_ms must be in [0, 32767], not {prepare_delay_ms!r}")
         passes = int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4) | \
             (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(bool(split_groups_on_device)) << 9) | \
-            (int(bool(split_fits_on_device)) << 10) | (int(prepare_delay_ms) << 16)
+            (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | (int(prepare_delay_ms) << 16)
         n = len(self)
         if getattr(self, "_cap", 0) < capacity:              # result buffers live with the genome (tens of megabytes of page faults per call otherwise)
             self._bufs = [(np.empty(capacity, CALL_DTYPE), np.empty(capacity, np.int32)) for _ in range(2)]
@@ -473,6 +477,31 @@ def split_signatures(ctx: Context, tid, pos, flag, mapq, ref_end, q_start, q_end
     _check(load().csvhost_split_signatures_dev(ctx.h, n, *[x.ctypes.data for x in a], n_targets, min_mapq, int(bool(device_groups)), int(bool(device_fits)),
                                                out.ctypes.data, cap, C.byref(k)))
     return out[: k.value].copy()
+
+
+def split_refs(tid, pos, flag, mapq, qname_id, n_targets: int, min_mapq: int = 20):
+    """The record references SplitPass::prepare() computes (qname of record i = "r<qname_id[i]>"; records in file order, any mix of tids): which
+    primaries have a supplementary record, in the iteration order of their contig's qname map, and those records in file order. Needs no
+    alignment intervals and no GPU. -> (SplitRefs, seg_off, supp_tid): segment t = tid t; record indices count within the tid's records (contig t
+    uploaded as its own shard); supp_tid[z] is the tid of entry z, whose supp_rec counts within that tid."""
+    from .context import SplitRefs
+    a = [np.ascontiguousarray(x, dt) for x, dt in ((tid, np.int32), (pos, np.int32), (flag, np.uint16), (mapq, np.uint8), (qname_id, np.uint32))]
+    n = len(a[0])
+    seg_off, member_rec, supp_off = np.zeros(n_targets + 1, np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(n + 1, np.uint64)
+    cap = max(n, 1)
+    for _ in range(2):
+        supp_rec, supp_where, supp_tid = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        k = np.zeros(2, np.uint64)
+        rc = load().csvhost_split_refs(n, *[x.ctypes.data for x in a], n_targets, min_mapq, seg_off.ctypes.data, member_rec.ctypes.data, supp_off.ctypes.data,
+                                       supp_rec.ctypes.data, supp_where.ctypes.data, supp_tid.ctypes.data, cap, k.ctypes.data)
+        if rc != _lib.CSV_ECAPACITY:
+            break
+        cap = int(k[1])
+    if rc == _lib.CSV_EINVAL:
+        raise ValueError((load().csvhost_last_error() or b"").decode())
+    _check(rc)
+    nm, ns = int(k[0]), int(k[1])
+    return SplitRefs(member_rec[:nm].copy(), supp_off[: nm + 1].copy(), supp_rec[:ns].copy(), supp_where[:ns].copy()), seg_off, supp_tid[:ns].copy()
 
 
 def split_fits_host(ctx: Context, tables, seg_off, groups, eps: float = 100.0, min_pts: int = 5):

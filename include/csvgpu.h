@@ -96,7 +96,7 @@ typedef enum csv_kernel_id {
     CSV_K_DBSCAN1D   = 4,   /* batched 1-D DBSCAN */
     CSV_K_WINDOW     = 5,   /* window log2 coverage */
     CSV_K_VITERBI    = 6,   /* emissions + Viterbi DP + backtrack */
-    CSV_K_MISC       = 7,   /* memsets, small scans, partition */
+    CSV_K_MISC       = 7,   /* the split-read tables built from resident shards (csvgpu_split_tables_resident, csvgpu_split_resident_fits) */
     CSV_K_SPLIT_ORDER = 8,  /* hash-map node order of the split-read pass (compaction + per-epoch sorts + survivors) */
     CSV_K_SPLIT_GROUPS = 9, /* overlap groups of the split-read pass (member order, links, seeds, fill + its sorts) */
     CSV_K_SPLIT_FITS = 10,  /* point sets, 1-D DBSCAN fits, largest clusters, medians and strand vote of the overlap groups */
@@ -416,6 +416,36 @@ int csvgpu_split_fits(csv_ctx *ctx, const csv_split_tables *tables, const uint64
  * out has room for tables->n_members records (there are never more groups than members). */
 int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *tables, const uint64_t *seg_off, uint64_t n_seg, double eps, int32_t min_pts,
                              uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups);
+
+/* §8f-4, the step in front: the tables themselves from the RESIDENT shards — pos, flag and the scan's ref_end / q_start / q_end of the records
+ * that take part lie in HBM already (csvgpu_chr_pipeline_dev / the jobs ran on every shard named here), so the caller passes record references
+ * instead of gathering the intervals, building the tables and sending them back. Segment c = members [seg_off[c], seg_off[c+1]), all of them
+ * records of shards[c]. */
+typedef struct csv_split_refs {
+    uint64_t n_members, n_supp;
+    const uint32_t *member_rec;   /* [n_members]: record index in its segment's shard */
+    const uint64_t *supp_off;     /* [n_members + 1] */
+    const uint32_t *supp_rec;     /* [n_supp]: record index in the SAME shard (ignored when supp_where != 0) */
+    const uint8_t  *supp_where;   /* [n_supp]: 0 same shard; 2 / 3 = on another tid, forward / reverse: the flags byte itself */
+} csv_split_refs;
+/* The tables of csv_split_tables for these references, copied to the host (the seam for tests and integrators): with S = shards[c] and
+ * r = member_rec[m], start = S.pos[r] + 1, end = S.ref_end[r], q_start = S.q_start[r], q_end = S.q_end[r], reverse = FLAG 0x10 of S.flag[r];
+ * supp_off as given; an entry with supp_where == 0 the same five from record supp_rec[z] of S (supp_flags = its FLAG 0x10), any other entry
+ * supp_flags = supp_where and the four coordinates 0. `out`: the caller sets the eleven pointers to writable arrays of the stated sizes, the call
+ * sets n_members / n_supp. One page-locked block each way, one launch, one wait.
+ * CSV_EINVAL (nothing written): a null array or shard, offsets not starting at 0, not ascending or not ending at the counts, a record index
+ * beyond its shard, supp_where outside {0, 2, 3}, 2^32 - 1 or more members or entries, a split order pending on the context — and a coordinate
+ * outside the domain of csvgpu_split_fits (negative, or end < start; members and same-shard entries), which the kernel itself finds: a shard
+ * whose coordinates all lie below 2^31 cannot hold one. Empty segments, n_seg == 0 and n_supp == 0 are valid. */
+int csvgpu_split_tables_resident(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *refs, const uint64_t *seg_off,
+                                 csv_split_tables *out);
+/* The product path: those tables built where csvgpu_split_groups_fits' chain reads them and that chain run on them — neither the intervals, the
+ * tables nor the groups reach the host; seg_group_off, *n_groups and one record per group come back, byte for byte what
+ * csvgpu_split_groups_fits returns on the tables of csvgpu_split_tables_resident. out has room for refs->n_members records. The same CSV_EINVAL
+ * cases (the domain is checked wherever the chain runs: a call in which no segment has two members has no group and launches nothing), eps / min_pts
+ * as csvgpu_dbscan_1d; CSV_EHIP also when a bounded device loop gave up. */
+int csvgpu_split_resident_fits(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *refs, const uint64_t *seg_off,
+                               double eps, int32_t min_pts, uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups);
 
 /* csvgpu_window_log2 on the depth map that the last csvgpu_chr_pipeline_dev() left resident in `shard`
  * (region tables and outputs are host memory; the depth map never leaves HBM). */
