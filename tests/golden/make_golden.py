@@ -56,7 +56,10 @@ def main():
 
     vals = []
     for x, mu, sd in [(0.0, 0.5, 0.044416), (0.0, 0.5, 0.057305), (0.3, 0.0, 1.0), (-1.2, 0.0, 1.0), (2.5, 0.0, 1.0), (0.0, 0.0, 0.163877),
-                      (0.1, 0.333333, 0.166946), (-3.7, -3.739099, 2.564467), (100.0, 100.0, 0.163877), (0.5, 0.25, 0.157236), (1e-9, 0.0, 0.155241)]:
+                      (0.1, 0.333333, 0.166946), (-3.7, -3.739099, 2.564467), (100.0, 100.0, 0.163877), (0.5, 0.25, 0.157236), (1e-9, 0.0, 0.155241),
+                      # the state-1 constant cdf_normal(0, B2_mean[4], B2_sd[4]) of hmm_params.CDF_SETS: gser, gser just below the
+                      # switch to gcf (x^2 = 1.39 < 1.5), gcf, the x <= 0 return, the positive errorf branch
+                      (0.0, 0.5, 0.5), (0.0, 0.5, 0.3), (0.0, 0.5, 0.25), (0.0, 0.0, 0.2), (0.0, -0.2, 0.3)]:
         vals.append({"x": x, "mu": mu, "sigma": sd, "pdf": ref.lib.ref_pdf_normal(x, mu, sd), "cdf": ref.lib.ref_cdf_normal(x, mu, sd)})
     json.dump({"source": "reference src/kc.cpp pdf_normal / cdf_normal via oracle/_ref (17 significant digits)", "values": vals},
               open(os.path.join(HERE, "kc_normal.json"), "w"))
