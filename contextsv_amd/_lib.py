@@ -127,6 +127,14 @@ ABI = {
     "csvgpu_viterbi_dev": (C.c_int, [_P, C.POINTER(csv_hmm), _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
 }
 
+# the CSV_TEST_HOOKS block of include/csvgpu.h beside csvgpu_test_fail_next_alloc: registered only where the loaded build exports them
+TEST_HOOKS = {
+    "csvgpu_test_radix_sort": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "csvgpu_test_radix_sort_devn": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int32, _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "csvgpu_test_exclusive_sum": (C.c_int, [_P, _P, C.c_uint64]),
+    "csvgpu_test_prefix_max": (C.c_int, [_P, _P, C.c_uint64, _P]),
+}
+
 _lib = None
 
 
@@ -149,6 +157,11 @@ def load() -> C.CDLL:
     if hasattr(lib, "csvgpu_test_fail_next_alloc"):          # only in the test build (libcsvgpu_testhooks.so via CSVGPU_LIB)
         lib.csvgpu_test_fail_next_alloc.restype = None
         lib.csvgpu_test_fail_next_alloc.argtypes = [C.c_int]
+    for name, (res, args) in TEST_HOOKS.items():             # the same build's hooks on the device primitives (tests/sort_primitives_check.py)
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -197,7 +197,9 @@ void launch_min_pts(hipStream_t s, ScanCounters *cnt, double min_pts_pct);
 void launch_depth_lookup(hipStream_t s, const uint32_t *depth, uint32_t depth_len, const uint32_t *pos, uint64_t n, int32_t *out);
 // sort.hip
 size_t radix_sort_tmp_bytes(uint64_t n);
-// stable LSD sort of (key,val) pairs by key bits [0,key_bits). Both buffer pairs are clobbered; returns 1 when the
+// stable LSD sort of (key,val) pairs by whole 8-bit digits: key bits [0, 8 * ceil(key_bits / 8)). No pass masks its digit, so bits at
+// and above key_bits inside the last digit take part in the order (every caller passes keys below 2^key_bits); bits above the last
+// digit do not, and all 64 bits travel with the key. Both buffer pairs are clobbered; returns 1 when the
 // result is in keys_out/vals_out, 0 when it is in keys_in/vals_in (even number of passes). onesweep: one launch per pass where n and
 // key_bits allow it, else (and with onesweep == false) histogram, table scan and scatter per pass — the same order bit for bit.
 int  launch_radix_sort_u64(hipStream_t s, uint64_t *keys_in, uint32_t *vals_in, uint64_t *keys_out, uint32_t *vals_out,

@@ -488,6 +488,26 @@ int csvgpu_viterbi_dev(csv_ctx *ctx, const csv_hmm *hmm, const double *d_o1, con
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
  * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster). */
 void csvgpu_test_fail_next_alloc(int n);
+
+/* Test build only: the device primitives under every kernel chain (kernels/sort.hip, launch_prefix_max of kernels/depth.hip), called
+ * unchanged on host arrays that are staged through the context's arena and stream as the chains stage theirs. Every device buffer a
+ * primitive may write is followed by CSVGPU_TEST_GUARD elements filled with a sentinel byte; the workspace is filled with it too.
+ *
+ * csvgpu_test_radix_sort: launch_radix_sort_u64 of n (key, val) pairs (onesweep != 0: the one-launch passes where the launcher takes
+ *   them). keys_out / vals_out [n]: the buffer pair the launcher names as the result. *gave_up: the word of radix_sort_gave_up, 0 where
+ *   that returns null. *tail_ok: 1 if the guards of all four ping-pong buffers and of the workspace still hold the sentinel.
+ * csvgpu_test_radix_sort_devn: launch_radix_sort_u64_devn queued with n_bound, the count n (<= n_bound) in a device word; only the n
+ *   pairs are staged. *tail_ok: 1 if slots [n, n_bound + guard) of all four buffers and the workspace's guard still hold the sentinel.
+ *   CSV_EINVAL when the launcher refuses n_bound (it is asked before anything is staged when n_bound >= 2^30: nothing is launched).
+ * csvgpu_test_exclusive_sum: launch_exclusive_sum_u32 on data[n], in place. csvgpu_test_prefix_max: launch_prefix_max, in[n] -> out[n].
+ *   Both return CSV_EHIP ("wrote past n") when a guard lost its sentinel. */
+#define CSVGPU_TEST_GUARD 4096
+int csvgpu_test_radix_sort(csv_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint64_t n, int32_t key_bits, int32_t onesweep,
+                           uint64_t *keys_out, uint32_t *vals_out, uint32_t *gave_up, int32_t *tail_ok);
+int csvgpu_test_radix_sort_devn(csv_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint64_t n, uint64_t n_bound, int32_t key_bits,
+                                uint64_t *keys_out, uint32_t *vals_out, uint32_t *gave_up, int32_t *tail_ok);
+int csvgpu_test_exclusive_sum(csv_ctx *ctx, uint32_t *data, uint64_t n);
+int csvgpu_test_prefix_max(csv_ctx *ctx, const int32_t *in, uint64_t n, int32_t *out);
 #endif
 
 #ifdef __cplusplus

@@ -16,6 +16,14 @@ def _declared():
     return sorted(set(re.findall(r"\b(csvgpu_[a-z0-9_]+)\s*\(", text)))
 
 
+def _test_hooks():
+    """What the CSV_TEST_HOOKS block of the header declares."""
+    text = open(os.path.join(ROOT, "include", "csvgpu.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    block = re.search(r"#ifdef CSV_TEST_HOOKS(.*?)#endif", text, flags=re.S).group(1)
+    return sorted(set(re.findall(r"\b(csvgpu_[a-z0-9_]+)\s*\(", block)))
+
+
 def test_header_symbols_exported():
     from contextsv_amd import _lib
     lib = _lib.load()
@@ -26,6 +34,11 @@ def test_header_symbols_exported():
     assert sorted(_lib.ABI) == names, "ctypes table and header disagree"
     assert lib.csvgpu_abi_version() == _lib.ABI_VERSION == 4
     assert not hasattr(lib, "csvgpu_test_fail_next_alloc"), "the allocation-failure hook must not be in the product library"
+    hooks = _test_hooks()
+    assert sorted(hooks) == sorted(["csvgpu_test_fail_next_alloc", *_lib.TEST_HOOKS]) and len(_lib.TEST_HOOKS) == 4
+    for n in hooks:
+        assert not hasattr(lib, n), f"{n}: a test hook must not be in the product library"
+        assert n not in _lib.ABI
     assert "csvgpu_set_tuning" in names and _lib.ABI["csvgpu_set_tuning"][1][1]._type_ is _lib.csv_tuning
 
 
@@ -85,11 +98,14 @@ def test_product_package_does_not_touch_the_oracle():
 
 
 def test_testhooks_build_exports_the_same_abi_plus_the_hook():
-    """libcsvgpu_testhooks.so (csvgpu.hip with -DCSV_TEST_HOOKS; loaded only by tests/test_gpu_job_errors.py) = the product ABI + the hook."""
+    """libcsvgpu_testhooks.so (csvgpu.hip with -DCSV_TEST_HOOKS; loaded only by tests/test_gpu_job_errors.py and
+    tests/test_gpu_sort_primitives.py) = the product ABI + the hooks: the allocation failure and the four on the device primitives."""
     from contextsv_amd import _lib
     lib = C.CDLL(os.path.join(ROOT, "contextsv_amd", "lib", "libcsvgpu_testhooks.so"))
     for n in _declared():
         assert hasattr(lib, n), n
     assert hasattr(lib, "csvgpu_test_fail_next_alloc")
+    for n in ("csvgpu_test_radix_sort", "csvgpu_test_radix_sort_devn", "csvgpu_test_exclusive_sum", "csvgpu_test_prefix_max"):
+        assert n in _test_hooks() and n in _lib.TEST_HOOKS and hasattr(lib, n), n
     lib.csvgpu_abi_version.restype = C.c_int
     assert lib.csvgpu_abi_version() == _lib.ABI_VERSION
