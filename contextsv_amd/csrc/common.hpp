@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/csvgpu.h"
+#include "arena.hpp"
 
 namespace csv {
 
@@ -33,11 +34,6 @@ struct Timer {
     int id;
     hipStream_t s;
     bool own_a = true, own_b = true;   // returned to the event pool when the timer is folded (an event may close one group and open the next)
-};
-
-struct Arena {                     // grow-only bump allocator over one device buffer; reset per entry point
-    char  *base = nullptr;
-    size_t cap = 0, used = 0;
 };
 
 }  // namespace csv
@@ -135,7 +131,6 @@ static_assert(sizeof(ScanCounters) == 256, "the counters head the 256-byte block
     } while (0)
 
 int   arena_reserve(csv_ctx *ctx, Arena &a, size_t bytes);       // grow (sync + realloc) if needed, then reset
-void *arena_alloc(Arena &a, size_t bytes);                       // 256-B aligned slice, nullptr if exhausted
 bool  timer_begin(csv_ctx *ctx, int id, hipStream_t s = nullptr);   // false: not recorded (timing off, or a group outside the selected level); s: the stream the group runs on (default: the context's)
 void  timer_end(csv_ctx *ctx);
 int   ensure_pinned(csv_ctx *ctx, size_t bytes);
@@ -147,7 +142,6 @@ struct TimerScope {
     ~TimerScope() { if (on) timer_end(c); }
 };
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int bits_of(uint64_t x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
 // ---------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <new>
 
-#include "common.hpp"
+#include "layouts.hpp"
 #include <chrono>
 #include <unordered_map>
 
@@ -45,12 +45,15 @@ int arena_reserve(csv_ctx *ctx, Arena &a, size_t bytes)
     return CSV_OK;
 }
 
-void *arena_alloc(Arena &a, size_t bytes)
+// Reserve `a` for a layout and carve it: carve(Arena &) -> bool runs on a planning arena (its `used` is the need), then on `a`. The carve
+// writes its pointers into a workspace struct of the caller's; the planning pass's values are overwritten by the real pass.
+template <class Carve>
+static int arena_reserve_for(csv_ctx *ctx, Arena &a, const char *what, Carve &&carve)
 {
-    const size_t off = align_up(a.used, 256);
-    if (off + bytes > a.cap) return nullptr;
-    a.used = off + bytes;
-    return a.base + off;
+    const int rc = arena_reserve(ctx, a, arena_plan_bytes(carve));
+    if (rc) return rc;
+    if (!carve(a)) { ctx->err = std::string("arena exhausted (") + what + ")"; return CSV_ENOMEM; }
+    return CSV_OK;
 }
 
 int ensure_pinned(csv_ctx *ctx, size_t bytes)
@@ -66,18 +69,34 @@ int ensure_pinned(csv_ctx *ctx, size_t bytes)
 // Host arrays of the host-pointer entry points travel through the context's page-locked block: the runtime stages a pageable
 // hipMemcpyAsync itself, in chunks and under a lock that the other contexts' launches also take (seen as millisecond gaps in the lanes'
 // big kernels whenever the caller's context copied its observation vectors). in(): bytes copied into the block, the block's address
-// returned for the async copy; out(): a slot of the block the device writes to, copied to the caller's array by finish() after the wait.
+// returned for the async copy; out(): a slot of the block the device writes to, copied to the caller's array by finish() after the wait;
+// slot(): bytes of the block for the caller's own use. Built without a context it plans: the three only advance `used`.
+// The block is sized like the arenas, by running the stage: pin_reserve_for plans `stage(PinStage &)`, grows the block once, then runs the
+// stage on the real one. Nothing may grow the block while a PinStage over it is live.
 struct PinStage {
     csv_ctx *ctx;
     size_t used = 0;
     struct Out { void *dst; const void *src; size_t bytes; };
     std::vector<Out> outs;
-    explicit PinStage(csv_ctx *c) : ctx(c) {}
-    static size_t need(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    const void *in(const void *src, size_t bytes) { void *p = (char *)ctx->pinned + used; if (bytes) memcpy(p, src, bytes); used += need(bytes); return p; }
-    void *out(void *dst, size_t bytes) { void *p = (char *)ctx->pinned + used; used += need(bytes); outs.push_back(Out{dst, p, bytes}); return p; }
+    explicit PinStage(csv_ctx *c = nullptr, size_t from = 0) : ctx(c), used(from) {}
+    void *slot(size_t bytes) { void *p = ctx ? (char *)ctx->pinned + used : nullptr; used += align_up(bytes, 256); return p; }
+    const void *in(const void *src, size_t bytes) { void *p = slot(bytes); if (ctx && bytes) memcpy(p, src, bytes); return p; }
+    void *out(void *dst, size_t bytes) { void *p = slot(bytes); if (ctx) outs.push_back(Out{dst, p, bytes}); return p; }
     void finish() { for (const Out &o : outs) if (o.bytes) memcpy(o.dst, o.src, o.bytes); outs.clear(); }
 };
+template <class Stage>
+static int pin_reserve_for(csv_ctx *ctx, PinStage &pin, Stage &&stage)
+{
+    PinStage plan(nullptr, pin.used);
+    stage(plan);
+    const int rc = ensure_pinned(ctx, plan.used);
+    if (rc) return rc;
+    stage(pin);
+    return CSV_OK;
+}
+// the scalars that read_counters, check_reads_dev and dbscan_iv_chain read back through the block's first bytes: a stage whose call runs
+// one of them while it is live starts with this slot, so that their ensure_pinned(kPinScalars) cannot grow the block under it
+static constexpr size_t kPinScalars = 4096;
 
 static hipEvent_t get_event(csv_ctx *ctx)
 {
@@ -128,46 +147,26 @@ struct DevReads {
     ScanCounters *cnt;
 };
 
-// device scalars + the ordering pass's bucket tables, zeroed together before every scan
-static constexpr size_t kCntBytes = 256 + 2 * (size_t)BK_N * 4;
 static constexpr uint64_t kMaxReadWords = 0x7ffff000ull;       // exclusive bound on one read's CIGAR words
 static inline uint32_t *bucket_off(ScanCounters *cnt) { return (uint32_t *)((char *)cnt + 256); }
 static inline uint32_t *bucket_cur(ScanCounters *cnt) { return bucket_off(cnt) + BK_N; }
 
-static size_t reads_bytes(const csv_reads *r)
+// copy a host shard into its carved slices (carve_reads); returns device views
+static int stage_reads(csv_ctx *ctx, const csv_reads *r, const ReadsWs &w, DevReads &o)
 {
     const uint64_t n = r->n_reads, m = r->n_cigar;
-    return align_up(n * 4, 256) + align_up(n * 2, 256) + align_up(n, 256) + align_up((n + 1) * 8, 256) + align_up(m * 4 + 16, 256) +
-           3 * align_up(n * 4, 256) + align_up(ckpt_bytes(m), 256) + align_up(kCntBytes, 256) + 512;
-}
-
-// copy a host shard into the arena; returns device views
-static int stage_reads(csv_ctx *ctx, const csv_reads *r, DevReads &o)
-{
-    Arena &a = ctx->arena;
-    const uint64_t n = r->n_reads, m = r->n_cigar;
-    int32_t *pos = (int32_t *)arena_alloc(a, n * 4);
-    uint16_t *flag = (uint16_t *)arena_alloc(a, n * 2);
-    uint8_t *mapq = (uint8_t *)arena_alloc(a, n);
-    uint64_t *coff = (uint64_t *)arena_alloc(a, (n + 1) * 8);
-    uint32_t *cig = (uint32_t *)arena_alloc(a, m * 4 + 16);
-    o.ref_end = (int32_t *)arena_alloc(a, n * 4);
-    o.q_start = (int32_t *)arena_alloc(a, n * 4);
-    o.q_end = (int32_t *)arena_alloc(a, n * 4);
-    o.cnt = (ScanCounters *)arena_alloc(a, kCntBytes);
-    o.ckpt = (uint32_t *)arena_alloc(a, ckpt_bytes(m));
-    if (!o.ckpt || !pos || !flag || !mapq || !coff || !cig || !o.ref_end || !o.q_start || !o.q_end || !o.cnt) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
     hipStream_t s = ctx->stream;
     if (n) {
-        CSV_HIP(ctx, hipMemcpyAsync(pos, r->pos, n * 4, hipMemcpyHostToDevice, s));
-        CSV_HIP(ctx, hipMemcpyAsync(flag, r->flag, n * 2, hipMemcpyHostToDevice, s));
-        CSV_HIP(ctx, hipMemcpyAsync(mapq, r->mapq, n, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(w.pos, r->pos, n * 4, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(w.flag, r->flag, n * 2, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(w.mapq, r->mapq, n, hipMemcpyHostToDevice, s));
     }
-    CSV_HIP(ctx, hipMemcpyAsync(coff, r->cigar_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (m) CSV_HIP(ctx, hipMemcpyAsync(cig, r->cigar, m * 4, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemsetAsync(o.cnt, 0, kCntBytes, s));
+    CSV_HIP(ctx, hipMemcpyAsync(w.coff, r->cigar_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (m) CSV_HIP(ctx, hipMemcpyAsync(w.cig, r->cigar, m * 4, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemsetAsync(w.cnt, 0, kCntBytes, s));
+    o.ref_end = w.ref_end; o.q_start = w.q_start; o.q_end = w.q_end; o.cnt = w.cnt; o.ckpt = w.ckpt;
     o.d = *r;
-    o.d.pos = pos; o.d.flag = flag; o.d.mapq = mapq; o.d.tid = nullptr; o.d.cigar_off = coff; o.d.cigar = cig;
+    o.d.pos = w.pos; o.d.flag = w.flag; o.d.mapq = w.mapq; o.d.tid = nullptr; o.d.cigar_off = w.coff; o.d.cigar = w.cig;
     return CSV_OK;
 }
 
@@ -200,7 +199,7 @@ static int check_reads_dev(csv_ctx *ctx, const csv_reads *r)
 {
     int rc = check_reads_ptrs(ctx, r);
     if (rc) return rc;
-    if ((rc = ensure_pinned(ctx, 4096))) return rc;
+    if ((rc = ensure_pinned(ctx, kPinScalars))) return rc;
     uint32_t *d_bad = nullptr;
     CSV_HIP(ctx, hipMalloc((void **)&d_bad, 256));
     hipError_t e = hipMemsetAsync(d_bad, 0, 4, ctx->stream);
@@ -245,29 +244,12 @@ static bool onesweep(const csv_ctx *ctx) { return !ctx->tuning.sort_three_launch
 
 static int read_counters(csv_ctx *ctx, const ScanCounters *d_cnt, ScanCounters &h)
 {
-    int rc = ensure_pinned(ctx, 4096);
+    int rc = ensure_pinned(ctx, kPinScalars);
     if (rc) return rc;
     CSV_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_cnt, sizeof(ScanCounters), hipMemcpyDeviceToHost, ctx->stream));
     CSV_HIP(ctx, wait_stream(ctx->stream));
     memcpy(&h, ctx->pinned, sizeof(ScanCounters));
     return CSV_OK;
-}
-
-// ordering workspace for n signatures
-struct SortWs {
-    uint64_t *k0, *k1;
-    uint32_t *v0, *v1;
-    void *tmp;
-    csv_sig *sig_tmp;        // bucketed copy of the signatures (bucket ordering); aliases the radix key arrays, which that path does not use
-};
-static size_t sortws_bytes(uint64_t n) { return 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256) + radix_sort_tmp_bytes(n) + 256; }
-static bool sortws_carve(Arena &a, uint64_t n, SortWs &w)
-{
-    w.k0 = (uint64_t *)arena_alloc(a, n * 8); w.k1 = (uint64_t *)arena_alloc(a, n * 8);
-    w.v0 = (uint32_t *)arena_alloc(a, n * 4); w.v1 = (uint32_t *)arena_alloc(a, n * 4);
-    w.tmp = arena_alloc(a, radix_sort_tmp_bytes(n));
-    w.sig_tmp = (csv_sig *)w.k0;                         // k0 and k1 are carved back to back: 2 x align_up(8n, 256) >= 16n bytes
-    return w.k0 && w.k1 && w.v0 && w.v1 && w.tmp && (char *)w.k1 == (char *)w.k0 + align_up(n * 8, 256);
 }
 
 // sig_raw[0..n) (arbitrary order) -> sig_sorted in the reference's vector order; optional SoA start/end.
@@ -313,9 +295,9 @@ static void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, u
     launch_sig_fix_ties_gather(ctx->stream, sig_raw, in_out ? w.k1 : w.k0, in_out ? w.v1 : w.v0, n, sig_sorted, start_out, end_out);
 }
 
-// depth chain on device arrays. pmax / ord / range scratch comes from `a`; `ranges` != nullptr: the scan already produced the
+// depth chain on device arrays. pmax / ord / range scratch is `ws` (carve_depth); `ranges` != nullptr: the scan already produced the
 // tiles' candidate ranges (coordinate-sorted shard) and only the tile kernel remains.
-static int depth_chain(csv_ctx *ctx, Arena &a, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
+static int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
                        uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges = nullptr, uint32_t cigar_pad = 0, void *items = nullptr,
                        int form = SCAN_FORM_WAVE)
 {
@@ -329,18 +311,16 @@ static int depth_chain(csv_ctx *ctx, Arena &a, const csv_reads &d, const int32_t
         launch_depth_tiles(ctx->stream, d, nullptr, ref_end, ckpt, depth_len, depth, cnt, ranges, cigar_pad, items, form);
         return CSV_OK;
     }
-    int32_t *pmax = (int32_t *)arena_alloc(a, n * 4);
-    void *ptmp = arena_alloc(a, prefix_max_tmp_bytes(n));
-    uint64_t *ttmp = (uint64_t *)arena_alloc(a, depth_tiles_tmp_bytes(depth_len));
-    if (!pmax || !ptmp || !ttmp) { ctx->err = "arena exhausted (depth)"; return CSV_ENOMEM; }
+    int32_t *pmax = ws.pmax;
+    void *ptmp = ws.ptmp;
+    uint64_t *ttmp = ws.ttmp;
     const uint32_t *ord = nullptr;
     const int32_t *pos_s = d.pos;
     const int32_t *end_s = ref_end;
     if (unsorted) {
         // shard not coordinate-sorted: sort the read indices by pos on device and feed the tile search through `ord`
-        SortWs w;
-        uint32_t *pos_g = (uint32_t *)arena_alloc(a, n * 4), *end_g = (uint32_t *)arena_alloc(a, n * 4);
-        if (!sortws_carve(a, n, w) || !pos_g || !end_g) { ctx->err = "arena exhausted (depth/unsorted)"; return CSV_ENOMEM; }
+        const SortWs &w = ws.w;
+        uint32_t *pos_g = ws.pos_g, *end_g = ws.end_g;
         launch_iota_keys_i32(ctx->stream, d.pos, n, w.k0, w.v0);
         const int io = launch_radix_sort_u64(ctx->stream, w.k0, w.v0, w.k1, w.v1, n, 32, w.tmp, onesweep(ctx));
         const uint32_t *perm = io ? w.v1 : w.v0;
@@ -353,22 +333,27 @@ static int depth_chain(csv_ctx *ctx, Arena &a, const csv_reads &d, const int32_t
     launch_depth_tiles(ctx->stream, d, ord, ref_end, ckpt, depth_len, depth, cnt, ttmp, cigar_pad, items, form);
     return CSV_OK;
 }
-static size_t depth_chain_bytes(uint64_t n, uint32_t depth_len = 0xffffffffu)
+// ctx->work for a shard's depth chain: reserved when the job begins (ws == nullptr), carved again — the same carve, the same arguments —
+// by whichever later step queues the chain
+static int depth_work(csv_ctx *ctx, const csv_shard *sh, DepthWs *ws)
 {
-    return depth_tiles_tmp_bytes(depth_len) + align_up(n * 4, 256) + prefix_max_tmp_bytes(n) + sortws_bytes(n) + 2 * align_up(n * 4, 256) + 1024;
+    DepthWs w;
+    if (!ws) return arena_reserve_for(ctx, ctx->work, "depth", [&](Arena &a) { return carve_depth(a, sh->d.n_reads, sh->depth_len, w); });
+    ctx->work.used = 0;
+    if (!carve_depth(ctx->work, sh->d.n_reads, sh->depth_len, *ws)) { ctx->err = "arena exhausted (depth)"; return CSV_ENOMEM; }
+    return CSV_OK;
 }
 
 // interval DBSCAN on device arrays in caller order
-static int dbscan_iv_chain(csv_ctx *ctx, Arena &a, const uint32_t *d_start, const uint32_t *d_end, uint64_t n, double eps,
+static int dbscan_iv_chain(csv_ctx *ctx, const DbscanIvWs &ws, const uint32_t *d_start, const uint32_t *d_end, uint64_t n, double eps,
                            int min_pts, int32_t *d_labels)
 {
     if (n == 0) return CSV_OK;
-    unsigned int *flag = (unsigned int *)arena_alloc(a, 256);
-    void *tmp = arena_alloc(a, dbscan_tmp_bytes(n));
-    if (!flag || !tmp) { ctx->err = "arena exhausted (dbscan)"; return CSV_ENOMEM; }
+    unsigned int *flag = ws.flag;
+    void *tmp = ws.tmp;
     CSV_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
     launch_check_sorted_u32(ctx->stream, d_start, n, flag);
-    int rc = ensure_pinned(ctx, 4096);
+    int rc = ensure_pinned(ctx, kPinScalars);
     if (rc) return rc;
     CSV_HIP(ctx, hipMemcpyAsync(ctx->pinned, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     CSV_HIP(ctx, wait_stream(ctx->stream));
@@ -378,9 +363,8 @@ static int dbscan_iv_chain(csv_ctx *ctx, Arena &a, const uint32_t *d_start, cons
         launch_dbscan_iv_sorted(ctx->stream, d_start, d_end, nullptr, n, n, eps, min_pts, nullptr, d_labels, tmp);
         return CSV_OK;
     }
-    SortWs w;
-    uint32_t *s_s = (uint32_t *)arena_alloc(a, n * 4), *e_s = (uint32_t *)arena_alloc(a, n * 4);
-    if (!sortws_carve(a, n, w) || !s_s || !e_s) { ctx->err = "arena exhausted (dbscan sort)"; return CSV_ENOMEM; }
+    const SortWs &w = ws.w;
+    uint32_t *s_s = ws.s_s, *e_s = ws.e_s;
     const uint32_t *perm;
     {
         TimerScope ts(ctx, CSV_K_SORT);
@@ -394,7 +378,6 @@ static int dbscan_iv_chain(csv_ctx *ctx, Arena &a, const uint32_t *d_start, cons
     launch_dbscan_iv_sorted(ctx->stream, s_s, e_s, perm, n, n, eps, min_pts, nullptr, d_labels, tmp);
     return CSV_OK;
 }
-static size_t dbscan_iv_chain_bytes(uint64_t n) { return 512 + dbscan_tmp_bytes(n) + sortws_bytes(n) + 2 * align_up(n * 4, 256) + 1024; }
 
 }  // namespace csv
 
@@ -510,12 +493,13 @@ int csvgpu_cigar_scan(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, 
     if (!n_out || (*n_out && !out)) { ctx->err = "cigar_scan: null output"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
     const uint64_t cap = std::min<uint64_t>(*n_out, reads->n_cigar);
-    rc = arena_reserve(ctx, ctx->arena, reads_bytes(reads) + align_up(cap * sizeof(csv_sig), 256) + 1024);
-    if (rc) return rc;
+    ReadsWs rw;
+    csv_sig *sig_raw = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "cigar_scan", [&](Arena &a) {
+            return carve_reads(a, reads->n_reads, reads->n_cigar, rw) && take(a, sig_raw, cap * sizeof(csv_sig) + 16);
+        }))) return rc;
     DevReads dr;
-    if ((rc = stage_reads(ctx, reads, dr))) return rc;
-    csv_sig *sig_raw = (csv_sig *)arena_alloc(ctx->arena, cap * sizeof(csv_sig) + 16);
-    if (!sig_raw) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, min_oplen, min_mapq, 1, sig_raw, cap, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt,
@@ -527,10 +511,9 @@ int csvgpu_cigar_scan(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, 
     *n_out = n;
     if (n > cap) { ctx->err = "cigar_scan: output capacity too small"; return CSV_ECAPACITY; }
     if (n == 0) return CSV_OK;
-    if ((rc = arena_reserve(ctx, ctx->work, sortws_bytes(n) + align_up(n * sizeof(csv_sig), 256) + 1024))) return rc;
     SortWs w;
-    csv_sig *sig_sorted = (csv_sig *)arena_alloc(ctx->work, n * sizeof(csv_sig));
-    if (!sortws_carve(ctx->work, n, w) || !sig_sorted) { ctx->err = "arena exhausted (sort)"; return CSV_ENOMEM; }
+    csv_sig *sig_sorted = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "sort", [&](Arena &a) { return take(a, sig_sorted, n * sizeof(csv_sig)) && sortws_carve(a, n, w); }))) return rc;
     order_signatures(ctx, sig_raw, n, depth_len, h.max_start, h.max_len, dr.cnt, false, w, sig_sorted, nullptr, nullptr);
     CSV_HIP(ctx, hipMemcpyAsync(out, sig_sorted, n * sizeof(csv_sig), hipMemcpyDeviceToHost, ctx->stream));
     CSV_HIP(ctx, wait_stream(ctx->stream));
@@ -543,9 +526,10 @@ int csvgpu_aln_intervals(csv_ctx *ctx, const csv_reads *reads, int32_t *ref_end,
     if (rc) return rc;
     if (reads->n_reads && (!ref_end || !q_start || !q_end)) { ctx->err = "aln_intervals: null output"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->arena, reads_bytes(reads) + 1024))) return rc;
+    ReadsWs rw;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "aln_intervals", [&](Arena &a) { return carve_reads(a, reads->n_reads, reads->n_cigar, rw); }))) return rc;
     DevReads dr;
-    if ((rc = stage_reads(ctx, reads, dr))) return rc;
+    if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, 0, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
@@ -566,11 +550,13 @@ int csvgpu_depth(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, uint3
     int rc = check_reads(ctx, reads);
     if (rc) return rc;
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->arena, reads_bytes(reads) + align_up((size_t)depth_len * 4 + 16, 256) + 1024))) return rc;
+    ReadsWs rw;
+    uint32_t *d_depth = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "depth", [&](Arena &a) {
+            return carve_reads(a, reads->n_reads, reads->n_cigar, rw) && take(a, d_depth, (size_t)depth_len * 4 + 16);
+        }))) return rc;
     DevReads dr;
-    if ((rc = stage_reads(ctx, reads, dr))) return rc;
-    uint32_t *d_depth = (uint32_t *)arena_alloc(ctx->arena, (size_t)depth_len * 4 + 16);
-    if (!d_depth) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
         launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
@@ -578,8 +564,9 @@ int csvgpu_depth(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, uint3
     }
     ScanCounters h;
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
-    if ((rc = arena_reserve(ctx, ctx->work, depth_chain_bytes(reads->n_reads, depth_len)))) return rc;
-    if ((rc = depth_chain(ctx, ctx->work, dr.d, dr.ref_end, dr.ckpt, h.unsorted != 0, depth_len, d_depth, dr.cnt, nullptr, 0, nullptr,
+    DepthWs dw;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "depth chain", [&](Arena &a) { return carve_depth(a, reads->n_reads, depth_len, dw); }))) return rc;
+    if ((rc = depth_chain(ctx, dw, dr.d, dr.ref_end, dr.ckpt, h.unsorted != 0, depth_len, d_depth, dr.cnt, nullptr, 0, nullptr,
                           scan_form(ctx, reads->n_reads, reads->n_cigar)))) return rc;
     if (depth && depth_len) CSV_HIP(ctx, hipMemcpyAsync(depth, d_depth, (size_t)depth_len * 4, hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
@@ -604,8 +591,9 @@ int csvgpu_dbscan_iv_dev(csv_ctx *ctx, const uint32_t *d_start, const uint32_t *
     if (n && (!d_start || !d_end || !d_labels)) { ctx->err = "dbscan: null array"; return CSV_EINVAL; }
     if (n >= 0xffffffffull) { ctx->err = "dbscan: n too large"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->work, dbscan_iv_chain_bytes(n)))) return rc;
-    return dbscan_iv_chain(ctx, ctx->work, d_start, d_end, n, eps, min_pts, d_labels);
+    DbscanIvWs ws;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "dbscan", [&](Arena &a) { return carve_dbscan_iv(a, n, ws); }))) return rc;
+    return dbscan_iv_chain(ctx, ws, d_start, d_end, n, eps, min_pts, d_labels);
 }
 
 int csvgpu_dbscan_iv(csv_ctx *ctx, const uint32_t *start, const uint32_t *end, uint64_t n, double eps, int32_t min_pts,
@@ -616,10 +604,9 @@ int csvgpu_dbscan_iv(csv_ctx *ctx, const uint32_t *start, const uint32_t *end, u
     if (n == 0) return CSV_OK;
     if (!start || !end || !labels) { ctx->err = "dbscan: null array"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->arena, 3 * align_up(n * 4, 256) + 1024))) return rc;
-    uint32_t *ds = (uint32_t *)arena_alloc(ctx->arena, n * 4), *de = (uint32_t *)arena_alloc(ctx->arena, n * 4);
-    int32_t *dl = (int32_t *)arena_alloc(ctx->arena, n * 4);
-    if (!ds || !de || !dl) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    uint32_t *ds = nullptr, *de = nullptr;
+    int32_t *dl = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "dbscan arrays", [&](Arena &a) { return take(a, ds, n * 4) && take(a, de, n * 4) && take(a, dl, n * 4); }))) return rc;
     CSV_HIP(ctx, hipMemcpyAsync(ds, start, n * 4, hipMemcpyHostToDevice, ctx->stream));
     CSV_HIP(ctx, hipMemcpyAsync(de, end, n * 4, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = csvgpu_dbscan_iv_dev(ctx, ds, de, n, eps, min_pts, dl))) return rc;
@@ -645,33 +632,36 @@ int csvgpu_dbscan_iv_batch(csv_ctx *ctx, const uint32_t *start, const uint32_t *
     if (!start || !end || !labels) { ctx->err = "dbscan batch: null array"; return CSV_EINVAL; }
     if (n >= 0xffffffffull) { ctx->err = "dbscan batch: n too large"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->arena, 3 * align_up(n * 4, 256) + align_up((n_seg + 1) * 8, 256) + 1024))) return rc;
-    uint32_t *ds = (uint32_t *)arena_alloc(ctx->arena, n * 4), *de = (uint32_t *)arena_alloc(ctx->arena, n * 4);
-    int32_t *dl = (int32_t *)arena_alloc(ctx->arena, n * 4);
-    uint64_t *doff = (uint64_t *)arena_alloc(ctx->arena, (n_seg + 1) * 8);
-    if (!ds || !de || !dl || !doff) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    uint32_t *ds = nullptr, *de = nullptr;
+    int32_t *dl = nullptr;
+    uint64_t *doff = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "dbscan batch arrays", [&](Arena &a) {
+            return take(a, ds, n * 4) && take(a, de, n * 4) && take(a, dl, n * 4) && take(a, doff, (n_seg + 1) * 8);
+        }))) return rc;
     hipStream_t st = ctx->stream;
-    if ((rc = ensure_pinned(ctx, 3 * PinStage::need(n * 4) + PinStage::need((n_seg + 1) * 8) + 4096))) return rc;
     PinStage pin(ctx);
-    CSV_HIP(ctx, hipMemcpyAsync(ds, pin.in(start, n * 4), n * 4, hipMemcpyHostToDevice, st));
-    CSV_HIP(ctx, hipMemcpyAsync(de, pin.in(end, n * 4), n * 4, hipMemcpyHostToDevice, st));
-    CSV_HIP(ctx, hipMemcpyAsync(doff, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, st));
+    const void *h_start, *h_end, *h_off;
+    void *h_labels;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) {
+            p.slot(kPinScalars);                             // the windowed path below reads its sortedness flag back through the block's first bytes
+            h_start = p.in(start, n * 4); h_end = p.in(end, n * 4); h_off = p.in(seg_off, (n_seg + 1) * 8); h_labels = p.out(labels, n * 4);
+        }))) return rc;
+    CSV_HIP(ctx, hipMemcpyAsync(ds, h_start, n * 4, hipMemcpyHostToDevice, st));
+    CSV_HIP(ctx, hipMemcpyAsync(de, h_end, n * 4, hipMemcpyHostToDevice, st));
+    CSV_HIP(ctx, hipMemcpyAsync(doff, h_off, (n_seg + 1) * 8, hipMemcpyHostToDevice, st));
     {
         TimerScope ts(ctx, CSV_K_DBSCAN);
         launch_dbscan_iv_small_batched(st, ds, de, doff, n_seg, eps, min_pts, dl, ctx->tuning.dbscan_all_pairs != 0);
     }
     if (max_len > DBSCAN_IV_SMALL_MAX) {                     // the few sets that do not fit a workgroup's LDS: windowed path, one at a time
-        CSV_HIP(ctx, wait_stream(st));                       // (that path reads its sortedness flag back through the same page-locked block)
-        const size_t keep = pin.used;
+        CSV_HIP(ctx, wait_stream(st));                       // (that path waits for its sortedness flag: nothing of it overtakes the batch)
         for (uint64_t s = 0; s < n_seg; s++) {
             const uint64_t len = seg_off[s + 1] - seg_off[s];
             if (len <= DBSCAN_IV_SMALL_MAX) continue;
             if ((rc = csvgpu_dbscan_iv_dev(ctx, ds + seg_off[s], de + seg_off[s], len, eps, min_pts, dl + seg_off[s]))) return rc;
         }
-        pin.used = keep;
-        if ((rc = ensure_pinned(ctx, keep + PinStage::need(n * 4) + 4096))) return rc;      // (a no-op: sized above)
     }
-    CSV_HIP(ctx, hipMemcpyAsync(pin.out(labels, n * 4), dl, n * 4, hipMemcpyDeviceToHost, st));
+    CSV_HIP(ctx, hipMemcpyAsync(h_labels, dl, n * 4, hipMemcpyDeviceToHost, st));
     CSV_HIP(ctx, wait_stream(st));
     pin.finish();
     return CSV_OK;
@@ -686,9 +676,9 @@ int csvgpu_dbscan_1d_dev(csv_ctx *ctx, const int32_t *d_pts, const uint64_t *d_s
     if (!d_seg_off || (n_pts && (!d_pts || !d_labels))) { ctx->err = "dbscan1d: null array"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
     const bool has_big = max_seg_len > DBSCAN1D_MAX_SEG;
-    size_t need = 1024 + (has_big ? (n_seg + 1) * 8 + dbscan1d_big_tmp_bytes(max_seg_len) + sortws_bytes(max_seg_len) + align_up((size_t)max_seg_len * 4, 256) : 0);
-    if ((rc = arena_reserve(ctx, ctx->work, need))) return rc;
-    unsigned int *flag = (unsigned int *)arena_alloc(ctx->work, 256);
+    Dbscan1dWs ws;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "dbscan1d", [&](Arena &a) { return carve_dbscan1d(a, max_seg_len, ws); }))) return rc;
+    unsigned int *flag = ws.flag;
     CSV_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
     {
         TimerScope ts(ctx, CSV_K_DBSCAN1D);
@@ -699,10 +689,9 @@ int csvgpu_dbscan_1d_dev(csv_ctx *ctx, const int32_t *d_pts, const uint64_t *d_s
     std::vector<uint64_t> off(n_seg + 1);
     CSV_HIP(ctx, hipMemcpyAsync(off.data(), d_seg_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     CSV_HIP(ctx, wait_stream(ctx->stream));
-    SortWs w;
-    uint32_t *ks = (uint32_t *)arena_alloc(ctx->work, (size_t)max_seg_len * 4);
-    void *tmp = arena_alloc(ctx->work, dbscan1d_big_tmp_bytes(max_seg_len));
-    if (!sortws_carve(ctx->work, max_seg_len, w) || !ks || !tmp) { ctx->err = "arena exhausted (dbscan1d big)"; return CSV_ENOMEM; }
+    const SortWs &w = ws.w;
+    uint32_t *ks = ws.ks;
+    void *tmp = ws.tmp;
     for (uint64_t s = 0; s < n_seg; s++) {
         const uint64_t n = off[s + 1] - off[s];
         if (n <= DBSCAN1D_MAX_SEG) continue;
@@ -734,18 +723,18 @@ int csvgpu_dbscan_1d(csv_ctx *ctx, const int32_t *pts, const uint64_t *seg_off, 
     if (!pts || !labels) { ctx->err = "dbscan1d: null array"; return CSV_EINVAL; }
     if (max_len >= 0xffffffffull) { ctx->err = "dbscan1d: segment too large"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    if ((rc = arena_reserve(ctx, ctx->arena, 2 * align_up(n * 4, 256) + align_up((n_seg + 1) * 8, 256) + 1024))) return rc;
-    int32_t *dp = (int32_t *)arena_alloc(ctx->arena, n * 4), *dl = (int32_t *)arena_alloc(ctx->arena, n * 4);
-    uint64_t *doff = (uint64_t *)arena_alloc(ctx->arena, (n_seg + 1) * 8);
-    if (!dp || !dl || !doff) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
-    if ((rc = ensure_pinned(ctx, 2 * PinStage::need(n * 4) + PinStage::need((n_seg + 1) * 8) + 4096))) return rc;
+    int32_t *dp = nullptr, *dl = nullptr;
+    uint64_t *doff = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "dbscan1d arrays", [&](Arena &a) { return take(a, dp, n * 4) && take(a, dl, n * 4) && take(a, doff, (n_seg + 1) * 8); }))) return rc;
     PinStage pin(ctx);
-    CSV_HIP(ctx, hipMemcpyAsync(dp, pin.in(pts, n * 4), n * 4, hipMemcpyHostToDevice, ctx->stream));
-    CSV_HIP(ctx, hipMemcpyAsync(doff, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (max_len > DBSCAN1D_MAX_SEG) CSV_HIP(ctx, wait_stream(ctx->stream));          // (the large-segment path may use the page-locked block itself)
-    if ((rc = csvgpu_dbscan_1d_dev(ctx, dp, doff, n_seg, n, (uint32_t)max_len, eps, min_pts, dl))) return rc;
-    if (max_len > DBSCAN1D_MAX_SEG && (rc = ensure_pinned(ctx, 2 * PinStage::need(n * 4) + PinStage::need((n_seg + 1) * 8) + 4096))) return rc;
-    CSV_HIP(ctx, hipMemcpyAsync(pin.out(labels, n * 4), dl, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    const void *h_pts, *h_off;
+    void *h_labels;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { h_pts = p.in(pts, n * 4); h_off = p.in(seg_off, (n_seg + 1) * 8); h_labels = p.out(labels, n * 4); }))) return rc;
+    CSV_HIP(ctx, hipMemcpyAsync(dp, h_pts, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    CSV_HIP(ctx, hipMemcpyAsync(doff, h_off, (n_seg + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (max_len > DBSCAN1D_MAX_SEG) CSV_HIP(ctx, wait_stream(ctx->stream));          // (the large-segment path reads the offsets back: nothing of it overtakes the staging)
+    if ((rc = csvgpu_dbscan_1d_dev(ctx, dp, doff, n_seg, n, (uint32_t)max_len, eps, min_pts, dl))) return rc;      // (leaves the page-locked block alone)
+    CSV_HIP(ctx, hipMemcpyAsync(h_labels, dl, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     CSV_HIP(ctx, wait_stream(ctx->stream));
     pin.finish();
     return CSV_OK;
@@ -780,16 +769,14 @@ int csvgpu_window_log2(csv_ctx *ctx, const uint32_t *depth, uint32_t depth_len, 
     if (nw == 0) return CSV_OK;
     if (!log2_cov || !win_start || !win_end) { ctx->err = "window_log2: null output"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->arena, align_up((size_t)depth_len * 4, 256) + 3 * align_up(n_regions * 4, 256) + align_up((n_regions + 1) * 8, 256) +
-                                                align_up(nw * 8, 256) + 2 * align_up(nw * 4, 256) + 4096);
+    uint32_t *dd = nullptr;
+    WindowWs w;
+    int rc = arena_reserve_for(ctx, ctx->arena, "window_log2", [&](Arena &a) { return take(a, dd, (size_t)depth_len * 4) && carve_window(a, n_regions, nw, w); });
     if (rc) return rc;
-    Arena &a = ctx->arena;
-    uint32_t *dd = (uint32_t *)arena_alloc(a, (size_t)depth_len * 4), *drs = (uint32_t *)arena_alloc(a, n_regions * 4), *dre = (uint32_t *)arena_alloc(a, n_regions * 4);
-    int32_t *dss = (int32_t *)arena_alloc(a, n_regions * 4);
-    uint64_t *dwo = (uint64_t *)arena_alloc(a, (n_regions + 1) * 8);
-    double *dl2 = (double *)arena_alloc(a, nw * 8);
-    uint32_t *dws = (uint32_t *)arena_alloc(a, nw * 4), *dwe = (uint32_t *)arena_alloc(a, nw * 4);
-    if (!dd || !drs || !dre || !dss || !dwo || !dl2 || !dws || !dwe) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    uint32_t *drs = w.rs, *dre = w.re, *dws = w.ws, *dwe = w.we;
+    int32_t *dss = w.ss;
+    uint64_t *dwo = w.wo;
+    double *dl2 = w.l2;
     hipStream_t s = ctx->stream;
     CSV_HIP(ctx, hipMemcpyAsync(dd, depth, (size_t)depth_len * 4, hipMemcpyHostToDevice, s));
     CSV_HIP(ctx, hipMemcpyAsync(drs, region_start, n_regions * 4, hipMemcpyHostToDevice, s));
@@ -812,10 +799,9 @@ int csvgpu_viterbi_dev(csv_ctx *ctx, const csv_hmm *hmm, const double *d_o1, con
     if (n_seq == 0) return CSV_OK;
     if (!d_seq_off || !d_loglik || (n_obs && (!d_o1 || !d_o2 || !d_pfb || !d_states))) { ctx->err = "viterbi: null array"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->work, viterbi_tmp_bytes(n_obs, n_seq) + 1024);
+    void *tmp = nullptr;
+    int rc = arena_reserve_for(ctx, ctx->work, "viterbi", [&](Arena &a) { return take(a, tmp, viterbi_tmp_bytes(n_obs, n_seq)); });
     if (rc) return rc;
-    void *tmp = arena_alloc(ctx->work, viterbi_tmp_bytes(n_obs, n_seq));
-    if (!tmp) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
     TimerScope ts(ctx, CSV_K_VITERBI);
     launch_viterbi(ctx->stream, *hmm, d_o1, d_o2, d_pfb, d_seq_off, n_seq, n_obs, d_states, d_loglik, tmp);
     return CSV_OK;
@@ -832,26 +818,30 @@ int csvgpu_viterbi(csv_ctx *ctx, const csv_hmm *hmm, const double *o1, const dou
     const uint64_t n = seq_off[n_seq];
     if (n && (!o1 || !o2 || !pfb || !states)) { ctx->err = "viterbi: null array"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->arena, 3 * align_up(n * 8, 256) + align_up((n_seq + 1) * 8, 256) + align_up(n * 4, 256) + align_up(n_seq * 8, 256) + 4096);
+    double *d1 = nullptr, *d2 = nullptr, *dp = nullptr, *dll = nullptr;
+    uint64_t *doff = nullptr;
+    int32_t *dst = nullptr;
+    int rc = arena_reserve_for(ctx, ctx->arena, "viterbi arrays", [&](Arena &a) {
+        return take(a, d1, n * 8 + 8) && take(a, d2, n * 8 + 8) && take(a, dp, n * 8 + 8) && take(a, doff, (n_seq + 1) * 8) && take(a, dst, n * 4 + 8) && take(a, dll, n_seq * 8);
+    });
     if (rc) return rc;
-    Arena &a = ctx->arena;
-    double *d1 = (double *)arena_alloc(a, n * 8 + 8), *d2 = (double *)arena_alloc(a, n * 8 + 8), *dp = (double *)arena_alloc(a, n * 8 + 8);
-    uint64_t *doff = (uint64_t *)arena_alloc(a, (n_seq + 1) * 8);
-    int32_t *dst = (int32_t *)arena_alloc(a, n * 4 + 8);
-    double *dll = (double *)arena_alloc(a, n_seq * 8);
-    if (!d1 || !d2 || !dp || !doff || !dst || !dll) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
     hipStream_t s = ctx->stream;
-    if ((rc = ensure_pinned(ctx, 3 * PinStage::need(n * 8) + PinStage::need((n_seq + 1) * 8) + PinStage::need(n * 4) + PinStage::need(n_seq * 8) + 4096))) return rc;
     PinStage pin(ctx);
+    const void *h1, *h2, *hp, *h_off;
+    void *h_states, *h_ll;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) {
+            h1 = p.in(o1, n * 8); h2 = p.in(o2, n * 8); hp = p.in(pfb, n * 8); h_off = p.in(seq_off, (n_seq + 1) * 8);
+            h_states = p.out(states, n * 4); h_ll = p.out(loglik, n_seq * 8);
+        }))) return rc;
     if (n) {
-        CSV_HIP(ctx, hipMemcpyAsync(d1, pin.in(o1, n * 8), n * 8, hipMemcpyHostToDevice, s));
-        CSV_HIP(ctx, hipMemcpyAsync(d2, pin.in(o2, n * 8), n * 8, hipMemcpyHostToDevice, s));
-        CSV_HIP(ctx, hipMemcpyAsync(dp, pin.in(pfb, n * 8), n * 8, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(d1, h1, n * 8, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(d2, h2, n * 8, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(dp, hp, n * 8, hipMemcpyHostToDevice, s));
     }
-    CSV_HIP(ctx, hipMemcpyAsync(doff, pin.in(seq_off, (n_seq + 1) * 8), (n_seq + 1) * 8, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(doff, h_off, (n_seq + 1) * 8, hipMemcpyHostToDevice, s));
     if ((rc = csvgpu_viterbi_dev(ctx, hmm, d1, d2, dp, doff, n_seq, n, dst, dll))) return rc;
-    if (n) CSV_HIP(ctx, hipMemcpyAsync(pin.out(states, n * 4), dst, n * 4, hipMemcpyDeviceToHost, s));
-    CSV_HIP(ctx, hipMemcpyAsync(pin.out(loglik, n_seq * 8), dll, n_seq * 8, hipMemcpyDeviceToHost, s));
+    if (n) CSV_HIP(ctx, hipMemcpyAsync(h_states, dst, n * 4, hipMemcpyDeviceToHost, s));
+    CSV_HIP(ctx, hipMemcpyAsync(h_ll, dll, n_seq * 8, hipMemcpyDeviceToHost, s));
     CSV_HIP(ctx, wait_stream(s));
     pin.finish();
     return CSV_OK;
@@ -993,12 +983,11 @@ int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *cons
     (void)hipSetDevice(ctx->device);
     // one page-locked block carries every shard's tables to the device and every shard's windows back
     const size_t in_bytes = align_up(R * 4, 8) * 3 + (R + (size_t)n_shards) * 8, out_bytes = W * 8 + 2 * align_up(W * 4, 8);
-    int rc = ensure_pinned(ctx, in_bytes + out_bytes + 4096);
+    char *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+    PinStage pin(ctx);
+    int rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { h_in = (char *)p.slot(in_bytes); h_out = (char *)p.slot(out_bytes); });
     if (rc) return rc;
-    if ((rc = arena_reserve(ctx, ctx->arena, in_bytes + out_bytes + 8192))) return rc;
-    char *h_in = (char *)ctx->pinned, *h_out = h_in + align_up(in_bytes, 256);
-    char *d_in = (char *)arena_alloc(ctx->arena, in_bytes), *d_out = (char *)arena_alloc(ctx->arena, out_bytes);
-    if (!d_in || !d_out) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "window_log2_many", [&](Arena &a) { return take(a, d_in, in_bytes) && take(a, d_out, out_bytes); }))) return rc;
     const size_t o_rs = 0, o_re = align_up(R * 4, 8), o_ss = 2 * align_up(R * 4, 8), o_wo = 3 * align_up(R * 4, 8);
     const size_t o_l2 = 0, o_ws = W * 8, o_we = W * 8 + align_up(W * 4, 8);
     uint64_t r0 = 0, w0 = 0;
@@ -1055,14 +1044,13 @@ int csvgpu_aln_intervals_gather_batch(csv_ctx *ctx, int n_shards, csv_shard *con
         for (uint64_t i = rec_off[c]; i < rec_off[c + 1]; i++) if (rec[i] >= shards[c]->d.n_reads) { ctx->err = "aln_intervals_gather: record index beyond the shard"; return CSV_EINVAL; }
     }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->arena, 4 * align_up(n * 4, 256) + 4096);
+    uint32_t *didx = nullptr, *dout = nullptr;
+    int rc = arena_reserve_for(ctx, ctx->arena, "aln_intervals_gather", [&](Arena &a) { return take(a, didx, n * 4) && take(a, dout, 3 * n * 4); });
     if (rc) return rc;
-    if ((rc = ensure_pinned(ctx, 4 * align_up(n * 4, 256) + 4096))) return rc;      // the index list goes out and the three arrays come back through one page-locked block
-    uint32_t *didx = (uint32_t *)arena_alloc(ctx->arena, n * 4);
-    uint32_t *dout = (uint32_t *)arena_alloc(ctx->arena, 3 * n * 4);
-    if (!didx || !dout) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
-    uint32_t *h_idx = (uint32_t *)ctx->pinned, *h_out = h_idx + align_up(n * 4, 256) / 4;
-    memcpy(h_idx, rec, n * 4);
+    const uint32_t *h_idx = nullptr;
+    uint32_t *h_out = nullptr;                                          // the index list goes out and the three arrays come back through one page-locked block
+    PinStage pin(ctx);
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { h_idx = (const uint32_t *)p.in(rec, n * 4); h_out = (uint32_t *)p.slot(3 * n * 4); }))) return rc;
     hipStream_t s = ctx->stream;
     CSV_HIP(ctx, hipMemcpyAsync(didx, h_idx, n * 4, hipMemcpyHostToDevice, s));
     for (int c = 0; c < n_shards; c++) {
@@ -1124,20 +1112,13 @@ static void split_order_epochs(uint64_t n_max, std::vector<uint64_t> &first_node
 }  // extern "C"
 
 // What csvgpu_split_order_begin leaves for csvgpu_split_order_finish (one pending order per context; device pointers into ctx->arena / ctx->work).
-struct csv_split_state {
+struct csv_split_state : SplitNodesWs, SplitEpochsWs {
     int n_contigs = 0;
     SplitOrderTab tab;
     std::vector<uint64_t> N;
     uint64_t n_nodes = 0, n_max = 0, total_reads = 0;
     int D = 0;
     SplitTailHost th;
-    uint64_t *node_hash = nullptr, *d_supp = nullptr;
-    uint32_t *node_rec = nullptr, *list = nullptr, *minT = nullptr;
-    SortWs w;
-    csv_split_survivor *d_out = nullptr;
-    unsigned long long *d_count = nullptr;
-    uint32_t *bitmap[SO_TAIL_MAX] = {nullptr, nullptr, nullptr}, *set[SO_TAIL_MAX + 1] = {nullptr, nullptr, nullptr, nullptr}, *prevrank = nullptr, *filter = nullptr;
-    uint8_t *is_surv = nullptr;
     size_t bm_words = 0;
     bool finished = false;
     bool self = false;                 // the supplementary hashes are taken from the same shards: the whole order was queued by _begin
@@ -1182,17 +1163,12 @@ static int split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
 
     // ---- nodes: the filter-passing primaries of every contig, file order ----
     // (the supplementary hashes arrive with _finish: at most one per record)
-    int rc = arena_reserve(ctx, ctx->arena, align_up((n_blocks + 1) * 4, 256) + exclusive_sum_tmp_bytes(n_blocks + 1) + align_up(total_reads * 8, 256) +
-                                                2 * align_up(total_reads * 4, 256) + align_up(total_reads * 8, 256) + 4096);
+    int rc = arena_reserve_for(ctx, ctx->arena, "split order", [&](Arena &a) { return carve_split_nodes(a, n_blocks, total_reads, *st); });
     if (rc) return rc;
-    unsigned int *d_nsupp = (unsigned int *)arena_alloc(ctx->arena, 256);
-    uint32_t *blk = (uint32_t *)arena_alloc(ctx->arena, (n_blocks + 1) * 4);
-    void *es_tmp = arena_alloc(ctx->arena, exclusive_sum_tmp_bytes(n_blocks + 1));
-    uint64_t *node_hash = (uint64_t *)arena_alloc(ctx->arena, total_reads * 8);
-    uint32_t *node_rec = (uint32_t *)arena_alloc(ctx->arena, total_reads * 4), *list = (uint32_t *)arena_alloc(ctx->arena, total_reads * 4);
-    st->d_supp = (uint64_t *)arena_alloc(ctx->arena, total_reads * 8);
-    if (!d_nsupp || !blk || !es_tmp || !node_hash || !node_rec || !list || !st->d_supp) { ctx->err = "arena exhausted (split order)"; return CSV_ENOMEM; }
-    st->node_hash = node_hash; st->node_rec = node_rec; st->list = list;
+    unsigned int *d_nsupp = st->d_nsupp;
+    uint32_t *blk = st->blk, *node_rec = st->node_rec, *list = st->list;
+    void *es_tmp = st->es_tmp;
+    uint64_t *node_hash = st->node_hash;
     CSV_HIP(ctx, hipMemsetAsync(blk + n_blocks, 0, 4, s));
     launch_so_count(s, tab, (uint32_t)n_blocks, min_mapq, blk);
     launch_exclusive_sum_u32(s, blk, n_blocks + 1, es_tmp);
@@ -1272,27 +1248,10 @@ static int split_order_begin(csv_ctx *ctx, int n_contigs, csv_shard *const *shar
     }
     const size_t bm_words = st->bm_words = (size_t)((tail_buckets + 31) / 32 + 8);
     const uint64_t n_sort = std::max(n_nodes, n_supp_self);
-    if ((rc = arena_reserve(ctx, ctx->work, align_up(scratch + 16, 256) + sortws_bytes(n_sort) + align_up(n_nodes * sizeof(csv_split_survivor), 256) +
-                                                (size_t)D * (align_up(bm_words * 4, 256) + align_up(n_nodes * 4, 256)) + align_up(n_nodes, 256) + align_up(n_nodes * 4, 256) +
-                                                align_up(st_filter_bytes(), 256) + 8192))) return rc;
-    uint32_t *minT = st->minT = (uint32_t *)arena_alloc(ctx->work, scratch + 16);
+    if ((rc = arena_reserve_for(ctx, ctx->work, "split order epochs", [&](Arena &a) { return carve_split_epochs(a, scratch, n_sort, n_nodes, D, bm_words, *st); }))) return rc;
+    uint32_t *minT = st->minT;
     SortWs &w = st->w;
-    if (!minT || !sortws_carve(ctx->work, n_sort, w)) { ctx->err = "arena exhausted (split order epochs)"; return CSV_ENOMEM; }
-    st->d_out = (csv_split_survivor *)arena_alloc(ctx->work, n_nodes * sizeof(csv_split_survivor));
-    st->d_count = (unsigned long long *)arena_alloc(ctx->work, 256);      // [0] survivors; 32-bit set sizes from byte 64 on
-    if (!st->d_out || !st->d_count) { ctx->err = "arena exhausted (split order survivors)"; return CSV_ENOMEM; }
     CSV_HIP(ctx, hipMemsetAsync(st->d_count, 0, 256, s));
-    if (D > 0) {
-        for (int j = 0; j < D; j++) {
-            st->bitmap[j] = (uint32_t *)arena_alloc(ctx->work, bm_words * 4);
-            st->set[j + 1] = (uint32_t *)arena_alloc(ctx->work, n_nodes * 4);
-            if (!st->bitmap[j] || !st->set[j + 1]) { ctx->err = "arena exhausted (split order tail)"; return CSV_ENOMEM; }
-        }
-        st->is_surv = (uint8_t *)arena_alloc(ctx->work, n_nodes);
-        st->prevrank = (uint32_t *)arena_alloc(ctx->work, n_nodes * 4);
-        st->filter = (uint32_t *)arena_alloc(ctx->work, st_filter_bytes());
-        if (!st->is_surv || !st->prevrank || !st->filter) { ctx->err = "arena exhausted (split order tail)"; return CSV_ENOMEM; }
-    }
 
     // the first epochs (nodes and buckets in LDS) in one launch, one workgroup per contig
     size_t n_small = 0;
@@ -1508,91 +1467,102 @@ int csvgpu_split_order(csv_ctx *ctx, int n_contigs, csv_shard *const *shards, ui
     return rc;
 }
 
+}  // extern "C" (the chain below is templated; the entry points keep the C linkage of their declarations in csvgpu.h)
+
 // The overlap groups that the order seeds (kernels/splitgroups.hip). One wait sizes the answer (members, groups, error word); the second is the
 // answer's own copy. Everything in front of the first wait is queued without the host looking at the device.
-// The chain in three steps, so that csvgpu_split_groups_fits can leave the groups where they lie: sg_queue reserves ctx->arena (+ arena_extra for
-// the caller's own arrays, carved after it returns) and the page-locked block (+ pin_extra, continued at pin_used), stages the intervals and queues
-// everything up to the copy of the three result words; sg_wait waits and reads them; sg_fill_reserve reserves ctx->work (+ work_extra), sg_fill_launch
-// queues the member lists' sort.
-constexpr uint32_t SG_ERR_DOMAIN = 2;             // in w.err: ORed in by an SgDeviceFill's kernel (the chain's own kernels OR in 1)
-struct SgChain {
-    SplitGroupsWs w;
-    SortWs sw;
-    int32_t *d_start = nullptr, *d_end = nullptr;
-    uint64_t *d_seg = nullptr;
+// The chain in three steps, so that csvgpu_split_groups_fits can leave the groups where they lie: sg_queue reserves ctx->arena and the page-locked
+// block (the chain's layout and stage, composed with the caller's: SgExtra below), stages the intervals and queues everything up to the copy of
+// the three result words; sg_wait waits and reads them; the caller then reserves ctx->work for the member lists' sort (with whatever it
+// needs beside it) and sg_fill_launch queues that sort.
+constexpr uint32_t SG_ERR_DOMAIN = 2;             // in w.err: ORed in by an extra's kernel (the chain's own kernels OR in 1)
+struct SgChain : SgWs {
     uint32_t n = 0;
     uint64_t n_seg = 0, max_len = 0;
     volatile uint64_t *h_res = nullptr;
-    size_t pin_used = 0;
+    size_t pin_used = 0;                       // the page-locked block behind the chain's own staging: where the extra's stage runs
     uint64_t total = 0, n_groups = 0;
     const uint32_t *d_members = nullptr;       // after sg_fill
     const uint32_t *sort_flag = nullptr;       // the fill sort's gave-up word (device), or null
 };
 
-// on_device: start / end are not the caller's but written on the device, into c.d_start / c.d_end, by what this function queues (it carves its own
-// arrays from ctx->arena and stages through `pin`, both sized by the extras); the chain then skips its upload — and the caller's host range check.
-// The chain's zeroed block (w.err with it) is cleared in front of the call: what it queues may OR SG_ERR_DOMAIN (the value 2) into *c.w.err, which
-// sg_wait reports as CSV_EINVAL.
-typedef int (*SgDeviceFill)(void *arg, SgChain &c, PinStage &pin);
+// host arrays on their way to carved device slices through the page-locked block
+struct Upload { const void *dst, *src; size_t bytes; const void *pin; };
+struct Uploads {                               // (the longest list: the eleven tables and four offset arrays of csvgpu_split_fits)
+    Upload v[16];
+    size_t n = 0;
+    void add(const void *dst, const void *src, size_t bytes) { v[n++] = Upload{dst, src, bytes, nullptr}; }
+    Upload *begin() { return v; }
+    Upload *end() { return v + n; }
+    const Upload *begin() const { return v; }
+    const Upload *end() const { return v + n; }
+};
+static void stage_uploads(PinStage &p, Uploads &u) { for (Upload &x : u) x.pin = p.in(x.src, x.bytes); }
+static int queue_uploads(csv_ctx *ctx, const Uploads &u, const char *what)
+{
+    for (const Upload &x : u) {
+        if (!x.bytes) continue;
+        const hipError_t e = hipMemcpyAsync((void *)x.dst, x.pin, x.bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { ctx->err = std::string(what) + hipGetErrorString(e); return CSV_EHIP; }
+    }
+    return CSV_OK;
+}
 
+// What a fused entry point adds to the chain's two reservations: carve() takes its slices of ctx->arena behind the chain's (carved() follows the
+// real pass: the upload list is built there, from the final pointers), stage() its slots of the page-locked block behind the chain's (planned by sg_queue; run for real by the extra's own queue(), or by the caller at c.pin_used once
+// sg_queue has returned). on_device: start / end are not the caller's but written on the device, into c.d_start / c.d_end, by what queue()
+// queues; the chain then skips its upload — and the caller's host range check. The chain's zeroed block (w.err with it) is cleared in front
+// of queue(): what it queues may OR SG_ERR_DOMAIN into *c.w.err, which sg_wait reports as CSV_EINVAL.
+struct SgNoExtra {
+    static constexpr bool on_device = false;
+    bool carve(Arena &) { return true; }
+    void carved() {}
+    void stage(PinStage &) {}
+    int queue(SgChain &, PinStage &) { return CSV_OK; }
+};
+
+template <class Extra>
 static int sg_queue(csv_ctx *ctx, const int32_t *start, const int32_t *end, const uint64_t *seg_off, uint64_t n_seg, uint32_t n, uint64_t max_len,
-                    size_t arena_extra, size_t pin_extra, SgChain &c, SgDeviceFill on_device = nullptr, void *on_device_arg = nullptr)
+                    SgChain &c, Extra &x)
 {
     (void)hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     int rc;
     c.n = n; c.n_seg = n_seg; c.max_len = max_len;
-    const size_t n4 = align_up(((size_t)n + 1) * 4, 256), nb = align_up((size_t)n / 64 * 4 + 4, 256), n1 = align_up((size_t)n, 256);
-    const size_t segb = align_up((n_seg + 1) * 8, 256);
-    const size_t zero_bytes = 3 * n4 + n1 + 256;             // hist, cnt, keep, state, total + err
-    const size_t need = 2 * n4 + segb                        /* start, end, seg_off */
-                        + sortws_bytes(n)
-                        + 10 * n4 + 2 * nb + n1              /* ss se sid posof plo lp1 cstart cend seed_of_group pm; block summaries; head */
-                        + align_up(((size_t)n + 1) * 8, 256) + segb + 256   /* group_off, seg_group_off, res */
-                        + zero_bytes + exclusive_sum_tmp_bytes((uint64_t)n + 1) + 16 * 256;
-    if ((rc = arena_reserve(ctx, ctx->arena, need + arena_extra))) return rc;
-    Arena &A = ctx->arena;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "split_groups", [&](Arena &a) { return carve_split_groups(a, n, n_seg, c) && x.carve(a); }))) return rc;
+    x.carved();
     SplitGroupsWs &w = c.w;
     SortWs &sw = c.sw;
-    int32_t *d_start = c.d_start = (int32_t *)arena_alloc(A, (size_t)n * 4), *d_end = c.d_end = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    uint64_t *d_seg = c.d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    const bool sort_ok = sortws_carve(A, n, sw);
-    w.ss = (int32_t *)arena_alloc(A, (size_t)n * 4); w.se = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    w.sid = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.posof = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.plo = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.lp1 = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.cstart = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.cend = (uint32_t *)arena_alloc(A, (size_t)n * 4);
-    w.seed_of_group = (uint32_t *)arena_alloc(A, (size_t)n * 4); w.pm = (int32_t *)arena_alloc(A, (size_t)n * 4);
-    w.blk_min_id = (uint32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4); w.blk_max_end = (int32_t *)arena_alloc(A, (size_t)n / 64 * 4 + 4);
-    w.head = (uint8_t *)arena_alloc(A, n);
-    w.group_off = (uint64_t *)arena_alloc(A, ((size_t)n + 1) * 8); w.seg_group_off = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    w.res = (uint64_t *)arena_alloc(A, 256);
-    char *zero = (char *)arena_alloc(A, zero_bytes);
-    void *es_tmp = arena_alloc(A, exclusive_sum_tmp_bytes((uint64_t)n + 1));
-    if (!d_start || !d_end || !d_seg || !sort_ok || !w.seed_of_group || !w.pm || !w.blk_max_end || !w.head || !w.seg_group_off || !w.res || !zero || !es_tmp) {
-        ctx->err = "arena exhausted (split_groups)"; return CSV_ENOMEM;
-    }
-    w.hist = (uint32_t *)zero; w.cnt = (uint32_t *)(zero + n4); w.keep = (uint32_t *)(zero + 2 * n4);
-    w.state = (uint8_t *)(zero + 3 * n4);
-    w.total = (unsigned long long *)(zero + 3 * n4 + n1); w.err = (uint32_t *)(zero + 3 * n4 + n1 + 64);
+    int32_t *d_start = c.d_start, *d_end = c.d_end;
+    uint64_t *d_seg = c.d_seg;
+    void *es_tmp = c.es_tmp;
+    constexpr bool on_device = Extra::on_device;
 
-    if ((rc = ensure_pinned(ctx, 2 * PinStage::need((size_t)n * 4) + PinStage::need((n_seg + 1) * 8) + 4096 + pin_extra))) return rc;
-    PinStage pin(ctx);
+    const void *h_start = nullptr, *h_end = nullptr, *h_seg = nullptr;
+    auto own = [&](PinStage &p) {
+        if (!on_device) { h_start = p.in(start, (size_t)n * 4); h_end = p.in(end, (size_t)n * 4); }
+        h_seg = p.in(seg_off, (n_seg + 1) * 8);
+        c.h_res = (volatile uint64_t *)p.slot(256);
+    };
+    PinStage plan, pin(ctx);
+    own(plan); x.stage(plan);
+    if ((rc = ensure_pinned(ctx, plan.used))) return rc;
+    own(pin);
+    c.pin_used = pin.used;
     if (!on_device) {
-        CSV_HIP(ctx, hipMemcpyAsync(d_start, pin.in(start, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
-        CSV_HIP(ctx, hipMemcpyAsync(d_end, pin.in(end, (size_t)n * 4), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(d_start, h_start, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        CSV_HIP(ctx, hipMemcpyAsync(d_end, h_end, (size_t)n * 4, hipMemcpyHostToDevice, s));
     }
-    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, h_seg, (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
     if (on_device) {
-        CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
-        if ((rc = on_device(on_device_arg, c, pin))) return rc;
+        CSV_HIP(ctx, hipMemsetAsync(c.zero, 0, c.zero_bytes, s));
+        if ((rc = x.queue(c, pin))) return rc;
     }
-    c.h_res = (volatile uint64_t *)((char *)ctx->pinned + pin.used);
-    c.pin_used = pin.used + 256;
     const int key_bits = 32 + bits_of(n_seg - 1);
     const bool one_launch = onesweep(ctx);
     {
         TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
-        if (!on_device) CSV_HIP(ctx, hipMemsetAsync(zero, 0, zero_bytes, s));
+        if (!on_device) CSV_HIP(ctx, hipMemsetAsync(c.zero, 0, c.zero_bytes, s));
         launch_sg_keys(s, d_start, d_seg, n_seg, n, sw.k0, sw.v0);
         const int io = launch_radix_sort_u64(s, sw.k0, sw.v0, sw.k1, sw.v1, n, key_bits, sw.tmp, one_launch);
         launch_sg_links(s, w, io ? sw.k1 : sw.k0, io ? sw.v1 : sw.v0, d_start, d_end, d_seg, n);
@@ -1617,13 +1587,6 @@ static int sg_wait(csv_ctx *ctx, SgChain &c)
 }
 
 // ---- the members: (group ‖ pre) keys, one stable sort for every group of the call ---------------------------------------------------------
-static int sg_fill_reserve(csv_ctx *ctx, SgChain &c, size_t work_extra, SortWs &fw)
-{
-    int rc;
-    if ((rc = arena_reserve(ctx, ctx->work, sortws_bytes(c.total) + 1024 + work_extra))) return rc;
-    if (!sortws_carve(ctx->work, c.total, fw)) { ctx->err = "arena exhausted (split_groups fill)"; return CSV_ENOMEM; }
-    return CSV_OK;
-}
 static void sg_fill_launch(csv_ctx *ctx, SgChain &c, SortWs &fw)
 {
     const int pre_bits = std::max(1, bits_of(c.max_len - 1)), fill_bits = pre_bits + bits_of(c.n_groups - 1);
@@ -1662,7 +1625,8 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
     }
     int rc;
     SgChain ch;
-    if ((rc = sg_queue(ctx, start, end, seg_off, n_seg, n, max_len, 0, 0, ch))) return rc;
+    SgNoExtra none;
+    if ((rc = sg_queue(ctx, start, end, seg_off, n_seg, n, max_len, ch, none))) return rc;
     if ((rc = sg_wait(ctx, ch))) return rc;
     hipStream_t s = ctx->stream;
     const uint64_t total = ch.total, n_groups = ch.n_groups;
@@ -1675,21 +1639,25 @@ int csvgpu_split_groups(csv_ctx *ctx, const int32_t *start, const int32_t *end, 
         return CSV_OK;
     }
     SortWs fw;
-    if ((rc = sg_fill_reserve(ctx, ch, 0, fw))) return rc;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "split_groups fill", [&](Arena &a) { return sortws_carve(a, total, fw); }))) return rc;
     constexpr size_t kPinnedOutMax = (size_t)64 << 20;       // larger answers are copied straight into the caller's array
     const bool members_pinned = total * 4 <= kPinnedOutMax;
-    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need((n_groups + 1) * 8) + (members_pinned ? PinStage::need(total * 4) : 0) + 4096))) return rc;
     PinStage out(ctx);
-    uint32_t *h_sort_err = (uint32_t *)out.in(nullptr, 0);
-    out.used += 256;
+    uint32_t *h_sort_err = nullptr;
+    void *h_sgo = nullptr, *h_go = nullptr, *h_mem = nullptr;
+    if ((rc = pin_reserve_for(ctx, out, [&](PinStage &p) {
+            h_sort_err = (uint32_t *)p.slot(256);
+            h_sgo = p.out(seg_group_off, (n_seg + 1) * 8); h_go = p.out(group_off, (n_groups + 1) * 8);
+            if (members_pinned) h_mem = p.out(members, total * 4);
+        }))) return rc;
     *h_sort_err = 0;
     {
         TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
         sg_fill_launch(ctx, ch, fw);
         if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(out.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(out.out(group_off, (n_groups + 1) * 8), ch.w.group_off, (n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (members_pinned) CSV_HIP(ctx, hipMemcpyAsync(out.out(members, total * 4), ch.d_members, total * 4, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(h_sgo, ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(h_go, ch.w.group_off, (n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (members_pinned) CSV_HIP(ctx, hipMemcpyAsync(h_mem, ch.d_members, total * 4, hipMemcpyDeviceToHost, s));
         else CSV_HIP(ctx, hipMemcpyAsync(members, ch.d_members, total * 4, hipMemcpyDeviceToHost, s));
     }
     CSV_HIP(ctx, wait_stream(s));
@@ -1733,71 +1701,42 @@ static int sf_check(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg
     return CSV_OK;
 }
 
-static size_t sf_tables_bytes(uint64_t nm, uint64_t ns, bool with_start_end)      // (false: start / end are the chain's own copies)
-{
-    return (with_start_end ? 4 : 2) * align_up(nm * 4, 256) + align_up(nm, 256) + align_up((nm + 1) * 8, 256) + 4 * align_up(ns * 4, 256) + align_up(ns, 256) + 12 * 256;
-}
-// (page-locked bytes: the same slices, PinStage::need rounds like align_up(, 256))
-
-// start / end already on the device (the chain's copies): d_start, d_end given
-static int sf_upload(csv_ctx *ctx, Arena &A, PinStage &pin, const csv_split_tables *t, const int32_t *d_start, const int32_t *d_end, SplitFitsIn &in)
+// the tables' way to their carved slices (carve_sf_tables with the same with_start_end)
+static void sf_uploads(const csv_split_tables *t, const SplitFitsIn &in, bool with_start_end, Uploads &u)
 {
     const uint64_t nm = t->n_members, ns = t->n_supp;
-    hipStream_t s = ctx->stream;
-    bool room = true;
-    hipError_t err = hipSuccess;
-    auto up = [&](const void *src, size_t bytes) -> const void * {
-        void *d = arena_alloc(A, bytes);
-        if (!d) { room = false; return nullptr; }
-        if (bytes && err == hipSuccess) err = hipMemcpyAsync(d, pin.in(src, bytes), bytes, hipMemcpyHostToDevice, s);
-        return d;
-    };
-    in.start = d_start ? d_start : (const int32_t *)up(t->start, nm * 4);
-    in.end = d_end ? d_end : (const int32_t *)up(t->end, nm * 4);
-    in.q_start = (const int32_t *)up(t->q_start, nm * 4); in.q_end = (const int32_t *)up(t->q_end, nm * 4);
-    in.reverse = (const uint8_t *)up(t->reverse, nm);
-    in.supp_off = (const uint64_t *)up(t->supp_off, (nm + 1) * 8);
-    in.supp_start = (const int32_t *)up(t->supp_start, ns * 4); in.supp_end = (const int32_t *)up(t->supp_end, ns * 4);
-    in.supp_q_start = (const int32_t *)up(t->supp_q_start, ns * 4); in.supp_q_end = (const int32_t *)up(t->supp_q_end, ns * 4);
-    in.supp_flags = (const uint8_t *)up(t->supp_flags, ns);
-    if (!room) { ctx->err = "arena exhausted (split_fits tables)"; return CSV_ENOMEM; }
-    if (err != hipSuccess) { ctx->err = std::string("split_fits: copying the tables: ") + hipGetErrorString(err); return CSV_EHIP; }
-    return CSV_OK;
+    if (with_start_end) { u.add(in.start, t->start, nm * 4); u.add(in.end, t->end, nm * 4); }
+    u.add(in.q_start, t->q_start, nm * 4); u.add(in.q_end, t->q_end, nm * 4); u.add(in.reverse, t->reverse, nm);
+    u.add(in.supp_off, t->supp_off, (nm + 1) * 8);
+    u.add(in.supp_start, t->supp_start, ns * 4); u.add(in.supp_end, t->supp_end, ns * 4);
+    u.add(in.supp_q_start, t->supp_q_start, ns * 4); u.add(in.supp_q_end, t->supp_q_end, ns * 4);
+    u.add(in.supp_flags, t->supp_flags, ns);
 }
 
-static size_t sf_big_bytes(uint64_t B)
-{
-    return B > DBSCAN1D_MAX_SEG ? sortws_bytes(B) + dbscan1d_big_tmp_bytes(B) + 4 * align_up(B * 4, 256) + 8 * 256 : 0;
-}
-static size_t sf_out_bytes(uint64_t n_groups) { return align_up(n_groups * sizeof(csv_split_fit), 256) + align_up(n_groups * 6 * 4, 256) + 4 * 256; }
-
-struct SfRun {
+struct SfRun : SfRunWs {                       // (carve_sf_run(n_groups, B) in the arena the run works in)
     SplitFitsIn in;
-    Arena *A = nullptr;                        // holds sf_out_bytes(n_groups) + sf_big_bytes(B) for this run
     uint64_t B = 0;                            // no set has more points
-    csv_split_fit *d_out = nullptr;
-    uint32_t *d_big_n = nullptr;
-    unsigned long long *d_res = nullptr;
     volatile uint64_t *h_res = nullptr;        // sets and points beyond the LDS kernel
+    void *h_out = nullptr;                     // the records' slot of the page-locked block
 };
+// the run's part of a stage: the two counters and the records
+static void sf_stage(PinStage &p, SfRun &r, csv_split_fit *out)
+{
+    r.h_res = (volatile uint64_t *)p.slot(256);
+    r.h_out = p.out(out, (size_t)r.in.n_groups * sizeof(csv_split_fit));
+}
 
 // the launch and the copies of the records and the two counters into the page-locked block; the caller adds its own copies and waits
-static int sf_queue(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, PinStage &pin, csv_split_fit *out)
+static int sf_queue(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts)
 {
     const uint64_t G = r.in.n_groups;
     hipStream_t s = ctx->stream;
-    r.d_out = (csv_split_fit *)arena_alloc(*r.A, G * sizeof(csv_split_fit));
-    r.d_big_n = (uint32_t *)arena_alloc(*r.A, G * 6 * 4);
-    r.d_res = (unsigned long long *)arena_alloc(*r.A, 256);
-    if (!r.d_out || !r.d_big_n || !r.d_res) { ctx->err = "arena exhausted (split_fits)"; return CSV_ENOMEM; }
-    r.h_res = (volatile uint64_t *)pin.in(nullptr, 0);
-    pin.used += 256;
     TimerScope ts(ctx, CSV_K_SPLIT_FITS);
     CSV_HIP(ctx, hipMemsetAsync(r.d_big_n, 0, G * 6 * 4, s));
     CSV_HIP(ctx, hipMemsetAsync(r.d_res, 0, 16, s));
     launch_sf_fits(s, r.in, eps, min_pts, r.d_out, r.d_big_n, r.d_res);
     CSV_HIP(ctx, hipMemcpyAsync((void *)r.h_res, r.d_res, 16, hipMemcpyDeviceToHost, s));
-    CSV_HIP(ctx, hipMemcpyAsync(pin.out(out, G * sizeof(csv_split_fit)), r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
+    CSV_HIP(ctx, hipMemcpyAsync(r.h_out, r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
     return CSV_OK;
 }
 
@@ -1811,16 +1750,14 @@ static int sf_big(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, csv_split
     CSV_HIP(ctx, hipMemcpyAsync(big_n.data(), r.d_big_n, G * 6 * 4, hipMemcpyDeviceToHost, s));
     CSV_HIP(ctx, wait_stream(s));
     if (B <= DBSCAN1D_MAX_SEG) { ctx->err = "split_fits: a set larger than its bound"; return CSV_EHIP; }
-    Arena &A = *r.A;
-    int32_t *pts = (int32_t *)arena_alloc(A, B * 4), *ks = (int32_t *)arena_alloc(A, B * 4), *labels = (int32_t *)arena_alloc(A, B * 4);
-    uint32_t *sizes = (uint32_t *)arena_alloc(A, B * 4);
-    void *tmp = arena_alloc(A, dbscan1d_big_tmp_bytes(B));
-    SortWs w;
-    if (!sortws_carve(A, B, w) || !pts || !ks || !labels || !sizes || !tmp) { ctx->err = "arena exhausted (split_fits, large sets)"; return CSV_ENOMEM; }
-    if ((rc = ensure_pinned(ctx, PinStage::need(G * sizeof(csv_split_fit)) + PinStage::need(n_big * 4) + 4096))) return rc;
+    int32_t *pts = r.pts, *ks = r.ks, *labels = r.labels;      // (carved with the run: B > DBSCAN1D_MAX_SEG)
+    uint32_t *sizes = r.sizes;
+    void *tmp = r.tmp;
+    const SortWs &w = r.w;
     PinStage pin(ctx);
-    uint32_t *h_flags = (uint32_t *)pin.in(nullptr, 0);
-    pin.used += PinStage::need(n_big * 4);
+    uint32_t *h_flags = nullptr;
+    void *h_out = nullptr;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { h_flags = (uint32_t *)p.slot(n_big * 4); h_out = p.out(out, G * sizeof(csv_split_fit)); }))) return rc;
     memset(h_flags, 0, n_big * 4);
     const bool one_launch = onesweep(ctx);
     {
@@ -1841,7 +1778,7 @@ static int sf_big(csv_ctx *ctx, SfRun &r, double eps, int32_t min_pts, csv_split
             launch_sf_big_reduce(s, ks, perm, labels, n, sizes, r.d_out + item / 6, (int)(item % 6));
             k++;
         }
-        CSV_HIP(ctx, hipMemcpyAsync(pin.out(out, G * sizeof(csv_split_fit)), r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(h_out, r.d_out, G * sizeof(csv_split_fit), hipMemcpyDeviceToHost, s));
     }
     CSV_HIP(ctx, wait_stream(s));
     for (uint64_t k = 0; k < n_big; k++) if (h_flags[k]) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
@@ -1865,22 +1802,26 @@ static int sgf_finish(csv_ctx *ctx, SgChain &ch, SfRun &r, uint64_t n_seg, uint6
     }
     r.B = std::max(std::min(total, max_len), ns);
     SortWs fw;
-    if ((rc = sg_fill_reserve(ctx, ch, sf_out_bytes(G) + sf_big_bytes(r.B), fw))) return rc;
-    r.A = &ctx->work;
-    if ((rc = ensure_pinned(ctx, PinStage::need((n_seg + 1) * 8) + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
+    if ((rc = arena_reserve_for(ctx, ctx->work, "split_fits work", [&](Arena &a) { return sortws_carve(a, total, fw) && carve_sf_run(a, G, r.B, r); }))) return rc;
+    r.in.n_groups = (uint32_t)G;
     PinStage pin(ctx);
-    uint32_t *h_sort_err = (uint32_t *)pin.in(nullptr, 0);
-    pin.used += 256;
+    uint32_t *h_sort_err = nullptr;
+    void *h_sgo = nullptr;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) {
+            h_sort_err = (uint32_t *)p.slot(256);
+            h_sgo = p.out(seg_group_off, (n_seg + 1) * 8);
+            sf_stage(p, r, out);
+        }))) return rc;
     *h_sort_err = 0;
     {
         TimerScope ts(ctx, CSV_K_SPLIT_GROUPS);
         sg_fill_launch(ctx, ch, fw);
         if (ch.sort_flag) CSV_HIP(ctx, hipMemcpyAsync(h_sort_err, ch.sort_flag, 4, hipMemcpyDeviceToHost, s));
-        CSV_HIP(ctx, hipMemcpyAsync(pin.out(seg_group_off, (n_seg + 1) * 8), ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
+        CSV_HIP(ctx, hipMemcpyAsync(h_sgo, ch.w.seg_group_off, (n_seg + 1) * 8, hipMemcpyDeviceToHost, s));
     }
     r.in.seg_off = ch.d_seg; r.in.seg_group_off = ch.w.seg_group_off; r.in.group_off = ch.w.group_off; r.in.members = ch.d_members;
-    r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
-    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
+    r.in.n_seg = n_seg;
+    if ((rc = sf_queue(ctx, r, eps, min_pts))) return rc;
     CSV_HIP(ctx, wait_stream(s));
     if (*h_sort_err) { ctx->err = "split_fits: a radix pass's look-back gave up"; return CSV_EHIP; }
     pin.finish();
@@ -1927,29 +1868,39 @@ int csvgpu_split_fits(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *s
     const uint64_t nm = t->n_members, ns = t->n_supp;
     SfRun r;
     r.B = std::max(max_group, ns);
-    const size_t segb = align_up((n_seg + 1) * 8, 256), gob = align_up((G + 1) * 8, 256), memb = align_up(total * 4, 256);
-    if ((rc = arena_reserve(ctx, ctx->arena, sf_tables_bytes(nm, ns, true) + 2 * segb + gob + memb + sf_out_bytes(G) + sf_big_bytes(r.B) + 1024))) return rc;
-    if ((rc = ensure_pinned(ctx, sf_tables_bytes(nm, ns, true) + 2 * segb + gob + memb + PinStage::need(G * sizeof(csv_split_fit)) + 4096))) return rc;
-    Arena &A = ctx->arena;
-    r.A = &A;
-    PinStage pin(ctx);
-    if ((rc = sf_upload(ctx, A, pin, t, nullptr, nullptr, r.in))) return rc;
-    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8), *d_sgo = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    uint64_t *d_go = (uint64_t *)arena_alloc(A, (G + 1) * 8);
-    uint32_t *d_mem = (uint32_t *)arena_alloc(A, total * 4);
-    if (!d_seg || !d_sgo || !d_go || !d_mem) { ctx->err = "arena exhausted (split_fits)"; return CSV_ENOMEM; }
-    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_sgo, pin.in(seg_group_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_go, pin.in(group_off, (G + 1) * 8), (G + 1) * 8, hipMemcpyHostToDevice, s));
-    if (total) CSV_HIP(ctx, hipMemcpyAsync(d_mem, pin.in(members, total * 4), total * 4, hipMemcpyHostToDevice, s));
+    uint64_t *d_seg = nullptr, *d_sgo = nullptr, *d_go = nullptr;
+    uint32_t *d_mem = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "split_fits", [&](Arena &a) {
+            return carve_sf_tables(a, nm, ns, true, r.in) && take(a, d_seg, (n_seg + 1) * 8) && take(a, d_sgo, (n_seg + 1) * 8) && take(a, d_go, (G + 1) * 8) &&
+                   take(a, d_mem, total * 4) && carve_sf_run(a, G, r.B, r);
+        }))) return rc;
     r.in.seg_off = d_seg; r.in.seg_group_off = d_sgo; r.in.group_off = d_go; r.in.members = d_mem;
     r.in.n_seg = n_seg; r.in.n_groups = (uint32_t)G;
-    if ((rc = sf_queue(ctx, r, eps, min_pts, pin, out))) return rc;
+    Uploads up;
+    sf_uploads(t, r.in, true, up);
+    up.add(d_seg, seg_off, (n_seg + 1) * 8); up.add(d_sgo, seg_group_off, (n_seg + 1) * 8);
+    up.add(d_go, group_off, (G + 1) * 8); up.add(d_mem, members, total * 4);
+    PinStage pin(ctx);
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { stage_uploads(p, up); sf_stage(p, r, out); }))) return rc;
+    if ((rc = queue_uploads(ctx, up, "split_fits: copying the tables: "))) return rc;
+    if ((rc = sf_queue(ctx, r, eps, min_pts))) return rc;
     CSV_HIP(ctx, wait_stream(s));
     pin.finish();
     if (r.h_res[0] == 0) return CSV_OK;
     return sf_big(ctx, r, eps, min_pts, out);
 }
+
+namespace {
+// the caller's tables beside the chain (SgExtra of csvgpu_split_groups_fits); start / end are the chain's copies
+struct SfTablesExtra {
+    static constexpr bool on_device = false;
+    const csv_split_tables *t; SplitFitsIn &in; Uploads up;
+    bool carve(Arena &a) { return carve_sf_tables(a, t->n_members, t->n_supp, false, in); }
+    void carved() { sf_uploads(t, in, false, up); }
+    void stage(PinStage &p) { stage_uploads(p, up); }
+    int queue(SgChain &, PinStage &) { return CSV_OK; }
+};
+}  // namespace
 
 int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *t, const uint64_t *seg_off, uint64_t n_seg, double eps, int32_t min_pts,
                              uint64_t *seg_group_off, csv_split_fit *out, uint64_t *n_groups)
@@ -1968,12 +1919,14 @@ int csvgpu_split_groups_fits(csv_ctx *ctx, const csv_split_tables *t, const uint
     }
     hipStream_t s = ctx->stream;
     SgChain ch;
-    if ((rc = sg_queue(ctx, t->start, t->end, seg_off, n_seg, (uint32_t)nm, max_len, sf_tables_bytes(nm, ns, false), sf_tables_bytes(nm, ns, false), ch))) return rc;
     SfRun r;
+    SfTablesExtra tables{t, r.in, {}};
+    if ((rc = sg_queue(ctx, t->start, t->end, seg_off, n_seg, (uint32_t)nm, max_len, ch, tables))) return rc;
+    r.in.start = ch.d_start; r.in.end = ch.d_end;
     {   // the tables travel while the chain runs
-        PinStage pin(ctx);
-        pin.used = ch.pin_used;
-        if ((rc = sf_upload(ctx, ctx->arena, pin, t, ch.d_start, ch.d_end, r.in))) { (void)wait_stream(s); return rc; }
+        PinStage pin(ctx, ch.pin_used);
+        tables.stage(pin);
+        if ((rc = queue_uploads(ctx, tables.up, "split_fits: copying the tables: "))) { (void)wait_stream(s); return rc; }
     }
     return sgf_finish(ctx, ch, r, n_seg, max_len, ns, eps, min_pts, seg_group_off, out, n_groups);
 }
@@ -2014,49 +1967,31 @@ static int sr_check(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, cons
     return CSV_OK;
 }
 
-static size_t sr_refs_bytes(uint64_t n_seg, uint64_t nm, uint64_t ns)
-{
-    return align_up(n_seg * sizeof(SplitTabSeg), 256) + align_up(nm * 4, 256) + align_up((nm + 1) * 8, 256) + align_up(ns * 4, 256) + align_up(ns, 256) + 8 * 256;
-}
-
-// the references and the shard table up (through `pin`), the launch; d_seg: seg_off on the device. in.supp_off is what the fits read afterwards.
-static int sr_queue(csv_ctx *ctx, Arena &A, PinStage &pin, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *d_seg,
-                    SplitTablesIn &in, const SplitTablesOut &out)
-{
-    const uint64_t nm = f->n_members, ns = f->n_supp;
-    hipStream_t s = ctx->stream;
-    std::vector<SplitTabSeg> tab(n_seg);
-    for (uint64_t c = 0; c < n_seg; c++) { const csv_shard *sh = shards[c]; tab[c] = SplitTabSeg{sh->d.pos, sh->d.flag, sh->ref_end, sh->q_start, sh->q_end}; }
-    bool room = true;
-    hipError_t err = hipSuccess;
-    auto up = [&](const void *src, size_t bytes) -> const void * {
-        void *d = arena_alloc(A, bytes);
-        if (!d) { room = false; return nullptr; }
-        if (bytes && err == hipSuccess) err = hipMemcpyAsync(d, pin.in(src, bytes), bytes, hipMemcpyHostToDevice, s);
-        return d;
-    };
-    in.seg = (const SplitTabSeg *)up(tab.data(), n_seg * sizeof(SplitTabSeg));
-    in.seg_off = d_seg; in.n_seg = n_seg;
-    in.member_rec = (const uint32_t *)up(f->member_rec, nm * 4);
-    in.supp_off = (const uint64_t *)up(f->supp_off, (nm + 1) * 8);
-    in.supp_rec = (const uint32_t *)up(f->supp_rec, ns * 4);
-    in.supp_where = (const uint8_t *)up(f->supp_where, ns);
-    in.n_members = (uint32_t)nm; in.n_supp = (uint32_t)ns;
-    if (!room) { ctx->err = "arena exhausted (split_tables_resident)"; return CSV_ENOMEM; }
-    if (err != hipSuccess) { ctx->err = std::string("split_tables_resident: copying the references: ") + hipGetErrorString(err); return CSV_EHIP; }
-    TimerScope ts(ctx, CSV_K_MISC);
-    launch_st_tables(s, in, out);
-    return CSV_OK;
-}
-
-// the arrays of SplitTablesOut behind start / end (which the caller places)
-static bool sr_carve(Arena &A, uint64_t nm, uint64_t ns, SplitTablesOut &o)
-{
-    o.q_start = (int32_t *)arena_alloc(A, nm * 4); o.q_end = (int32_t *)arena_alloc(A, nm * 4); o.reverse = (uint8_t *)arena_alloc(A, nm);
-    o.supp_start = (int32_t *)arena_alloc(A, ns * 4); o.supp_end = (int32_t *)arena_alloc(A, ns * 4);
-    o.supp_q_start = (int32_t *)arena_alloc(A, ns * 4); o.supp_q_end = (int32_t *)arena_alloc(A, ns * 4); o.supp_flags = (uint8_t *)arena_alloc(A, ns);
-    return o.q_start && o.q_end && o.reverse && o.supp_start && o.supp_end && o.supp_q_start && o.supp_q_end && o.supp_flags;
-}
+// the references and the shard table on their way to carve_sr_refs' slices, and the launch behind them. d_seg: seg_off on the device.
+// in.supp_off is what the fits read afterwards.
+struct SrRefs {
+    std::vector<SplitTabSeg> tab;
+    Uploads up;
+    SplitTablesIn in;
+    void uploads(uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f)       // after the carve
+    {
+        const uint64_t nm = f->n_members, ns = f->n_supp;
+        tab.resize(n_seg);
+        for (uint64_t c = 0; c < n_seg; c++) { const csv_shard *sh = shards[c]; tab[c] = SplitTabSeg{sh->d.pos, sh->d.flag, sh->ref_end, sh->q_start, sh->q_end}; }
+        up.add(in.seg, tab.data(), n_seg * sizeof(SplitTabSeg)); up.add(in.member_rec, f->member_rec, nm * 4); up.add(in.supp_off, f->supp_off, (nm + 1) * 8);
+        up.add(in.supp_rec, f->supp_rec, ns * 4); up.add(in.supp_where, f->supp_where, ns);
+        in.n_seg = n_seg; in.n_members = (uint32_t)nm; in.n_supp = (uint32_t)ns;
+    }
+    int launch(csv_ctx *ctx, const uint64_t *d_seg, const SplitTablesOut &out)
+    {
+        const int rc = queue_uploads(ctx, up, "split_tables_resident: copying the references: ");
+        if (rc) return rc;
+        in.seg_off = d_seg;
+        TimerScope ts(ctx, CSV_K_MISC);
+        launch_st_tables(ctx->stream, in, out);
+        return CSV_OK;
+    }
+};
 
 int csvgpu_split_tables_resident(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *shards, const csv_split_refs *f, const uint64_t *seg_off, csv_split_tables *t)
 {
@@ -2075,31 +2010,35 @@ int csvgpu_split_tables_resident(csv_ctx *ctx, uint64_t n_seg, csv_shard *const 
     }
     (void)hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
-    const size_t segb = align_up((n_seg + 1) * 8, 256);
-    if ((rc = arena_reserve(ctx, ctx->arena, sf_tables_bytes(nm, ns, true) + sr_refs_bytes(n_seg, nm, ns) + segb + 1024))) return rc;
-    if ((rc = ensure_pinned(ctx, sf_tables_bytes(nm, ns, true) + sr_refs_bytes(n_seg, nm, ns) + segb + 4096))) return rc;
-    Arena &A = ctx->arena;
-    PinStage pin(ctx);
     SplitTablesOut o;
-    o.start = (int32_t *)arena_alloc(A, nm * 4); o.end = (int32_t *)arena_alloc(A, nm * 4);
-    uint64_t *d_seg = (uint64_t *)arena_alloc(A, (n_seg + 1) * 8);
-    o.err = (uint32_t *)arena_alloc(A, 256); o.err_bit = 1;
-    if (!sr_carve(A, nm, ns, o) || !o.start || !o.end || !d_seg || !o.err) { ctx->err = "arena exhausted (split_tables_resident)"; return CSV_ENOMEM; }
+    SrRefs refs;
+    uint64_t *d_seg = nullptr;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "split_tables_resident", [&](Arena &a) {
+            return take(a, o.start, nm * 4) && take(a, o.end, nm * 4) && take(a, d_seg, (n_seg + 1) * 8) && take(a, o.err, 256) && sr_carve(a, nm, ns, o) &&
+                   carve_sr_refs(a, n_seg, nm, ns, refs.in);
+        }))) return rc;
+    o.err_bit = 1;
+    refs.uploads(n_seg, shards, f);
+    struct Down { void *dst; const void *src; size_t bytes; void *pin; };
+    Down down[] = {{(void *)t->start, o.start, nm * 4, nullptr}, {(void *)t->end, o.end, nm * 4, nullptr}, {(void *)t->q_start, o.q_start, nm * 4, nullptr},
+                   {(void *)t->q_end, o.q_end, nm * 4, nullptr}, {(void *)t->reverse, o.reverse, nm, nullptr},
+                   {(void *)t->supp_start, o.supp_start, ns * 4, nullptr}, {(void *)t->supp_end, o.supp_end, ns * 4, nullptr},
+                   {(void *)t->supp_q_start, o.supp_q_start, ns * 4, nullptr}, {(void *)t->supp_q_end, o.supp_q_end, ns * 4, nullptr},
+                   {(void *)t->supp_flags, o.supp_flags, ns, nullptr}};
+    PinStage pin(ctx);
+    const void *h_seg = nullptr;
+    volatile uint32_t *h_err = nullptr;
+    if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) {
+            h_seg = p.in(seg_off, (n_seg + 1) * 8);
+            stage_uploads(p, refs.up);
+            h_err = (volatile uint32_t *)p.slot(256);
+            for (Down &d : down) d.pin = p.out(d.dst, d.bytes);
+        }))) return rc;
     CSV_HIP(ctx, hipMemsetAsync(o.err, 0, 4, s));
-    CSV_HIP(ctx, hipMemcpyAsync(d_seg, pin.in(seg_off, (n_seg + 1) * 8), (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
-    SplitTablesIn in;
-    if ((rc = sr_queue(ctx, A, pin, n_seg, shards, f, d_seg, in, o))) { (void)wait_stream(s); return rc; }
-    volatile uint32_t *h_err = (volatile uint32_t *)pin.in(nullptr, 0);
-    pin.used += 256;
+    CSV_HIP(ctx, hipMemcpyAsync(d_seg, h_seg, (n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+    if ((rc = refs.launch(ctx, d_seg, o))) { (void)wait_stream(s); return rc; }
     CSV_HIP(ctx, hipMemcpyAsync((void *)h_err, o.err, 4, hipMemcpyDeviceToHost, s));
-    auto down = [&](const void *dst, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(pin.out((void *)dst, bytes), src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-    };
-    CSV_HIP(ctx, down(t->start, o.start, nm * 4)); CSV_HIP(ctx, down(t->end, o.end, nm * 4));
-    CSV_HIP(ctx, down(t->q_start, o.q_start, nm * 4)); CSV_HIP(ctx, down(t->q_end, o.q_end, nm * 4)); CSV_HIP(ctx, down(t->reverse, o.reverse, nm));
-    CSV_HIP(ctx, down(t->supp_start, o.supp_start, ns * 4)); CSV_HIP(ctx, down(t->supp_end, o.supp_end, ns * 4));
-    CSV_HIP(ctx, down(t->supp_q_start, o.supp_q_start, ns * 4)); CSV_HIP(ctx, down(t->supp_q_end, o.supp_q_end, ns * 4));
-    CSV_HIP(ctx, down(t->supp_flags, o.supp_flags, ns));
+    for (const Down &d : down) if (d.bytes) CSV_HIP(ctx, hipMemcpyAsync(d.pin, d.src, d.bytes, hipMemcpyDeviceToHost, s));
     CSV_HIP(ctx, wait_stream(s));
     if (*h_err) { ctx->err = "split_tables_resident: a coordinate of the shards is negative or end < start"; return CSV_EINVAL; }
     pin.finish();
@@ -2109,22 +2048,25 @@ int csvgpu_split_tables_resident(csv_ctx *ctx, uint64_t n_seg, csv_shard *const 
 }
 
 namespace {
+// the tables built on the device in front of the chain (SgExtra of csvgpu_split_resident_fits)
 struct SrFill {
+    static constexpr bool on_device = true;
     csv_ctx *ctx; uint64_t n_seg; csv_shard *const *shards; const csv_split_refs *f;
     SplitFitsIn *fits_in;
-    static int queue(void *arg, SgChain &c, PinStage &pin) { return ((SrFill *)arg)->run(c, pin); }
-    int run(SgChain &c, PinStage &pin)
+    SplitTablesOut o;
+    SrRefs refs;
+    bool carve(Arena &a) { return sr_carve(a, f->n_members, f->n_supp, o) && carve_sr_refs(a, n_seg, f->n_members, f->n_supp, refs.in); }
+    void carved() { refs.uploads(n_seg, shards, f); }
+    void stage(PinStage &p) { stage_uploads(p, refs.up); }
+    int queue(SgChain &c, PinStage &pin)
     {
-        const uint64_t nm = f->n_members, ns = f->n_supp;
-        SplitTablesOut o;
         o.start = c.d_start; o.end = c.d_end;
         o.err = c.w.err; o.err_bit = SG_ERR_DOMAIN;
-        if (!sr_carve(ctx->arena, nm, ns, o)) { ctx->err = "arena exhausted (split_resident_fits)"; return CSV_ENOMEM; }
-        SplitTablesIn in;
-        const int rc = sr_queue(ctx, ctx->arena, pin, n_seg, shards, f, c.d_seg, in, o);
+        stage(pin);
+        const int rc = refs.launch(ctx, c.d_seg, o);
         if (rc) return rc;
         SplitFitsIn &r = *fits_in;
-        r.start = o.start; r.end = o.end; r.q_start = o.q_start; r.q_end = o.q_end; r.reverse = o.reverse; r.supp_off = in.supp_off;
+        r.start = o.start; r.end = o.end; r.q_start = o.q_start; r.q_end = o.q_end; r.reverse = o.reverse; r.supp_off = refs.in.supp_off;
         r.supp_start = o.supp_start; r.supp_end = o.supp_end; r.supp_q_start = o.supp_q_start; r.supp_q_end = o.supp_q_end; r.supp_flags = o.supp_flags;
         return CSV_OK;
     }
@@ -2151,10 +2093,11 @@ int csvgpu_split_resident_fits(csv_ctx *ctx, uint64_t n_seg, csv_shard *const *s
     SfRun r;
     SrFill fill;
     fill.ctx = ctx; fill.n_seg = n_seg; fill.shards = shards; fill.f = f; fill.fits_in = &r.in;
-    const size_t extra = sf_tables_bytes(nm, ns, false) + sr_refs_bytes(n_seg, nm, ns);
-    if ((rc = sg_queue(ctx, nullptr, nullptr, seg_off, n_seg, (uint32_t)nm, max_len, extra, extra, ch, SrFill::queue, &fill))) { (void)wait_stream(ctx->stream); return rc; }
+    if ((rc = sg_queue(ctx, nullptr, nullptr, seg_off, n_seg, (uint32_t)nm, max_len, ch, fill))) { (void)wait_stream(ctx->stream); return rc; }
     return sgf_finish(ctx, ch, r, n_seg, max_len, ns, eps, min_pts, seg_group_off, out, n_groups);
 }
+
+extern "C" {
 
 int csvgpu_window_log2_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *region_start, const uint32_t *region_end,
                                 const int32_t *sample_size, const uint64_t *win_off, uint64_t n_regions, double mean_cov,
@@ -2172,16 +2115,13 @@ int csvgpu_window_log2_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *reg
     if (nw == 0) return CSV_OK;
     if (!log2_cov || !win_start || !win_end) { ctx->err = "window_log2: null output"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->arena, 3 * align_up(n_regions * 4, 256) + align_up((n_regions + 1) * 8, 256) + align_up(nw * 8, 256) +
-                                                2 * align_up(nw * 4, 256) + 4096);
+    WindowWs w;
+    int rc = arena_reserve_for(ctx, ctx->arena, "window_log2", [&](Arena &a) { return carve_window(a, n_regions, nw, w); });
     if (rc) return rc;
-    Arena &a = ctx->arena;
-    uint32_t *drs = (uint32_t *)arena_alloc(a, n_regions * 4), *dre = (uint32_t *)arena_alloc(a, n_regions * 4);
-    int32_t *dss = (int32_t *)arena_alloc(a, n_regions * 4);
-    uint64_t *dwo = (uint64_t *)arena_alloc(a, (n_regions + 1) * 8);
-    double *dl2 = (double *)arena_alloc(a, nw * 8);
-    uint32_t *dws = (uint32_t *)arena_alloc(a, nw * 4), *dwe = (uint32_t *)arena_alloc(a, nw * 4);
-    if (!drs || !dre || !dss || !dwo || !dl2 || !dws || !dwe) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
+    uint32_t *drs = w.rs, *dre = w.re, *dws = w.ws, *dwe = w.we;
+    int32_t *dss = w.ss;
+    uint64_t *dwo = w.wo;
+    double *dl2 = w.l2;
     hipStream_t s = ctx->stream;
     CSV_HIP(ctx, hipMemcpyAsync(drs, region_start, n_regions * 4, hipMemcpyHostToDevice, s));
     CSV_HIP(ctx, hipMemcpyAsync(dre, region_end, n_regions * 4, hipMemcpyHostToDevice, s));
@@ -2202,11 +2142,10 @@ int csvgpu_depth_lookup_resident(csv_ctx *ctx, csv_shard *sh, const uint32_t *po
     if (!pos || !depth_out) { ctx->err = "depth_lookup: null array"; return CSV_EINVAL; }
     if (!sh->depth) { ctx->err = "depth_lookup: shard has no depth map (run csvgpu_chr_pipeline_dev first)"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
-    int rc = arena_reserve(ctx, ctx->arena, 2 * align_up(n * 4, 256) + 4096);
+    uint32_t *dpos = nullptr;
+    int32_t *dout = nullptr;
+    int rc = arena_reserve_for(ctx, ctx->arena, "depth_lookup", [&](Arena &a) { return take(a, dpos, n * 4) && take(a, dout, n * 4); });
     if (rc) return rc;
-    uint32_t *dpos = (uint32_t *)arena_alloc(ctx->arena, n * 4);
-    int32_t *dout = (int32_t *)arena_alloc(ctx->arena, n * 4);
-    if (!dpos || !dout) { ctx->err = "arena exhausted"; return CSV_ENOMEM; }
     hipStream_t s = ctx->stream;
     CSV_HIP(ctx, hipMemcpyAsync(dpos, pos, n * 4, hipMemcpyHostToDevice, s));
     csv::launch_depth_lookup(s, sh->depth, sh->depth_len, dpos, n, dout);
@@ -2411,8 +2350,9 @@ static int job_queue_front(csv_ctx *ctx, csv_job *job)
             CSV_HIP(ctx, hipStreamWaitEvent(cs, job->ev_scan, 0));
             CSV_HIP(ctx, hipMemcpyAsync(job->pin, cnt, sizeof(ScanCounters), hipMemcpyDeviceToHost, cs));
             CSV_HIP(ctx, hipEventRecord(job->ev_mid, cs));
-            ctx->work.used = 0;
-            if ((rc = depth_chain(ctx, ctx->work, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt,
+            DepthWs dw;
+            if ((rc = depth_work(ctx, sh, &dw))) return rc;
+            if ((rc = depth_chain(ctx, dw, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt,
                                   sorted ? sh->tile_range : nullptr, sh->cigar_pad, sh->depth_items, sh->form))) return rc;
             launch_min_pts(s, cnt, job->min_pts_pct);
         }
@@ -2453,7 +2393,7 @@ csv_job *csvgpu_chr_job_begin(csv_ctx *ctx, csv_shard *sh, uint32_t min_oplen, u
     job->pin = job_pin_slot(ctx);
     if (!job->pin && ctx->job_pin) { ctx->err = "job: more than CSV_MAX_JOBS jobs open on this context"; job_free(ctx, job); return nullptr; }
     if (!job->pin || !job->ev_zero || !job->ev_scan || !job->ev_depth || !job->ev_mid || !job->ev_done) { ctx->err = "job: cannot allocate events / page-locked memory"; job_free(ctx, job); return nullptr; }
-    if (arena_reserve(ctx, ctx->work, depth_chain_bytes(sh->d.n_reads, sh->depth_len)) || job_queue_front(ctx, job)) { job_free(ctx, job); return nullptr; }
+    if (depth_work(ctx, sh, nullptr) || job_queue_front(ctx, job)) { job_free(ctx, job); return nullptr; }
     return job;
 }
 
@@ -2496,7 +2436,8 @@ int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host
     const uint32_t max_bucket = h.max_len;
 
     // shard scratch: sorted signatures, SoA start/end, labels, sort + dbscan workspace (grow-only)
-    const size_t need = align_up(n * sizeof(csv_sig), 256) + 3 * align_up(n * 4 + 16, 256) + sortws_bytes(n) + dbscan_tmp_bytes(n) + 4096;
+    JobScratch js;
+    const size_t need = arena_plan_bytes([&](Arena &a) { return carve_job_scratch(a, n, js); });
     if (need > sh->scratch_cap) {
         if (sh->scratch) CSV_HIP(ctx, hipFree(sh->scratch));
         sh->scratch = nullptr; sh->scratch_cap = 0;
@@ -2504,18 +2445,18 @@ int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host
         sh->scratch_cap = need + need / 4;
     }
     Arena sa; sa.base = sh->scratch; sa.cap = sh->scratch_cap; sa.used = 0;
-    csv_sig *sig_sorted = (csv_sig *)arena_alloc(sa, n * sizeof(csv_sig));
-    uint32_t *st = (uint32_t *)arena_alloc(sa, n * 4 + 16), *en = (uint32_t *)arena_alloc(sa, n * 4 + 16);
-    int32_t *labels = (int32_t *)arena_alloc(sa, n * 4 + 16);
-    SortWs w;
-    const bool ws_ok = sortws_carve(sa, n, w);
-    void *db_tmp = arena_alloc(sa, dbscan_tmp_bytes(n));
-    if (!sig_sorted || !st || !en || !labels || !ws_ok || !db_tmp) { ctx->err = "shard scratch exhausted"; return CSV_ENOMEM; }
+    if (!carve_job_scratch(sa, n, js)) { ctx->err = "shard scratch exhausted"; return CSV_ENOMEM; }
+    csv_sig *sig_sorted = js.sig_sorted;
+    uint32_t *st = js.st, *en = js.en;
+    int32_t *labels = js.labels;
+    SortWs &w = js.w;
+    void *db_tmp = js.db_tmp;
 
     // depth map + mean coverage + min_pts (device scalar), unless already queued behind the scan
     if (!job->depth_queued) {
-        ctx->work.used = 0;
-        if ((rc = depth_chain(ctx, ctx->work, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt, nullptr, sh->cigar_pad, sh->depth_items, sh->form))) return rc;
+        DepthWs dw;
+        if ((rc = depth_work(ctx, sh, &dw))) return rc;
+        if ((rc = depth_chain(ctx, dw, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt, nullptr, sh->cigar_pad, sh->depth_items, sh->form))) return rc;
         launch_min_pts(s, cnt, job->min_pts_pct);
     }
 
@@ -2601,13 +2542,12 @@ static int hook_sort_stage(csv_ctx *ctx, const uint64_t *keys, const uint32_t *v
 {
     const uint64_t m = room + CSVGPU_TEST_GUARD;
     Arena &a = ctx->arena;
-    int rc = arena_reserve(ctx, a, sortws_bytes(m) + align_up(radix_sort_tmp_bytes(room), 256) + CSVGPU_TEST_GUARD + 1024);
+    const int rc = arena_reserve_for(ctx, a, "test hook", [&](Arena &p) {
+        return sortws_carve(p, m, w) &&
+               take(p, w.tmp, radix_sort_tmp_bytes(room)) &&      // (not the one carved for m slots: the size a chain gives a sort of `room` keys)
+               take(p, tmp_guard, CSVGPU_TEST_GUARD) && take(p, d_n, 256);
+    });
     if (rc) return rc;
-    const bool ok = sortws_carve(a, m, w);
-    w.tmp = arena_alloc(a, radix_sort_tmp_bytes(room));          // (not the one carved for m slots: the size a chain gives a sort of `room` keys)
-    tmp_guard = arena_alloc(a, CSVGPU_TEST_GUARD);
-    d_n = (uint32_t *)arena_alloc(a, 256);
-    if (!ok || !w.tmp || !tmp_guard || !d_n) { ctx->err = "arena exhausted (test hook)"; return CSV_ENOMEM; }
     CSV_HIP(ctx, hipMemsetAsync(a.base, kHookFill, a.used, ctx->stream));
     if (n) {
         CSV_HIP(ctx, hipMemcpyAsync(w.k0, keys, n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -2682,12 +2622,12 @@ int csvgpu_test_exclusive_sum(csv_ctx *ctx, uint32_t *data, uint64_t n)
     if (n >= (1ull << 32)) { ctx->err = "test_exclusive_sum: n out of range"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
     Arena &a = ctx->arena;
-    int rc = arena_reserve(ctx, a, align_up((n + CSVGPU_TEST_GUARD) * 4, 256) + exclusive_sum_tmp_bytes(n) + CSVGPU_TEST_GUARD + 1024);
+    uint32_t *d = nullptr;
+    void *tmp = nullptr, *tmp_guard = nullptr;
+    int rc = arena_reserve_for(ctx, a, "test hook", [&](Arena &p) {
+        return take(p, d, (n + CSVGPU_TEST_GUARD) * 4) && take(p, tmp, exclusive_sum_tmp_bytes(n)) && take(p, tmp_guard, CSVGPU_TEST_GUARD);
+    });
     if (rc) return rc;
-    uint32_t *d = (uint32_t *)arena_alloc(a, (n + CSVGPU_TEST_GUARD) * 4);
-    void *tmp = arena_alloc(a, exclusive_sum_tmp_bytes(n));
-    void *tmp_guard = arena_alloc(a, CSVGPU_TEST_GUARD);
-    if (!d || !tmp || !tmp_guard) { ctx->err = "arena exhausted (test hook)"; return CSV_ENOMEM; }
     CSV_HIP(ctx, hipMemsetAsync(a.base, kHookFill, a.used, ctx->stream));
     if (n) CSV_HIP(ctx, hipMemcpyAsync(d, data, n * 4, hipMemcpyHostToDevice, ctx->stream));
     launch_exclusive_sum_u32(ctx->stream, d, n, tmp);
@@ -2706,13 +2646,12 @@ int csvgpu_test_prefix_max(csv_ctx *ctx, const int32_t *in, uint64_t n, int32_t 
     if (n >= (1ull << 32)) { ctx->err = "test_prefix_max: n out of range"; return CSV_EINVAL; }
     (void)hipSetDevice(ctx->device);
     Arena &a = ctx->arena;
-    int rc = arena_reserve(ctx, a, align_up(n * 4, 256) + align_up((n + CSVGPU_TEST_GUARD) * 4, 256) + prefix_max_tmp_bytes(n) + CSVGPU_TEST_GUARD + 1024);
+    int32_t *di = nullptr, *dout = nullptr;
+    void *tmp = nullptr, *tmp_guard = nullptr;
+    int rc = arena_reserve_for(ctx, a, "test hook", [&](Arena &p) {
+        return take(p, di, n * 4) && take(p, dout, (n + CSVGPU_TEST_GUARD) * 4) && take(p, tmp, prefix_max_tmp_bytes(n)) && take(p, tmp_guard, CSVGPU_TEST_GUARD);
+    });
     if (rc) return rc;
-    int32_t *di = (int32_t *)arena_alloc(a, n * 4);
-    int32_t *dout = (int32_t *)arena_alloc(a, (n + CSVGPU_TEST_GUARD) * 4);
-    void *tmp = arena_alloc(a, prefix_max_tmp_bytes(n));
-    void *tmp_guard = arena_alloc(a, CSVGPU_TEST_GUARD);
-    if (!di || !dout || !tmp || !tmp_guard) { ctx->err = "arena exhausted (test hook)"; return CSV_ENOMEM; }
     CSV_HIP(ctx, hipMemsetAsync(a.base, kHookFill, a.used, ctx->stream));
     if (n) CSV_HIP(ctx, hipMemcpyAsync(di, in, n * 4, hipMemcpyHostToDevice, ctx->stream));
     launch_prefix_max(ctx->stream, di, dout, n, tmp);

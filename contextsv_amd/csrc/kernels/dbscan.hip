@@ -24,7 +24,7 @@
 // are original indices, else an exclusive scan) -> labels.
 // The same machinery, instantiated with the 1-D metric |a-b| <= eps, serves DBSCAN1D segments that
 // are too large for the LDS kernel (dbscan1d.hip).
-#include "../common.hpp"
+#include "../layouts.hpp"
 #include "../devutil.hpp"
 
 namespace csv {
@@ -387,11 +387,10 @@ __global__ void __launch_bounds__(DB_THREADS) db_label_kernel(M m, uint64_t n, u
     }
 }
 
-// tmp: core u8[n] | parent u32[n] | root_of u32[n] | is_root/cid u32[n+1] | scan tmp
+// tmp: carve_dbscan_tmp (layouts.hpp), sized by planning the same carve
 size_t dbscan_tmp_bytes(uint64_t n)
 {
-    const uint64_t nt = (n + UF_TILE) / UF_TILE + 1;
-    return align_up(n, 256) + 2 * align_up(n * 4, 256) + align_up((n + 1) * 4, 256) + exclusive_sum_tmp_bytes(n + 1) + 2 * align_up(nt * 4, 256) + 256;
+    return arena_plan_bytes([&](Arena &a) { DbscanTmp t; return carve_dbscan_tmp(a, n, UF_TILE, t); });
 }
 
 template <class M>
@@ -399,16 +398,14 @@ static void run_dbscan(hipStream_t s, M m, const uint32_t *oid, uint64_t n, uint
                        int32_t *labels, void *tmp)
 {
     if (n == 0) return;
-    char *p = (char *)tmp;
-    uint8_t *core = (uint8_t *)p;      p += align_up(n, 256);
-    uint32_t *parent = (uint32_t *)p;  p += align_up(n * 4, 256);
-    uint32_t *root_of = (uint32_t *)p; p += align_up(n * 4, 256);
-    uint32_t *cid = (uint32_t *)p;     p += align_up((n + 1) * 4, 256);
-    void *es_tmp = p;                  p += exclusive_sum_tmp_bytes(n + 1);
-    const uint32_t n_tiles = (uint32_t)((n + UF_TILE) / UF_TILE);          // tiles of positions 0..n (rank[n] included)
-    uint32_t *tile_count = (uint32_t *)p;  p += align_up(((uint64_t)n_tiles + 1) * 4, 256);
-    uint32_t *tile_prefix = (uint32_t *)p; p += align_up(((uint64_t)n_tiles + 1) * 4, 256);
-    unsigned int *ticket = (unsigned int *)p;
+    Arena view = arena_view(tmp);
+    DbscanTmp t;
+    (void)carve_dbscan_tmp(view, n, UF_TILE, t);
+    uint8_t *core = t.core;
+    uint32_t *parent = t.parent, *root_of = t.root_of, *cid = t.cid, *tile_count = t.tile_count, *tile_prefix = t.tile_prefix;
+    void *es_tmp = t.es_tmp;
+    unsigned int *ticket = t.ticket;
+    const uint32_t n_tiles = t.n_tiles;
     const dim3 grid((unsigned)((n + 255) / 256)), grid1((unsigned)((n + 1 + 255) / 256)), blk(256);
     const dim3 wide(DB_THREADS);
     hipLaunchKernelGGL(db_count_union_kernel<M>, grid1, wide, 0, s, m, n, split, min_pts, d_min_pts, oid, core, parent, cid, ticket);

@@ -12,7 +12,7 @@
 //   6 lanes each (lane = state); the max-plus step reads the six predecessor deltas with shuffles,
 //   strict '>' from -1e11 keeps the reference's lowest-index tie-break; psi goes to a byte array,
 //   the group's first lane backtracks. fp64 throughout, compiled with -ffp-contract=off.
-#include "../common.hpp"
+#include "../layouts.hpp"
 #include "../devutil.hpp"
 
 namespace csv {
@@ -266,17 +266,19 @@ __global__ __launch_bounds__(64) void hmm_viterbi_kernel(const HmmDev *__restric
 size_t viterbi_tmp_bytes(uint64_t n_obs, uint64_t n_seq)
 {
     (void)n_seq;
-    return align_up(sizeof(HmmDev), 256) + align_up(n_obs * 6 * sizeof(double), 256) + align_up(n_obs * 6, 256);
+    return arena_plan_bytes([&](Arena &a) { ViterbiTmp t; return carve_viterbi_tmp(a, n_obs, sizeof(HmmDev), t); });
 }
 
 void launch_viterbi(hipStream_t s, const csv_hmm &hmm, const double *o1, const double *o2, const double *pfb,
                     const uint64_t *seq_off, uint64_t n_seq, uint64_t n_obs, int32_t *states, double *loglik, void *tmp)
 {
     if (n_seq == 0) return;
-    char *p = (char *)tmp;
-    HmmDev *d = (HmmDev *)p;        p += align_up(sizeof(HmmDev), 256);
-    double *biot = (double *)p;     p += align_up(n_obs * 6 * sizeof(double), 256);
-    uint8_t *psi = (uint8_t *)p;
+    Arena view = arena_view(tmp);
+    ViterbiTmp t;
+    (void)carve_viterbi_tmp(view, n_obs, sizeof(HmmDev), t);
+    HmmDev *d = (HmmDev *)t.model;
+    double *biot = t.biot;
+    uint8_t *psi = t.psi;
     (void)hipMemcpyAsync(&d->h, &hmm, sizeof(csv_hmm), hipMemcpyHostToDevice, s);
     hipLaunchKernelGGL(hmm_prep_kernel, dim3(1), dim3(64), 0, s, d);
     if (n_obs) hipLaunchKernelGGL(hmm_emit_kernel, dim3((unsigned)((n_obs * 6 + 255) / 256)), dim3(256), 0, s, d, o1, o2, pfb, n_obs, biot);

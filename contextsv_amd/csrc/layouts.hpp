@@ -1,0 +1,218 @@
+// layouts.hpp — every device workspace layout of the library as one carve function over an Arena (arena.hpp). The entry points in
+// csvgpu.hip and the launchers in kernels/ reserve by planning these and then carve with them; nothing else says how large a workspace
+// is. Pads that a kernel relies on are part of their slice and are named where they are taken. Free of HIP calls: the CPU-only check
+// (tools/fuzz/arena_layouts_check.cpp) runs every function listed in kLayoutNames at the rounding edges.
+#pragma once
+#include "common.hpp"
+
+namespace csv {
+
+#ifdef CSV_ARENA_LOG               // (the check program's build alone)
+// the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
+static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "dbscan_tmp", "viterbi_tmp"};
+constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
+#endif
+
+// device scalars + the ordering pass's bucket tables, zeroed together before every scan
+static constexpr size_t kCntBytes = 256 + 2 * (size_t)BK_N * 4;
+
+// a host shard staged in the arena, with the scan's per-read outputs
+struct ReadsWs {
+    int32_t *pos; uint16_t *flag; uint8_t *mapq; uint64_t *coff; uint32_t *cig;
+    int32_t *ref_end, *q_start, *q_end;
+    ScanCounters *cnt;
+    uint32_t *ckpt;
+};
+static inline bool carve_reads(Arena &a, uint64_t n, uint64_t m, ReadsWs &w)
+{
+    return take(a, w.pos, n * 4) && take(a, w.flag, n * 2) && take(a, w.mapq, n) && take(a, w.coff, (n + 1) * 8) &&
+           take(a, w.cig, m * 4 + 16) &&                                  // + 16: the scan's 16-byte word loads at the last read's end
+           take(a, w.ref_end, n * 4) && take(a, w.q_start, n * 4) && take(a, w.q_end, n * 4) && take(a, w.cnt, kCntBytes) && take(a, w.ckpt, ckpt_bytes(m));
+}
+
+// ordering workspace for n signatures
+struct SortWs {
+    uint64_t *k0, *k1;
+    uint32_t *v0, *v1;
+    void *tmp;
+    csv_sig *sig_tmp;        // bucketed copy of the signatures (bucket ordering); aliases the radix key arrays, which that path does not use
+};
+static inline bool sortws_carve(Arena &a, uint64_t n, SortWs &w)
+{
+    const bool ok = take(a, w.k0, n * 8) && take(a, w.k1, n * 8) && take(a, w.v0, n * 4) && take(a, w.v1, n * 4) && take(a, w.tmp, radix_sort_tmp_bytes(n));
+    w.sig_tmp = (csv_sig *)w.k0;                         // k0 and k1 are carved back to back: 2 x align_up(8n, 256) >= 16n bytes
+    return ok && (char *)w.k1 == (char *)w.k0 + align_up(n * 8, 256);
+}
+
+// depth chain of a shard whose tile ranges the scan did not leave: prefix maximum, ranges, and (the larger branch, taken after a
+// readback) the reads ordered by position
+struct DepthWs {
+    int32_t *pmax; void *ptmp; uint64_t *ttmp;
+    uint32_t *pos_g, *end_g; SortWs w;
+};
+static inline bool carve_depth(Arena &a, uint64_t n, uint32_t depth_len, DepthWs &d)
+{
+    return take(a, d.pmax, n * 4) && take(a, d.ptmp, prefix_max_tmp_bytes(n)) && take(a, d.ttmp, depth_tiles_tmp_bytes(depth_len)) &&
+           take(a, d.pos_g, n * 4) && take(a, d.end_g, n * 4) && sortws_carve(a, n, d.w);
+}
+
+// interval DBSCAN on arrays in caller order: sortedness flag, the kernels' temporaries, and (unsorted input) the sorted copies
+struct DbscanIvWs {
+    unsigned int *flag; void *tmp;
+    uint32_t *s_s, *e_s; SortWs w;
+};
+static inline bool carve_dbscan_iv(Arena &a, uint64_t n, DbscanIvWs &d)
+{
+    return take(a, d.flag, 256) && take(a, d.tmp, dbscan_tmp_bytes(n)) && take(a, d.s_s, n * 4) && take(a, d.e_s, n * 4) && sortws_carve(a, n, d.w);
+}
+
+// batched 1-D DBSCAN: the too-large flag, and for segments beyond the LDS kernel the sorted-window path's buffers
+struct Dbscan1dWs {
+    unsigned int *flag;
+    uint32_t *ks; void *tmp; SortWs w;
+};
+static inline bool carve_dbscan1d(Arena &a, uint32_t max_seg_len, Dbscan1dWs &d)
+{
+    if (max_seg_len <= DBSCAN1D_MAX_SEG) { d = Dbscan1dWs(); return take(a, d.flag, 256); }
+    return take(a, d.flag, 256) && take(a, d.ks, (size_t)max_seg_len * 4) && take(a, d.tmp, dbscan1d_big_tmp_bytes(max_seg_len)) && sortws_carve(a, max_seg_len, d.w);
+}
+
+// split order, nodes: the filter-passing primaries of every contig (at most one per record; the supplementary hashes likewise)
+struct SplitNodesWs {
+    unsigned int *d_nsupp = nullptr; uint32_t *blk = nullptr; void *es_tmp = nullptr;
+    uint64_t *node_hash = nullptr, *d_supp = nullptr;
+    uint32_t *node_rec = nullptr, *list = nullptr;
+};
+static inline bool carve_split_nodes(Arena &a, uint64_t n_blocks, uint64_t total_reads, SplitNodesWs &w)
+{
+    return take(a, w.d_nsupp, 256) && take(a, w.blk, (n_blocks + 1) * 4) && take(a, w.es_tmp, exclusive_sum_tmp_bytes(n_blocks + 1)) &&
+           take(a, w.node_hash, total_reads * 8) && take(a, w.node_rec, total_reads * 4) && take(a, w.list, total_reads * 4) && take(a, w.d_supp, total_reads * 8);
+}
+
+// split order, epochs: bucket minima, the sorts' workspace, survivors, and the D survivors-only levels
+struct SplitEpochsWs {
+    uint32_t *minT = nullptr;
+    SortWs w;
+    csv_split_survivor *d_out = nullptr;
+    unsigned long long *d_count = nullptr;       // [0] survivors; 32-bit set sizes from byte 64 on
+    uint32_t *bitmap[SO_TAIL_MAX] = {nullptr, nullptr, nullptr}, *set[SO_TAIL_MAX + 1] = {nullptr, nullptr, nullptr, nullptr}, *prevrank = nullptr, *filter = nullptr;
+    uint8_t *is_surv = nullptr;
+};
+static inline bool carve_split_epochs(Arena &a, uint64_t scratch, uint64_t n_sort, uint64_t n_nodes, int D, size_t bm_words, SplitEpochsWs &w)
+{
+    bool ok = take(a, w.minT, scratch + 16) && sortws_carve(a, n_sort, w.w) && take(a, w.d_out, n_nodes * sizeof(csv_split_survivor)) && take(a, w.d_count, 256);
+    for (int j = 0; j < D; j++) ok = ok && take(a, w.bitmap[j], bm_words * 4) && take(a, w.set[j + 1], n_nodes * 4);
+    if (D > 0) ok = ok && take(a, w.is_surv, n_nodes) && take(a, w.prevrank, n_nodes * 4) && take(a, w.filter, st_filter_bytes());
+    return ok;
+}
+
+// the overlap-group chain of one call: staged intervals, the (segment, start) sort, SplitGroupsWs, and the block cleared by one memset
+struct SgWs {
+    SplitGroupsWs w;
+    SortWs sw;
+    int32_t *d_start = nullptr, *d_end = nullptr;
+    uint64_t *d_seg = nullptr;
+    char *zero = nullptr;                      // hist | cnt | keep | state | total, err: ONE slice, cleared together
+    size_t zero_bytes = 0;
+    void *es_tmp = nullptr;
+};
+static inline bool carve_split_groups(Arena &a, uint32_t n, uint64_t n_seg, SgWs &c)
+{
+    SplitGroupsWs &w = c.w;
+    const size_t n4 = (size_t)n * 4, nb = (size_t)n / 64 * 4 + 4;
+    const size_t z4 = align_up(((size_t)n + 1) * 4, 256), z1 = align_up((size_t)n, 256);       // sub-offsets inside `zero`
+    c.zero_bytes = 3 * z4 + z1 + 256;
+    const bool ok = take(a, c.d_start, n4) && take(a, c.d_end, n4) && take(a, c.d_seg, (n_seg + 1) * 8) && sortws_carve(a, n, c.sw) &&
+                    take(a, w.ss, n4) && take(a, w.se, n4) && take(a, w.sid, n4) && take(a, w.posof, n4) && take(a, w.plo, n4) && take(a, w.lp1, n4) &&
+                    take(a, w.cstart, n4) && take(a, w.cend, n4) && take(a, w.seed_of_group, n4) && take(a, w.pm, n4) &&
+                    take(a, w.blk_min_id, nb) && take(a, w.blk_max_end, nb) && take(a, w.head, n) &&
+                    take(a, w.group_off, ((size_t)n + 1) * 8) && take(a, w.seg_group_off, (n_seg + 1) * 8) && take(a, w.res, 256) &&
+                    take(a, c.zero, c.zero_bytes) && take(a, c.es_tmp, exclusive_sum_tmp_bytes((uint64_t)n + 1));
+    if (!ok) return false;
+    char *z = c.zero;
+    w.hist = (uint32_t *)z; w.cnt = (uint32_t *)(z + z4); w.keep = (uint32_t *)(z + 2 * z4);
+    w.state = (uint8_t *)(z + 3 * z4);
+    w.total = (unsigned long long *)(z + 3 * z4 + z1); w.err = (uint32_t *)(z + 3 * z4 + z1 + 64);
+    return true;
+}
+
+// the fits' tables on the device. with_start_end false: start / end are the chain's own copies (set by the caller)
+static inline bool carve_sf_tables(Arena &a, uint64_t nm, uint64_t ns, bool with_start_end, SplitFitsIn &in)
+{
+    bool ok = true;
+    if (with_start_end) ok = take(a, in.start, nm * 4) && take(a, in.end, nm * 4);
+    return ok && take(a, in.q_start, nm * 4) && take(a, in.q_end, nm * 4) && take(a, in.reverse, nm) && take(a, in.supp_off, (nm + 1) * 8) &&
+           take(a, in.supp_start, ns * 4) && take(a, in.supp_end, ns * 4) && take(a, in.supp_q_start, ns * 4) && take(a, in.supp_q_end, ns * 4) && take(a, in.supp_flags, ns);
+}
+
+// one run of the fits: its records and counters, and (a set can exceed the LDS kernel: B > DBSCAN1D_MAX_SEG) the buffers of the
+// large-set path
+struct SfRunWs {
+    csv_split_fit *d_out = nullptr;
+    uint32_t *d_big_n = nullptr;
+    unsigned long long *d_res = nullptr;
+    int32_t *pts = nullptr, *ks = nullptr, *labels = nullptr; uint32_t *sizes = nullptr; void *tmp = nullptr; SortWs w;
+};
+static inline bool carve_sf_run(Arena &a, uint64_t G, uint64_t B, SfRunWs &r)
+{
+    const bool ok = take(a, r.d_out, G * sizeof(csv_split_fit)) && take(a, r.d_big_n, G * 6 * 4) && take(a, r.d_res, 256);
+    if (B <= DBSCAN1D_MAX_SEG) return ok;
+    return ok && take(a, r.pts, B * 4) && take(a, r.ks, B * 4) && take(a, r.labels, B * 4) && take(a, r.sizes, B * 4) &&
+           take(a, r.tmp, dbscan1d_big_tmp_bytes(B)) && sortws_carve(a, B, r.w);
+}
+
+// record references into resident shards, as the tables' kernel reads them
+static inline bool carve_sr_refs(Arena &a, uint64_t n_seg, uint64_t nm, uint64_t ns, SplitTablesIn &in)
+{
+    return take(a, in.seg, n_seg * sizeof(SplitTabSeg)) && take(a, in.member_rec, nm * 4) && take(a, in.supp_off, (nm + 1) * 8) &&
+           take(a, in.supp_rec, ns * 4) && take(a, in.supp_where, ns);
+}
+// the arrays of SplitTablesOut behind start / end (which the caller places)
+static inline bool sr_carve(Arena &a, uint64_t nm, uint64_t ns, SplitTablesOut &o)
+{
+    return take(a, o.q_start, nm * 4) && take(a, o.q_end, nm * 4) && take(a, o.reverse, nm) && take(a, o.supp_start, ns * 4) && take(a, o.supp_end, ns * 4) &&
+           take(a, o.supp_q_start, ns * 4) && take(a, o.supp_q_end, ns * 4) && take(a, o.supp_flags, ns);
+}
+
+// shard scratch of one chromosome job: sorted signatures, SoA start / end, labels, sort + dbscan workspace
+struct JobScratch {
+    csv_sig *sig_sorted; uint32_t *st, *en; int32_t *labels;
+    SortWs w; void *db_tmp;
+};
+static inline bool carve_job_scratch(Arena &a, uint64_t n, JobScratch &j)
+{
+    // + 16 on start / end / labels: the clustering kernels' 16-byte loads at the arrays' ends
+    return take(a, j.sig_sorted, n * sizeof(csv_sig)) && take(a, j.st, n * 4 + 16) && take(a, j.en, n * 4 + 16) && take(a, j.labels, n * 4 + 16) &&
+           sortws_carve(a, n, j.w) && take(a, j.db_tmp, dbscan_tmp_bytes(n));
+}
+
+// region tables in, windows out (csvgpu_window_log2*)
+struct WindowWs { uint32_t *rs, *re; int32_t *ss; uint64_t *wo; double *l2; uint32_t *ws, *we; };
+static inline bool carve_window(Arena &a, uint64_t n_regions, uint64_t nw, WindowWs &w)
+{
+    return take(a, w.rs, n_regions * 4) && take(a, w.re, n_regions * 4) && take(a, w.ss, n_regions * 4) && take(a, w.wo, (n_regions + 1) * 8) &&
+           take(a, w.l2, nw * 8) && take(a, w.ws, nw * 4) && take(a, w.we, nw * 4);
+}
+
+// ---- the kernels' own temporaries (one opaque `tmp` to their callers) ----------------------------------------------------------------
+// dbscan.hip: core u8[n] | parent u32[n] | root_of u32[n] | is_root/cid u32[n+1] | scan tmp | tile counts, prefixes | ticket
+struct DbscanTmp {
+    uint8_t *core; uint32_t *parent, *root_of, *cid; void *es_tmp;
+    uint32_t *tile_count, *tile_prefix; unsigned int *ticket;
+    uint32_t n_tiles;                            // tiles of positions 0..n (rank[n] included)
+};
+static inline bool carve_dbscan_tmp(Arena &a, uint64_t n, uint64_t uf_tile, DbscanTmp &t)
+{
+    t.n_tiles = (uint32_t)((n + uf_tile) / uf_tile);
+    return take(a, t.core, n) && take(a, t.parent, n * 4) && take(a, t.root_of, n * 4) && take(a, t.cid, (n + 1) * 4) && take(a, t.es_tmp, exclusive_sum_tmp_bytes(n + 1)) &&
+           take(a, t.tile_count, ((uint64_t)t.n_tiles + 1) * 4) && take(a, t.tile_prefix, ((uint64_t)t.n_tiles + 1) * 4) && take(a, t.ticket, 256);
+}
+// hmm.hip: the model in device form | emission logs f64[6 n_obs] | back-pointers u8[6 n_obs]
+struct ViterbiTmp { void *model; double *biot; uint8_t *psi; };
+static inline bool carve_viterbi_tmp(Arena &a, uint64_t n_obs, size_t model_bytes, ViterbiTmp &t)
+{
+    return take(a, t.model, model_bytes) && take(a, t.biot, n_obs * 6 * sizeof(double)) && take(a, t.psi, n_obs * 6);
+}
+
+}  // namespace csv

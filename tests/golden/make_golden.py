@@ -4,7 +4,7 @@
 container only (needs /root/reference); the JSON files are committed and are what the GPU box and the
 CPU suite check against. Inputs are seeded; expected outputs are whatever the reference code returns.
 Also writes tests/golden/ref_answers.npz: the reference code's answers to every call the tests that check against it make
-(tests/test_oracle_golden.py, test_oracle_windowed.py, test_gpu_ref_sweep.py, through the `ref` fixture), which that fixture
+(tests/test_oracle_golden.py, test_oracle_windowed.py, test_gpu_ref_sweep.py, test_gpu_reservation_edges.py, through the `ref` fixture), which that fixture
 gives them where oracle/_ref is not built. The tests' own bodies are run to record them; the device side of the GPU tests is
 answered by the reference code here, so no GPU is needed.
 
@@ -68,7 +68,8 @@ def main():
 
 
 class _DeviceFromRef:
-    """the Context calls of tests/test_gpu_ref_sweep.py, answered by the reference code (their answers must equal it to pass)"""
+    """the Context calls of tests/test_gpu_ref_sweep.py and test_gpu_reservation_edges.py, answered by the reference code (their answers
+    must equal it to pass)"""
 
     def __init__(self, ref):
         self.ref = ref
@@ -77,15 +78,19 @@ class _DeviceFromRef:
         return self.ref.dbscan_iv(s, e, eps, min_pts)
 
     def dbscan_1d(self, p, off, eps, min_pts):
-        assert len(off) == 2
-        return self.ref.dbscan_1d(p, eps, min_pts)
+        off = [int(o) for o in off]
+        return np.concatenate([self.ref.dbscan_1d(p[a:b], eps, min_pts) if b > a else np.zeros(0, np.int32) for a, b in zip(off[:-1], off[1:])])
 
     def dbscan_iv_batch(self, s, e, off, eps, min_pts):
         return np.concatenate([self.ref.dbscan_iv(s[off[k]: off[k + 1]], e[off[k]: off[k + 1]], eps, min_pts) for k in range(len(off) - 1)])
 
+    def close(self):
+        pass
+
 
 def record_ref_answers(ref):
     import test_gpu_ref_sweep as t_gpu
+    import test_gpu_reservation_edges as t_edges
     import test_oracle_golden as t_golden
     import test_oracle_windowed as t_windowed
     rec = oracle_lib.RecordingRef(ref)
@@ -96,6 +101,7 @@ def record_ref_answers(ref):
     t_gpu.test_interval_dbscan_vs_reference_code(dev, rec)
     t_gpu.test_dbscan1d_vs_reference_code(dev, rec)
     t_gpu.test_interval_dbscan_batch_against_reference(dev, rec)
+    t_edges.dbscan_edges(lambda: dev, rec)
     rec.save(oracle_lib.REF_ANSWERS)
     print("reference answers written:", len(rec.answers), "calls,", os.path.getsize(oracle_lib.REF_ANSWERS), "bytes")
 
