@@ -31,6 +31,11 @@ namespace csv {
 
 constexpr uint32_t NONE = 0xffffffffu;
 
+// Window widths are computed in double and can leave uint64_t inside the documented eps domains (eps * len / (1 - eps) for eps next
+// to 1; a 1-D eps up to infinity), where the conversion is undefined. Keys are 32-bit, so a width of 2^32 already spans every key:
+// clamped there before the conversion, the pad and k + w stay inside uint64_t.
+constexpr double DB_MAX_WIDTH = 4294967296.0;
+
 // A metric names the per-point record (Elem), how to fetch it, its sort key, the key window that can hold neighbours, and the
 // reference's neighbour predicate. Kernels stage the Elems of a tile (plus a halo) in LDS: the window loops are chains of
 // dependent loads, and an LDS hit costs a tenth of an L2 hit.
@@ -44,8 +49,8 @@ struct IntervalMetric {
     {
         const int li = (int)(a.e - a.s);
         const double l = li > 0 ? (double)li : 0.0;
-        const uint64_t wf = (uint64_t)(eps * l) + 2;
-        const uint64_t wb = (uint64_t)(eps * l / (1.0 - eps)) + 2;
+        const uint64_t wf = (uint64_t)(eps * l) + 2;                                   // eps < 1, l < 2^31
+        const uint64_t wb = (uint64_t)min(eps * l / (1.0 - eps), DB_MAX_WIDTH) + 2;
         hi = (uint64_t)a.s + wf;
         lo = (uint64_t)a.s > wb ? (uint64_t)a.s - wb : 0;
     }
@@ -60,7 +65,7 @@ struct PointMetric {                   // p = points sorted ascending (int order
     __device__ __forceinline__ static uint32_t key(const Elem &a) { return (uint32_t)a.p ^ 0x80000000u; }
     __device__ __forceinline__ void window(const Elem &a, uint64_t &lo, uint64_t &hi) const
     {
-        const uint64_t w = (uint64_t)eps + 1, k = key(a);
+        const uint64_t w = (uint64_t)min(eps, DB_MAX_WIDTH) + 1, k = key(a);
         hi = k + w;
         lo = k > w ? k - w : 0;
     }

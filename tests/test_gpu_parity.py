@@ -226,6 +226,12 @@ def test_ordering_with_heavy_ties(ctx, oracle, n_reads, n_pos):
         kind = sig["qpos_kind"] & 3
         _same_sigs(out["sig_del"], sig[kind == 1]); _same_sigs(out["sig_ins"], sig[kind != 1])
         assert res.n_sig == 3 * n_reads
+        # the piles are windows of up to n_reads candidates, far beyond the staged halo: labels too
+        _, dsum, dnz = oracle.depth(reads, depth_len)
+        min_pts = int(np.ceil(dsum / dnz * 0.1))
+        assert res.min_pts == min_pts
+        for name, x in (("label_del", sig[kind == 1]), ("label_ins", sig[kind != 1])):
+            assert np.array_equal(out[name], oracle.dbscan_iv(x["start"], x["end"], 0.1, min_pts)), name
     finally:
         sh.free()
 
