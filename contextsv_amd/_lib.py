@@ -67,6 +67,12 @@ class csv_split_refs(C.Structure):
                 ("supp_where", C.c_void_p)]
 
 
+class csv_cn_regions(C.Structure):
+    _fields_ = [("n_shards", C.c_int32), ("shards", C.c_void_p), ("mean_cov", C.c_void_p), ("reg_off", C.c_void_p), ("region_start", C.c_void_p),
+                ("region_end", C.c_void_p), ("sample_size", C.c_void_p), ("snp_off", C.c_void_p), ("snp_pos", C.c_void_p), ("snp_baf", C.c_void_p),
+                ("snp_pfb", C.c_void_p)]
+
+
 # every symbol include/csvgpu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 ABI = {
@@ -116,6 +122,8 @@ ABI = {
     "csvgpu_split_groups_fits": (C.c_int, [_P, C.POINTER(csv_split_tables), _P, C.c_uint64, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_split_tables_resident": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.POINTER(csv_split_tables)]),
     "csvgpu_split_resident_fits": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_cn_observations_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_cn_decode_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), C.POINTER(csv_hmm), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

@@ -363,6 +363,71 @@ class Context:
         self._check(self.lib.csvgpu_split_fits(self.h, C.byref(t), ptr(seg_off), n_seg, ptr(sgo), ptr(go), ptr(mem), eps, min_pts, ptr(out)))
         return sgo, out[: int(sgo[n_seg])]
 
+    @staticmethod
+    def _cn_regions(shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb, what):
+        """csv_cn_regions over these arrays -> (struct, keep-alive tuple, R)."""
+        reg_off = np.ascontiguousarray(reg_off, np.uint64)
+        if len(reg_off) != len(shards) + 1 or len(mean_cov) != len(shards):
+            raise ValueError(what + ": reg_off needs one entry more than there are shards, mean_cov one per shard")
+        rs, re = np.ascontiguousarray(region_start, np.uint32), np.ascontiguousarray(region_end, np.uint32)
+        ss = np.ascontiguousarray(sample_size, np.int32)
+        so = np.ascontiguousarray(snp_off, np.uint64)
+        sp = np.ascontiguousarray(snp_pos, np.uint32)
+        sb, sf = np.ascontiguousarray(snp_baf, np.float64), np.ascontiguousarray(snp_pfb, np.float64)
+        R = len(rs)
+        if not (len(re) == R and len(ss) == R and len(so) == R + 1 and len(sb) == len(sp) and len(sf) == len(sp)):
+            raise ValueError(what + ": array lengths disagree")
+        if (len(reg_off) and int(reg_off[-1]) != R) or int(so[-1]) != len(sp):
+            raise ValueError(what + ": reg_off must end at the number of regions, snp_off at the number of SNP records")
+        hs = (C.c_void_p * max(len(shards), 1))(*[s.h for s in shards])
+        mc = np.ascontiguousarray(mean_cov, np.float64)
+        t = _lib.csv_cn_regions(len(shards), C.cast(hs, C.c_void_p), ptr(mc), ptr(reg_off), ptr(rs), ptr(re), ptr(ss), ptr(so), ptr(sp), ptr(sb), ptr(sf))
+        return t, (hs, mc, reg_off, rs, re, ss, so, sp, sb, sf), R
+
+    def cn_observations(self, shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb,
+                        capacity: int | None = None) -> dict:
+        """csvgpu_cn_observations_resident_many: the copy-number pass's observation vectors of regions [reg_off[c], reg_off[c + 1]) on
+        shards[c] (resident depth maps), built on the device: region r has max(sample_size[r], its SNP records) windows, its SNP records are
+        snp_*[snp_off[r]:snp_off[r + 1]] with non-decreasing positions. -> dict(obs_off, pos, baf, pfb, log2_cov, is_snp), region r at
+        [obs_off[r], obs_off[r + 1]). capacity None: sized by the bound (windows + 3 records); given: CsvError(CSV_ECAPACITY) when too small,
+        with the exact count in the exception's `needed`."""
+        t, keep, R = self._cn_regions(shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb, "cn_observations")
+        cap = capacity if capacity is not None else int(np.maximum(keep[5], np.diff(keep[6]).astype(np.int64)).sum()) + 3 * len(keep[7])
+        off = np.zeros(R + 1, np.uint64)
+        pos = np.zeros(max(cap, 1), np.uint32)
+        baf, pfb, l2 = (np.zeros(max(cap, 1), np.float64) for _ in range(3))
+        snp = np.zeros(max(cap, 1), np.uint8)
+        n = C.c_uint64(cap)
+        rc = self.lib.csvgpu_cn_observations_resident_many(self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n))
+        if rc == _lib.CSV_ECAPACITY:
+            e = CsvError(rc, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+            e.needed = int(n.value)
+            raise e
+        self._check(rc)
+        k = int(n.value)
+        return dict(obs_off=off, pos=pos[:k].copy(), baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
+
+    def cn_decode(self, hmm: csv_hmm, shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb,
+                  want_observations: bool = False) -> dict:
+        """csvgpu_cn_decode_resident_many: cn_observations and viterbi on them in one call, the observations staying on the device.
+        -> dict(obs_off, pos, states, loglik), and baf / pfb / log2_cov / is_snp with want_observations."""
+        t, keep, R = self._cn_regions(shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb, "cn_decode")
+        cap = int(np.maximum(keep[5], np.diff(keep[6]).astype(np.int64)).sum()) + 3 * len(keep[7])
+        off = np.zeros(R + 1, np.uint64)
+        pos = np.zeros(max(cap, 1), np.uint32)
+        states = np.zeros(max(cap, 1), np.int32)
+        ll = np.zeros(max(R, 1), np.float64)
+        baf, pfb, l2 = ((np.zeros(max(cap, 1), np.float64) if want_observations else None) for _ in range(3))
+        snp = np.zeros(max(cap, 1), np.uint8) if want_observations else None
+        n = C.c_uint64(cap)
+        self._check(self.lib.csvgpu_cn_decode_resident_many(self.h, C.byref(t), C.byref(hmm), ptr(off), ptr(pos), ptr(states), ptr(ll), ptr(baf), ptr(pfb),
+                                                            ptr(l2), ptr(snp), C.byref(n)))
+        k = int(n.value)
+        out = dict(obs_off=off, pos=pos[:k].copy(), states=states[:k].copy(), loglik=ll[:R].copy())
+        if want_observations:
+            out.update(baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
+        return out
+
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):
         self._check(self.lib.csvgpu_synchronize(self.h))

@@ -356,6 +356,28 @@ struct SplitTablesOut {
 };
 constexpr uint32_t ST_MAX_BLOCKS = 1024;     // of 256 threads; larger calls stride
 void launch_st_tables(hipStream_t s, const SplitTablesIn &in, const SplitTablesOut &out);
+// cnobs.hip — the copy-number pass's observation vectors from the window kernel's output (csvgpu_cn_observations_resident_many / _cn_decode_)
+constexpr uint32_t CN_MAX_WINDOWS = 5087;    // windows of a region: the last bucket count whose epoch fits the LDS (SO_SMALL_B)
+constexpr uint32_t CN_SMALL_MAX = 127;       // regions of up to this many windows take the wave-per-region form (bucket counts 13 .. 127)
+constexpr uint32_t CN_MAX_EPOCHS = 12;
+constexpr uint32_t CN_MAX_BLOCKS_SMALL = 4096, CN_MAX_BLOCKS_BIG = 256;   // larger calls stride
+constexpr uint32_t CN_SLOT_UNUSED = 0xffffffffu;
+struct CnEpochs {                            // by value: epoch k holds the nodes inserted from first[k] on, in B[k] buckets; first[n] = 2^32 - 1
+    uint32_t n = 0;
+    uint32_t first[CN_MAX_EPOCHS + 1] = {0};
+    uint32_t B[CN_MAX_EPOCHS] = {0};
+};
+struct CnSlots {                             // per window slot (region's first window + list position p): what the node at p contributes
+    uint32_t *fw, *lw;                       // [W] first / last window of the node's run (global window index)
+    uint32_t *lo, *cnt;                      // [W] its SNP slice: first record, length (0: the dummy observation; CN_SLOT_UNUSED: no node at p)
+    uint32_t *off, *reg;                     // [W] first observation inside its region; the region
+    uint32_t *tot;                           // [R + 1] observations per region, tot[R] = 0: the exclusive sum makes it obs_off
+};
+struct CnObs { uint64_t *obs_off; uint32_t *pos; double *baf, *pfb, *log2_cov; uint8_t *is_snp; };
+void launch_cn_order(hipStream_t s, const uint32_t *ws, const uint32_t *we, const uint32_t *win_base, const uint32_t *snp_off, const uint32_t *snp_pos,
+                     const uint32_t *regions_small, uint32_t n_small, const uint32_t *regions_big, uint32_t n_big, const CnEpochs &ep, const CnSlots &out);
+void launch_cn_fill(hipStream_t s, const CnSlots &sl, uint32_t n_slots, uint32_t n_regions, const uint32_t *obs_off32, const uint32_t *ws, const uint32_t *we,
+                    const double *l2, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const CnObs &o);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

@@ -164,4 +164,20 @@ __device__ __forceinline__ uint32_t bk_bucket(const csv_sig &sg, int type_pos, i
 __device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v); }
 
+// h % B for a 32-bit B, exactly, without the 64-bit integer division (some 150 instructions with branches, and every node of every epoch
+// and level pays it): the quotient in two 32-bit steps estimated in double precision (error far below 1), remainder in integers, fixed up.
+__device__ __forceinline__ uint32_t so_mod(uint64_t h, uint32_t B, double inv /* 1.0 / B */)
+{
+    const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
+    int64_t r = (int64_t)hi - (int64_t)((uint64_t)(uint32_t)((double)hi * inv) * B);
+    while (r < 0) r += B;
+    while (r >= (int64_t)B) r -= B;
+    const uint64_t x = ((uint64_t)(uint32_t)r << 32) | lo;                          // < B * 2^32: the quotient fits 32 bits
+    const double xf = fma((double)(uint32_t)r, 4294967296.0, (double)lo);
+    int64_t r2 = (int64_t)(x - (uint64_t)(uint32_t)(xf * inv) * B);
+    while (r2 < 0) r2 += B;
+    while (r2 >= (int64_t)B) r2 -= B;
+    return (uint32_t)r2;
+}
+
 }  // namespace csv

@@ -192,12 +192,110 @@ void CNVCaller::assembleRegion(const RegionBatch &B, size_t i, ObsChunk &out) co
     out.off.push_back(out.pos.size());
 }
 
+// The tables of csv_cn_regions for the valid regions of some batches (row = the batches' slots, batch after batch), and what the two
+// device calls return for them.
+struct CNVCaller::DeviceObs {
+    std::vector<csv_shard *> shards;
+    std::vector<double> mean;
+    std::vector<uint64_t> reg_off{0}, snp_off{0};
+    std::vector<uint32_t> rs, re, spos;
+    std::vector<int32_t> ss;
+    std::vector<double> sbaf, spfb;
+    uint64_t bound = 0;                        // windows + 3 x records: no region yields more observations
+    std::vector<uint64_t> obs_off;
+    std::vector<uint32_t> pos;
+    std::vector<double> baf, pfb, l2, ll;
+    std::vector<uint8_t> is_snp;
+    std::vector<int32_t> states;
+
+    // false: the batch lies outside the device form's domain (csvgpu.h) — the caller takes the host route
+    bool add(const RegionBatch &B, csv_shard *shard, double mean_chr_cov)
+    {
+        for (size_t i = 0; i < B.regions.size(); i++) {
+            if (B.slot[i] == SIZE_MAX) continue;
+            const SnpChunk &sc = B.snp[i / kChunk];
+            const uint32_t s0 = sc.off[i % kChunk], s1 = sc.off[i % kChunk + 1];
+            const int32_t n_win = B.r_ss[B.slot[i]];
+            if (n_win > 5087 || B.regions[i].second >= 0x7fffffffu) return false;
+            for (uint32_t k = s0 + 1; k < s1; k++) if (sc.pos[k] < sc.pos[k - 1]) return false;
+            rs.push_back(B.regions[i].first); re.push_back(B.regions[i].second); ss.push_back(n_win);
+            spos.insert(spos.end(), sc.pos.begin() + s0, sc.pos.begin() + s1);
+            sbaf.insert(sbaf.end(), sc.baf.begin() + s0, sc.baf.begin() + s1);
+            spfb.insert(spfb.end(), sc.pfb.begin() + s0, sc.pfb.begin() + s1);
+            snp_off.push_back(spos.size());
+            bound += (uint64_t)n_win + 3ull * (s1 - s0);
+        }
+        shards.push_back(shard); mean.push_back(mean_chr_cov); reg_off.push_back(rs.size());
+        return true;
+    }
+    csv_cn_regions tables() const
+    {
+        return csv_cn_regions{(int32_t)shards.size(), shards.data(), mean.data(), reg_off.data(), rs.data(), re.data(), ss.data(), snp_off.data(), spos.data(),
+                              sbaf.data(), spfb.data()};
+    }
+    void decode(csv_ctx *ctx, const CHMM &hmm, bool want_arrays)
+    {
+        const csv_hmm p = to_pod(hmm);
+        const csv_cn_regions t = tables();
+        obs_off.assign(rs.size() + 1, 0); pos.resize(bound); states.resize(bound); ll.assign(rs.size(), 0.0);
+        if (want_arrays) { baf.resize(bound); pfb.resize(bound); l2.resize(bound); is_snp.resize(bound); }
+        uint64_t n = bound;
+        check(ctx, csvgpu_cn_decode_resident_many(ctx, &t, &p, obs_off.data(), pos.data(), states.data(), ll.data(), want_arrays ? baf.data() : nullptr,
+                                                  want_arrays ? pfb.data() : nullptr, want_arrays ? l2.data() : nullptr, want_arrays ? is_snp.data() : nullptr, &n),
+              "copy-number observations");
+    }
+    void observe(csv_ctx *ctx)
+    {
+        const csv_cn_regions t = tables();
+        obs_off.assign(rs.size() + 1, 0); pos.resize(bound); baf.resize(bound); pfb.resize(bound); l2.resize(bound); is_snp.resize(bound);
+        uint64_t n = bound;
+        check(ctx, csvgpu_cn_observations_resident_many(ctx, &t, obs_off.data(), pos.data(), baf.data(), pfb.data(), l2.data(), is_snp.data(), &n), "querySNPRegion");
+    }
+    void toSNPData(size_t row, SNPData &d) const
+    {
+        const std::ptrdiff_t a = (std::ptrdiff_t)obs_off[row], b = (std::ptrdiff_t)obs_off[row + 1];
+        d.pos.assign(pos.begin() + a, pos.begin() + b); d.baf.assign(baf.begin() + a, baf.begin() + b); d.pfb.assign(pfb.begin() + a, pfb.begin() + b);
+        d.log2_cov.assign(l2.begin() + a, l2.begin() + b); d.is_snp.assign(is_snp.begin() + a, is_snp.begin() + b);
+    }
+};
+
+// querySNPRegions and runViterbi of `regions` in one device call; false (nothing done) where the batch is outside its domain. data[i] is
+// filled only with want_arrays; predictions[i] always (an invalid region: empty path, as runViterbi gives it).
+bool CNVCaller::decodeRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov, const SNPSource &snps,
+                              const CHMM &hmm, bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions) const
+{
+    RegionBatch B;
+    B.regions = regions;
+    prepareWindows(B, snps);
+    DeviceObs D;
+    if (!D.add(B, shard, mean_chr_cov)) return false;
+    if (!D.rs.empty()) D.decode(ctx, hmm, want_arrays);
+    data.assign(regions.size(), SNPData());
+    predictions.assign(regions.size(), std::make_pair(std::vector<int>(), -100000000000.0));      // T = 0: testVit_CHMM's -VITHUGE
+    for (size_t i = 0; i < regions.size(); i++) {
+        if (B.slot[i] == SIZE_MAX) { printError("ERROR: No SNP data found for Viterbi algorithm."); continue; }
+        const size_t row = B.slot[i];
+        if (want_arrays) D.toSNPData(row, data[i]);
+        predictions[i] = std::make_pair(std::vector<int>(D.states.begin() + (std::ptrdiff_t)D.obs_off[row], D.states.begin() + (std::ptrdiff_t)D.obs_off[row + 1]), D.ll[row]);
+    }
+    return true;
+}
+
 void CNVCaller::querySNPRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov,
                                 const SNPSource &snps, std::vector<SNPData> &out) const
 {
     RegionBatch B;
     B.regions = regions;
     prepareWindows(B, snps);
+    if (device_observations) {
+        DeviceObs D;
+        if (D.add(B, shard, mean_chr_cov)) {
+            if (!D.rs.empty()) D.observe(ctx);
+            out.assign(regions.size(), SNPData());
+            for (size_t i = 0; i < regions.size(); i++) if (B.slot[i] != SIZE_MAX) D.toSNPData(B.slot[i], out[i]);
+            return;
+        }
+    }
     launchWindows(B, shard, mean_chr_cov);
     out.assign(regions.size(), SNPData());
     csvhost::parallel_for(regions.size(), host_threads, [&](size_t i) {
@@ -231,7 +329,13 @@ struct CNVCaller::GenomeObs {
     std::vector<uint64_t> seq_off;             // candidate q's observations in the flat Viterbi batch
     std::vector<int> states;
     std::vector<double> ll;
-    const uint32_t *pos(size_t q) const { const ObsChunk &c = chunks[q / kChunk]; return c.pos.data() + c.off[q % kChunk]; }
+    std::vector<uint32_t> dev_pos;             // device route: every candidate's positions back to back (chunks stay empty)
+    bool on_device = false;
+    const uint32_t *pos(size_t q) const
+    {
+        if (on_device) return dev_pos.data() + seq_off[q];
+        const ObsChunk &c = chunks[q / kChunk]; return c.pos.data() + c.off[q % kChunk];
+    }
     size_t len(size_t q) const { return (size_t)(seq_off[q + 1] - seq_off[q]); }
 };
 
@@ -251,6 +355,24 @@ void CNVCaller::observeAndDecode(std::vector<RegionBatch> &batches, const std::v
         }
         csvhost::parallel_for(tasks.size(), host_threads, [&](size_t t) { queryChunk(batches[tasks[t].first], *jobs[tasks[t].first].snps, tasks[t].second); });
         for (size_t j = 0; j < jobs.size(); j++) if (!batches[j].regions.empty()) finishWindows(batches[j]);
+    }
+    const size_t n = G.cands.size();
+    G.chunks.assign((n + kChunk - 1) / kChunk, ObsChunk());
+    if (device_observations) {
+        // one decode call for all jobs: row q of its tables is candidate q (the candidates were listed job by job, region by region)
+        csvhost::TraceScope tr("cn: decode on device");
+        DeviceObs D;
+        bool ok = true;
+        for (size_t j = 0; j < jobs.size() && ok; j++) if (!batches[j].r_start.empty()) ok = D.add(batches[j], jobs[j].shard, jobs[j].mean_chr_cov);
+        if (ok && D.rs.size() == n) {
+            D.decode(ctx, hmm, false);
+            G.on_device = true;
+            G.seq_off = std::move(D.obs_off); G.dev_pos = std::move(D.pos); G.ll = std::move(D.ll);
+            G.states.assign(D.states.begin(), D.states.begin() + (std::ptrdiff_t)G.seq_off[n]);
+            for (size_t q = 0; q < n; q++)
+                if (G.len(q) == 0) printError("ERROR: No SNP data found for Viterbi algorithm.");
+            return;
+        }
     }
     {
         csvhost::TraceScope tr("cn: window launches");
@@ -274,8 +396,6 @@ void CNVCaller::observeAndDecode(std::vector<RegionBatch> &batches, const std::v
             check(ctx, csvgpu_window_log2_resident_many(ctx, (int)sh.size(), sh.data(), rs.data(), re.data(), ss.data(), wo.data(), nr.data(), mean.data(), l2.data(),
                                                         ws.data(), we.data()), "querySNPRegion");
     }
-    const size_t n = G.cands.size();
-    G.chunks.assign((n + kChunk - 1) / kChunk, ObsChunk());
     {
         csvhost::TraceScope tr("cn: assemble");
         csvhost::parallel_for(G.chunks.size(), host_threads, [&](size_t c) {
@@ -411,10 +531,12 @@ void CNVCaller::runCopyNumberPredictions(const std::string &chr, const CHMM &hmm
         }
     }
     std::vector<SNPData> data;
-    querySNPRegions(batch, shard, mean_chr_cov, snps, data);
-    std::vector<SNPData> sv_data(data.begin(), data.begin() + (std::ptrdiff_t)nv);
     std::vector<std::pair<std::vector<int>, double>> pred;
-    runViterbi(hmm, sv_data, pred);
+    if (!device_observations || !decodeRegions(batch, shard, mean_chr_cov, snps, hmm, save_cnv_data, data, pred)) {
+        querySNPRegions(batch, shard, mean_chr_cov, snps, data);
+        std::vector<SNPData> sv_data(data.begin(), data.begin() + (std::ptrdiff_t)nv);
+        runViterbi(hmm, sv_data, pred);
+    }
     for (size_t q = 0; q < idx.size(); q++) {
         std::vector<int> &seq = pred[q].first;
         if (seq.empty()) continue;                                       // :206-209

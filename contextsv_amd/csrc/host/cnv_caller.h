@@ -100,6 +100,11 @@ public:
     size_t runCIGARCopyNumberPredictionAll(std::vector<ContigJob> &jobs, const CHMM &hmm) const;
     void runSplitReadCopyNumberPredictionsAll(std::vector<ContigJob> &jobs, const CHMM &hmm) const;
     int host_threads = 0;            // host pool threads for the per-region work (0: all); results do not depend on it
+    // The observation vectors on the device (csvgpu_cn_observations_resident_many / csvgpu_cn_decode_resident_many, kernels/cnobs.hip)
+    // instead of the window launches, assembleRegion on the pool and the Viterbi call: one device call per batch, the SNP queries and the
+    // votes stay on the pool. A batch outside that call's domain (an unsorted SNPSource, a region of more than 5087 windows, an end at or
+    // above 2^31 - 1) takes the host route, whole. Same results either way.
+    bool device_observations = false;
 
     // sv_caller.cpp:983-1064 — the five-way update / duplicate rule for split-read candidates
     void runSplitReadCopyNumberPredictions(const std::string &chr, std::vector<SVCall> &split_sv_calls, const CHMM &hmm,
@@ -111,6 +116,9 @@ private:
     struct SnpChunk;
     struct ObsChunk;
     struct GenomeObs;
+    struct DeviceObs;
+    bool decodeRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov, const SNPSource &snps, const CHMM &hmm,
+                       bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions) const;
     void prepareWindows(RegionBatch &B, const SNPSource &snps) const;
     void queryChunk(RegionBatch &B, const SNPSource &snps, size_t c) const;
     void finishWindows(RegionBatch &B) const;

@@ -600,14 +600,62 @@ int csvhost_query_snp_region(csv_ctx *ctx, csv_shard *shard, uint32_t start, uin
     })
 }
 
+// querySNPRegion for many regions of one shard in one batch: region i's observations at [obs_off[i], obs_off[i + 1]) of the five arrays
+// (an invalid region, start > end, has none). on_device: CNVCaller::device_observations. *n_out = the observations in all; nothing is
+// written to the arrays when it exceeds cap.
+int csvhost_query_snp_regions(csv_ctx *ctx, csv_shard *shard, uint64_t n_regions, const uint32_t *start, const uint32_t *end, double mean_cov, int sample_size,
+                              const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp, int on_device,
+                              uint64_t *obs_off, uint32_t *pos_out, double *baf_out, double *pfb_out, double *log2_out, uint8_t *is_snp_out, uint64_t cap, uint64_t *n_out)
+{
+    GUARD({
+        CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.device_observations = on_device != 0;
+        SNPTable t = snp_table(snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp);
+        std::vector<std::pair<uint32_t, uint32_t>> regions;
+        for (uint64_t i = 0; i < n_regions; i++) regions.emplace_back(start[i], end[i]);
+        std::vector<SNPData> d;
+        cnv.querySNPRegions(regions, shard, mean_cov, t, d);
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < n_regions; i++) { obs_off[i] = total; total += d[i].pos.size(); }
+        obs_off[n_regions] = total;
+        *n_out = total;
+        if (total <= cap)
+            for (uint64_t i = 0; i < n_regions; i++)
+                for (size_t k = 0; k < d[i].pos.size(); k++) {
+                    const uint64_t at = obs_off[i] + k;
+                    pos_out[at] = d[i].pos[k]; baf_out[at] = d[i].baf[k]; pfb_out[at] = d[i].pfb[k]; log2_out[at] = d[i].log2_cov[k]; is_snp_out[at] = d[i].is_snp[k];
+                }
+    })
+}
+
+static int cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out, const csv_hmm *hmm,
+                         double mean_cov, int sample_size, uint32_t min_cnv, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb,
+                         const uint8_t *snp_has_pfb, uint64_t n_snp, bool observations_on_device);
+
+// csvhost_cn_prediction with the observation vectors built on the device (observations_on_device != 0: CNVCaller::device_observations)
+int csvhost_cn_prediction_device(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out,
+                                 const csv_hmm *hmm, double mean_cov, int sample_size, uint32_t min_cnv,
+                                 const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp,
+                                 int observations_on_device)
+{
+    return cn_prediction(ctx, shard, split, calls, n, cap, n_out, hmm, mean_cov, sample_size, min_cnv, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp,
+                         observations_on_device != 0);
+}
+
 // runCIGARCopyNumberPrediction (split == 0, in place) or runSplitReadCopyNumberPredictions (split == 1, may grow the list)
 int csvhost_cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out,
                           const csv_hmm *hmm, double mean_cov, int sample_size, uint32_t min_cnv,
                           const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp)
 {
+    return cn_prediction(ctx, shard, split, calls, n, cap, n_out, hmm, mean_cov, sample_size, min_cnv, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp, false);
+}
+
+static int cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out, const csv_hmm *hmm,
+                         double mean_cov, int sample_size, uint32_t min_cnv, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb,
+                         const uint8_t *snp_has_pfb, uint64_t n_snp, bool observations_on_device)
+{
     GUARD({
         csvhost::set_context(ctx);
-        CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.min_cnv_length = min_cnv;
+        CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.min_cnv_length = min_cnv; cnv.device_observations = observations_on_device;
         SNPTable t = snp_table(snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp);
         CHMM h = chmm_from_pod(hmm);
         std::vector<SVCall> v; v.reserve(n);
@@ -780,7 +828,8 @@ void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n
 // One step: SVCaller::runResident over every staged contig. passes: bit 0 split-read pass, bit 1 CIGAR copy-number pass, bit 2 the two
 // final merges, bit 3 keep the qname map's order on the host (umap_order.h) instead of csvgpu_split_order,
 // bit 4 do not run the split pass's first half beside the CIGAR pass; bit 9 the overlap groups from csvgpu_split_groups (split_groups_on_device), bit 10 the groups' fits from csvgpu_split_fits
-// (split_fits_on_device), bit 11 the members' tables built on the device from the resident shards, groups and fits with them (split_tables_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
+// (split_fits_on_device), bit 11 the members' tables built on the device from the resident shards, groups and fits with them (split_tables_on_device), bit 12 the copy-number
+// passes' observation vectors built and decoded on the device (cn_observations_on_device); the RunSchedule (no result depends on it): bits 5-6 early_batches
 // (0 timed, 1 none, 2 all at once, 3 every three), bit 7 no split chain beside the pass, bit 8 the two-call split order, bits 16-30
 // prepare_delay_ms. Calls come back grouped by contig in staging order with the contig's GLOBAL tid in out_tid; stats[i] per contig.
 int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *const *lane_ctxs, const csv_hmm *hmm, double eps, double min_pts_pct,
@@ -806,6 +855,7 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         P.split_groups_on_device = (passes & 512) != 0;
         P.split_fits_on_device = (passes & 1024) != 0;
         P.split_tables_on_device = (passes & 2048) != 0;
+        P.cn_observations_on_device = (passes & 4096) != 0;
         P.schedule.prepare_delay_ms = (passes >> 16) & 0x7fff;
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);

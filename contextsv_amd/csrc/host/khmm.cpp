@@ -35,6 +35,8 @@ bool read_scalar_line(std::ifstream &f, double &v)
     return true;
 }
 
+}  // namespace
+
 csv_hmm to_pod(const CHMM &h)
 {
     if (h.N != 6 || h.A.size() != 6 || h.pi.size() != 6 || h.B1_mean.size() != 6 || h.B1_sd.size() != 6 || h.B2_mean.size() != 5 || h.B2_sd.size() != 5)
@@ -49,8 +51,6 @@ csv_hmm to_pod(const CHMM &h)
     p.B1_uf = h.B1_uf; p.B2_uf = h.B2_uf;
     return p;
 }
-
-}  // namespace
 
 CHMM ReadCHMM(const std::string filename)
 {

@@ -33,4 +33,6 @@ struct VitBatch {
     std::vector<uint64_t> seq_off{0};
     void add(const std::vector<double> &a, const std::vector<double> &b, const std::vector<double> &c);
 };
+struct csv_hmm;
+csv_hmm to_pod(const CHMM &hmm);                  // the model as the C-ABI takes it
 void testVit_CHMM_batch(const CHMM &hmm, const VitBatch &batch, std::vector<int> &states, std::vector<double> &loglik);

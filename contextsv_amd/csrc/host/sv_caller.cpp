@@ -635,6 +635,7 @@ CNVCaller makeCnv(csv_ctx *ctx, const RunParams &P)
 {
     CNVCaller cn(ctx);
     cn.sample_size = P.sample_size; cn.min_cnv_length = P.min_cnv_length; cn.host_threads = P.host_threads;
+    cn.device_observations = P.cn_observations_on_device;
     return cn;
 }
 

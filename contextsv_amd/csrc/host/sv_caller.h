@@ -108,6 +108,9 @@ struct RunParams {
     bool split_tables_on_device = false;    // the members' and supplementary records' tables of the split-read pass built on the device from the resident shards
                                             // (csvgpu_split_resident_fits): no interval gather, no members on the pool, no upload; groups and fits then come from the
                                             // device too, whatever the two switches above say; the calls do not depend on it
+    bool cn_observations_on_device = false; // the copy-number passes' observation vectors built on the device from the window kernel's output and decoded there
+                                            // (csvgpu_cn_decode_resident_many) instead of windows back, assembleRegion on the pool and observations up again; the
+                                            // calls do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it

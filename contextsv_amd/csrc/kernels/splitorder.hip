@@ -35,22 +35,6 @@ __device__ __forceinline__ bool so_pass(uint16_t flag, uint8_t mapq, uint32_t mi
     return !(flag & (F_SECONDARY | F_UNMAP | F_DUP | F_QCFAIL | F_SUPP)) && mapq >= min_mapq;
 }
 
-// h % B for a 32-bit B, exactly, without the 64-bit integer division (some 150 instructions with branches, and every node of every epoch
-// and level pays it): the quotient in two 32-bit steps estimated in double precision (error far below 1), remainder in integers, fixed up.
-__device__ __forceinline__ uint32_t so_mod(uint64_t h, uint32_t B, double inv /* 1.0 / B */)
-{
-    const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
-    int64_t r = (int64_t)hi - (int64_t)((uint64_t)(uint32_t)((double)hi * inv) * B);
-    while (r < 0) r += B;
-    while (r >= (int64_t)B) r -= B;
-    const uint64_t x = ((uint64_t)(uint32_t)r << 32) | lo;                          // < B * 2^32: the quotient fits 32 bits
-    const double xf = fma((double)(uint32_t)r, 4294967296.0, (double)lo);
-    int64_t r2 = (int64_t)(x - (uint64_t)(uint32_t)(xf * inv) * B);
-    while (r2 < 0) r2 += B;
-    while (r2 >= (int64_t)B) r2 -= B;
-    return (uint32_t)r2;
-}
-
 // ---- nodes = the filter-passing primary records in file order (the insertion order of the map) ------------------------------------
 __global__ __launch_bounds__(SO_THREADS) void so_count_kernel(SplitOrderTab tab, uint32_t min_mapq, uint32_t *__restrict__ blk_cnt)
 {

@@ -10,7 +10,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "dbscan_tmp", "viterbi_tmp"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -193,6 +193,41 @@ static inline bool carve_window(Arena &a, uint64_t n_regions, uint64_t nw, Windo
 {
     return take(a, w.rs, n_regions * 4) && take(a, w.re, n_regions * 4) && take(a, w.ss, n_regions * 4) && take(a, w.wo, (n_regions + 1) * 8) &&
            take(a, w.l2, nw * 8) && take(a, w.ws, nw * 4) && take(a, w.we, nw * 4);
+}
+
+// the copy-number observations of R regions with W windows and S SNP records in all (csvgpu_cn_observations_resident_many / _cn_decode_):
+// the tables as they come up (`in`: one slice, one copy; the sub-arrays at CnInLayout's offsets), the windows, the per-slot records, the
+// regions' totals, and the answer sized by its bound W + 3 S (a position lies in at most three distinct keys) plus, for the fused call, the
+// Viterbi outputs
+struct CnInLayout {
+    size_t rs, re, ss, wo, wbase, soff, spos, sbaf, spfb, small, big, bytes;
+    CnInLayout(uint64_t R, uint64_t n_shards, uint64_t S)
+    {
+        size_t o = 0;
+        auto put = [&](size_t b) { const size_t at = o; o += align_up(b, 256); return at; };
+        rs = put(R * 4); re = put(R * 4); ss = put(R * 4); wo = put((R + n_shards) * 8); wbase = put((R + 1) * 4); soff = put((R + 1) * 4);
+        spos = put(S * 4); sbaf = put(S * 8); spfb = put(S * 8); small = put(R * 4); big = put(R * 4);
+        bytes = o;
+    }
+};
+struct CnWs {
+    char *in = nullptr;
+    double *l2 = nullptr; uint32_t *ws = nullptr, *we = nullptr;
+    CnSlots sl{};
+    void *es_tmp = nullptr;
+    CnObs o{};
+    int32_t *states = nullptr; double *loglik = nullptr;
+};
+static inline bool carve_cn_obs(Arena &a, uint64_t R, uint64_t W, uint64_t n_shards, uint64_t S, bool decode, CnWs &w)
+{
+    const uint64_t bound = W + 3 * S;
+    const bool ok = take(a, w.in, CnInLayout(R, n_shards, S).bytes) && take(a, w.l2, W * 8) && take(a, w.ws, W * 4) && take(a, w.we, W * 4) &&
+                    take(a, w.sl.fw, W * 4) && take(a, w.sl.lw, W * 4) && take(a, w.sl.lo, W * 4) && take(a, w.sl.cnt, W * 4) && take(a, w.sl.off, W * 4) &&
+                    take(a, w.sl.reg, W * 4) && take(a, w.sl.tot, (R + 1) * 4) && take(a, w.es_tmp, exclusive_sum_tmp_bytes(R + 1)) &&
+                    take(a, w.o.obs_off, (R + 1) * 8) && take(a, w.o.pos, bound * 4) && take(a, w.o.baf, bound * 8 + 8) && take(a, w.o.pfb, bound * 8 + 8) &&
+                    take(a, w.o.log2_cov, bound * 8 + 8) && take(a, w.o.is_snp, bound);
+    if (!decode) return ok;
+    return ok && take(a, w.states, bound * 4 + 8) && take(a, w.loglik, R * 8);
 }
 
 // ---- the kernels' own temporaries (one opaque `tmp` to their callers) ----------------------------------------------------------------

@@ -64,6 +64,10 @@ def load() -> C.CDLL:
                                              _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_cn_prediction.argtypes = [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_lib.csv_hmm),
                                           C.c_double, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint64]
+    lib.csvhost_query_snp_regions.argtypes = [_P, _P, C.c_uint64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, C.c_uint64, C.c_int,
+                                              _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.csvhost_cn_prediction_device.argtypes = [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_lib.csv_hmm),
+                                                 C.c_double, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_int]
     lib.csvhost_split_signatures.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_opts.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_dev.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -286,7 +290,8 @@ class Genome:
     def run(self, ctx: Context, hmm, lanes=None, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, merges=True,
             host_threads=0, capacity: int = 1 << 20, host_split_order: bool = False, overlap_split: bool = True, copy: bool = True,
             early_batches: str = "timed", split_beside_pass: bool = True, split_order_self: bool = True, prepare_delay_ms: int = 0,
-            split_groups_on_device: bool = False, split_fits_on_device: bool = False, split_tables_on_device: bool = False):
+            split_groups_on_device: bool = False, split_fits_on_device: bool = False, split_tables_on_device: bool = False,
+            cn_observations_on_device: bool = False):
         """-> (calls[CALL_DTYPE], global tid per call, stage_times, per-contig chr_stats list). copy=False: the two arrays are views of buffers
         the genome owns (two sets, used alternately) and stay valid until the run after the next one. early_batches ("timed" | "none" | "all" |
         "every3"), split_beside_pass, split_order_self and prepare_delay_ms are RunParams::schedule: no result depends on them, they force
@@ -296,14 +301,16 @@ class Genome:
         csvgpu_split_groups_fits, the groups then staying on the device — instead of the host's sets and one DBSCAN1D batch; the calls are the same.
         split_tables_on_device: the members' and supplementary records' tables built on the device from the resident shards and fed straight into
         that chain (csvgpu_split_resident_fits): no interval gather, no members on the host, no upload; groups and fits then come from the device
-        whatever the two other switches say; the calls are the same."""
+        whatever the two other switches say; the calls are the same. cn_observations_on_device: the observation vectors of both copy-number
+        passes built on the device from the window kernel's output and decoded there (csvgpu_cn_decode_resident_many) instead of windows back,
+        the vectors assembled on the host pool and sent up again; the calls are the same."""
         if early_batches not in _EARLY_BATCHES:
             raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {early_batches!r}")
         if not 0 <= int(prepare_delay_ms) < 1 << 15:
             raise ValueError(f"prepare_delay_ms must be in [0, 32767], not {prepare_delay_ms!r}")
         passes = int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4) | \
             (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(bool(split_groups_on_device)) << 9) | \
-            (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | (int(prepare_delay_ms) << 16)
+            (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | (int(bool(cn_observations_on_device)) << 12) | (int(prepare_delay_ms) << 16)
         n = len(self)
         if getattr(self, "_cap", 0) < capacity:              # result buffers live with the genome (tens of megabytes of page faults per call otherwise)
             self._bufs = [(np.empty(capacity, CALL_DTYPE), np.empty(capacity, np.int32)) for _ in range(2)]
@@ -445,16 +452,42 @@ def query_snp_region(ctx: Context, shard: Shard, start: int, end: int, mean_cov:
     return {"pos": o_pos[:k], "baf": o_baf[:k], "pfb": o_pfb[:k], "log2_cov": o_l2[:k], "is_snp": o_is[:k].astype(bool)}
 
 
+def query_snp_regions(ctx: Context, shard: Shard, starts, ends, mean_cov: float, sample_size: int, snps: dict, on_device: bool = False,
+                      cap: int | None = None) -> dict:
+    """CNVCaller::querySNPRegions mirror: many regions of one shard in one batch -> dict(obs_off, pos, baf, pfb, log2_cov, is_snp), region i
+    at [obs_off[i], obs_off[i + 1]). on_device: the observation vectors from csvgpu_cn_observations_resident_many instead of the window
+    launch and the host's assembly (same arrays; a batch outside that call's domain takes the host route)."""
+    pos, baf, pfb, has = _snp_arrays(snps)
+    st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
+    if len(st) != len(en):
+        raise ValueError("query_snp_regions: starts and ends differ in length")
+    if cap is None:
+        cap = int(len(st)) * max(int(sample_size), 1) + 4 * int(len(pos)) * max(len(st), 1) + 16
+        cap = min(cap, 1 << 26)
+    off = np.zeros(len(st) + 1, np.uint64)
+    o_pos = np.zeros(cap, np.uint32); o_baf = np.zeros(cap); o_pfb = np.zeros(cap); o_l2 = np.zeros(cap); o_is = np.zeros(cap, np.uint8)
+    n = C.c_uint64(0)
+    _check(load().csvhost_query_snp_regions(ctx.h, shard.h, len(st), st.ctypes.data, en.ctypes.data, mean_cov, sample_size, pos.ctypes.data, baf.ctypes.data,
+                                            pfb.ctypes.data, has.ctypes.data, len(pos), int(bool(on_device)), off.ctypes.data, o_pos.ctypes.data,
+                                            o_baf.ctypes.data, o_pfb.ctypes.data, o_l2.ctypes.data, o_is.ctypes.data, cap, C.byref(n)))
+    k = n.value
+    if k > cap:
+        return query_snp_regions(ctx, shard, starts, ends, mean_cov, sample_size, snps, on_device, cap=int(k))
+    return {"obs_off": off, "pos": o_pos[:k].copy(), "baf": o_baf[:k].copy(), "pfb": o_pfb[:k].copy(), "log2_cov": o_l2[:k].copy(), "is_snp": o_is[:k].astype(bool)}
+
+
 def cn_prediction(ctx: Context, shard: Shard, calls: np.ndarray, hmm, mean_cov: float, snps: dict, split: bool, sample_size: int = 20,
-                  min_cnv: int = 2000) -> np.ndarray:
-    """runCIGARCopyNumberPrediction (split=False) / runSplitReadCopyNumberPredictions (split=True) mirror."""
+                  min_cnv: int = 2000, observations_on_device: bool = False) -> np.ndarray:
+    """runCIGARCopyNumberPrediction (split=False) / runSplitReadCopyNumberPredictions (split=True) mirror. observations_on_device:
+    CNVCaller::device_observations (the observation vectors built and decoded on the device; same calls)."""
     pos, baf, pfb, has = _snp_arrays(snps)
     cap = 2 * len(calls) + 16
     buf = np.zeros(cap, CALL_DTYPE)
     buf[: len(calls)] = np.ascontiguousarray(calls, CALL_DTYPE)
     n = C.c_uint64(0)
-    _check(load().csvhost_cn_prediction(ctx.h, shard.h, int(split), buf.ctypes.data, len(calls), cap, C.byref(n), C.byref(hmm), mean_cov,
-                                        sample_size, min_cnv, pos.ctypes.data, baf.ctypes.data, pfb.ctypes.data, has.ctypes.data, len(pos)))
+    _check(load().csvhost_cn_prediction_device(ctx.h, shard.h, int(split), buf.ctypes.data, len(calls), cap, C.byref(n), C.byref(hmm), mean_cov,
+                                               sample_size, min_cnv, pos.ctypes.data, baf.ctypes.data, pfb.ctypes.data, has.ctypes.data, len(pos),
+                                               int(bool(observations_on_device))))
     return buf[: n.value].copy()
 
 

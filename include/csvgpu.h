@@ -461,6 +461,41 @@ int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *cons
                                      const uint64_t *n_regions, const double *mean_cov, double *const *log2_cov, uint32_t *const *win_start,
                                      uint32_t *const *win_end);
 
+/* The copy-number pass's observation vectors on the device (kernels/cnobs.hip; CNVCaller::querySNPRegion, cnv_caller.cpp:65-164): the
+ * regions' windows are evaluated as by csvgpu_window_log2_resident_many and consumed where they lie. Regions [reg_off[c], reg_off[c+1])
+ * lie on shards[c] and are evaluated against mean_cov[c]; region r has max(sample_size[r], snp_off[r+1] - snp_off[r]) windows, and
+ * snp_pos / snp_baf / snp_pfb [snp_off[r], snp_off[r+1]) are its SNP records as SNPSource::queryFlat returns them (the two hash maps'
+ * values already resolved per record). */
+typedef struct csv_cn_regions {
+    int32_t n_shards;
+    csv_shard *const *shards;     /* [n_shards] */
+    const double   *mean_cov;     /* [n_shards] */
+    const uint64_t *reg_off;      /* [n_shards + 1], reg_off[0] == 0; R = reg_off[n_shards] */
+    const uint32_t *region_start, *region_end;   /* [R] */
+    const int32_t  *sample_size;  /* [R] */
+    const uint64_t *snp_off;      /* [R + 1], snp_off[0] == 0; S = snp_off[R] */
+    const uint32_t *snp_pos;      /* [S] */
+    const double   *snp_baf, *snp_pfb;           /* [S] */
+} csv_cn_regions;
+/* The seam for tests and integrators: obs_off[R + 1] and, for region r at [obs_off[r], obs_off[r+1]), the observations in the order the
+ * reference's unordered_map<std::string,double> of "ws-we" keys iterates its windows (a libstdc++ container: the order is replayed from the
+ * library's own rehash policy and std::hash<std::string>): per window in that order the region's SNPs inside [ws, we], both ends inclusive,
+ * else one dummy observation (pos = (ws + we) / 2, baf = -1, pfb = 0.5, is_snp = 0); log2_cov is the window's — of the LAST window with that
+ * key. *n_obs: in, the capacity of the five arrays in observations; out, the exact count (never above sum of windows + 3 S).
+ * CSV_ECAPACITY (obs_off and the arrays untouched, *n_obs set): the capacity is too small — call again with room for *n_obs.
+ * CSV_EINVAL (nothing written): a null array, offsets not starting at 0 or not ascending, sample_size <= 0, start > end, a region's end at or
+ * above 2^31 - 1 (a window coordinate could reach 2^31: the reference parses its keys back with std::stoi), SNP positions decreasing inside a
+ * region, more than 5087 windows in a region, 2^32 - 1 or more windows, records or observations in all, a split order pending on the context.
+ * One page-locked block each way; R == 0 is valid. */
+int csvgpu_cn_observations_resident_many(csv_ctx *ctx, const csv_cn_regions *regions, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb,
+                                         double *log2_cov, uint8_t *is_snp, uint64_t *n_obs);
+/* The product path: windows -> observations -> emissions -> Viterbi without a return to the host in between (csvgpu_viterbi on o1 = log2_cov,
+ * o2 = baf, pfb, seq_off = obs_off, bit for bit). Returns obs_off, pos, states[n_obs], loglik[R]; baf / pfb / log2_cov / is_snp only where
+ * the pointer is not NULL. *n_obs, CSV_ECAPACITY and CSV_EINVAL as above. One 8-byte readback of the count sizes the Viterbi workspace,
+ * then one wait. */
+int csvgpu_cn_decode_resident_many(csv_ctx *ctx, const csv_cn_regions *regions, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos,
+                                   int32_t *states, double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs);
+
 /* depth_out[i] = depth[pos[i]] on the depth map resident in `shard`, or -1 where pos[i] >= depth_len: the VCF writer's
  * SUPPORT / DP lookups (SVCaller::getReadDepth, sv_caller.cpp:1332-1344, called at :1306) without moving the map. */
 int csvgpu_depth_lookup_resident(csv_ctx *ctx, csv_shard *shard, const uint32_t *pos, uint64_t n, int32_t *depth_out);

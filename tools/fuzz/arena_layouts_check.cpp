@@ -99,6 +99,17 @@ int main()
             { ReadsWs w; run_case(tag("reads", {n, m}), [&](Arena &a) { return carve_reads(a, n, m, w); }); }
             { SplitNodesWs w; run_case(tag("split_nodes", {n, m}), [&](Arena &a) { return carve_split_nodes(a, n, m, w); }); }
             { WindowWs w; run_case(tag("window", {n, m}), [&](Arena &a) { return carve_window(a, n, m, w); }); }
+            for (int dec : {0, 1}) {   // n regions, m windows; shards and SNP records run along
+                CnWs w;
+                const uint64_t n_sh = n % 5 + 1, S = (n + m) % 1009;
+                run_case(tag("cn_obs", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_obs(a, n, m, n_sh, S, dec != 0, w); }, [&](char *, char *) {
+                    const CnInLayout L(n, n_sh, S);
+                    const size_t at[] = {L.rs, L.re, L.ss, L.wo, L.wbase, L.soff, L.spos, L.sbaf, L.spfb, L.small, L.big, L.bytes};
+                    const size_t need[] = {n * 4, n * 4, n * 4, (n + n_sh) * 8, (n + 1) * 4, (n + 1) * 4, S * 4, S * 8, S * 8, n * 4, n * 4};
+                    for (int i = 0; i < 11; i++) if (at[i] % 256 || at[i] + need[i] > at[i + 1]) return false;
+                    return true;
+                });
+            }
             { SplitTablesOut w; run_case(tag("sr_tables", {n, m}), [&](Arena &a) { return sr_carve(a, n, m, w); }); }
             for (int with : {0, 1}) { SplitFitsIn w; run_case(tag("sf_tables", {n, m, (uint64_t)with}), [&](Arena &a) { return carve_sf_tables(a, n, m, with != 0, w); }); }
             {   // n members in m segments; the block cleared by one memset holds six sub-slices
@@ -137,7 +148,7 @@ int main()
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
     const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
-                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
+                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
         const auto it = n_counts.find(kv.first);
