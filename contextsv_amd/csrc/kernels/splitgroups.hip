@@ -335,7 +335,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_offsets_kernel(const uint32_t *
     } else if (t == n) {
         group_off[goff[n]] = *total;
         // (both give-up flags are exactly 1 — sg_seeds ORs 1 into *err, a onesweep pass stores 1 —, so that the value 2 in this word stays the table
-        // kernel's domain bit, SG_ERR_DOMAIN in csvgpu.hip, which sg_wait tells apart)
+        // kernel's domain bit, SG_ERR_DOMAIN in api/split_fits.hip, which sg_wait tells apart)
         res[0] = *total; res[1] = goff[n]; res[2] = (uint64_t)(*err | (sort_err ? *sort_err : 0u));
     } else if (t - n - 1 <= n_seg) {
         const uint64_t c = t - n - 1;

@@ -1,5 +1,5 @@
 // layouts.hpp — every device workspace layout of the library as one carve function over an Arena (arena.hpp). The entry points in
-// csvgpu.hip and the launchers in kernels/ reserve by planning these and then carve with them; nothing else says how large a workspace
+// api/*.hip and the launchers in kernels/ reserve by planning these and then carve with them; nothing else says how large a workspace
 // is. Pads that a kernel relies on are part of their slice and are named where they are taken. Free of HIP calls: the CPU-only check
 // (tools/fuzz/arena_layouts_check.cpp) runs every function listed in kLayoutNames at the rounding edges.
 #pragma once

@@ -77,9 +77,9 @@ RETIRED_DEVICE_SWITCHES = ("CSV_SCAN_FORM", "CSV_SORT_ONESWEEP", "CSV_DBSCAN_SMA
 
 def test_device_library_reads_no_environment():
     csrc = os.path.join(ROOT, "contextsv_amd", "csrc")
-    files = [os.path.join(csrc, f) for f in ("csvgpu.hip", "common.hpp", "devutil.hpp")]
-    files += [os.path.join(csrc, "kernels", f) for f in sorted(os.listdir(os.path.join(csrc, "kernels")))]
-    assert len(files) >= 10
+    files = [os.path.join(d, f) for d in (csrc, os.path.join(csrc, "api"), os.path.join(csrc, "kernels")) for f in sorted(os.listdir(d))
+             if f.endswith((".hip", ".hpp"))]
+    assert len(files) >= 25 and os.path.join(csrc, "api", "job.hip") in files and os.path.join(csrc, "kernels", "scan.hip") in files
     for f in files:
         txt = open(f, errors="ignore").read()
         assert "getenv" not in txt and not [s for s in RETIRED_DEVICE_SWITCHES if s in txt], f
@@ -98,8 +98,9 @@ def test_product_package_does_not_touch_the_oracle():
 
 
 def test_testhooks_build_exports_the_same_abi_plus_the_hook():
-    """libcsvgpu_testhooks.so (csvgpu.hip with -DCSV_TEST_HOOKS; loaded only by tests/test_gpu_job_errors.py and
-    tests/test_gpu_sort_primitives.py) = the product ABI + the hooks: the allocation failure and the four on the device primitives."""
+    """libcsvgpu_testhooks.so (the product library's own objects, with csrc/api/testhooks.hip linked in the place of nohooks.hip; loaded only by
+    tests/test_gpu_job_errors.py and tests/test_gpu_sort_primitives.py) = the product ABI + the hooks: the allocation failure and the four
+    on the device primitives."""
     from contextsv_amd import _lib
     lib = C.CDLL(os.path.join(ROOT, "contextsv_amd", "lib", "libcsvgpu_testhooks.so"))
     for n in _declared():

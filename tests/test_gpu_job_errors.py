@@ -72,7 +72,7 @@ def test_signature_buffer_growth(ctx, oracle):
 
 
 def test_injected_allocation_failure_in_the_testhooks_build():
-    """The allocation-failure hook lives in libcsvgpu_testhooks.so only (csvgpu.hip with -DCSV_TEST_HOOKS): a child process loads that build
+    """The allocation-failure hook lives in libcsvgpu_testhooks.so only (csrc/api/testhooks.hip, linked there in the place of nohooks.hip): a child process loads that build
     (CSVGPU_LIB) and runs the scenario — the larger signature buffer cannot be had, the shard keeps a usable buffer + capacity pair, the
     next job succeeds with the oracle's signatures."""
     import os, subprocess, sys
