@@ -67,6 +67,15 @@ class csv_split_refs(C.Structure):
                 ("supp_where", C.c_void_p)]
 
 
+class csv_bgzf_block(C.Structure):
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32), ("crc32", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+# the same 32 bytes as a numpy record
+BGZF_BLOCK_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
+
+
 class csv_cn_regions(C.Structure):
     _fields_ = [("n_shards", C.c_int32), ("shards", C.c_void_p), ("mean_cov", C.c_void_p), ("reg_off", C.c_void_p), ("region_start", C.c_void_p),
                 ("region_end", C.c_void_p), ("sample_size", C.c_void_p), ("snp_off", C.c_void_p), ("snp_pos", C.c_void_p), ("snp_baf", C.c_void_p),
@@ -124,6 +133,8 @@ ABI = {
     "csvgpu_split_resident_fits": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_cn_observations_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_cn_decode_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), C.POINTER(csv_hmm), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_bgzf_inflate": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
+    "csvgpu_bgzf_inflate_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

@@ -130,6 +130,7 @@ class Context:
 
     def __init__(self, device: int = 0, stream: int | None = None, background: bool = False):
         self.lib = _lib.load()
+        self.device = device
         self.h = self.lib.csvgpu_create_background(device) if background else self.lib.csvgpu_create(device, stream)
         if not self.h:
             msg = self.lib.csvgpu_last_error(None)
@@ -427,6 +428,35 @@ class Context:
         if want_observations:
             out.update(baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
         return out
+
+    # -------------------------------------------------------------------------------- BGZF members
+    def bgzf_inflate(self, comp, blocks, out):
+        """csvgpu_bgzf_inflate: the members `blocks` (_lib.BGZF_BLOCK_DTYPE records) of the compressed bytes `comp` (uint8) inflated on the
+        device into `out` (uint8, written in place, only inside the decoded members' ranges). -> (number of declined members, status bytes:
+        0 decoded and CRC-checked, 1 declined — decode that member on the host)."""
+        comp, blocks = np.ascontiguousarray(comp, np.uint8), np.ascontiguousarray(blocks, _lib.BGZF_BLOCK_DTYPE)
+        if out.dtype != np.uint8 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError("bgzf_inflate: out must be a writeable contiguous uint8 array")
+        status = np.full(max(len(blocks), 1), 0xFF, np.uint8)
+        rc = self.lib.csvgpu_bgzf_inflate(self.h, ptr(comp), len(comp), ptr(blocks), len(blocks), ptr(out), len(out), ptr(status))
+        if rc < 0:
+            self._check(rc)
+        return rc, status[: len(blocks)]
+
+    def bgzf_inflate_dev(self, d_comp, blocks, d_out, d_status) -> int:
+        """csvgpu_bgzf_inflate_dev: the same with comp / out / status as uint8 torch tensors on this context's device; the decoded bytes stay
+        there. -> number of declined members."""
+        blocks = np.ascontiguousarray(blocks, _lib.BGZF_BLOCK_DTYPE)
+        for t in (d_comp, d_out, d_status):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 1:
+                raise ValueError("bgzf_inflate_dev: contiguous uint8 device tensors expected")
+        if d_status.numel() < len(blocks):
+            raise ValueError("bgzf_inflate_dev: status shorter than the member table")
+        rc = self.lib.csvgpu_bgzf_inflate_dev(self.h, d_comp.data_ptr(), d_comp.numel(), ptr(blocks), len(blocks), d_out.data_ptr(), d_out.numel(),
+                                              d_status.data_ptr())
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):

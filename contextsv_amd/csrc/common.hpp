@@ -378,6 +378,10 @@ void launch_cn_order(hipStream_t s, const uint32_t *ws, const uint32_t *we, cons
                      const uint32_t *regions_small, uint32_t n_small, const uint32_t *regions_big, uint32_t n_big, const CnEpochs &ep, const CnSlots &out);
 void launch_cn_fill(hipStream_t s, const CnSlots &sl, uint32_t n_slots, uint32_t n_regions, const uint32_t *obs_off32, const uint32_t *ws, const uint32_t *we,
                     const double *l2, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const CnObs &o);
+// inflate.hip — BGZF members (raw DEFLATE + CRC-32), one wave per member: status[i] = 0 decoded and written, 1 declined (nothing written);
+// *n_declined (zeroed by the caller) counts the declined ones
+void launch_bgzf_inflate(hipStream_t s, const uint8_t *comp, const csv_bgzf_block *blocks, uint32_t n_blocks, uint8_t *out, uint8_t *status,
+                         unsigned int *n_declined);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

@@ -248,7 +248,9 @@ bool BamReader::stream(uint64_t start_voffset, const BamReadOptions &opt, const 
         b.next_coff = coff;
         b.head = head;
         b.data.resize_uninit(head + total);
-        if (!bgzf::inflate_range(file.data(), b.blocks, 0, b.blocks.size(), b.data.data() + head, opt.threads, &b.err)) b.ok = false;
+        const bool ok = opt.device_inflate ? bgzf::inflate_range_device(opt.device_inflate, file.data(), b.blocks, 0, b.blocks.size(), b.data.data() + head, opt.threads, &b.err)
+                                           : bgzf::inflate_range(file.data(), b.blocks, 0, b.blocks.size(), b.data.data() + head, opt.threads, &b.err);
+        if (!ok) b.ok = false;
     };
     Batch batch[2];
     uint64_t coff = start_voffset >> 16;

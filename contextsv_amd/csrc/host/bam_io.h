@@ -47,6 +47,9 @@ struct BamReadOptions {
     bool want_qnames = false;
     int threads = 8;                                  // inflate threads (hts_set_threads)
     uint32_t window_blocks = 2048;                    // BGZF blocks inflated per batch (<= 128 MiB of records)
+    csv_ctx *device_inflate = nullptr;                // not null: the batches are inflated on this context's device (bgzf::inflate_range_device), whatever it
+                                                      // declines on the host. The batches are loaded on a thread of their own, so the context is the reader's
+                                                      // own, never one that runs anything else meanwhile. Null: the host's decoders. Same records either way.
 };
 
 class BamReader {

@@ -1,6 +1,8 @@
 #include "bgzf.h"
 #include "fast_inflate.h"
 
+#include "../../../include/csvgpu.h"
+
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -120,6 +122,69 @@ bool inflate_range(const uint8_t *file, const std::vector<Block> &blocks, size_t
             if (i >= last || failed.load(std::memory_order_relaxed)) return;
             std::string e;
             if (!z.run(file, blocks[i], dst + uoff[i - first], &e)) {
+                failed = true;
+                if (!err_lock.test_and_set()) first_err = e;
+                return;
+            }
+        }
+    };
+    if (nt == 1) work();
+    else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nt; t++) pool.emplace_back(work);
+        for (auto &t : pool) t.join();
+    }
+    if (failed) { set(err, first_err); return false; }
+    return true;
+}
+
+// Weak: a program that links this file without the device library (the thread-sanitizer build of the pools) has no device route.
+extern "C" __attribute__((weak)) int csvgpu_bgzf_inflate(csv_ctx *ctx, const uint8_t *comp, uint64_t comp_len, const csv_bgzf_block *blocks, uint32_t n_blocks,
+                                                         uint8_t *out, uint64_t out_len, uint8_t *status);
+extern "C" __attribute__((weak)) const char *csvgpu_last_error(const csv_ctx *ctx);
+
+bool inflate_range_device(csv_ctx *ctx, const uint8_t *file, const std::vector<Block> &blocks, size_t first, size_t last, uint8_t *dst, int threads, std::string *err)
+{
+    if (first >= last) return true;
+    if (!ctx || !csvgpu_bgzf_inflate || !csvgpu_last_error) { set(err, "BGZF: no device to inflate on"); return false; }
+    const size_t n = last - first;
+    const uint64_t base = blocks[first].coffset;
+    std::vector<csv_bgzf_block> tab(n);
+    uint64_t acc = 0;
+    for (size_t i = 0; i < n; i++) {
+        const Block &b = blocks[first + i];
+        if (b.coffset < base || b.csize < (uint32_t)b.data_off + 8) { set(err, "BGZF: block table out of order at offset " + std::to_string(b.coffset)); return false; }
+        csv_bgzf_block &t = tab[i];
+        t.in_off = b.coffset - base + b.data_off;
+        t.in_len = b.csize - b.data_off - 8;
+        t.out_off = acc;
+        t.out_len = b.isize;
+        t.crc32 = le32(file + b.coffset + b.csize - 8);
+        t.reserved = 0;
+        acc += b.isize;
+    }
+    const uint64_t span = blocks[last - 1].coffset + blocks[last - 1].csize - base;
+    std::vector<uint8_t> status(n, 1);
+    // (an empty range of output — EOF markers only — still goes through the call: the device checks those members, too)
+    uint8_t none = 0;
+    const int rc = csvgpu_bgzf_inflate(ctx, file + base, span, tab.data(), (uint32_t)n, acc ? dst : &none, acc ? acc : 1, status.data());
+    if (rc < 0) { set(err, std::string("BGZF: device inflate failed: ") + csvgpu_last_error(ctx)); return false; }
+    if (rc == 0) return true;
+    // the declined blocks on the host, as inflate_range runs all of them
+    std::vector<size_t> todo;
+    for (size_t i = 0; i < n; i++) if (status[i]) todo.push_back(i);
+    const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), todo.size()));
+    std::atomic<size_t> next{0};
+    std::atomic<bool> failed{false};
+    std::string first_err;
+    std::atomic_flag err_lock = ATOMIC_FLAG_INIT;
+    auto work = [&] {
+        Inflater z;
+        for (;;) {
+            const size_t k = next.fetch_add(1);
+            if (k >= todo.size() || failed.load(std::memory_order_relaxed)) return;
+            std::string e;
+            if (!z.run(file, blocks[first + todo[k]], dst + tab[todo[k]].out_off, &e)) {
                 failed = true;
                 if (!err_lock.test_and_set()) first_err = e;
                 return;

@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+struct csv_ctx;
+
 namespace bgzf {
 
 constexpr uint32_t kMaxBlock = 0x10000;      // both compressed and uncompressed block sizes are <= 64 KiB
@@ -33,6 +35,12 @@ bool inflate_block(const uint8_t *file, const Block &b, uint8_t *dst, std::strin
 
 // Inflate blocks[first..last) into dst (back to back) with up to `threads` threads.
 bool inflate_range(const uint8_t *file, const std::vector<Block> &blocks, size_t first, size_t last, uint8_t *dst, int threads, std::string *err);
+
+// The same through csvgpu_bgzf_inflate on `ctx` (one call for the range: blocks[first..last) are back to back in the file, as scan_blocks and
+// the reader's batches lay them out). Every block the device declines goes through inflate_block on up to `threads` threads — the fast
+// decoder, then zlib, the CRC behind either — so a corrupt file fails with the same message as inflate_range. `ctx` must not be in use by
+// another thread during the call.
+bool inflate_range_device(csv_ctx *ctx, const uint8_t *file, const std::vector<Block> &blocks, size_t first, size_t last, uint8_t *dst, int threads, std::string *err);
 
 // Read-only memory map of a file.
 class MappedFile {

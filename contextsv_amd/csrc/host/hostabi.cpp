@@ -1001,7 +1001,11 @@ int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fas
 }
 
 // ---- BAM / BAI reader and writer (bam_io) --------------------------------------------------------------
-struct csvhost_bam { BamReader r; std::vector<BamShard> shards; std::string names; };
+struct csvhost_bam {
+    BamReader r; std::vector<BamShard> shards; std::string names;
+    csv_ctx *inflate_ctx = nullptr;          // csvhost_bam_set_device_inflate: the reader's own context
+    ~csvhost_bam() { if (inflate_ctx) csvgpu_destroy(inflate_ctx); }
+};
 
 csvhost_bam *csvhost_bam_open(const char *path, int load_index)
 {
@@ -1016,6 +1020,50 @@ const char *csvhost_bam_names(const csvhost_bam *h) { return h->names.c_str(); }
 const char *csvhost_bam_text(const csvhost_bam *h) { return h->r.header().text.c_str(); }
 uint32_t csvhost_bam_ref_len(const csvhost_bam *h, int tid) { return h->r.header().lens[(size_t)tid]; }
 
+// device >= 0: the reads that follow inflate the BGZF blocks on that device, on a context of the handle's own (BamReadOptions::device_inflate);
+// -1: on the host again. 0, or -1 with the reason in csvhost_last_error.
+int csvhost_bam_set_device_inflate(csvhost_bam *h, int device_or_minus_1)
+{
+    try {
+        if (h->inflate_ctx) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; }
+        if (device_or_minus_1 < 0) return 0;
+        h->inflate_ctx = csvgpu_create(device_or_minus_1, nullptr);
+        if (!h->inflate_ctx) { g_err = std::string("no device context for the BAM reader: ") + csvgpu_last_error(nullptr); return -1; }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// Every BGZF block of a file inflated in batches of window_blocks, on `threads` host threads (ctx null: bgzf::inflate_range) or on ctx's device
+// (bgzf::inflate_range_device), into one buffer that is reused: what tools/bench_inflate.py times. *ms: the inflate alone (the block scan before it).
+int csvhost_bgzf_inflate_file(const char *path, int threads, csv_ctx *ctx, uint32_t window_blocks, uint64_t *n_blocks, uint64_t *in_bytes, uint64_t *out_bytes, double *ms)
+{
+    GUARD({
+        bgzf::MappedFile f;
+        std::string e;
+        if (!f.open(path, &e)) throw std::runtime_error(e);
+        std::vector<bgzf::Block> blocks;
+        if (!bgzf::scan_blocks(f.data(), f.size(), 0, blocks, &e)) throw std::runtime_error(e);
+        const size_t W = std::max<uint32_t>(window_blocks, 1);
+        uint64_t largest = 0, total = 0;
+        for (size_t i = 0; i < blocks.size(); i += W) {
+            uint64_t acc = 0;
+            for (size_t k = i; k < std::min(blocks.size(), i + W); k++) acc += blocks[k].isize;
+            largest = std::max(largest, acc); total += acc;
+        }
+        HugeVec<uint8_t> buf;
+        buf.resize_uninit(largest + 1);
+        memset(buf.data(), 0, largest + 1);                           // pages touched before the clock starts
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t i = 0; i < blocks.size(); i += W) {
+            const size_t last = std::min(blocks.size(), i + W);
+            const bool ok = ctx ? bgzf::inflate_range_device(ctx, f.data(), blocks, i, last, buf.data(), threads, &e) : bgzf::inflate_range(f.data(), blocks, i, last, buf.data(), threads, &e);
+            if (!ok) throw std::runtime_error(e);
+        }
+        *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *n_blocks = blocks.size(); *in_bytes = f.size(); *out_bytes = total;
+    })
+}
+
 // chr != nullptr: readContig (needs the index) -> one shard; chr == nullptr: readAll -> one shard per contig with records.
 // Returns the number of shards now held by the handle (replacing the previous ones), or -1.
 int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qnames, int threads, uint32_t window_blocks, uint64_t *n_unplaced)
@@ -1024,6 +1072,7 @@ int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qna
         BamReadOptions opt;
         opt.want_seq = want_seq != 0; opt.want_qnames = want_qnames != 0; opt.threads = threads;
         if (window_blocks) opt.window_blocks = window_blocks;
+        opt.device_inflate = h->inflate_ctx;
         h->shards.clear();
         bool ok;
         if (chr) { h->shards.emplace_back(); ok = h->r.readContig(chr, opt, h->shards.back()); }
@@ -1153,7 +1202,7 @@ struct csvhost_bam_stats { uint64_t n_contigs, n_reads, n_cigar, bam_bytes; doub
 // SVCaller::runBam: chrs = '\n'-separated contig names or null (all). SNPs: none (every window gets the dummy observation).
 // Calls come back grouped by contig in header order, with their contig index in out_tid.
 int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int threads, const csv_hmm *hmm, double eps, double min_pts_pct,
-                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
+                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv; 9-13, 24-30: below */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
                     const char *file_date, csvhost_call *out, int32_t *out_tid, uint64_t cap, uint64_t *n_out, csvhost_bam_stats *stats,
                     const char *snp_vcf, const char *pfb_table, const char *ethnicity)
 {
@@ -1166,6 +1215,10 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         }
         RunParams P; P.dbscan_epsilon = eps; P.dbscan_min_pts_pct = min_pts_pct; P.sample_size = sample_size; P.min_cnv_length = min_cnv;
         P.split_svs = (passes & 1) != 0; P.cigar_cn = (passes & 2) != 0; P.save_cnv = (passes & 4) != 0;
+        // the opt-in device forms, as csvhost_run numbers them; bit 13: the BAM inflated on the device, whose index is in bits 24-30
+        P.split_groups_on_device = (passes & 512) != 0; P.split_fits_on_device = (passes & 1024) != 0; P.split_tables_on_device = (passes & 2048) != 0;
+        P.cn_observations_on_device = (passes & 4096) != 0;
+        P.inflate_on_device = (passes & 8192) != 0; P.inflate_device = (passes >> 24) & 0x7f;
         P.snp_vcf = snp_vcf ? snp_vcf : ""; P.pfb_table = pfb_table ? pfb_table : ""; P.ethnicity = ethnicity ? ethnicity : "";
         if (fasta && vcf_dir) {
             P.ref_genome = fasta_genome(fasta);

@@ -1206,6 +1206,10 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
                       std::unordered_map<std::string, std::vector<SVCall>> &whole_genome_sv_calls, BamRunStats *bam_stats)
 {
     const double t0 = now_ms();
+    // With RunParams::inflate_on_device the reader inflates one contig ahead on a thread of its own, beside this run on the device: its context is
+    // its own (two threads must not share one), on the same device, for the length of the run — declared in front of the source, so that it
+    // outlives a read that is still in flight when the source goes.
+    struct OwnCtx { csv_ctx *c = nullptr; ~OwnCtx() { if (c) csvgpu_destroy(c); } } inflate_ctx;
     BamSource src;
     if (!src.reader.open(bam_path)) throw std::runtime_error("ERROR failed to open BAM file " + bam_path + ": " + src.reader.error());
     if (!src.reader.loadIndex()) throw std::runtime_error("ERROR failed to load index for " + bam_path);
@@ -1218,6 +1222,11 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
         }
     }
     src.opt.threads = std::max(1, threads);
+    if (P.inflate_on_device) {
+        inflate_ctx.c = csvgpu_create(P.inflate_device, nullptr);
+        if (!inflate_ctx.c) throw std::runtime_error(std::string("ERROR: no device context for the BAM reader: ") + csvgpu_last_error(nullptr));
+        src.opt.device_inflate = inflate_ctx.c;
+    }
     SNPFile snp_file;
     AlleleFreqFiles af_files;
     if (!P.snp_vcf.empty()) {

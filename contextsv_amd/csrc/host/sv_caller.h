@@ -111,6 +111,9 @@ struct RunParams {
     bool cn_observations_on_device = false; // the copy-number passes' observation vectors built on the device from the window kernel's output and decoded there
                                             // (csvgpu_cn_decode_resident_many) instead of windows back, assembleRegion on the pool and observations up again; the
                                             // calls do not depend on it
+    bool inflate_on_device = false;         // runBam: the BAM's BGZF blocks inflated on the device (csvgpu_bgzf_inflate on a context of the reader's own, created on
+    int inflate_device = 0;                 // device `inflate_device` — the run's — for the run's length) instead of on the host's threads; whatever the device declines is
+                                            // decoded on the host, every block is CRC-checked either way; the records, and so the calls, do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it

@@ -10,7 +10,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "bgzf", "dbscan_tmp", "viterbi_tmp"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -228,6 +228,16 @@ static inline bool carve_cn_obs(Arena &a, uint64_t R, uint64_t W, uint64_t n_sha
                     take(a, w.o.log2_cov, bound * 8 + 8) && take(a, w.o.is_snp, bound);
     if (!decode) return ok;
     return ok && take(a, w.states, bound * 4 + 8) && take(a, w.loglik, R * 8);
+}
+
+// BGZF members inflated on the device (csvgpu_bgzf_inflate / _dev): the member table and the count of declined members, and for the
+// host-pointer form (io) the compressed bytes, the decoded bytes and the status bytes
+struct BgzfWs { csv_bgzf_block *blocks = nullptr; unsigned int *n_declined = nullptr; uint8_t *comp = nullptr, *out = nullptr, *status = nullptr; };
+static inline bool carve_bgzf(Arena &a, uint64_t n_blocks, bool io, uint64_t comp_len, uint64_t out_len, BgzfWs &w)
+{
+    const bool ok = take(a, w.blocks, n_blocks * sizeof(csv_bgzf_block)) && take(a, w.n_declined, 256);
+    if (!io) return ok;
+    return ok && take(a, w.comp, comp_len) && take(a, w.out, out_len) && take(a, w.status, n_blocks);
 }
 
 // ---- the kernels' own temporaries (one opaque `tmp` to their callers) ----------------------------------------------------------------

@@ -103,6 +103,8 @@ def load() -> C.CDLL:
     lib.csvhost_bam_ref_len.restype = C.c_uint32
     lib.csvhost_bam_ref_len.argtypes = [_P, C.c_int]
     lib.csvhost_bam_read.argtypes = [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
+    lib.csvhost_bam_set_device_inflate.argtypes = [_P, C.c_int]
+    lib.csvhost_bgzf_inflate_file.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     lib.csvhost_bam_shard.argtypes = [_P, C.c_int, C.POINTER(_lib.csv_reads), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P)]
     lib.csvhost_bam_shard_qnames.restype = C.c_int64
     lib.csvhost_bam_shard_qnames.argtypes = [_P, C.c_int, _P, C.c_uint64]
@@ -738,6 +740,7 @@ class BamFile:
     {tid, name, target_len, reads: Reads, seq_off, seq, qnames}."""
 
     def __init__(self, path: str, load_index: bool = True):
+        self._inflate_device = -1
         self.h = load().csvhost_bam_open(os.fsencode(path), int(load_index))
         if not self.h:
             raise RuntimeError((load().csvhost_last_error() or b"cannot open BAM").decode())
@@ -776,18 +779,37 @@ class BamFile:
             out["qnames"] = buf.raw[:ln].decode(errors="replace").split("\n")[:-1]
         return out
 
-    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0):
+    def _inflate_on(self, on, device):
+        """where the next read inflates the BGZF blocks: on `device` (a context of the reader's own; what the device declines is decoded on
+        the host, every block CRC-checked either way) or on the host's threads"""
+        want = int(device) if on else -1
+        if want != self._inflate_device:
+            if load().csvhost_bam_set_device_inflate(self.h, want) != 0:
+                raise RuntimeError((load().csvhost_last_error() or b"no device context for the BAM reader").decode())
+            self._inflate_device = want
+
+    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0):
+        self._inflate_on(inflate_on_device, device)
         k = load().csvhost_bam_read(self.h, chr.encode(), int(want_seq), int(want_qnames), threads, window_blocks, None)
         if k < 0:
             raise RuntimeError((load().csvhost_last_error() or b"BAM read failed").decode())
         return self._shard(0, want_seq, want_qnames)
 
-    def read_all(self, want_seq=False, want_qnames=False, threads=8, window_blocks=0):
+    def read_all(self, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0):
+        self._inflate_on(inflate_on_device, device)
         un = C.c_uint64(0)
         k = load().csvhost_bam_read(self.h, None, int(want_seq), int(want_qnames), threads, window_blocks, C.byref(un))
         if k < 0:
             raise RuntimeError((load().csvhost_last_error() or b"BAM read failed").decode())
         return [self._shard(i, want_seq, want_qnames) for i in range(k)], un.value
+
+
+def bgzf_inflate_file(path: str, threads: int = 16, ctx: "Context | None" = None, window_blocks: int = 2048) -> dict:
+    """Every BGZF block of a file inflated in batches, on the host's threads (ctx None) or on ctx's device (what the device declines on the
+    host) -> dict(n_blocks, in_bytes, out_bytes, ms): the inflate alone, for tools/bench_inflate.py."""
+    nb, ib, ob, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+    _check(load().csvhost_bgzf_inflate_file(os.fsencode(path), threads, ctx.h if ctx is not None else None, window_blocks, C.byref(nb), C.byref(ib), C.byref(ob), C.byref(ms)))
+    return {"n_blocks": nb.value, "in_bytes": ib.value, "out_bytes": ob.value, "ms": ms.value}
 
 
 def write_bam(path: str, ref_names, ref_lens, tid, reads: Reads, qnames, seq_off=None, seq=None, l_seq=None, text="", level=1, threads=4):
@@ -808,14 +830,19 @@ def write_bam(path: str, ref_names, ref_lens, tid, reads: Reads, qnames, seq_off
 
 def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, save_cnv=False,
             genome: ReferenceGenome | None = None, vcf_dir=None, gap_path=None, file_date=None, capacity: int = 1 << 20,
-            snp_vcf=None, pfb_table=None, ethnicity=""):
-    """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict)."""
+            snp_vcf=None, pfb_table=None, ethnicity="", inflate_on_device: bool = False, split_groups_on_device: bool = False, split_fits_on_device: bool = False,
+            split_tables_on_device: bool = False, cn_observations_on_device: bool = False):
+    """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict).
+    inflate_on_device: the BAM's BGZF blocks are inflated on ctx's device (csvgpu_bgzf_inflate, on a context of the reader's own) instead of
+    on the host's threads; the other switches as in run(). None of them changes the calls."""
+    opt_in = (int(bool(split_groups_on_device)) << 9) | (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | \
+             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
     out = np.zeros(capacity, CALL_DTYPE)
     tid = np.zeros(capacity, np.int32)
     n = C.c_uint64(0)
     st = bam_stats()
     _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm), eps,
-                                  min_pts_pct, sample_size, min_cnv, int(split_svs) | (int(cigar_cn) << 1) | (int(save_cnv) << 2), genome.h if genome is not None and vcf_dir else None,
+                                  min_pts_pct, sample_size, min_cnv, int(split_svs) | (int(cigar_cn) << 1) | (int(save_cnv) << 2) | opt_in, genome.h if genome is not None and vcf_dir else None,
                                   os.fsencode(vcf_dir) if vcf_dir else None, os.fsencode(gap_path) if gap_path else None,
                                   file_date.encode() if file_date else None, out.ctypes.data, tid.ctypes.data, capacity, C.byref(n), C.byref(st),
                                   os.fsencode(snp_vcf) if snp_vcf else None, os.fsencode(pfb_table) if pfb_table else None, ethnicity.encode()))

@@ -519,6 +519,36 @@ int csvgpu_viterbi_dev(csv_ctx *ctx, const csv_hmm *hmm, const double *d_o1, con
                        const double *d_pfb, const uint64_t *d_seq_off, uint64_t n_seq,
                        uint64_t n_obs, int32_t *d_states, double *d_loglik);
 
+/* ------------------------------------------------------------------------------------------ */
+/* BGZF members inflated on the device (opt-in: the from-file path decodes on the host by default) */
+/* One member (SAMv1 §4.1): the raw DEFLATE stream comp[in_off .. in_off + in_len), which decodes to out_len bytes at out[out_off ..] whose
+ * CRC-32 (the member's trailer) is crc32. in_len and out_len are at most 65536. */
+typedef struct csv_bgzf_block {
+    uint64_t in_off;
+    uint64_t out_off;
+    uint32_t in_len;
+    uint32_t out_len;
+    uint32_t crc32;
+    uint32_t reserved;
+} csv_bgzf_block;  /* 32 bytes */
+
+/* Inflates n_blocks members. status[i] = 0: member i decoded to exactly out_len bytes, its stream was consumed to the last byte (only
+ * that byte's padding bits left) and the CRC-32 of the bytes equals crc32 — the bytes are in place. status[i] = 1: declined — the bytes
+ * at out_off are unspecified and the caller decodes the member itself (zlib). The decoder declines whatever it does not recognise as a
+ * plain, well-formed stream of exactly the announced sizes, so the result never depends on it being right about a corner of the format;
+ * whatever the input, it reads nothing outside [in_off, in_off + in_len) and writes nothing outside [out_off, out_off + out_len).
+ * Returns the number of declined members (>= 0), or a CSV_E* code: CSV_EINVAL for a null pointer, a member whose ranges leave
+ * comp_len / out_len, in_len or out_len above 65536, or output ranges that overlap in the order given (out_off may not decrease).
+ * n_blocks == 0 does nothing and returns 0. Timed under CSV_K_MISC.
+ * Host pointers: the compressed bytes travel up and the decoded bytes and status back through the context's page-locked block, in pieces
+ * (comp may be a mapped file). */
+int csvgpu_bgzf_inflate(csv_ctx *ctx, const uint8_t *comp, uint64_t comp_len, const csv_bgzf_block *blocks, uint32_t n_blocks,
+                        uint8_t *out, uint64_t out_len, uint8_t *status);
+/* Device pointers for comp / out / status (blocks from the host): the decoded bytes stay on the device — the seam for a later
+ * record-unpacking kernel. Waits for the kernel (the return value is its count of declined members). */
+int csvgpu_bgzf_inflate_dev(csv_ctx *ctx, const uint8_t *d_comp, uint64_t comp_len, const csv_bgzf_block *blocks, uint32_t n_blocks,
+                            uint8_t *d_out, uint64_t out_len, uint8_t *d_status);
+
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
  * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster). */
