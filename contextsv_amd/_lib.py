@@ -76,6 +76,23 @@ class csv_bgzf_block(C.Structure):
 BGZF_BLOCK_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])
 
 
+class csv_bam_out(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("flag", C.c_void_p), ("mapq", C.c_void_p), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p), ("seq_off", C.c_void_p),
+                ("seq", C.c_void_p), ("name_off", C.c_void_p), ("name", C.c_void_p), ("name_hash", C.c_void_p), ("cap_records", C.c_uint64),
+                ("cap_cigar", C.c_uint64), ("cap_seq", C.c_uint64), ("cap_name", C.c_uint64)]
+
+
+class csv_bam_counts(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("kept_first", C.c_uint64), ("n_kept", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq", C.c_uint64),
+                ("n_name", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint64), ("stopped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# csv_bam_counts::status: (offset << 8) | reason
+BAM_SHORT, BAM_LONG, BAM_NEG_LSEQ, BAM_FIELDS, BAM_ANCHOR = 1, 2, 3, 4, 5
+BAM_REASONS = {1: "record shorter than its fixed fields", 2: "implausible record length", 3: "negative sequence length",
+               4: "record fields exceed the record length", 5: "anchor missed"}
+
+
 class csv_cn_regions(C.Structure):
     _fields_ = [("n_shards", C.c_int32), ("shards", C.c_void_p), ("mean_cov", C.c_void_p), ("reg_off", C.c_void_p), ("region_start", C.c_void_p),
                 ("region_end", C.c_void_p), ("sample_size", C.c_void_p), ("snp_off", C.c_void_p), ("snp_pos", C.c_void_p), ("snp_baf", C.c_void_p),
@@ -135,11 +152,18 @@ ABI = {
     "csvgpu_cn_decode_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), C.POINTER(csv_hmm), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_bgzf_inflate": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "csvgpu_bgzf_inflate_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
+    "csvgpu_bam_unpack": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(csv_bam_out),
+                                    C.POINTER(csv_bam_counts)]),
+    "csvgpu_bam_unpack_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(csv_bam_out),
+                                        C.POINTER(csv_bam_counts)]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),
     "csvgpu_depth_lookup_resident": (C.c_int, [_P, _P, _P, C.c_uint64, _P]),
     "csvgpu_download": (C.c_int, [_P, _P, _P, C.c_size_t]),
+    "csvgpu_dev_alloc": (_P, [_P, C.c_size_t]),
+    "csvgpu_dev_free": (None, [_P, _P]),
+    "csvgpu_upload": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "csvgpu_dbscan_iv_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_double, C.c_int32, _P]),
     "csvgpu_dbscan_1d_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_int32, _P]),
     "csvgpu_window_log2_dev": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_double, _P, _P, _P]),

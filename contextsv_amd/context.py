@@ -458,6 +458,100 @@ class Context:
             self._check(rc)
         return rc
 
+    # -------------------------------------------------------------------------------- BAM records
+    _BAM_DTYPES = dict(pos=np.int32, flag=np.uint16, mapq=np.uint8, cigar_off=np.uint64, cigar=np.uint32, seq_off=np.uint64, seq=np.uint8,
+                       name_off=np.uint64, name=np.uint8, name_hash=np.uint64)
+    _BAM_SIZES = dict(pos=4, flag=2, mapq=1, cigar_off=8, cigar=4, seq_off=8, seq=1, name_off=8, name=1, name_hash=8)
+
+    @staticmethod
+    def _bam_out(arrays, address, numel, what):
+        """csv_bam_out over the caller's arrays (numpy or torch, by the two accessors): the capacities are what the arrays hold."""
+        o = _lib.csv_bam_out()
+        for k in ("pos", "flag", "mapq", "cigar_off", "cigar"):
+            if arrays.get(k) is None:
+                raise ValueError(f"{what}: array '{k}' is required")
+        for k in Context._BAM_SIZES:
+            a = arrays.get(k)
+            setattr(o, k, address(a, k) if a is not None else None)
+        per_record = [numel(arrays[k]) for k in ("pos", "flag", "mapq", "name_hash") if arrays.get(k) is not None]
+        per_record += [numel(arrays[k]) - 1 for k in ("cigar_off", "seq_off", "name_off") if arrays.get(k) is not None]
+        if min(per_record) < 0:
+            raise ValueError(f"{what}: an offset array needs at least one entry")
+        o.cap_records = min(per_record)
+        o.cap_cigar = numel(arrays["cigar"])
+        o.cap_seq = numel(arrays["seq"]) if arrays.get("seq") is not None else 0
+        o.cap_name = numel(arrays["name"]) if arrays.get("name") is not None else 0
+        return o
+
+    @staticmethod
+    def _bam_counts(c) -> dict:
+        d = {k: int(getattr(c, k)) for k in ("n_records", "kept_first", "n_kept", "n_cigar", "n_seq", "n_name", "consumed", "status")}
+        d["stopped"] = bool(c.stopped)
+        d["reason"], d["offset"] = d["status"] & 0xFF, d["status"] >> 8
+        return d
+
+    def _bam_call(self, fn, data_ptr, length, anchors, tid, end, bases, o):
+        anchors = np.ascontiguousarray(anchors, np.uint32)
+        c = _lib.csv_bam_counts()
+        rc = fn(self.h, data_ptr, length, ptr(anchors), len(anchors), int(tid), int(end), int(bases[0]), int(bases[1]), int(bases[2]), C.byref(o), C.byref(c))
+        if rc < 0 and rc != _lib.CSV_ECAPACITY:
+            self._check(rc)
+        return rc, self._bam_counts(c)
+
+    def bam_unpack_into(self, data, anchors, out: dict, tid: int = -1, end: int = 0, bases=(0, 0, 0)):
+        """csvgpu_bam_unpack: the decoded BAM record stream `data` (uint8) unpacked on the device into the caller's numpy arrays `out`
+        (pos int32, flag uint16, mapq uint8, cigar_off uint64 [records + 1], cigar uint32; optional seq_off + seq, name_off + name,
+        name_hash); the capacities are the arrays' lengths. anchors: ascending offsets of record starts, anchors[0] the first record's.
+        -> (rc, counts): rc 0 written, 1 declined (counts['reason'] at counts['offset']), CSV_ECAPACITY with the exact counts."""
+        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+
+        def address(a, k):
+            if a.dtype != self._BAM_DTYPES[k] or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise ValueError(f"bam_unpack: '{k}' must be a writeable contiguous {np.dtype(self._BAM_DTYPES[k]).name} array")
+            return a.ctypes.data
+        o = self._bam_out(out, address, len, "bam_unpack")
+        return self._bam_call(self.lib.csvgpu_bam_unpack, ptr(data), len(data), anchors, tid, end, bases, o)
+
+    def bam_unpack(self, data, anchors, tid: int = -1, end: int = 0, bases=(0, 0, 0), want_seq=False, want_names=False, want_hashes=False):
+        """The same into arrays of exactly the kept records' sizes (a sizing call first: CSV_ECAPACITY carries the exact counts).
+        -> dict of the counts and, unless the stream was declined (status != 0), the arrays."""
+        def alloc(n_rec, n_cigar, n_seq, n_name):
+            a = dict(pos=np.zeros(max(n_rec, 1), np.int32), flag=np.zeros(max(n_rec, 1), np.uint16), mapq=np.zeros(max(n_rec, 1), np.uint8),
+                     cigar_off=np.zeros(n_rec + 1, np.uint64), cigar=np.zeros(max(n_cigar, 1), np.uint32))
+            if want_seq:
+                a.update(seq_off=np.zeros(n_rec + 1, np.uint64), seq=np.zeros(max(n_seq, 1), np.uint8))
+            if want_names:
+                a.update(name_off=np.zeros(n_rec + 1, np.uint64), name=np.zeros(max(n_name, 1), np.uint8))
+            if want_hashes:
+                a.update(name_hash=np.zeros(max(n_rec, 1), np.uint64))
+            return a
+        arrays = alloc(0, 0, 0, 0)
+        rc, c = self.bam_unpack_into(data, anchors, arrays, tid, end, bases)
+        if rc == _lib.CSV_ECAPACITY:
+            arrays = alloc(c["n_kept"], c["n_cigar"], c["n_seq"], c["n_name"])
+            rc, c = self.bam_unpack_into(data, anchors, arrays, tid, end, bases)
+            if rc < 0:
+                self._check(rc)
+        if rc == 0:
+            n = c["n_kept"]
+            for k, a in arrays.items():
+                total = {"cigar": c["n_cigar"], "seq": c["n_seq"], "name": c["n_name"]}.get(k, n + 1 if k.endswith("_off") else n)
+                c[k] = a[:total]
+        return c
+
+    def bam_unpack_dev(self, d_bytes, anchors, out: dict, tid: int = -1, end: int = 0, bases=(0, 0, 0)):
+        """csvgpu_bam_unpack_dev: the same with the stream and the outputs as torch tensors on this context's device (element sizes of the
+        numpy form: int32 / int16 / uint8 / int64 / int32 bit patterns) — behind bgzf_inflate_dev the bytes never leave the device, and
+        pos / flag / mapq / cigar_off / cigar are what wrap_device takes. -> (rc, counts) as bam_unpack_into."""
+        def address(t, k):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != self._BAM_SIZES[k]:
+                raise ValueError(f"bam_unpack_dev: '{k}' must be a contiguous device tensor of {self._BAM_SIZES[k]}-byte elements")
+            return t.data_ptr()
+        if not d_bytes.is_cuda or not d_bytes.is_contiguous() or d_bytes.element_size() != 1:
+            raise ValueError("bam_unpack_dev: contiguous uint8 device tensor expected")
+        o = self._bam_out(out, address, lambda t: int(t.numel()), "bam_unpack_dev")
+        return self._bam_call(self.lib.csvgpu_bam_unpack_dev, d_bytes.data_ptr(), int(d_bytes.numel()), anchors, tid, end, bases, o)
+
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):
         self._check(self.lib.csvgpu_synchronize(self.h))

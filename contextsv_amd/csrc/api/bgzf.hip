@@ -10,7 +10,6 @@ using namespace csv;
 namespace {
 
 constexpr uint32_t kMaxMember = 65536;
-constexpr size_t kPiece = (size_t)4 << 20;               // bytes per copy: the page-locked block holds two pieces, one in flight, one being filled / emptied
 
 int check_blocks(csv_ctx *ctx, const csv_bgzf_block *blocks, uint32_t n_blocks, uint64_t comp_len, uint64_t out_len)
 {
@@ -26,6 +25,10 @@ int check_blocks(csv_ctx *ctx, const csv_bgzf_block *blocks, uint32_t n_blocks, 
     }
     return CSV_OK;
 }
+
+}  // namespace
+
+namespace csv {
 
 // `bytes` between pageable host memory and the device through the two halves of the page-locked block (2 * kPiece, reserved by the caller).
 // up: host -> device, queued; the last pieces may still be in flight on return (the stream orders them in front of the kernel).
@@ -44,7 +47,6 @@ int copy_up(csv_ctx *ctx, void *d_dst, const void *h_src, size_t bytes, hipEvent
 // down: device -> host; piece k + 1 travels while piece k is copied out of the block. Only the bytes inside `runs` (ascending, disjoint
 // [first, second) offsets into the range) reach the caller's memory: the bytes between two members are not the library's to write.
 // Complete on return.
-typedef std::vector<std::pair<uint64_t, uint64_t>> Runs;
 int copy_down(csv_ctx *ctx, void *h_dst, const void *d_src, size_t bytes, hipEvent_t ev[2], const Runs &runs)
 {
     const size_t n_pieces = (bytes + kPiece - 1) / kPiece;
@@ -69,20 +71,9 @@ int copy_down(csv_ctx *ctx, void *h_dst, const void *d_src, size_t bytes, hipEve
     return CSV_OK;
 }
 
-struct Events {                                           // two events of the context's pool, returned to it
-    csv_ctx *ctx;
-    hipEvent_t ev[2];
-    bool done = false;                                    // set by the entry point on its way out with everything waited for
-    explicit Events(csv_ctx *c) : ctx(c) { ev[0] = get_event(c); ev[1] = get_event(c); }
-    // An early return (a HIP error part-way through the pieces) may leave copies queued that read or write the page-locked halves and events
-    // recorded but not waited for: the stream is drained before the events go back to the pool and the block to its next user.
-    ~Events()
-    {
-        if (!done) (void)hipStreamSynchronize(ctx->stream);
-        for (hipEvent_t e : ev) if (e) ctx->event_pool.push_back(e);
-    }
-    bool ok() const { return ev[0] && ev[1]; }
-};
+}  // namespace csv
+
+namespace {
 
 // table up, kernel, count back: what both entry points share. The page-locked block holds 2 * kPiece bytes; its first bytes take the count.
 int run_members(csv_ctx *ctx, const BgzfWs &w, const uint8_t *d_comp, const csv_bgzf_block *blocks, uint32_t n_blocks, uint8_t *d_out, uint8_t *d_status,

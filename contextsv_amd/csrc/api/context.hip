@@ -177,6 +177,39 @@ int csvgpu_timing_get(csv_ctx *ctx, int kernel_id, double *total_ms, uint64_t *l
     return CSV_OK;
 }
 
+void *csvgpu_dev_alloc(csv_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return nullptr;
+    (void)hipSetDevice(ctx->device);
+    void *p = nullptr;
+    if (test_fail_alloc() || hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); ctx->err = "hipMalloc failed (csvgpu_dev_alloc)"; return nullptr; }
+    return p;
+}
+
+void csvgpu_dev_free(csv_ctx *ctx, void *dev_ptr)
+{
+    if (!ctx || !dev_ptr) return;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dev_ptr);
+}
+
+int csvgpu_upload(csv_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes)
+{
+    if (!ctx || (bytes && (!dev_dst || !host_src))) return CSV_EINVAL;
+    if (!bytes) return CSV_OK;
+    (void)hipSetDevice(ctx->device);
+    int rc = ensure_pinned(ctx, 2 * kPiece);
+    if (rc) return rc;
+    Events e(ctx);
+    if (!e.ok()) { ctx->err = "csvgpu_upload: no event"; return CSV_EHIP; }
+    size_t piece_no = 0;
+    if ((rc = copy_up(ctx, dev_dst, host_src, bytes, e.ev, piece_no))) return rc;
+    CSV_HIP(ctx, wait_stream(ctx->stream));
+    e.done = true;
+    return CSV_OK;
+}
+
 int csvgpu_download(csv_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes)
 {
     if (!ctx || (bytes && (!host_dst || !dev_src))) return CSV_EINVAL;

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <utility>
+#include <vector>
 
 #include "../layouts.hpp"
 
@@ -106,6 +108,25 @@ static inline const uint32_t *sorted_perm(csv_ctx *ctx, const int32_t *keys, uin
 }
 
 // ---- defined in one file, used by others ----
+// bgzf.hip: pieced copies between pageable host memory and the device through the two halves of the page-locked block
+constexpr size_t kPiece = (size_t)4 << 20;               // bytes per copy: the page-locked block holds two pieces (ensure_pinned(2 * kPiece)), one in flight, one being filled / emptied
+typedef std::vector<std::pair<uint64_t, uint64_t>> Runs;
+int copy_up(csv_ctx *ctx, void *d_dst, const void *h_src, size_t bytes, hipEvent_t ev[2], size_t &piece_no);
+int copy_down(csv_ctx *ctx, void *h_dst, const void *d_src, size_t bytes, hipEvent_t ev[2], const Runs &runs);
+struct Events {                                           // two events of the context's pool, returned to it
+    csv_ctx *ctx;
+    hipEvent_t ev[2];
+    bool done = false;                                    // set by the entry point on its way out with everything waited for
+    explicit Events(csv_ctx *c) : ctx(c) { ev[0] = get_event(c); ev[1] = get_event(c); }
+    // An early return (a HIP error part-way through the pieces) may leave copies queued that read or write the page-locked halves and events
+    // recorded but not waited for: the stream is drained before the events go back to the pool and the block to its next user.
+    ~Events()
+    {
+        if (!done) (void)hipStreamSynchronize(ctx->stream);
+        for (hipEvent_t e : ev) if (e) ctx->event_pool.push_back(e);
+    }
+    bool ok() const { return ev[0] && ev[1]; }
+};
 // reads.hip
 int check_reads(csv_ctx *ctx, const csv_reads *r);           // host arrays
 int check_reads_dev(csv_ctx *ctx, const csv_reads *r);       // arrays in HBM: one small kernel

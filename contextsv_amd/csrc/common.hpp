@@ -382,6 +382,35 @@ void launch_cn_fill(hipStream_t s, const CnSlots &sl, uint32_t n_slots, uint32_t
 // *n_declined (zeroed by the caller) counts the declined ones
 void launch_bgzf_inflate(hipStream_t s, const uint8_t *comp, const csv_bgzf_block *blocks, uint32_t n_blocks, uint8_t *out, uint8_t *status,
                          unsigned int *n_declined);
+// bamunpack.hip — a decoded BAM record stream in HBM to the arrays of csv_reads (+ sequences, names, name hashes); csvgpu_bam_unpack / _dev
+struct BamUnpackOut {                        // device arrays of this call's kept records, passed to the kernels by value (seq / name / hash: null = not wanted)
+    int32_t *pos; uint16_t *flag; uint8_t *mapq;
+    uint64_t *cigar_off; uint32_t *cigar;
+    uint64_t *seq_off; uint8_t *seq;
+    uint64_t *name_off; uint8_t *name;
+    uint64_t *name_hash;
+};
+// the words of BamUnpackWs::res (preset to all-ones with status and bounds: one slice, one memset, one copy back)
+enum : uint32_t { BU_RES_NKEPT = 0, BU_RES_FIRST = 1, BU_RES_NCIGAR = 2, BU_RES_NSEQ = 3, BU_RES_NNAME = 4, BU_RES_STOPPED = 5, BU_RES_CONSUMED = 6, BU_RES_NREC = 7, BU_RES_WORDS = 8 };
+constexpr size_t BU_HEAD_BYTES = 64;         // res[8] | status u64 | bounds[2]
+constexpr unsigned long long BU_STATUS_NONE = ~0ull;
+struct BamUnpackWs {
+    uint32_t *res = nullptr; unsigned long long *status = nullptr; uint32_t *bounds = nullptr;      // the head
+    uint32_t *anchors = nullptr, *count = nullptr;                                                   // [n_anchors], [n_anchors + 1]
+    uint32_t *rec_off = nullptr; uint32_t rec_cap = 0;                                               // [rec_cap] every record's start; rec_cap = len / 36
+    uint32_t *cig_src = nullptr, *cig_n = nullptr, *seq_n = nullptr, *name_n = nullptr;              // [rec_cap + 1] per kept record
+    void *es_tmp = nullptr;
+    // the host-pointer form alone: the stream and the outputs staged on the device
+    uint8_t *bytes = nullptr;
+    BamUnpackOut out{};
+};
+// chain: anchors on the device, head preset; leaves rec_off[], res[BU_RES_NREC], res[BU_RES_CONSUMED] and the status
+void launch_bam_chain(hipStream_t s, const uint8_t *bytes, uint32_t len, uint32_t n_anchors, const BamUnpackWs &w);
+// filter, checks and CG rule of the kept records, the three sums, the counts into res[0..5]
+void launch_bam_fields(hipStream_t s, const uint8_t *bytes, uint32_t n_rec, int32_t tid, int64_t end, const BamUnpackWs &w);
+// the outputs, after the caller has held the counts against its capacities
+void launch_bam_emit(hipStream_t s, const uint8_t *bytes, uint32_t first, uint32_t n_kept, uint32_t n_cigar, uint32_t n_seq, uint32_t n_name,
+                     uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const BamUnpackWs &w, const BamUnpackOut &out);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

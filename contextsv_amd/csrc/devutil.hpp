@@ -180,4 +180,14 @@ __device__ __forceinline__ uint32_t so_mod(uint64_t h, uint32_t B, double inv /*
     return (uint32_t)r2;
 }
 
+// libstdc++'s _Hash_bytes for 64-bit size_t (std::hash<std::string>: a Murmur-style hash, seed 0xc70f6907), in the steps its loop takes:
+// hb_init(len), hb_block for every whole 8 bytes (little-endian), hb_tail for the 1..7 bytes left (as one little-endian number), hb_final.
+// cnobs.hip hashes its key texts out of registers with them, bamunpack.hip the query names out of the record stream.
+constexpr uint64_t HB_MUL = (0xc6a4a793ull << 32) + 0x5bd1e995ull;
+__device__ __forceinline__ uint64_t hb_shift_mix(uint64_t v) { return v ^ (v >> 47); }
+__device__ __forceinline__ uint64_t hb_init(uint32_t len) { return 0xc70f6907ull ^ ((uint64_t)len * HB_MUL); }
+__device__ __forceinline__ uint64_t hb_block(uint64_t hash, uint64_t w) { return (hash ^ (hb_shift_mix(w * HB_MUL) * HB_MUL)) * HB_MUL; }
+__device__ __forceinline__ uint64_t hb_tail(uint64_t hash, uint64_t w) { return (hash ^ w) * HB_MUL; }
+__device__ __forceinline__ uint64_t hb_final(uint64_t hash) { return hb_shift_mix(hb_shift_mix(hash) * HB_MUL); }
+
 }  // namespace csv

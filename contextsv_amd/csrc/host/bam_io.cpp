@@ -109,7 +109,10 @@ void BamShard::clear()
 
 // ---- BAI -----------------------------------------------------------------------------------------------
 struct BamReader::Index {
-    struct Ref { bool any = false; uint64_t min_beg = ~0ull, max_end = 0; };
+    struct Ref {
+        bool any = false; uint64_t min_beg = ~0ull, max_end = 0;
+        std::vector<uint64_t> anchors;     // chunk begins and linear-index offsets, ascending: virtual offsets that CLAIM to be record starts (device_unpack's hints)
+    };
     std::vector<Ref> refs;
 };
 
@@ -202,14 +205,21 @@ bool BamReader::loadIndex(const std::string &index_path)
                     idx->refs[r].any = true;
                     idx->refs[r].min_beg = std::min(idx->refs[r].min_beg, beg);
                     idx->refs[r].max_end = std::max(idx->refs[r].max_end, end);
+                    idx->refs[r].anchors.push_back(beg);
                 }
             }
             o += 16ull * n_chunk;
         }
         if (o + 4 > n) { err = "BAI: truncated"; return false; }
         const uint32_t n_intv = le32(p + o);
+        const size_t lin = o + 4;
         o += 4 + 8ull * n_intv;
         if (o > n) { err = "BAI: truncated"; return false; }
+        // (the values size nothing and are believed nowhere: unpackBatch holds each against the batch's block table, the device against the record chain)
+        std::vector<uint64_t> &a = idx->refs[r].anchors;
+        for (uint32_t k = 0; k < n_intv; k++) a.push_back(le64(p + lin + 8ull * k));
+        std::sort(a.begin(), a.end());
+        a.erase(std::unique(a.begin(), a.end()), a.end());
     }
     index = std::move(idx);
     return true;
@@ -228,10 +238,83 @@ void parallel_chunks(int nt, F fn)
 }
 }  // namespace
 
+// The device library's entry points where it is linked (the stand-alone check programs build without it: no device route there)
+extern "C" {
+__attribute__((weak)) int csvgpu_bam_unpack_dev(csv_ctx *ctx, const uint8_t *d_bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
+                                                uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const csv_bam_out *d_out, csv_bam_counts *counts);
+__attribute__((weak)) int csvgpu_bgzf_inflate_dev(csv_ctx *ctx, const uint8_t *d_comp, uint64_t comp_len, const csv_bgzf_block *blocks, uint32_t n_blocks, uint8_t *d_out,
+                                                  uint64_t out_len, uint8_t *d_status);
+__attribute__((weak)) void *csvgpu_dev_alloc(csv_ctx *ctx, size_t bytes);
+__attribute__((weak)) void csvgpu_dev_free(csv_ctx *ctx, void *dev_ptr);
+__attribute__((weak)) int csvgpu_upload(csv_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
+__attribute__((weak)) int csvgpu_download(csv_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
+__attribute__((weak)) const char *csvgpu_last_error(const csv_ctx *ctx);
+}
+
+// Device memory of one stream() with BamReadOptions::device_unpack: the batch's decoded bytes behind kDevHead bytes of room for the carried
+// partial record, the compressed bytes + status bytes of the device inflate, and the unpacked arrays. Grown when needed, freed with the stream.
+struct BamReader::DevBufs {
+    csv_ctx *ctx = nullptr;
+    struct Buf { uint8_t *p = nullptr; size_t cap = 0; } bytes, comp, out;
+    ~DevBufs() { for (Buf *b : {&bytes, &comp, &out}) if (b->p && csvgpu_dev_free) csvgpu_dev_free(ctx, b->p); }
+    bool ensure(Buf &b, size_t need, std::string &err)
+    {
+        if (need <= b.cap) return true;
+        if (b.p) csvgpu_dev_free(ctx, b.p);
+        b.cap = need + need / 4 + 4096;
+        b.p = (uint8_t *)csvgpu_dev_alloc(ctx, b.cap);
+        if (!b.p) { b.cap = 0; err = std::string("BAM: no device memory for the batch: ") + csvgpu_last_error(ctx); return false; }
+        return true;
+    }
+};
+static const size_t kDevHead = 1 << 20;
+
 // Decompressed record stream from a virtual offset: batches of blocks are inflated by the pool while the previous batch is parsed.
-bool BamReader::stream(uint64_t start_voffset, const BamReadOptions &opt, const std::function<size_t(const RecRef *, size_t)> &on_batch)
+bool BamReader::stream(uint64_t start_voffset, const BamReadOptions &opt, const std::function<size_t(const RecRef *, size_t)> &on_batch, const RawFn &on_raw)
 {
-    struct Batch { std::vector<bgzf::Block> blocks; HugeVec<uint8_t> data; size_t head = 0; bool ok = true; std::string err; uint64_t next_coff = 0; };
+    struct Batch {
+        std::vector<bgzf::Block> blocks; HugeVec<uint8_t> data; size_t head = 0; bool ok = true; std::string err; uint64_t next_coff = 0;
+        bool resident = false;       // the decoded bytes are in dev.bytes at kDevHead, not in `data` (device inflate straight into the unpack's buffer)
+        size_t total = 0;
+    };
+    // device_unpack: a batch's bytes go to the reader's device buffer and the arrays come back from there. With the inflate on the same
+    // context the members are inflated straight into that buffer (kernel to kernel): the bytes come down only when the device declines the batch.
+    const bool dev_route = on_raw && opt.device_unpack && csvgpu_dev_alloc && csvgpu_upload && csvgpu_download;
+    const bool chain = dev_route && opt.device_inflate == opt.device_unpack && csvgpu_bgzf_inflate_dev;
+    DevBufs dev;
+    dev.ctx = opt.device_unpack;
+    // the batch's members inflated on the device into dev.bytes; what the device declines is decoded on the host (bgzf::inflate_block: the
+    // fast decoder, then zlib, the CRC behind either — the host route's messages) and copied into place
+    auto load_chain = [&](Batch &b, uint64_t total) -> bool {
+        const size_t n = b.blocks.size();
+        b.resident = true; b.total = (size_t)total;
+        b.data.clear();
+        if (n == 0) return true;
+        const uint64_t base = b.blocks[0].coffset;
+        std::vector<csv_bgzf_block> tab(n);
+        uint64_t acc = 0;
+        for (size_t i = 0; i < n; i++) {
+            const bgzf::Block &k = b.blocks[i];
+            if (k.coffset < base || k.csize < (uint32_t)k.data_off + 8) { b.err = "BGZF: block table out of order at offset " + std::to_string(k.coffset); return false; }
+            tab[i] = csv_bgzf_block{k.coffset - base + k.data_off, acc, k.csize - k.data_off - 8, k.isize, le32(file.data() + k.coffset + k.csize - 8), 0};
+            acc += k.isize;
+        }
+        const uint64_t span = b.blocks[n - 1].coffset + b.blocks[n - 1].csize - base;
+        if (!dev.ensure(dev.bytes, kDevHead + (size_t)total + 8, b.err) || !dev.ensure(dev.comp, (size_t)span + 256 + n, b.err)) return false;
+        uint8_t *const d_status = dev.comp.p + (((size_t)span + 255) & ~(size_t)255);
+        int rc = csvgpu_upload(dev.ctx, dev.comp.p, file.data() + base, (size_t)span);
+        if (rc == 0) rc = csvgpu_bgzf_inflate_dev(dev.ctx, dev.comp.p, span, tab.data(), (uint32_t)n, dev.bytes.p + kDevHead, std::max<uint64_t>(total, 1), d_status);
+        if (rc < 0) { b.err = std::string("BGZF: device inflate failed: ") + csvgpu_last_error(dev.ctx); return false; }
+        if (rc == 0) return true;
+        std::vector<uint8_t> status(n), tmp(bgzf::kMaxBlock);
+        if (csvgpu_download(dev.ctx, status.data(), d_status, n)) { b.err = std::string("BGZF: device inflate failed: ") + csvgpu_last_error(dev.ctx); return false; }
+        for (size_t i = 0; i < n; i++) {
+            if (!status[i]) continue;
+            if (!bgzf::inflate_block(file.data(), b.blocks[i], tmp.data(), &b.err)) return false;
+            if (csvgpu_upload(dev.ctx, dev.bytes.p + kDevHead + tab[i].out_off, tmp.data(), b.blocks[i].isize)) { b.err = std::string("BGZF: device inflate failed: ") + csvgpu_last_error(dev.ctx); return false; }
+        }
+        return true;
+    };
     const uint32_t W = std::max<uint32_t>(opt.window_blocks, 1);
     const size_t kHead = 1 << 20;                        // room in front of each batch for the carried partial record (grown when needed)
     auto load = [&](uint64_t coff, Batch &b, size_t head) {
@@ -247,6 +330,8 @@ bool BamReader::stream(uint64_t start_voffset, const BamReadOptions &opt, const 
         }
         b.next_coff = coff;
         b.head = head;
+        b.resident = false; b.total = (size_t)total;
+        if (chain) { if (!load_chain(b, total)) b.ok = false; return; }
         b.data.resize_uninit(head + total);
         const bool ok = opt.device_inflate ? bgzf::inflate_range_device(opt.device_inflate, file.data(), b.blocks, 0, b.blocks.size(), b.data.data() + head, opt.threads, &b.err)
                                            : bgzf::inflate_range(file.data(), b.blocks, 0, b.blocks.size(), b.data.data() + head, opt.threads, &b.err);
@@ -267,22 +352,69 @@ bool BamReader::stream(uint64_t start_voffset, const BamReadOptions &opt, const 
         if (b.blocks.empty()) break;
         std::future<void> ahead;
         const bool more = b.next_coff < file.size();
-        if (more) ahead = std::async(std::launch::async, load, b.next_coff, std::ref(batch[cur ^ 1]), kHead);
+        // (one context serves one thread at a time: with the unpack on the inflate's context the next batch is loaded behind this one's unpack)
+        const bool beside = !(on_raw && opt.device_inflate && opt.device_inflate == opt.device_unpack);
+        if (more) ahead = std::async(beside ? std::launch::async : std::launch::deferred, load, b.next_coff, std::ref(batch[cur ^ 1]), kHead);
         auto fail = [&](const std::string &m) { err = m; if (more) ahead.get(); return false; };
         // records of this batch = carried bytes + inflated bytes
-        uint8_t *p = b.data.data() + b.head;
-        size_t n = b.data.size() - b.head;
-        if (skip) { if (skip > n) return fail("BAM: virtual offset beyond its block"); p += skip; n -= skip; skip = 0; }
-        if (!carry.empty()) {
-            if (carry.size() <= (size_t)(p - b.data.data())) { p -= carry.size(); memcpy(p, carry.data(), carry.size()); n += carry.size(); }
-            else {
-                joined.clear();
-                joined.append(carry.data(), carry.size());
-                joined.append(p, n);
-                p = joined.data(); n = joined.size();
+        uint8_t *p = nullptr;
+        size_t n = 0;
+        const size_t skipped = skip, carried = carry.size();
+        if (skip > b.total) return fail("BAM: virtual offset beyond its block");
+        // the bytes of a resident batch brought to the host (the device declined the batch, or the carried record is larger than the room)
+        auto materialize = [&]() -> bool {
+            if (!b.resident) return true;
+            b.data.resize_uninit(b.head + b.total);
+            if (b.total && csvgpu_download(dev.ctx, b.data.data() + b.head, dev.bytes.p + kDevHead, b.total)) { err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(dev.ctx); return false; }
+            b.resident = false;
+            unpack_stats.batches_downloaded++;
+            return true;
+        };
+        auto assemble = [&] {                            // on the host: p[0, n)
+            p = b.data.data() + b.head + skip;
+            n = b.total - skip;
+            skip = 0;
+            if (!carry.empty()) {
+                if (carry.size() <= (size_t)(p - b.data.data())) { p -= carry.size(); memcpy(p, carry.data(), carry.size()); n += carry.size(); }
+                else {
+                    joined.clear();
+                    joined.append(carry.data(), carry.size());
+                    joined.append(p, n);
+                    p = joined.data(); n = joined.size();
+                }
+                carry.clear();
             }
-            carry.clear();
+        };
+        if (dev_route) {
+            // on the device: d[0, dn) = the carried bytes in the room in front + the batch's bytes from `skip` on
+            const size_t dn = carried + b.total - skip;
+            const bool fits = carried <= kDevHead;
+            uint8_t *d = nullptr;
+            bool up = fits;
+            if (fits && !b.resident) up = dev.ensure(dev.bytes, kDevHead + b.total + 8, err) && csvgpu_upload(dev.ctx, dev.bytes.p + kDevHead, b.data.data() + b.head, b.total) == 0;
+            if (fits && up && carried) up = csvgpu_upload(dev.ctx, dev.bytes.p + kDevHead + skip - carried, carry.data(), carried) == 0;
+            if (fits && !up) { if (err.empty()) err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(dev.ctx); if (more) ahead.get(); return false; }
+            if (fits) d = dev.bytes.p + kDevHead + skip - carried;
+            int took = 0;
+            size_t consumed = 0;
+            bool stop = false;
+            if (!d) unpack_stats.batches_host++;             // (a carried record larger than the room: the host parser)
+            if (d) took = on_raw(RawBatch{d, dn, carried, skipped, &b.blocks, &dev}, &consumed, &stop);
+            if (took < 0) { if (more) ahead.get(); return false; }
+            if (took > 0) {
+                if (b.resident && dn) unpack_stats.batches_kept_on_device++;      // (an empty batch — the EOF marker alone — is nobody's)
+                if (stop) { if (more && beside) ahead.get(); return err.empty(); }       // (a deferred load that nobody waits for never runs)
+                skip = 0;
+                carry.resize(dn - consumed);
+                if (dn > consumed && csvgpu_download(dev.ctx, carry.data(), d + consumed, dn - consumed)) return fail(std::string("BAM: device unpack failed: ") + csvgpu_last_error(dev.ctx));
+                if (!more) break;
+                ahead.get();
+                cur ^= 1;
+                continue;
+            }
+            if (!materialize()) { if (more) ahead.get(); return false; }
         }
+        assemble();
         recs.clear();
         size_t o = 0;
         while (o + 4 <= n) {
@@ -365,6 +497,94 @@ bool BamReader::append(const RecRef *recs, size_t n, const BamReadOptions &opt, 
     return true;
 }
 
+// One batch's records unpacked on the device and appended to `out` (BamReadOptions::device_unpack). The bytes are in the reader's device
+// buffer already. The anchor candidates that lie in this batch are mapped from virtual offset to buffer offset through its block table; a
+// sizing call gives the exact counts (CSV_ECAPACITY, the library's convention; the bytes stay where they are, only the chain, filter and
+// field kernels run twice), the second call writes device arrays of exactly those sizes, and they are copied into the shard's arrays.
+int BamReader::unpackBatch(const RawBatch &b, int tid, int64_t end, const std::vector<uint64_t> &candidates, const BamReadOptions &opt, BamShard &out, size_t *consumed, bool *stop)
+{
+    if (!csvgpu_bam_unpack_dev || !csvgpu_last_error) { err = "BAM: no device to unpack on"; return -1; }
+    if (b.n == 0) { *consumed = 0; *stop = false; return 1; }
+    if (b.n >= (1ull << 32)) { unpack_stats.batches_host++; return 0; }   // beyond the device's 32-bit offsets: the host parser
+    std::vector<uint32_t> anchors(1, 0);                                  // d[0] is a record start: the carry's, or the stream's first
+    {
+        // block i's bytes start at buffer offset carried + (bytes of the blocks before it) - skip
+        const std::vector<bgzf::Block> &bl = *b.blocks;
+        size_t i = 0;
+        uint64_t before = 0;
+        auto it = bl.empty() ? candidates.end() : std::lower_bound(candidates.begin(), candidates.end(), bgzf::voffset(bl[0].coffset, 0));
+        for (; it != candidates.end(); ++it) {
+            const uint64_t coff = *it >> 16, uoff = *it & 0xffff;
+            while (i < bl.size() && bl[i].coffset < coff) { before += bl[i].isize; i++; }
+            if (i == bl.size()) break;
+            if (bl[i].coffset != coff || uoff >= bl[i].isize) continue;   // not a block of this file, or beyond its bytes: not a hint
+            const uint64_t at = b.carried + before + uoff;
+            if (at <= b.skip + anchors.back() || at - b.skip >= b.n) continue;
+            anchors.push_back((uint32_t)(at - b.skip));
+        }
+    }
+    DevBufs &dev = *b.dev;
+    auto dev_fail = [&] { err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(opt.device_unpack); return -1; };
+    const size_t r0 = out.pos.size();
+    const uint64_t cig_at = out.cigar.size(), seq_at = out.seq.size();
+    if (!dev.ensure(dev.out, 4096, err)) return -1;
+    csv_bam_out o{};
+    csv_bam_counts c{};
+    // sizing call: capacities of zero (with no record kept the three offset arrays still take their first entry: 8 bytes of scratch each)
+    o.pos = (int32_t *)dev.out.p; o.flag = (uint16_t *)dev.out.p; o.mapq = dev.out.p; o.cigar = (uint32_t *)dev.out.p;
+    o.cigar_off = (uint64_t *)(dev.out.p + 256);
+    if (opt.want_seq) { o.seq_off = (uint64_t *)(dev.out.p + 512); o.seq = dev.out.p; }
+    if (opt.want_qnames) { o.name_off = (uint64_t *)(dev.out.p + 768); o.name = dev.out.p; }
+    int rc = csvgpu_bam_unpack_dev(opt.device_unpack, b.d, b.n, anchors.data(), (uint32_t)anchors.size(), tid, end, cig_at, seq_at, 0, &o, &c);
+    if (rc == 1) { unpack_stats.batches_host++; return 0; }              // declined: the host parser reads this batch and words the refusal
+    if (rc != CSV_OK && rc != CSV_ECAPACITY) return dev_fail();
+    if (rc == CSV_ECAPACITY) {
+        const size_t k = (size_t)c.n_kept;
+        const csv_bam_counts sized = c;
+        size_t at = 0;
+        auto slot = [&](size_t bytes) { const size_t a = at; at += (bytes + 255) & ~(size_t)255; return a; };
+        const size_t a_pos = slot(k * 4), a_flag = slot(k * 2), a_mapq = slot(k), a_coff = slot((k + 1) * 8), a_cig = slot(c.n_cigar * 4 + 4);
+        const size_t a_soff = slot((k + 1) * 8), a_seq = slot(c.n_seq + 4), a_noff = slot((k + 1) * 8), a_name = slot(c.n_name + 4);
+        if (!dev.ensure(dev.out, at, err)) return -1;
+        uint8_t *const q = dev.out.p;
+        o.pos = (int32_t *)(q + a_pos); o.flag = (uint16_t *)(q + a_flag); o.mapq = q + a_mapq; o.cigar_off = (uint64_t *)(q + a_coff); o.cigar = (uint32_t *)(q + a_cig);
+        o.cap_records = k; o.cap_cigar = c.n_cigar;
+        if (opt.want_seq) { o.seq_off = (uint64_t *)(q + a_soff); o.seq = q + a_seq; o.cap_seq = c.n_seq; }
+        if (opt.want_qnames) { o.name_off = (uint64_t *)(q + a_noff); o.name = q + a_name; o.cap_name = c.n_name; }
+        rc = csvgpu_bam_unpack_dev(opt.device_unpack, b.d, b.n, anchors.data(), (uint32_t)anchors.size(), tid, end, cig_at, seq_at, 0, &o, &c);
+        if (rc < 0) return dev_fail();
+        if (rc != CSV_OK || c.n_kept != sized.n_kept || c.n_cigar != sized.n_cigar || c.n_seq != sized.n_seq || c.n_name != sized.n_name) {
+            err = "BAM: device unpack failed: the second call disagrees with the first";
+            return -1;
+        }
+        // the arrays come down into the shard where they stand
+        csv_ctx *const x = opt.device_unpack;
+        out.pos.resize(r0 + k); out.flag.resize(r0 + k); out.mapq.resize(r0 + k);
+        out.cigar_off.resize(r0 + 1 + k);
+        out.cigar.resize_uninit(cig_at + c.n_cigar);
+        if (csvgpu_download(x, out.pos.data() + r0, o.pos, k * 4) || csvgpu_download(x, out.flag.data() + r0, o.flag, k * 2) || csvgpu_download(x, out.mapq.data() + r0, o.mapq, k) ||
+            csvgpu_download(x, out.cigar_off.data() + r0, o.cigar_off, (k + 1) * 8) || (c.n_cigar && csvgpu_download(x, out.cigar.data() + cig_at, o.cigar, c.n_cigar * 4))) return dev_fail();
+        if (opt.want_seq) {
+            out.seq_off.resize(r0 + 1 + k);
+            out.seq.resize_uninit(seq_at + c.n_seq);
+            if (csvgpu_download(x, out.seq_off.data() + r0, o.seq_off, (k + 1) * 8) || (c.n_seq && csvgpu_download(x, out.seq.data() + seq_at, o.seq, c.n_seq))) return dev_fail();
+        }
+        if (opt.want_qnames) {
+            std::vector<uint64_t> name_off(k + 1);
+            std::vector<uint8_t> name((size_t)c.n_name + 1);
+            if (csvgpu_download(x, name_off.data(), o.name_off, (k + 1) * 8) || (c.n_name && csvgpu_download(x, name.data(), o.name, c.n_name))) return dev_fail();
+            out.qnames.resize(r0 + k);
+            for (size_t i = 0; i < k; i++) out.qnames[r0 + i].assign((const char *)name.data() + name_off[i], (size_t)(name_off[i + 1] - name_off[i]));
+        }
+    }
+    unpack_stats.batches_device++;
+    unpack_stats.anchors += anchors.size();
+    unpack_stats.records += c.n_kept;
+    *consumed = (size_t)c.consumed;
+    *stop = c.stopped != 0;
+    return 1;
+}
+
 bool BamReader::readContig(const std::string &chr, const BamReadOptions &opt, BamShard &out)
 {
     err.clear();
@@ -372,6 +592,7 @@ bool BamReader::readContig(const std::string &chr, const BamReadOptions &opt, Ba
     if (tid < 0) { err = "BAM: unknown contig " + chr; return false; }
     if (!index) { err = "BAM: no index loaded for " + path; return false; }
     out.clear();
+    unpack_stats = UnpackStats();
     out.tid = tid; out.name = chr; out.target_len = hdr.lens[tid];
     if ((size_t)tid >= index->refs.size() || !index->refs[tid].any) return true;
     const Index::Ref &ref = index->refs[tid];
@@ -381,6 +602,8 @@ bool BamReader::readContig(const std::string &chr, const BamReadOptions &opt, Ba
     const uint64_t span = std::min<uint64_t>((ref.max_end >> 16) - (ref.min_beg >> 16), file.size()) + bgzf::kMaxBlock;
     out.cigar.reserve((size_t)(span * 4 / 4));            // ~4x compression of CIGAR words is typical; growth is by mremap anyway
     const int64_t end = hdr.lens[tid];
+    RawFn on_raw;
+    if (opt.device_unpack) on_raw = [&](const RawBatch &b, size_t *consumed, bool *stop) { return unpackBatch(b, tid, end, ref.anchors, opt, out, consumed, stop); };
     return stream(ref.min_beg, opt, [&](const RecRef *recs, size_t n) -> size_t {
         // the contig's records are one run in a sorted file: skip an earlier contig's tail, stop at a later one / unplaced / past the end
         size_t a = 0;
@@ -389,7 +612,7 @@ bool BamReader::readContig(const std::string &chr, const BamReadOptions &opt, Ba
         while (b < n && (int32_t)le32(recs[b].p) == tid && (int32_t)le32(recs[b].p + 4) < end) b++;
         if (!append(recs + a, b - a, opt, out)) return 0;
         return b == n ? n : b;                            // anything left over ends the iteration
-    }) && err.empty();
+    }, on_raw) && err.empty();
 }
 
 bool BamReader::readAll(const BamReadOptions &opt, const std::function<void(BamShard &&)> &sink, uint64_t *n_unplaced)

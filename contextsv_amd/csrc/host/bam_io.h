@@ -50,6 +50,11 @@ struct BamReadOptions {
     csv_ctx *device_inflate = nullptr;                // not null: the batches are inflated on this context's device (bgzf::inflate_range_device), whatever it
                                                       // declines on the host. The batches are loaded on a thread of their own, so the context is the reader's
                                                       // own, never one that runs anything else meanwhile. Null: the host's decoders. Same records either way.
+    csv_ctx *device_unpack = nullptr;                 // not null (readContig alone): every batch's records are unpacked on this context's device
+                                                      // (csvgpu_bam_unpack, cut at the index's chunk begins and linear offsets) straight into the shard's
+                                                      // arrays; a batch the device declines goes through the host parser, so records and messages are the
+                                                      // host route's. The reader's own context: the same one as device_inflate when both are set (the next
+                                                      // batch is then loaded behind the unpack, not beside it). Null: the host parser.
 };
 
 class BamReader {
@@ -74,16 +79,32 @@ public:
 
     uint64_t bytes() const { return file.size(); }
 
+    // What BamReadOptions::device_unpack did in the last readContig: batches the device unpacked / declined or was not given (the host parser
+    // read those), anchors handed to the device in the unpacked batches (1 per batch = none from the index), records it wrote, batches whose
+    // decoded bytes never came to the host (inflated on the device straight into the unpack's buffer), batches brought down after all.
+    struct UnpackStats { uint64_t batches_device = 0, batches_host = 0, anchors = 0, records = 0, batches_kept_on_device = 0, batches_downloaded = 0; };
+    const UnpackStats &unpackStats() const { return unpack_stats; }
+
 private:
     struct Index;
     struct RecRef { const uint8_t *p; uint32_t len; };        // one record behind its block_size field
+    struct DevBufs;
+    // One inflated batch as bytes ON THE DEVICE (the reader's own buffer), before the host parser has looked at it: d[0, n) = `carried` bytes
+    // of the batch before + the batch's blocks from `skip` bytes into the first one on.
+    struct RawBatch { const uint8_t *d; size_t n, carried, skip; const std::vector<bgzf::Block> *blocks; DevBufs *dev; };
+    // 0: not taken, the host parser takes the batch; 1: taken, *consumed = offset of the first incomplete record, *stop = the stream ends here;
+    // -1: failed (error() set)
+    typedef std::function<int(const RawBatch &, size_t *consumed, bool *stop)> RawFn;
     // Hands the records of each inflated batch to on_batch, which returns how many of them it consumed: fewer than n ends the stream.
-    bool stream(uint64_t start_voffset, const BamReadOptions &opt, const std::function<size_t(const RecRef *, size_t)> &on_batch);
+    // on_raw (optional) sees every batch first.
+    bool stream(uint64_t start_voffset, const BamReadOptions &opt, const std::function<size_t(const RecRef *, size_t)> &on_batch, const RawFn &on_raw = nullptr);
+    int unpackBatch(const RawBatch &b, int tid, int64_t end, const std::vector<uint64_t> &candidates, const BamReadOptions &opt, BamShard &out, size_t *consumed, bool *stop);
     bool append(const RecRef *recs, size_t n, const BamReadOptions &opt, BamShard &out);
     bgzf::MappedFile file;
     BamHeader hdr;
     uint64_t first_record_voffset = 0;
     std::unique_ptr<Index> index;
+    UnpackStats unpack_stats;
     std::string path, err;
 };
 

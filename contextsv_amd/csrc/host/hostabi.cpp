@@ -1003,7 +1003,9 @@ int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fas
 // ---- BAM / BAI reader and writer (bam_io) --------------------------------------------------------------
 struct csvhost_bam {
     BamReader r; std::vector<BamShard> shards; std::string names;
-    csv_ctx *inflate_ctx = nullptr;          // csvhost_bam_set_device_inflate: the reader's own context
+    csv_ctx *inflate_ctx = nullptr;          // csvhost_bam_set_device_inflate / _unpack: the reader's own context, one for both
+    int ctx_device = -1;
+    bool inflate_on = false, unpack_on = false;
     ~csvhost_bam() { if (inflate_ctx) csvgpu_destroy(inflate_ctx); }
 };
 
@@ -1022,16 +1024,34 @@ uint32_t csvhost_bam_ref_len(const csvhost_bam *h, int tid) { return h->r.header
 
 // device >= 0: the reads that follow inflate the BGZF blocks on that device, on a context of the handle's own (BamReadOptions::device_inflate);
 // -1: on the host again. 0, or -1 with the reason in csvhost_last_error.
-int csvhost_bam_set_device_inflate(csvhost_bam *h, int device_or_minus_1)
+// The handle has ONE context for both options: a second option must name the device of the first (refused otherwise, nothing changed).
+static int bam_set_device(csvhost_bam *h, bool &on, int device_or_minus_1)
 {
     try {
-        if (h->inflate_ctx) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; }
-        if (device_or_minus_1 < 0) return 0;
-        h->inflate_ctx = csvgpu_create(device_or_minus_1, nullptr);
-        if (!h->inflate_ctx) { g_err = std::string("no device context for the BAM reader: ") + csvgpu_last_error(nullptr); return -1; }
+        const bool other = &on == &h->inflate_on ? h->unpack_on : h->inflate_on;
+        if (device_or_minus_1 < 0) {
+            on = false;
+            if (!other && h->inflate_ctx) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
+            return 0;
+        }
+        if (other && h->inflate_ctx && h->ctx_device != device_or_minus_1) {
+            g_err = "the BAM reader's context is on device " + std::to_string(h->ctx_device) + ": inflate and unpack share it, switch the other option off first";
+            return -1;
+        }
+        if (h->inflate_ctx && h->ctx_device != device_or_minus_1) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
+        if (!h->inflate_ctx) {
+            h->inflate_ctx = csvgpu_create(device_or_minus_1, nullptr);
+            if (!h->inflate_ctx) { on = false; g_err = std::string("no device context for the BAM reader: ") + csvgpu_last_error(nullptr); return -1; }
+            h->ctx_device = device_or_minus_1;
+        }
+        on = true;
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+int csvhost_bam_set_device_inflate(csvhost_bam *h, int device_or_minus_1) { return bam_set_device(h, h->inflate_on, device_or_minus_1); }
+// device >= 0: the readContig calls that follow unpack every batch's records on that device (BamReadOptions::device_unpack), on the handle's
+// own context — the one the inflate uses when both are set; -1: the host parser again. readAll keeps the host parser either way.
+int csvhost_bam_set_device_unpack(csvhost_bam *h, int device_or_minus_1) { return bam_set_device(h, h->unpack_on, device_or_minus_1); }
 
 // Every BGZF block of a file inflated in batches of window_blocks, on `threads` host threads (ctx null: bgzf::inflate_range) or on ctx's device
 // (bgzf::inflate_range_device), into one buffer that is reused: what tools/bench_inflate.py times. *ms: the inflate alone (the block scan before it).
@@ -1072,7 +1092,8 @@ int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qna
         BamReadOptions opt;
         opt.want_seq = want_seq != 0; opt.want_qnames = want_qnames != 0; opt.threads = threads;
         if (window_blocks) opt.window_blocks = window_blocks;
-        opt.device_inflate = h->inflate_ctx;
+        opt.device_inflate = h->inflate_on ? h->inflate_ctx : nullptr;
+        opt.device_unpack = h->unpack_on && chr ? h->inflate_ctx : nullptr;
         h->shards.clear();
         bool ok;
         if (chr) { h->shards.emplace_back(); ok = h->r.readContig(chr, opt, h->shards.back()); }
@@ -1080,6 +1101,13 @@ int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qna
         if (!ok) { g_err = h->r.error(); h->shards.clear(); return -1; }
         return (int)h->shards.size();
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// BamReader::UnpackStats of the last csvhost_bam_read with a contig name: batches the device unpacked, batches the host parser read, anchors
+// given to the device, records the device wrote, batches whose decoded bytes never came to the host, batches brought down after all
+void csvhost_bam_unpack_stats(const csvhost_bam *h, uint64_t out[6])
+{
+    const BamReader::UnpackStats &u = h->r.unpackStats();
+    out[0] = u.batches_device; out[1] = u.batches_host; out[2] = u.anchors; out[3] = u.records; out[4] = u.batches_kept_on_device; out[5] = u.batches_downloaded;
 }
 // view of shard i: arrays stay owned by the handle until the next read / close
 void csvhost_bam_shard(const csvhost_bam *h, int i, csv_reads *reads, int32_t *tid, uint32_t *target_len, const uint64_t **seq_off, const uint8_t **seq)
@@ -1197,12 +1225,13 @@ int csvhost_bam_writer_close(csvhost_bam_writer *h)
     })
 }
 
-struct csvhost_bam_stats { uint64_t n_contigs, n_reads, n_cigar, bam_bytes; double ms_decode, ms_total; };
+struct csvhost_bam_stats { uint64_t n_contigs, n_reads, n_cigar, bam_bytes; double ms_decode, ms_total;
+                           uint64_t unpack_batches_device, unpack_batches_host, unpack_anchors, unpack_batches_kept_on_device; };
 
 // SVCaller::runBam: chrs = '\n'-separated contig names or null (all). SNPs: none (every window gets the dummy observation).
 // Calls come back grouped by contig in header order, with their contig index in out_tid.
 int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int threads, const csv_hmm *hmm, double eps, double min_pts_pct,
-                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv; 9-13, 24-30: below */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
+                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv; 9-14, 24-30: below */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
                     const char *file_date, csvhost_call *out, int32_t *out_tid, uint64_t cap, uint64_t *n_out, csvhost_bam_stats *stats,
                     const char *snp_vcf, const char *pfb_table, const char *ethnicity)
 {
@@ -1219,6 +1248,7 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         P.split_groups_on_device = (passes & 512) != 0; P.split_fits_on_device = (passes & 1024) != 0; P.split_tables_on_device = (passes & 2048) != 0;
         P.cn_observations_on_device = (passes & 4096) != 0;
         P.inflate_on_device = (passes & 8192) != 0; P.inflate_device = (passes >> 24) & 0x7f;
+        P.unpack_on_device = (passes & 16384) != 0;
         P.snp_vcf = snp_vcf ? snp_vcf : ""; P.pfb_table = pfb_table ? pfb_table : ""; P.ethnicity = ethnicity ? ethnicity : "";
         if (fasta && vcf_dir) {
             P.ref_genome = fasta_genome(fasta);
@@ -1246,7 +1276,9 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         }
         *n_out = k;
         if (stats) { stats->n_contigs = bs.n_contigs; stats->n_reads = bs.n_reads; stats->n_cigar = bs.n_cigar; stats->bam_bytes = bs.bam_bytes;
-                     stats->ms_decode = bs.ms_decode; stats->ms_total = bs.ms_total; }
+                     stats->ms_decode = bs.ms_decode; stats->ms_total = bs.ms_total;
+                     stats->unpack_batches_device = bs.unpack_batches_device; stats->unpack_batches_host = bs.unpack_batches_host;
+                     stats->unpack_anchors = bs.unpack_anchors; stats->unpack_batches_kept_on_device = bs.unpack_batches_kept_on_device; }
     })
 }
 

@@ -1183,6 +1183,11 @@ struct BamSource : ContigSource {
         const bool ok = pending.get();
         st.ms_decode += now_ms() - t0;
         if (!ok) throw std::runtime_error(reader.error());
+        {   // (the reader is between two contigs here: the counters are this contig's)
+            const BamReader::UnpackStats &u = reader.unpackStats();
+            st.unpack_batches_device += u.batches_device; st.unpack_batches_host += u.batches_host; st.unpack_anchors += u.anchors;
+            st.unpack_batches_kept_on_device += u.batches_kept_on_device;
+        }
         std::swap(cur, ahead);
         if (i + 1 < chrs.size()) launch(i + 1);
         seq.seq_off = cur.seq_off.data();
@@ -1222,10 +1227,11 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
         }
     }
     src.opt.threads = std::max(1, threads);
-    if (P.inflate_on_device) {
+    if (P.inflate_on_device || P.unpack_on_device) {
         inflate_ctx.c = csvgpu_create(P.inflate_device, nullptr);
         if (!inflate_ctx.c) throw std::runtime_error(std::string("ERROR: no device context for the BAM reader: ") + csvgpu_last_error(nullptr));
-        src.opt.device_inflate = inflate_ctx.c;
+        if (P.inflate_on_device) src.opt.device_inflate = inflate_ctx.c;
+        if (P.unpack_on_device) src.opt.device_unpack = inflate_ctx.c;         // (one context for both: the reader's thread is its only user)
     }
     SNPFile snp_file;
     AlleleFreqFiles af_files;

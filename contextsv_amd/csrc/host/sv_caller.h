@@ -114,6 +114,9 @@ struct RunParams {
     bool inflate_on_device = false;         // runBam: the BAM's BGZF blocks inflated on the device (csvgpu_bgzf_inflate on a context of the reader's own, created on
     int inflate_device = 0;                 // device `inflate_device` — the run's — for the run's length) instead of on the host's threads; whatever the device declines is
                                             // decoded on the host, every block is CRC-checked either way; the records, and so the calls, do not depend on it
+    bool unpack_on_device = false;          // runBam: every batch's records unpacked on the device (csvgpu_bam_unpack, BamReadOptions::device_unpack) on the reader's own
+                                            // context — the inflate's when both are set — instead of by the host parser; a batch the device declines goes through
+                                            // the host parser, so the records, and so the calls, do not depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it
@@ -130,6 +133,9 @@ struct BamRunStats {
     uint64_t n_contigs = 0, n_reads = 0, n_cigar = 0, bam_bytes = 0;
     double ms_decode = 0.0;          // wall time spent waiting for decoded contigs (decode not hidden behind the device)
     double ms_total = 0.0;
+    // RunParams::unpack_on_device: batches the device unpacked / the host parser read, anchors given to the device, batches whose decoded
+    // bytes never came to the host (BamReader::UnpackStats, summed over the contigs)
+    uint64_t unpack_batches_device = 0, unpack_batches_host = 0, unpack_anchors = 0, unpack_batches_kept_on_device = 0;
 };
 
 // A SplitGroupSource that asks csvgpu_split_groups on `ctx` (SplitParams::device_groups); the caller keeps the context alive and uses it from the

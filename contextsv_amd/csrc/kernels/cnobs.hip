@@ -22,20 +22,16 @@
 namespace csv {
 
 // ---- std::hash<std::string> of "ws-we" -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t cn_shift_mix(uint64_t v) { return v ^ (v >> 47); }
-
-// libstdc++'s _Hash_bytes for 64-bit size_t (a Murmur-style hash, seed 0xc70f6907) of the `len` <= 24 bytes held little-endian in w0, w1, w2
-// (bytes beyond len are zero): whole 8-byte blocks, then the 1..7 tail bytes as one little-endian number.
+// libstdc++'s _Hash_bytes (the steps of devutil.hpp) of the `len` <= 24 bytes held little-endian in w0, w1, w2 (bytes beyond len are
+// zero): whole 8-byte blocks, then the 1..7 tail bytes as one little-endian number.
 __device__ __forceinline__ uint64_t cn_hash_bytes(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t len)
 {
-    constexpr uint64_t mul = (0xc6a4a793ull << 32) + 0x5bd1e995ull;
-    uint64_t hash = 0xc70f6907ull ^ ((uint64_t)len * mul);
+    uint64_t hash = hb_init(len);
     const uint32_t blocks = len >> 3;
-    if (blocks >= 1) { hash ^= cn_shift_mix(w0 * mul) * mul; hash *= mul; }
-    if (blocks >= 2) { hash ^= cn_shift_mix(w1 * mul) * mul; hash *= mul; }
-    if (len & 7u) { hash ^= blocks == 0 ? w0 : (blocks == 1 ? w1 : w2); hash *= mul; }
-    hash = cn_shift_mix(hash) * mul;
-    return cn_shift_mix(hash);
+    if (blocks >= 1) hash = hb_block(hash, w0);
+    if (blocks >= 2) hash = hb_block(hash, w1);
+    if (len & 7u) hash = hb_tail(hash, blocks == 0 ? w0 : (blocks == 1 ? w1 : w2));
+    return hb_final(hash);
 }
 
 // The key text is built from its last character to its first — a division yields the digits in that order — by shifting the three words

@@ -3,6 +3,8 @@
 // is. Pads that a kernel relies on are part of their slice and are named where they are taken. Free of HIP calls: the CPU-only check
 // (tools/fuzz/arena_layouts_check.cpp) runs every function listed in kLayoutNames at the rounding edges.
 #pragma once
+#include <algorithm>
+
 #include "common.hpp"
 
 namespace csv {
@@ -10,7 +12,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "bgzf", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "bgzf", "bam_unpack", "dbscan_tmp", "viterbi_tmp"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -238,6 +240,33 @@ static inline bool carve_bgzf(Arena &a, uint64_t n_blocks, bool io, uint64_t com
     const bool ok = take(a, w.blocks, n_blocks * sizeof(csv_bgzf_block)) && take(a, w.n_declined, 256);
     if (!io) return ok;
     return ok && take(a, w.comp, comp_len) && take(a, w.out, out_len) && take(a, w.status, n_blocks);
+}
+
+// BAM records unpacked on the device (csvgpu_bam_unpack / _dev) from a stream of `len` bytes cut at n_anchors anchors: the head (counts,
+// status, filter bounds), the anchors and their intervals' counts, every record's start and the kept records' counts — a record takes at
+// least 36 bytes, which bounds them all before anything has run — and for the host-pointer form (io) the stream itself and the outputs,
+// sized by the caller's capacities where those are below what the stream can hold (n_seq / n_name 0, hash false: not wanted)
+static inline uint64_t bam_unpack_max_records(uint64_t len) { return len / 36; }
+static inline bool carve_bam_unpack(Arena &a, uint64_t len, uint64_t n_anchors, bool io, uint64_t n_rec, uint64_t n_cigar, uint64_t n_seq, uint64_t n_name, bool hash,
+                                    BamUnpackWs &w)
+{
+    const uint64_t R = bam_unpack_max_records(len);
+    char *head = nullptr;
+    const bool ok = take(a, head, 256) && take(a, w.anchors, n_anchors * 4) && take(a, w.count, (n_anchors + 1) * 4) && take(a, w.rec_off, R * 4) &&
+                    take(a, w.cig_src, (R + 1) * 4) && take(a, w.cig_n, (R + 1) * 4) && take(a, w.seq_n, (R + 1) * 4) && take(a, w.name_n, (R + 1) * 4) &&
+                    take(a, w.es_tmp, exclusive_sum_tmp_bytes(std::max(R, n_anchors) + 1));
+    if (!ok) return false;
+    w.res = (uint32_t *)head; w.status = (unsigned long long *)(head + BU_RES_WORDS * 4); w.bounds = (uint32_t *)(head + BU_RES_WORDS * 4 + 8);
+    w.rec_cap = (uint32_t)R;
+    w.bytes = nullptr; w.out = BamUnpackOut{};
+    if (!io) return true;
+    n_rec = std::min(n_rec, R); n_cigar = std::min(n_cigar, len / 4); n_seq = std::min(n_seq, len); n_name = std::min(n_name, len);
+    bool k = take(a, w.bytes, len + 4) && take(a, w.out.pos, n_rec * 4) && take(a, w.out.flag, n_rec * 2) && take(a, w.out.mapq, n_rec) &&
+             take(a, w.out.cigar_off, (n_rec + 1) * 8) && take(a, w.out.cigar, n_cigar * 4);
+    if (n_seq) k = k && take(a, w.out.seq_off, (n_rec + 1) * 8) && take(a, w.out.seq, n_seq);
+    if (n_name) k = k && take(a, w.out.name_off, (n_rec + 1) * 8) && take(a, w.out.name, n_name);
+    if (hash) k = k && take(a, w.out.name_hash, n_rec * 8);
+    return k;
 }
 
 // ---- the kernels' own temporaries (one opaque `tmp` to their callers) ----------------------------------------------------------------

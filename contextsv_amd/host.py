@@ -25,7 +25,8 @@ class chr_stats(C.Structure):
 
 class bam_stats(C.Structure):
     _fields_ = [("n_contigs", C.c_uint64), ("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("bam_bytes", C.c_uint64),
-                ("ms_decode", C.c_double), ("ms_total", C.c_double)]
+                ("ms_decode", C.c_double), ("ms_total", C.c_double), ("unpack_batches_device", C.c_uint64), ("unpack_batches_host", C.c_uint64),
+                ("unpack_anchors", C.c_uint64), ("unpack_batches_kept_on_device", C.c_uint64)]
 
 
 class stage_times(C.Structure):
@@ -104,6 +105,9 @@ def load() -> C.CDLL:
     lib.csvhost_bam_ref_len.argtypes = [_P, C.c_int]
     lib.csvhost_bam_read.argtypes = [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
     lib.csvhost_bam_set_device_inflate.argtypes = [_P, C.c_int]
+    lib.csvhost_bam_set_device_unpack.argtypes = [_P, C.c_int]
+    lib.csvhost_bam_unpack_stats.restype = None
+    lib.csvhost_bam_unpack_stats.argtypes = [_P, C.POINTER(C.c_uint64 * 6)]
     lib.csvhost_bgzf_inflate_file.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     lib.csvhost_bam_shard.argtypes = [_P, C.c_int, C.POINTER(_lib.csv_reads), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P)]
     lib.csvhost_bam_shard_qnames.restype = C.c_int64
@@ -741,6 +745,7 @@ class BamFile:
 
     def __init__(self, path: str, load_index: bool = True):
         self._inflate_device = -1
+        self._unpack_device = -1
         self.h = load().csvhost_bam_open(os.fsencode(path), int(load_index))
         if not self.h:
             raise RuntimeError((load().csvhost_last_error() or b"cannot open BAM").decode())
@@ -788,8 +793,25 @@ class BamFile:
                 raise RuntimeError((load().csvhost_last_error() or b"no device context for the BAM reader").decode())
             self._inflate_device = want
 
-    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0):
+    def _unpack_on(self, on, device):
+        """where the next read_contig unpacks the records of its batches: on `device` (csvgpu_bam_unpack on the reader's own context, the
+        inflate's when both are on; a batch the device declines is parsed on the host) or by the host parser"""
+        want = int(device) if on else -1
+        if want != self._unpack_device:
+            if load().csvhost_bam_set_device_unpack(self.h, want) != 0:
+                raise RuntimeError((load().csvhost_last_error() or b"no device context for the BAM reader").decode())
+            self._unpack_device = want
+
+    def unpack_stats(self) -> dict:
+        """what unpack_on_device did in the last read_contig: batches the device unpacked / the host parser read (declined, or not given),
+        anchors handed to the device, records it wrote, batches whose decoded bytes never came to the host, batches brought down after all"""
+        v = (C.c_uint64 * 6)()
+        load().csvhost_bam_unpack_stats(self.h, C.byref(v))
+        return dict(zip(("batches_device", "batches_host", "anchors", "records", "batches_kept_on_device", "batches_downloaded"), (int(x) for x in v)))
+
+    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0, unpack_on_device=False):
         self._inflate_on(inflate_on_device, device)
+        self._unpack_on(unpack_on_device, device)
         k = load().csvhost_bam_read(self.h, chr.encode(), int(want_seq), int(want_qnames), threads, window_blocks, None)
         if k < 0:
             raise RuntimeError((load().csvhost_last_error() or b"BAM read failed").decode())
@@ -831,12 +853,14 @@ def write_bam(path: str, ref_names, ref_lens, tid, reads: Reads, qnames, seq_off
 def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, save_cnv=False,
             genome: ReferenceGenome | None = None, vcf_dir=None, gap_path=None, file_date=None, capacity: int = 1 << 20,
             snp_vcf=None, pfb_table=None, ethnicity="", inflate_on_device: bool = False, split_groups_on_device: bool = False, split_fits_on_device: bool = False,
-            split_tables_on_device: bool = False, cn_observations_on_device: bool = False):
+            split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False):
     """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict).
+    unpack_on_device: the records of every batch are unpacked on ctx's device (csvgpu_bam_unpack, on the reader's own context) instead of
+    by the host parser; a batch the device declines is parsed on the host.
     inflate_on_device: the BAM's BGZF blocks are inflated on ctx's device (csvgpu_bgzf_inflate, on a context of the reader's own) instead of
     on the host's threads; the other switches as in run(). None of them changes the calls."""
     opt_in = (int(bool(split_groups_on_device)) << 9) | (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | \
-             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
+             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | (int(bool(unpack_on_device)) << 14) | ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
     out = np.zeros(capacity, CALL_DTYPE)
     tid = np.zeros(capacity, np.int32)
     n = C.c_uint64(0)

@@ -503,6 +503,13 @@ int csvgpu_depth_lookup_resident(csv_ctx *ctx, csv_shard *shard, const uint32_t 
 /* Copy `bytes` from device memory returned by this library (csv_chr_result pointers) to host memory;
  * synchronous with respect to the context's stream. For host code above the ABI that does not link HIP. */
 int csvgpu_download(csv_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
+/* Device memory for a caller that links the C-ABI alone and chains `_dev` entry points (the host mirror's BAM reader keeps a batch's decoded
+ * bytes and the unpacked arrays in such buffers between csvgpu_bgzf_inflate_dev and csvgpu_bam_unpack_dev). alloc: NULL on failure
+ * (csvgpu_last_error); free waits for the context's stream first. csvgpu_upload copies host bytes (pageable: through the context's page-locked
+ * block, in pieces) to device memory and waits. */
+void *csvgpu_dev_alloc(csv_ctx *ctx, size_t bytes);
+void  csvgpu_dev_free(csv_ctx *ctx, void *dev_ptr);
+int   csvgpu_upload(csv_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
 
 /* Device-pointer twins of the clustering / HMM entry points (same semantics as above). */
 int csvgpu_dbscan_iv_dev(csv_ctx *ctx, const uint32_t *d_start, const uint32_t *d_end, uint64_t n,
@@ -548,6 +555,70 @@ int csvgpu_bgzf_inflate(csv_ctx *ctx, const uint8_t *comp, uint64_t comp_len, co
  * record-unpacking kernel. Waits for the kernel (the return value is its count of declined members). */
 int csvgpu_bgzf_inflate_dev(csv_ctx *ctx, const uint8_t *d_comp, uint64_t comp_len, const csv_bgzf_block *blocks, uint32_t n_blocks,
                             uint8_t *d_out, uint64_t out_len, uint8_t *d_status);
+
+/* ------------------------------------------------------------------------------------------ */
+/* BAM records unpacked on the device (opt-in: the from-file path parses on the host by default) */
+/* A decoded BAM record stream bytes[0, len) (what the members of a BGZF file decode to, behind the header; len < 2^32) to the arrays of
+ * csv_reads: what the host reader makes of the same bytes from bam1_core_t's fields, bam_get_cigar / bam_get_qname / bam_get_seq and
+ * bam_tag2cigar (a CIGAR of more than 65 535 operations is taken from its CG:B,I tag), bit for bit.
+ * The outputs of ONE call: every pointer is where this call's first kept record goes (a caller that appends behind an earlier call
+ * advances them). pos / flag / mapq [cap_records]; cigar_off [cap_records + 1], cigar [cap_cigar] words. Optional, null = not wanted:
+ * seq_off [cap_records + 1] with seq [cap_seq] (4-bit packed, (l_seq + 1) / 2 bytes a record), name_off [cap_records + 1] with name
+ * [cap_name] (strnlen within l_name bytes a record, no terminator), name_hash [cap_records] (libstdc++'s std::hash<std::string> of the
+ * name: what csvgpu_shard_set_qname_hash takes). An offset array and its data are wanted together. */
+typedef struct csv_bam_out {
+    int32_t  *pos;
+    uint16_t *flag;
+    uint8_t  *mapq;
+    uint64_t *cigar_off;
+    uint32_t *cigar;
+    uint64_t *seq_off;
+    uint8_t  *seq;
+    uint64_t *name_off;
+    uint8_t  *name;
+    uint64_t *name_hash;
+    uint64_t  cap_records, cap_cigar, cap_seq, cap_name;
+} csv_bam_out;
+
+/* reasons in csv_bam_counts::status (bits 0-7; bits 8-39: the offset the check failed at) */
+enum { CSV_BAM_SHORT = 1,        /* block_size < 32 */
+       CSV_BAM_LONG = 2,         /* block_size > 2^30 */
+       CSV_BAM_NEG_LSEQ = 3,     /* l_seq < 0 (a kept record) */
+       CSV_BAM_FIELDS = 4,       /* name + CIGAR + sequence + qualities longer than the record (a kept record) */
+       CSV_BAM_ANCHOR = 5 };     /* anchor missed: no record starts at this anchor */
+
+typedef struct csv_bam_counts {
+    uint64_t n_records;          /* whole records in the stream */
+    uint64_t kept_first;         /* index of the first kept record among them */
+    uint64_t n_kept;             /* records written */
+    uint64_t n_cigar, n_seq, n_name;   /* CIGAR words, sequence bytes, name bytes of the kept records */
+    uint64_t consumed;           /* offset of the first incomplete record: [consumed, len) is the caller's carry */
+    uint64_t status;             /* 0, or why the stream was declined: (offset << 8) | reason, the lowest failing offset */
+    uint32_t stopped;            /* a record behind the kept run exists: the contig has ended */
+    uint32_t reserved;
+} csv_bam_counts;
+
+/* anchors[0 .. n_anchors): strictly ascending offsets in [0, len) that are claimed to be record starts (a BAI's chunk begins and linear-index
+ * offsets mapped into the buffer, or a walk of the caller's); anchors[0] IS the first record's start. They only divide the walk along the
+ * record chain among the lanes and are never believed: a walk that does not land exactly on the next anchor declines the stream
+ * (CSV_BAM_ANCHOR). One anchor is a walk by one lane: correct, and slow.
+ * tid >= 0: the records of that contig as the host reader's readContig selects them — a leading run with 0 <= refID < tid is skipped,
+ * records are kept while refID == tid and pos < end, the first other record ends the run (counts->stopped). tid < 0: every record.
+ * The host reader's checks apply in its order (block_size on every record; l_seq and the fixed part on the kept ones); offsets written are
+ * cigar_base / seq_base / name_base + the exclusive sums of the kept records' counts, so that a second call appends behind a first.
+ * Returns CSV_OK with the counts filled and the arrays written; 1 when the stream is declined: counts->status says why and where,
+ * consumed and the other counts are 0, the outputs are unspecified (nothing outside their capacities is ever written) and the caller parses
+ * the bytes itself; CSV_ECAPACITY when a capacity is too small: the exact counts are filled in, nothing is written; CSV_EINVAL for a null
+ * pointer, len >= 2^32, no anchor for a non-empty stream (len == 0 does nothing and returns CSV_OK with zero counts), anchors that are not strictly ascending or lie outside [0, len), an offset
+ * array without its data — nothing reaches the device then. Whatever the bytes are, nothing outside [0, len) is read beyond the aligned
+ * 4-byte word that holds a byte of it. Timed under CSV_K_MISC.
+ * _dev: bytes and the outputs are device pointers (anchors and counts the host's): behind csvgpu_bgzf_inflate_dev the bytes never leave
+ * the device, and the arrays are what csvgpu_shard_wrap_dev takes. Host pointers: the stream travels up and the arrays back through the
+ * context's page-locked block, in pieces. Both wait for their kernels. */
+int csvgpu_bam_unpack_dev(csv_ctx *ctx, const uint8_t *d_bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
+                          uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const csv_bam_out *d_out, csv_bam_counts *counts);
+int csvgpu_bam_unpack(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
+                      uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const csv_bam_out *out, csv_bam_counts *counts);
 
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations

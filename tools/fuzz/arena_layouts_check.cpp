@@ -111,6 +111,15 @@ int main()
                 });
             }
             for (int io : {0, 1}) { BgzfWs w; run_case(tag("bgzf", {n, m, (uint64_t)io}), [&](Arena &a) { return carve_bgzf(a, n, io != 0, m, (n + m) % 1009 * 65, w); }); }   // n members, m compressed bytes
+            for (int io : {0, 1}) {   // a stream of n * 36 + m % 36 bytes (n records at most) cut at m anchors; the outputs' capacities run along
+                BamUnpackWs w;
+                const uint64_t len = n * 36 + m % 36;
+                run_case(tag("bam_unpack", {n, m, (uint64_t)io}), [&](Arena &a) { return carve_bam_unpack(a, len, m, io != 0, (n + m) % 1009, m, n % 3 ? m : 0, m % 3 ? n : 0, (n + m) % 2 != 0, w); },
+                         [&](char *lo, char *hi) {
+                             return bam_unpack_max_records(len) == n && (char *)w.res >= lo && (char *)(w.bounds + 2) <= (char *)w.res + BU_HEAD_BYTES && (char *)w.res + 256 <= hi &&
+                                    (char *)w.status == (char *)w.res + 32 && ((uintptr_t)w.status & 7) == 0;
+                         });
+            }
             { SplitTablesOut w; run_case(tag("sr_tables", {n, m}), [&](Arena &a) { return sr_carve(a, n, m, w); }); }
             for (int with : {0, 1}) { SplitFitsIn w; run_case(tag("sf_tables", {n, m, (uint64_t)with}), [&](Arena &a) { return carve_sf_tables(a, n, m, with != 0, w); }); }
             {   // n members in m segments; the block cleared by one memset holds six sub-slices
@@ -149,7 +158,7 @@ int main()
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
     const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
-                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"bgzf", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
+                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"bgzf", 2}, {"bam_unpack", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
         const auto it = n_counts.find(kv.first);
