@@ -87,6 +87,13 @@ class csv_bam_counts(C.Structure):
                 ("n_name", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint64), ("stopped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class csv_shard_sizes(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq", C.c_uint64), ("n_name", C.c_uint64)]
+
+
+# csv_shard_builder's `want` bits
+SB_SEQ, SB_NAMES, SB_NAME_HASH = 1, 2, 4
+
 # csv_bam_counts::status: (offset << 8) | reason
 BAM_SHORT, BAM_LONG, BAM_NEG_LSEQ, BAM_FIELDS, BAM_ANCHOR = 1, 2, 3, 4, 5
 BAM_REASONS = {1: "record shorter than its fixed fields", 2: "implausible record length", 3: "negative sequence length",
@@ -156,6 +163,17 @@ ABI = {
                                     C.POINTER(csv_bam_counts)]),
     "csvgpu_bam_unpack_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(csv_bam_out),
                                         C.POINTER(csv_bam_counts)]),
+    "csvgpu_shard_builder_create": (_P, [_P, C.c_uint32, C.POINTER(csv_shard_sizes)]),
+    "csvgpu_shard_builder_append_bam": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.POINTER(csv_bam_counts)]),
+    "csvgpu_shard_builder_append_host": (C.c_int, [_P, _P, C.POINTER(csv_reads), _P, _P, _P, _P, _P]),
+    "csvgpu_shard_builder_sizes": (C.c_int, [_P, _P, C.POINTER(csv_shard_sizes)]),
+    "csvgpu_shard_builder_finish": (_P, [_P, _P, C.c_uint32]),
+    "csvgpu_shard_builder_destroy": (None, [_P, _P]),
+    "csvgpu_shard_sizes": (C.c_int, [_P, _P, C.POINTER(csv_shard_sizes)]),
+    "csvgpu_shard_fetch_reads": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "csvgpu_shard_fetch_names": (C.c_int, [_P, _P, _P, _P, _P]),
+    "csvgpu_shard_drop_sequences": (C.c_int, [_P, _P]),
+    "csvgpu_alt_bases_resident": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, _P]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

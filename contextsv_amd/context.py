@@ -604,6 +604,104 @@ class Context:
                                      keep=(pos, flag, mapq, cigar_off, cigar))
 
 
+    # -------------------------------------------------------------------------------- shards built on the device
+    def shard_builder(self, want: int = 0, reserve=None) -> "ShardBuilder":
+        """csvgpu_shard_builder_create: a resident shard that grows on the device, batch by batch. want: _lib.SB_SEQ | SB_NAMES |
+        SB_NAME_HASH; reserve: (n_reads, n_cigar, n_seq, n_name) allocated now, or None."""
+        return ShardBuilder(self, want, reserve)
+
+    def alt_bases(self, shard: "Shard", read, qpos, lengths):
+        """csvgpu_alt_bases_resident: for item i the `lengths[i]` bases from query offset qpos[i] of record read[i], cut from the packed
+        sequences a built shard holds (ambiguity codes as N; all N where the bases leave the stored sequence) -> list of str."""
+        read, qpos = np.ascontiguousarray(read, np.uint32), np.ascontiguousarray(qpos, np.uint32)
+        off = np.zeros(len(read) + 1, np.uint64)
+        off[1:] = np.cumsum(np.asarray(lengths, np.uint64), dtype=np.uint64)
+        if len(qpos) != len(read) or len(off) != len(read) + 1:
+            raise ValueError("alt_bases: array lengths disagree")
+        out = np.zeros(max(int(off[-1]), 1), np.uint8)
+        self._check(self.lib.csvgpu_alt_bases_resident(self.h, shard.h, ptr(read), ptr(qpos), ptr(off), len(read), ptr(out)))
+        text = out.tobytes().decode("latin-1")
+        return [text[int(off[i]): int(off[i + 1])] for i in range(len(read))]
+
+
+class ShardBuilder:
+    """csv_shard_builder: BAM batches appended on the device into arrays the library owns; finish() turns them into a Shard."""
+
+    def __init__(self, ctx: Context, want: int = 0, reserve=None):
+        self.ctx, self.want = ctx, int(want)
+        r = _lib.csv_shard_sizes(*[int(x) for x in reserve]) if reserve is not None else None
+        self.h = ctx.lib.csvgpu_shard_builder_create(ctx.h, self.want, C.byref(r) if r is not None else None)
+        if not self.h:
+            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+
+    def _live(self):
+        if not self.h:
+            raise ValueError("ShardBuilder: already finished or destroyed")
+
+    def append_bam(self, stream_or_dev, anchors, tid: int = -1, end: int = 0):
+        """csvgpu_shard_builder_append_bam: a decoded BAM record stream — host bytes / a uint8 numpy array (copied to a device buffer for the
+        call) or a uint8 torch tensor on the context's device, e.g. what bgzf_inflate_dev left there — unpacked behind the builder's tail.
+        -> (rc, counts) as Context.bam_unpack_into: rc 0 appended, 1 declined (nothing appended; counts['reason'] at counts['offset']);
+        CsvError otherwise (CSV_ENOMEM: a failed growth, the builder keeps its contents)."""
+        ctx = self.ctx
+        if hasattr(stream_or_dev, "data_ptr"):
+            t = stream_or_dev
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 1:
+                raise ValueError("append_bam: contiguous uint8 device tensor expected")
+            return self.append_bam_ptr(t.data_ptr(), int(t.numel()), anchors, tid, end)
+        data = stream_or_dev
+        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        dev = ctx.lib.csvgpu_dev_alloc(ctx.h, max(len(data), 1))
+        if not dev:
+            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+        try:
+            ctx._check(ctx.lib.csvgpu_upload(ctx.h, dev, ptr(data), len(data)))
+            return self.append_bam_ptr(dev, len(data), anchors, tid, end)
+        finally:
+            ctx.lib.csvgpu_dev_free(ctx.h, dev)
+
+    def append_bam_ptr(self, dev_ptr: int, length: int, anchors, tid: int = -1, end: int = 0):
+        """The same for `length` bytes at a device address (csvgpu_dev_alloc, or a tensor's data_ptr())."""
+        self._live()
+        anchors = np.ascontiguousarray(anchors, np.uint32)
+        c = _lib.csv_bam_counts()
+        rc = self.ctx.lib.csvgpu_shard_builder_append_bam(self.ctx.h, self.h, dev_ptr, int(length), ptr(anchors), len(anchors), int(tid), int(end), C.byref(c))
+        if rc < 0:
+            self.ctx._check(rc)
+        return rc, Context._bam_counts(c)
+
+    def append_host(self, reads: Reads, seq_off=None, seq=None, name_off=None, name=None, name_hash=None):
+        """csvgpu_shard_builder_append_host: a batch the host parser read, as host arrays (offsets relative to the batch)."""
+        self._live()
+        u64 = lambda a: np.ascontiguousarray(a, np.uint64) if a is not None else None
+        u8 = lambda a: np.ascontiguousarray(a, np.uint8) if a is not None else None
+        so, sq, no, nm, nh = u64(seq_off), u8(seq), u64(name_off), u8(name), u64(name_hash)
+        rs = reads.c_struct()
+        self.ctx._check(self.ctx.lib.csvgpu_shard_builder_append_host(self.ctx.h, self.h, C.byref(rs), ptr(so), ptr(sq), ptr(no), ptr(nm), ptr(nh)))
+
+    def sizes(self) -> dict:
+        self._live()
+        s = _lib.csv_shard_sizes()
+        self.ctx._check(self.ctx.lib.csvgpu_shard_builder_sizes(self.ctx.h, self.h, C.byref(s)))
+        return dict(n_reads=s.n_reads, n_cigar=s.n_cigar, n_seq=s.n_seq, n_name=s.n_name)
+
+    def finish(self, depth_len: int) -> "Shard":
+        """csvgpu_shard_builder_finish: the builder's arrays become a Shard (the builder is consumed, also on failure)."""
+        self._live()
+        n = self.sizes()["n_reads"]
+        h, self.h = self.ctx.lib.csvgpu_shard_builder_finish(self.ctx.h, self.h, depth_len), None
+        if not h:
+            raise CsvError(_lib.CSV_ENOMEM, (self.ctx.lib.csvgpu_last_error(self.ctx.h) or b"").decode())
+        return Shard(self.ctx, h, n, depth_len)
+
+    def destroy(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.csvgpu_shard_builder_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    __del__ = destroy
+
+
 @dataclass
 class SplitRefs:
     """Record references into resident shards from which the device builds SplitTables (include/csvgpu.h csv_split_refs): segment by segment,
@@ -664,6 +762,40 @@ class Shard:
         qhash = np.ascontiguousarray(qhash, np.uint64)
         assert len(qhash) == self.n_reads
         self.ctx._check(self.ctx.lib.csvgpu_shard_set_qname_hash(self.ctx.h, self.h, ptr(qhash)))
+
+    def sizes(self) -> dict:
+        """csvgpu_shard_sizes: records, CIGAR words, and the sequence / name bytes the shard holds (0 where it holds none)."""
+        s = _lib.csv_shard_sizes()
+        self.ctx._check(self.ctx.lib.csvgpu_shard_sizes(self.ctx.h, self.h, C.byref(s)))
+        return dict(n_reads=s.n_reads, n_cigar=s.n_cigar, n_seq=s.n_seq, n_name=s.n_name)
+
+    def fetch_reads(self, want_cigar: bool = True) -> Reads:
+        """csvgpu_shard_fetch_reads: the shard's reads copied to the host (want_cigar False: pos / flag / mapq only, the CIGAR arrays empty)."""
+        z = self.sizes()
+        n, m = z["n_reads"], z["n_cigar"] if want_cigar else 0
+        pos, flag, mapq = np.zeros(n, np.int32), np.zeros(n, np.uint16), np.zeros(n, np.uint8)
+        off, cig = np.zeros(n + 1, np.uint64), np.zeros(m, np.uint32)
+        self.ctx._check(self.ctx.lib.csvgpu_shard_fetch_reads(self.ctx.h, self.h, ptr(pos), ptr(flag), ptr(mapq), ptr(off) if want_cigar else None,
+                                                              ptr(cig) if want_cigar else None))
+        return Reads(pos, flag, mapq, off, cig)
+
+    def fetch_names(self, want_names: bool = True, want_hashes: bool = True) -> dict:
+        """csvgpu_shard_fetch_names -> dict(name_off, name, names) and / or dict(name_hash) of a shard built with them."""
+        z = self.sizes()
+        n = z["n_reads"]
+        off, name = (np.zeros(n + 1, np.uint64), np.zeros(z["n_name"], np.uint8)) if want_names else (None, None)
+        nh = np.zeros(n, np.uint64) if want_hashes else None
+        self.ctx._check(self.ctx.lib.csvgpu_shard_fetch_names(self.ctx.h, self.h, ptr(off), ptr(name), ptr(nh)))
+        out = {}
+        if want_names:
+            raw = name.tobytes()
+            out.update(name_off=off, name=name, names=[raw[int(off[i]): int(off[i + 1])] for i in range(n)])
+        if want_hashes:
+            out["name_hash"] = nh
+        return out
+
+    def drop_sequences(self):
+        self.ctx._check(self.ctx.lib.csvgpu_shard_drop_sequences(self.ctx.h, self.h))
 
     def pipeline(self, eps: float = 0.1, min_pts_pct: float = 0.1, min_oplen: int = 50, min_mapq: int = 20) -> ChrResult:
         res = csv_chr_result()

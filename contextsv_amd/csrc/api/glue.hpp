@@ -138,6 +138,9 @@ void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, uint32_t
 int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
                 uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges = nullptr, uint32_t cigar_pad = 0, void *items = nullptr,
                 int form = SCAN_FORM_WAVE);
+// shard.hip
+void shard_release(csv_shard *sh);                            // frees what the shard owns, and the shard
+csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh);         // the side arrays and the scan's split of a shard whose reads are in place; releases it on failure
 // cluster.hip
 int check_dbscan_args(csv_ctx *ctx, double eps, int32_t min_pts, bool interval);
 // split_order.hip

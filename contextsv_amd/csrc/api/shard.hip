@@ -3,9 +3,9 @@
 
 #include "glue.hpp"
 
-using namespace csv;
+namespace csv {
 
-static void shard_release(csv_shard *sh)
+void shard_release(csv_shard *sh)
 {
     if (!sh) return;
     if (sh->owned) {
@@ -17,11 +17,12 @@ static void shard_release(csv_shard *sh)
     (void)hipFree(sh->depth_items);
     (void)hipFree(sh->scan_split);
     (void)hipFree(sh->qhash);
+    (void)hipFree(sh->seq_off); (void)hipFree(sh->seq); (void)hipFree(sh->name_off); (void)hipFree(sh->name);
     (void)hipFree(sh->depth); (void)hipFree(sh->sig_raw); (void)hipFree(sh->scratch); (void)hipFree(sh->counters);
     delete sh;
 }
 
-static csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh)
+csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh)
 {
     const uint64_t n = sh->d.n_reads;
     bool ok = true;
@@ -44,6 +45,10 @@ static csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh)
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "scan split failed (shard)"; shard_release(sh); return nullptr; }
     return sh;
 }
+
+}  // namespace csv
+
+using namespace csv;
 
 csv_shard *csvgpu_shard_upload(csv_ctx *ctx, const csv_reads *r, uint32_t depth_len)
 {

@@ -94,6 +94,12 @@ struct csv_shard {
     void     *depth_items = nullptr;  // depth_items_bytes(depth_len): the depth tiles' work lists (depth.hip)
     uint64_t *qhash = nullptr;        // [n_reads] std::hash<std::string> of every record's query name (csvgpu_shard_set_qname_hash), or null
     size_t    counters_bytes = 0;
+    // a shard built on the device (csvgpu_shard_builder_finish) also owns what the builder kept beside the reads; null / 0 otherwise
+    uint64_t *seq_off = nullptr;      // [n_reads + 1] with seq [n_seq]: 4-bit packed sequences, (l_seq + 1) / 2 bytes a record (until csvgpu_shard_drop_sequences)
+    uint8_t  *seq = nullptr;
+    uint64_t *name_off = nullptr;     // [n_reads + 1] with name [n_name]: query names, no terminator
+    uint8_t  *name = nullptr;
+    uint64_t  n_seq = 0, n_name = 0;
 };
 
 namespace csv {
@@ -411,6 +417,13 @@ void launch_bam_fields(hipStream_t s, const uint8_t *bytes, uint32_t n_rec, int3
 // the outputs, after the caller has held the counts against its capacities
 void launch_bam_emit(hipStream_t s, const uint8_t *bytes, uint32_t first, uint32_t n_kept, uint32_t n_cigar, uint32_t n_seq, uint32_t n_name,
                      uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const BamUnpackWs &w, const BamUnpackOut &out);
+// shardbuild.hip — a resident shard built on the device (csvgpu_shard_builder_*), and the ALT strings cut from its sequences
+// *unsorted |= pos[i] < pos[i - 1] for the records [first, first + n) (the first one against its predecessor, if there is one)
+void launch_sb_unsorted(hipStream_t s, const int32_t *pos, uint64_t first, uint64_t n, uint32_t *unsorted);
+void launch_sb_add(hipStream_t s, uint64_t *off, uint64_t n, uint64_t delta);      // off[0 .. n) += delta (modulo 2^64)
+// item i: out[out_off[i] .. out_off[i + 1]) = the bases from qpos[i] on of record read[i], or N's where they leave its sequence (alt_bases_core.hpp)
+void launch_alt_bases(hipStream_t s, const uint64_t *seq_off, const uint8_t *seq, const uint32_t *read, const uint32_t *qpos, const uint64_t *out_off, uint64_t n,
+                      uint8_t *out);
 // dbscan1d.hip
 void launch_dbscan_1d_batched(hipStream_t s, const int32_t *pts, const uint64_t *seg_off, uint64_t n_seg,
                               double eps, int min_pts, int32_t *labels, unsigned int *too_large_flag);

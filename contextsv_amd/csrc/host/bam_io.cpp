@@ -103,6 +103,7 @@ csv_reads BamShard::view() const
 void BamShard::clear()
 {
     pos.clear(); flag.clear(); mapq.clear(); cigar.clear(); seq.clear(); qnames.clear();
+    resident.reset(); resident_cigar = 0;
     cigar_off.assign(1, 0);
     seq_off.assign(1, 0);
 }
@@ -249,7 +250,20 @@ __attribute__((weak)) void csvgpu_dev_free(csv_ctx *ctx, void *dev_ptr);
 __attribute__((weak)) int csvgpu_upload(csv_ctx *ctx, void *dev_dst, const void *host_src, size_t bytes);
 __attribute__((weak)) int csvgpu_download(csv_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes);
 __attribute__((weak)) const char *csvgpu_last_error(const csv_ctx *ctx);
+__attribute__((weak)) csv_shard_builder *csvgpu_shard_builder_create(csv_ctx *ctx, uint32_t want, const csv_shard_sizes *reserve);
+__attribute__((weak)) int csvgpu_shard_builder_append_bam(csv_ctx *ctx, csv_shard_builder *b, const uint8_t *d_bytes, uint64_t len, const uint32_t *anchors,
+                                                          uint32_t n_anchors, int32_t tid, int64_t end, csv_bam_counts *counts);
+__attribute__((weak)) int csvgpu_shard_builder_append_host(csv_ctx *ctx, csv_shard_builder *b, const csv_reads *batch, const uint64_t *seq_off, const uint8_t *seq,
+                                                           const uint64_t *name_off, const uint8_t *name, const uint64_t *name_hash);
+__attribute__((weak)) csv_shard *csvgpu_shard_builder_finish(csv_ctx *ctx, csv_shard_builder *b, uint32_t depth_len);
+__attribute__((weak)) void csvgpu_shard_builder_destroy(csv_ctx *ctx, csv_shard_builder *b);
+__attribute__((weak)) int csvgpu_shard_sizes(csv_ctx *ctx, const csv_shard *shard, csv_shard_sizes *out);
+__attribute__((weak)) int csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *shard, int32_t *pos, uint16_t *flag, uint8_t *mapq, uint64_t *cigar_off, uint32_t *cigar);
+__attribute__((weak)) int csvgpu_shard_fetch_names(csv_ctx *ctx, csv_shard *shard, uint64_t *name_off, uint8_t *name, uint64_t *name_hash);
+__attribute__((weak)) void csvgpu_shard_free(csv_ctx *ctx, csv_shard *shard);
 }
+
+void BamShard::ResidentFree::operator()(csv_shard *s) const { if (s && ctx && csvgpu_shard_free) csvgpu_shard_free(ctx, s); }
 
 // Device memory of one stream() with BamReadOptions::device_unpack: the batch's decoded bytes behind kDevHead bytes of room for the carried
 // partial record, the compressed bytes + status bytes of the device inflate, and the unpacked arrays. Grown when needed, freed with the stream.
@@ -525,6 +539,19 @@ int BamReader::unpackBatch(const RawBatch &b, int tid, int64_t end, const std::v
     }
     DevBufs &dev = *b.dev;
     auto dev_fail = [&] { err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(opt.device_unpack); return -1; };
+    if (shard_builder) {
+        // BamReadOptions::device_shard: the records go behind the builder's tail where they are; nothing comes down
+        csv_bam_counts c{};
+        const int rc = csvgpu_shard_builder_append_bam(opt.device_unpack, shard_builder, b.d, b.n, anchors.data(), (uint32_t)anchors.size(), tid, end, &c);
+        if (rc == 1) { unpack_stats.batches_host++; return 0; }          // declined, nothing appended: the host parser reads this batch
+        if (rc != CSV_OK) return dev_fail();
+        unpack_stats.batches_device++;
+        unpack_stats.anchors += anchors.size();
+        unpack_stats.records += c.n_kept;
+        *consumed = (size_t)c.consumed;
+        *stop = c.stopped != 0;
+        return 1;
+    }
     const size_t r0 = out.pos.size();
     const uint64_t cig_at = out.cigar.size(), seq_at = out.seq.size();
     if (!dev.ensure(dev.out, 4096, err)) return -1;
@@ -562,6 +589,7 @@ int BamReader::unpackBatch(const RawBatch &b, int tid, int64_t end, const std::v
         out.pos.resize(r0 + k); out.flag.resize(r0 + k); out.mapq.resize(r0 + k);
         out.cigar_off.resize(r0 + 1 + k);
         out.cigar.resize_uninit(cig_at + c.n_cigar);
+        unpack_stats.cigar_words_downloaded += c.n_cigar;
         if (csvgpu_download(x, out.pos.data() + r0, o.pos, k * 4) || csvgpu_download(x, out.flag.data() + r0, o.flag, k * 2) || csvgpu_download(x, out.mapq.data() + r0, o.mapq, k) ||
             csvgpu_download(x, out.cigar_off.data() + r0, o.cigar_off, (k + 1) * 8) || (c.n_cigar && csvgpu_download(x, out.cigar.data() + cig_at, o.cigar, c.n_cigar * 4))) return dev_fail();
         if (opt.want_seq) {
@@ -600,19 +628,88 @@ bool BamReader::readContig(const std::string &chr, const BamReadOptions &opt, Ba
     // (offsets come from the index file: a corrupt one must not size an allocation — found by tools/fuzz)
     if ((ref.max_end >> 16) < (ref.min_beg >> 16) || (ref.min_beg >> 16) > file.size()) { err = "BAI: chunk offsets outside " + path; return false; }
     const uint64_t span = std::min<uint64_t>((ref.max_end >> 16) - (ref.min_beg >> 16), file.size()) + bgzf::kMaxBlock;
-    out.cigar.reserve((size_t)(span * 4 / 4));            // ~4x compression of CIGAR words is typical; growth is by mremap anyway
     const int64_t end = hdr.lens[tid];
+    // BamReadOptions::device_shard: the contig's records are appended on the device to a builder held for this call; whatever way out is
+    // taken, the builder does not outlive it
+    struct BuilderGuard {
+        BamReader &r; csv_ctx *ctx;
+        ~BuilderGuard() { if (r.shard_builder) { csvgpu_shard_builder_destroy(ctx, r.shard_builder); r.shard_builder = nullptr; } }
+    } guard{*this, opt.device_unpack};
+    if (opt.device_shard) {
+        if (!opt.device_unpack || !csvgpu_shard_builder_create || !csvgpu_shard_builder_append_bam || !csvgpu_shard_builder_append_host || !csvgpu_shard_builder_finish ||
+            !csvgpu_shard_builder_destroy || !csvgpu_shard_sizes || !csvgpu_shard_fetch_reads || !csvgpu_shard_fetch_names || !csvgpu_shard_free || !csvgpu_last_error) {
+            err = "BAM: device_shard needs device_unpack (and the device library)";
+            return false;
+        }
+        // The reserve from the compressed span, like the host arrays' — but device memory is committed when it is allocated (the host's reserve
+        // is address space only) and a finished shard keeps its blocks: as many bytes of CIGAR words as the span has compressed bytes, an
+        // eighth of that for sequences; whatever a contig holds beyond it comes by growth (at least 1.5x a step).
+        const csv_shard_sizes reserve{span / 256, span / 4, opt.want_seq ? span / 8 : 0, opt.want_qnames ? span / 64 : 0};
+        shard_builder = csvgpu_shard_builder_create(opt.device_unpack, (opt.want_seq ? CSV_SB_SEQ : 0) | (opt.want_qnames ? CSV_SB_NAMES | CSV_SB_NAME_HASH : 0), &reserve);
+        if (!shard_builder) { err = std::string("BAM: no shard builder: ") + csvgpu_last_error(opt.device_unpack); return false; }
+    } else {
+        out.cigar.reserve((size_t)(span * 4 / 4));        // ~4x compression of CIGAR words is typical; growth is by mremap anyway
+    }
     RawFn on_raw;
     if (opt.device_unpack) on_raw = [&](const RawBatch &b, size_t *consumed, bool *stop) { return unpackBatch(b, tid, end, ref.anchors, opt, out, consumed, stop); };
-    return stream(ref.min_beg, opt, [&](const RecRef *recs, size_t n) -> size_t {
+    // a batch the host parser read, on the device_shard route: its arrays go up behind the builder's tail
+    auto append_to_builder = [&](const RecRef *recs, size_t n) -> bool {
+        BamShard part;
+        part.clear();
+        if (!append(recs, n, opt, part)) return false;
+        std::vector<uint64_t> name_off, name_hash;
+        std::vector<uint8_t> name;
+        if (opt.want_qnames) {
+            name_off.assign(1, 0);
+            for (const std::string &q : part.qnames) {
+                name.insert(name.end(), q.begin(), q.end());
+                name_off.push_back(name.size());
+                name_hash.push_back((uint64_t)std::hash<std::string>{}(q));
+            }
+            name.push_back(0);                            // (never a null array)
+            name_hash.push_back(0);
+        }
+        const csv_reads v = part.view();
+        if (csvgpu_shard_builder_append_host(opt.device_unpack, shard_builder, &v, opt.want_seq ? part.seq_off.data() : nullptr, opt.want_seq ? part.seq.data() : nullptr,
+                                             opt.want_qnames ? name_off.data() : nullptr, opt.want_qnames ? name.data() : nullptr,
+                                             opt.want_qnames ? name_hash.data() : nullptr) != CSV_OK) {
+            err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(opt.device_unpack);
+            return false;
+        }
+        if (n) unpack_stats.batches_appended_host++;
+        return true;
+    };
+    const bool ok = stream(ref.min_beg, opt, [&](const RecRef *recs, size_t n) -> size_t {
         // the contig's records are one run in a sorted file: skip an earlier contig's tail, stop at a later one / unplaced / past the end
         size_t a = 0;
         while (a < n && (int32_t)le32(recs[a].p) >= 0 && (int32_t)le32(recs[a].p) < tid) a++;
         size_t b = a;
         while (b < n && (int32_t)le32(recs[b].p) == tid && (int32_t)le32(recs[b].p + 4) < end) b++;
-        if (!append(recs + a, b - a, opt, out)) return 0;
+        if (!(shard_builder ? append_to_builder(recs + a, b - a) : append(recs + a, b - a, opt, out))) return 0;
         return b == n ? n : b;                            // anything left over ends the iteration
     }, on_raw) && err.empty();
+    if (!ok || !shard_builder) return ok;
+    // the builder becomes the contig's shard; the small per-record arrays come down for the host-side passes
+    csv_ctx *const x = opt.device_unpack;
+    csv_shard_builder *const done = shard_builder;
+    shard_builder = nullptr;                              // (finish consumes it, also on failure)
+    out.resident = std::unique_ptr<csv_shard, BamShard::ResidentFree>(csvgpu_shard_builder_finish(x, done, (uint32_t)hdr.lens[tid] + 1), BamShard::ResidentFree(x));
+    auto fail = [&] { err = std::string("BAM: device unpack failed: ") + csvgpu_last_error(x); out.resident.reset(); return false; };
+    if (!out.resident) return fail();
+    csv_shard_sizes z{};
+    if (csvgpu_shard_sizes(x, out.resident.get(), &z)) return fail();
+    out.pos.resize(z.n_reads); out.flag.resize(z.n_reads); out.mapq.resize(z.n_reads);
+    out.resident_cigar = z.n_cigar;
+    if (csvgpu_shard_fetch_reads(x, out.resident.get(), out.pos.data(), out.flag.data(), out.mapq.data(), nullptr, nullptr)) return fail();
+    if (opt.want_qnames) {
+        std::vector<uint64_t> name_off(z.n_reads + 1);
+        std::vector<uint8_t> name(z.n_name + 1);
+        if (csvgpu_shard_fetch_names(x, out.resident.get(), name_off.data(), name.data(), nullptr)) return fail();
+        out.qnames.resize(z.n_reads);
+        for (uint64_t i = 0; i < z.n_reads; i++) out.qnames[i].assign((const char *)name.data() + name_off[i], (size_t)(name_off[i + 1] - name_off[i]));
+    }
+    unpack_stats.shard_resident = 1;
+    return true;
 }
 
 bool BamReader::readAll(const BamReadOptions &opt, const std::function<void(BamShard &&)> &sink, uint64_t *n_unplaced)

@@ -37,6 +37,18 @@ struct BamShard {
     std::vector<uint64_t> seq_off;                    // [n + 1] byte offsets into seq (want_seq)
     HugeVec<uint8_t> seq;                             // 4-bit packed, high nibble first, as bam_get_seq
     std::vector<std::string> qnames;                  // (want_qnames)
+    // BamReadOptions::device_shard: the contig's records as a resident shard the reader built on its device (csvgpu_shard_builder_finish;
+    // sequences and query-name hashes inside it when wanted). pos / flag / mapq and qnames above are fetched from it; cigar_off, cigar, seq_off
+    // and seq stay empty. The BamShard owns it — freed through the reader's context, which must outlive the BamShard — until release() hands
+    // it to the caller, who frees it with csvgpu_shard_free on a context of the same device.
+    struct ResidentFree {
+        csv_ctx *ctx;
+        ResidentFree() : ctx(nullptr) {}
+        explicit ResidentFree(csv_ctx *c) : ctx(c) {}
+        void operator()(csv_shard *s) const;
+    };
+    std::unique_ptr<csv_shard, ResidentFree> resident;
+    uint64_t resident_cigar = 0;                      // its CIGAR words (cigar is empty)
     uint64_t n_reads() const { return pos.size(); }
     csv_reads view() const;                           // host pointers into this shard (tid = nullptr)
     void clear();
@@ -55,6 +67,11 @@ struct BamReadOptions {
                                                       // arrays; a batch the device declines goes through the host parser, so records and messages are the
                                                       // host route's. The reader's own context: the same one as device_inflate when both are set (the next
                                                       // batch is then loaded behind the unpack, not beside it). Null: the host parser.
+    bool device_shard = false;                        // (readContig alone; requires device_unpack, on whose context it runs) every batch is appended on the device
+                                                      // to a shard builder the reader holds for the contig (csvgpu_shard_builder_append_bam) instead of coming
+                                                      // down into the BamShard; a batch the device declines is parsed on the host as above and its arrays go
+                                                      // up behind the others (csvgpu_shard_builder_append_host). At the contig's end BamShard::resident is the
+                                                      // finished shard. Same records either way.
 };
 
 class BamReader {
@@ -82,7 +99,12 @@ public:
     // What BamReadOptions::device_unpack did in the last readContig: batches the device unpacked / declined or was not given (the host parser
     // read those), anchors handed to the device in the unpacked batches (1 per batch = none from the index), records it wrote, batches whose
     // decoded bytes never came to the host (inflated on the device straight into the unpack's buffer), batches brought down after all.
-    struct UnpackStats { uint64_t batches_device = 0, batches_host = 0, anchors = 0, records = 0, batches_kept_on_device = 0, batches_downloaded = 0; };
+    // With BamReadOptions::device_shard: shard_resident = 1 when the contig ended as a resident shard, batches_appended_host = batches that went
+    // into it from the host parser's arrays, cigar_words_downloaded = CIGAR words that came down into the BamShard (0 on that route).
+    struct UnpackStats {
+        uint64_t batches_device = 0, batches_host = 0, anchors = 0, records = 0, batches_kept_on_device = 0, batches_downloaded = 0;
+        uint64_t shard_resident = 0, batches_appended_host = 0, cigar_words_downloaded = 0;
+    };
     const UnpackStats &unpackStats() const { return unpack_stats; }
 
 private:
@@ -105,6 +127,7 @@ private:
     uint64_t first_record_voffset = 0;
     std::unique_ptr<Index> index;
     UnpackStats unpack_stats;
+    csv_shard_builder *shard_builder = nullptr;              // readContig with BamReadOptions::device_shard: the contig's builder, between its creation and finish
     std::string path, err;
 };
 

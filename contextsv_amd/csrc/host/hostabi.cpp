@@ -235,6 +235,23 @@ int csvhost_process_resident_chromosome_alts(csv_ctx *ctx, csv_shard *shard, con
     })
 }
 
+// The same with the ALT strings cut on the device from the sequences the shard itself holds (a shard built by csvgpu_shard_builder_finish with
+// CSV_SB_SEQ): SeqStore's device form.
+int csvhost_process_resident_chromosome_alts_resident(csv_ctx *ctx, csv_shard *shard, double eps, double min_pts_pct, char *buf, uint64_t cap, uint64_t *len)
+{
+    GUARD({
+        SVCaller caller(ctx);
+        SeqStore ss; ss.resident = shard;
+        std::vector<SVCall> calls;
+        ChrStats cs;
+        caller.processResidentChromosome("chr", shard, &ss, eps, min_pts_pct, calls, cs);
+        std::string t;
+        for (const SVCall &c : calls) t += std::to_string(c.start) + "\t" + std::to_string(c.end) + "\t" + c.alt_allele + "\n";
+        if (buf && cap) memcpy(buf, t.data(), (size_t)std::min<uint64_t>(cap, t.size()));
+        *len = t.size();
+    })
+}
+
 // The host half alone (no device): ordered signatures + labels -> merged calls; `reps` timed repetitions, *ms = mean time of one.
 int csvhost_merge_ordered(const csv_sig *sig, const int32_t *labels, uint64_t n_del, uint64_t n_ins, int reps, csvhost_call *out, uint64_t cap,
                           uint64_t *n_out, double *ms)
@@ -1005,8 +1022,9 @@ struct csvhost_bam {
     BamReader r; std::vector<BamShard> shards; std::string names;
     csv_ctx *inflate_ctx = nullptr;          // csvhost_bam_set_device_inflate / _unpack: the reader's own context, one for both
     int ctx_device = -1;
-    bool inflate_on = false, unpack_on = false;
-    ~csvhost_bam() { if (inflate_ctx) csvgpu_destroy(inflate_ctx); }
+    bool inflate_on = false, unpack_on = false, shard_on = false;
+    void drop_residents() { for (BamShard &s : shards) s.resident.reset(); }      // (they are freed through inflate_ctx: before it goes)
+    ~csvhost_bam() { drop_residents(); if (inflate_ctx) csvgpu_destroy(inflate_ctx); }
 };
 
 csvhost_bam *csvhost_bam_open(const char *path, int load_index)
@@ -1031,14 +1049,14 @@ static int bam_set_device(csvhost_bam *h, bool &on, int device_or_minus_1)
         const bool other = &on == &h->inflate_on ? h->unpack_on : h->inflate_on;
         if (device_or_minus_1 < 0) {
             on = false;
-            if (!other && h->inflate_ctx) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
+            if (!other && h->inflate_ctx) { h->drop_residents(); csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
             return 0;
         }
         if (other && h->inflate_ctx && h->ctx_device != device_or_minus_1) {
             g_err = "the BAM reader's context is on device " + std::to_string(h->ctx_device) + ": inflate and unpack share it, switch the other option off first";
             return -1;
         }
-        if (h->inflate_ctx && h->ctx_device != device_or_minus_1) { csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
+        if (h->inflate_ctx && h->ctx_device != device_or_minus_1) { h->drop_residents(); csvgpu_destroy(h->inflate_ctx); h->inflate_ctx = nullptr; h->ctx_device = -1; }
         if (!h->inflate_ctx) {
             h->inflate_ctx = csvgpu_create(device_or_minus_1, nullptr);
             if (!h->inflate_ctx) { on = false; g_err = std::string("no device context for the BAM reader: ") + csvgpu_last_error(nullptr); return -1; }
@@ -1052,6 +1070,8 @@ int csvhost_bam_set_device_inflate(csvhost_bam *h, int device_or_minus_1) { retu
 // device >= 0: the readContig calls that follow unpack every batch's records on that device (BamReadOptions::device_unpack), on the handle's
 // own context — the one the inflate uses when both are set; -1: the host parser again. readAll keeps the host parser either way.
 int csvhost_bam_set_device_unpack(csvhost_bam *h, int device_or_minus_1) { return bam_set_device(h, h->unpack_on, device_or_minus_1); }
+// on != 0: the readContig calls that follow, while the unpack is on the device, build the contig's resident shard there (BamReadOptions::device_shard)
+void csvhost_bam_set_device_shard(csvhost_bam *h, int on) { h->shard_on = on != 0; }
 
 // Every BGZF block of a file inflated in batches of window_blocks, on `threads` host threads (ctx null: bgzf::inflate_range) or on ctx's device
 // (bgzf::inflate_range_device), into one buffer that is reused: what tools/bench_inflate.py times. *ms: the inflate alone (the block scan before it).
@@ -1094,6 +1114,7 @@ int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qna
         if (window_blocks) opt.window_blocks = window_blocks;
         opt.device_inflate = h->inflate_on ? h->inflate_ctx : nullptr;
         opt.device_unpack = h->unpack_on && chr ? h->inflate_ctx : nullptr;
+        opt.device_shard = h->shard_on && opt.device_unpack;
         h->shards.clear();
         bool ok;
         if (chr) { h->shards.emplace_back(); ok = h->r.readContig(chr, opt, h->shards.back()); }
@@ -1104,10 +1125,21 @@ int csvhost_bam_read(csvhost_bam *h, const char *chr, int want_seq, int want_qna
 }
 // BamReader::UnpackStats of the last csvhost_bam_read with a contig name: batches the device unpacked, batches the host parser read, anchors
 // given to the device, records the device wrote, batches whose decoded bytes never came to the host, batches brought down after all
-void csvhost_bam_unpack_stats(const csvhost_bam *h, uint64_t out[6])
+// — and, for BamReadOptions::device_shard: whether the contig ended as a resident shard, batches appended to it from the host parser's arrays,
+// CIGAR words that came down into the host shard
+void csvhost_bam_unpack_stats(const csvhost_bam *h, uint64_t out[9])
 {
     const BamReader::UnpackStats &u = h->r.unpackStats();
     out[0] = u.batches_device; out[1] = u.batches_host; out[2] = u.anchors; out[3] = u.records; out[4] = u.batches_kept_on_device; out[5] = u.batches_downloaded;
+    out[6] = u.shard_resident; out[7] = u.batches_appended_host; out[8] = u.cigar_words_downloaded;
+}
+// The resident shard of shard i (BamReadOptions::device_shard), handed to the caller, who frees it with csvgpu_shard_free on a context of the
+// same device; null when there is none (a contig without records, the option off, or taken before). *n_cigar: its CIGAR words.
+csv_shard *csvhost_bam_shard_take_resident(csvhost_bam *h, int i, uint64_t *n_cigar)
+{
+    BamShard &s = h->shards[(size_t)i];
+    if (n_cigar) *n_cigar = s.resident_cigar;
+    return s.resident.release();
 }
 // view of shard i: arrays stay owned by the handle until the next read / close
 void csvhost_bam_shard(const csvhost_bam *h, int i, csv_reads *reads, int32_t *tid, uint32_t *target_len, const uint64_t **seq_off, const uint8_t **seq)
@@ -1226,12 +1258,13 @@ int csvhost_bam_writer_close(csvhost_bam_writer *h)
 }
 
 struct csvhost_bam_stats { uint64_t n_contigs, n_reads, n_cigar, bam_bytes; double ms_decode, ms_total;
-                           uint64_t unpack_batches_device, unpack_batches_host, unpack_anchors, unpack_batches_kept_on_device; };
+                           uint64_t unpack_batches_device, unpack_batches_host, unpack_anchors, unpack_batches_kept_on_device;
+                           uint64_t contigs_resident, unpack_batches_appended_host; };
 
 // SVCaller::runBam: chrs = '\n'-separated contig names or null (all). SNPs: none (every window gets the dummy observation).
 // Calls come back grouped by contig in header order, with their contig index in out_tid.
 int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int threads, const csv_hmm *hmm, double eps, double min_pts_pct,
-                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv; 9-14, 24-30: below */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
+                    int sample_size, uint32_t min_cnv, int passes /* bit 0: split-read pass, bit 1: CIGAR copy-number pass, bit 2: --save-cnv; 9-15, 24-30: below */, const csvhost_fasta *fasta, const char *vcf_dir, const char *gap_path,
                     const char *file_date, csvhost_call *out, int32_t *out_tid, uint64_t cap, uint64_t *n_out, csvhost_bam_stats *stats,
                     const char *snp_vcf, const char *pfb_table, const char *ethnicity)
 {
@@ -1249,6 +1282,7 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         P.cn_observations_on_device = (passes & 4096) != 0;
         P.inflate_on_device = (passes & 8192) != 0; P.inflate_device = (passes >> 24) & 0x7f;
         P.unpack_on_device = (passes & 16384) != 0;
+        P.shard_on_device = (passes & 32768) != 0;
         P.snp_vcf = snp_vcf ? snp_vcf : ""; P.pfb_table = pfb_table ? pfb_table : ""; P.ethnicity = ethnicity ? ethnicity : "";
         if (fasta && vcf_dir) {
             P.ref_genome = fasta_genome(fasta);
@@ -1278,7 +1312,8 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         if (stats) { stats->n_contigs = bs.n_contigs; stats->n_reads = bs.n_reads; stats->n_cigar = bs.n_cigar; stats->bam_bytes = bs.bam_bytes;
                      stats->ms_decode = bs.ms_decode; stats->ms_total = bs.ms_total;
                      stats->unpack_batches_device = bs.unpack_batches_device; stats->unpack_batches_host = bs.unpack_batches_host;
-                     stats->unpack_anchors = bs.unpack_anchors; stats->unpack_batches_kept_on_device = bs.unpack_batches_kept_on_device; }
+                     stats->unpack_anchors = bs.unpack_anchors; stats->unpack_batches_kept_on_device = bs.unpack_batches_kept_on_device;
+                     stats->contigs_resident = bs.contigs_resident; stats->unpack_batches_appended_host = bs.unpack_batches_appended_host; }
     })
 }
 

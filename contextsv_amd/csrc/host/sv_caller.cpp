@@ -1,5 +1,6 @@
 #include "sv_caller.h"
 #include <cstddef>
+#include <cstring>
 
 #include <deque>
 
@@ -30,6 +31,8 @@ void check(csv_ctx *ctx, int rc, const char *what)
 }
 }  // namespace
 
+namespace { constexpr char kAltNote = '\x01'; }   // first byte of an ALT field that holds toSVCall's note instead of bases (no ALT string starts with it)
+
 // Field values of the SVCall the reference builds per op (sv_caller.cpp:569-643): INS from I (CIGARINS) or
 // from a soft clip (CIGARCLIP), DEL from D (CIGARDEL); ALT is the inserted sequence only when op_len <= 50
 // (i.e. exactly 50, ambiguity codes RYKMSWBDHV in either case -> N), otherwise "<INS>"; DEL -> "<DEL>".
@@ -47,6 +50,15 @@ SVCall SVCaller::toSVCall(const csv_sig &s, const SeqStore *seq)
     if (op_len <= 50) {
         alt.assign(op_len, 'N');
         const uint32_t q0 = CSV_SIG_QPOS(s);
+        if (seq && seq->resident && !seq->seq) {
+            // the sequences are on the device: the call carries (read, query offset) in the place of its bases until patchResidentAlts
+            // has run — nothing in between reads an ALT field (the representative rule compares lengths of start .. end only)
+            alt.assign(1, kAltNote);
+            alt.append((const char *)&s.read, 4);
+            alt.append((const char *)&q0, 4);
+            alt.append((const char *)&op_len, 4);
+            return SVCall(s.start, s.end, SVType::INS, alt, flags, Genotype::UNKNOWN, 0.0, 0, 0, 0);
+        }
         // a record stored without its sequence ("*", l_seq = 0) has nothing to copy from: the ALT stays N's
         if (seq && seq->seq && seq->seq_off && ((uint64_t)q0 + op_len + 1) / 2 <= seq->seq_off[s.read + 1] - seq->seq_off[s.read]) {
             static const char nt16[] = "=ACMGRSVTWYHKDBN";              // BAM 4-bit code table (SAM spec §4.2.3)
@@ -62,6 +74,27 @@ SVCall SVCaller::toSVCall(const csv_sig &s, const SeqStore *seq)
         }
     }
     return SVCall(s.start, s.end, SVType::INS, alt, flags, Genotype::UNKNOWN, 0.0, 0, 0, 0);
+}
+
+void SVCaller::patchResidentAlts(csv_ctx *ctx, csv_shard *shard, std::vector<SVCall> &calls)
+{
+    std::vector<size_t> which;
+    std::vector<uint32_t> read, qpos;
+    std::vector<uint64_t> off(1, 0);
+    for (size_t i = 0; i < calls.size(); i++) {
+        const std::string &a = calls[i].alt_allele;
+        if (a.size() != 13 || a[0] != kAltNote) continue;
+        uint32_t r, q, len;
+        memcpy(&r, a.data() + 1, 4); memcpy(&q, a.data() + 5, 4); memcpy(&len, a.data() + 9, 4);
+        // (the note holds the operation's own length: a merge that moved the call's ends must not change what is cut)
+        if (len != calls[i].end - calls[i].start + 1) throw std::logic_error("patchResidentAlts: a call's ends changed between toSVCall and the patch");
+        which.push_back(i); read.push_back(r); qpos.push_back(q);
+        off.push_back(off.back() + len);
+    }
+    if (which.empty()) return;
+    std::string bases((size_t)off.back(), 'N');
+    check(ctx, csvgpu_alt_bases_resident(ctx, shard, read.data(), qpos.data(), off.data(), which.size(), &bases[0]), "patchResidentAlts");
+    for (size_t k = 0; k < which.size(); k++) calls[which[k]].alt_allele.assign(bases, (size_t)off[k], (size_t)(off[k + 1] - off[k]));
 }
 
 // mergeTypeWithLabels (sv_object.cpp) specialised to raw CIGAR signatures, keep_noise = false: same bucket order,
@@ -262,6 +295,7 @@ void SVCaller::processResidentChromosome(const std::string &chr, csv_shard *shar
     DeviceOut d;
     runDeviceChain(chr, shard, eps, pct, d, st);
     hostMerge(chr, d, seq, chr_sv_calls, st);
+    if (seq && seq->resident && !seq->seq) patchResidentAlts(ctx, seq->resident, chr_sv_calls);
 }
 
 void SVCaller::processResidentChromosomesPipelined(const std::vector<csv_shard *> &shards, const SeqStore *seq, double eps, double pct,
@@ -275,6 +309,7 @@ void SVCaller::processResidentChromosomesPipelined(const std::vector<csv_shard *
 {
     const size_t n = shards.size();
     if (!seqs.empty() && seqs.size() != n) throw std::invalid_argument("processResidentChromosomesPipelined: one SeqStore per shard, or none");
+    for (const SeqStore *q : seqs) if (q && q->resident && !q->seq) throw std::invalid_argument("processResidentChromosomesPipelined: a SeqStore in its device form (host arrays, or none)");
     calls.assign(n, {});
     stats.assign(n, ChrStats());
     // The representative choice of one chromosome (~0.5 ms for chr22: a sequential selection over the noise bucket) takes about as
@@ -912,6 +947,8 @@ void SVCaller::run(ContigSource &source, const CHMM &hmm, const RunParams &P,
         ChromosomeInput c;
         while (source.next(c)) {
             const size_t i = contigs.size();
+            // a resident shard is this run's from the moment next() returned it: held here until contigs[i] (and with it free_all) has it
+            struct Taken { csv_ctx *x; csv_shard *s; ~Taken() { if (s) csvgpu_shard_free(x, s); } } taken{ctx, c.resident};
             contigs.emplace_back();
             stats.emplace_back();
             kept.emplace_back(new Kept());
@@ -919,7 +956,18 @@ void SVCaller::run(ContigSource &source, const CHMM &hmm, const RunParams &P,
             contigs[i].seq = nullptr;                                 // the sequences are only valid until the next contig: ALT strings are cut now
             contigs[i].split.tid = (int32_t)i;
             std::vector<SVCall> calls;
-            if (P.cigar_svs) processChromosome(c.name, c.reads, c.seq, c.depth_len, P.dbscan_epsilon, P.dbscan_min_pts_pct, calls, stats[i], &contigs[i].shard);
+            if (c.resident) {
+                // the reader built the shard on the device (another context of this device; its finish has synchronised): nothing to upload
+                contigs[i].shard = c.resident;                        // (owned from here: free_all)
+                taken.s = nullptr;
+                if (P.cigar_svs) {
+                    printMessage(c.name + ": CIGAR SVs...");
+                    processResidentChromosome(c.name, c.resident, c.seq, P.dbscan_epsilon, P.dbscan_min_pts_pct, calls, stats[i]);
+                }
+                // the ALT strings are cut: the packed sequences, the largest of the shard's arrays, go
+                check(ctx, csvgpu_shard_drop_sequences(ctx, c.resident), "run: drop_sequences");
+                if (!P.cigar_svs) { csvgpu_shard_free(ctx, c.resident); contigs[i].shard = nullptr; }
+            } else if (P.cigar_svs) processChromosome(c.name, c.reads, c.seq, c.depth_len, P.dbscan_epsilon, P.dbscan_min_pts_pct, calls, stats[i], &contigs[i].shard);
             whole_genome_sv_calls[c.name] = std::move(calls);
             if (P.split_svs && c.qnames && contigs[i].shard) {                          // inputs of the split-read pass (:133-175)
                 const uint64_t n = c.reads.n_reads;
@@ -1187,19 +1235,30 @@ struct BamSource : ContigSource {
             const BamReader::UnpackStats &u = reader.unpackStats();
             st.unpack_batches_device += u.batches_device; st.unpack_batches_host += u.batches_host; st.unpack_anchors += u.anchors;
             st.unpack_batches_kept_on_device += u.batches_kept_on_device;
+            st.unpack_batches_appended_host += u.batches_appended_host;
         }
         std::swap(cur, ahead);
         if (i + 1 < chrs.size()) launch(i + 1);
+        seq = SeqStore();
         seq.seq_off = cur.seq_off.data();
         seq.seq = cur.seq.data();
         out = ChromosomeInput();
         out.name = cur.name;
         out.reads = cur.view();
+        uint64_t n_cigar = cur.cigar.size();
+        if (cur.resident) {
+            // the contig is a resident shard: the run takes it; the host has the small per-record arrays only
+            n_cigar = cur.resident_cigar;
+            out.resident = cur.resident.release();
+            out.reads.cigar_off = nullptr; out.reads.cigar = nullptr; out.reads.n_cigar = n_cigar;
+            seq.seq_off = nullptr; seq.seq = nullptr; seq.resident = out.resident;
+            st.contigs_resident++;
+        }
         out.seq = opt.want_seq ? &seq : nullptr;
         out.depth_len = cur.target_len + 1;                       // cnv_caller.cpp:482
         out.qnames = opt.want_qnames ? &cur.qnames : nullptr;
         if (snp_file) out.snps = &snp_file->table(cur.name, af_files ? af_files->get(cur.name) : std::string(), ethnicity, opt.threads);
-        st.n_contigs++; st.n_reads += cur.n_reads(); st.n_cigar += cur.cigar.size();
+        st.n_contigs++; st.n_reads += cur.n_reads(); st.n_cigar += n_cigar;
         i++;
         return true;
     }
@@ -1227,11 +1286,12 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
         }
     }
     src.opt.threads = std::max(1, threads);
-    if (P.inflate_on_device || P.unpack_on_device) {
+    if (P.inflate_on_device || P.unpack_on_device || P.shard_on_device) {
         inflate_ctx.c = csvgpu_create(P.inflate_device, nullptr);
         if (!inflate_ctx.c) throw std::runtime_error(std::string("ERROR: no device context for the BAM reader: ") + csvgpu_last_error(nullptr));
         if (P.inflate_on_device) src.opt.device_inflate = inflate_ctx.c;
-        if (P.unpack_on_device) src.opt.device_unpack = inflate_ctx.c;         // (one context for both: the reader's thread is its only user)
+        if (P.unpack_on_device || P.shard_on_device) src.opt.device_unpack = inflate_ctx.c;         // (one context for both: the reader's thread is its only user)
+        src.opt.device_shard = P.shard_on_device;
     }
     SNPFile snp_file;
     AlleleFreqFiles af_files;

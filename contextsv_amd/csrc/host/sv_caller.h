@@ -20,9 +20,14 @@
 #include "vcf_writer.h"
 
 // 4-bit packed read sequences (BAM encoding, two bases per byte, high nibble first); optional.
+// The device form: `resident` is a shard built with its sequences (csvgpu_shard_builder_finish, CSV_SB_SEQ) and the host arrays are null.
+// toSVCall then cannot cut the bases: it leaves a note (read, query offset, length) in the call's ALT field, and patchResidentAlts replaces the
+// notes of a contig's merged calls with the bases in one csvgpu_alt_bases_resident call. Only processResidentChromosome (and so
+// processChromosome's callers and run()) takes this form; the pipelined passes over many shards take host arrays or none.
 struct SeqStore {
     const uint64_t *seq_off = nullptr;   // [n_reads+1] byte offset of each read's packed sequence
     const uint8_t *seq = nullptr;
+    csv_shard *resident = nullptr;
 };
 
 struct ChrStats {
@@ -38,6 +43,11 @@ struct ChrStats {
 struct ChromosomeInput {
     std::string name;
     csv_reads reads{};                      // host arrays, file order
+    csv_shard *resident = nullptr;          // not null: the contig's records are this resident shard already (BamReadOptions::device_shard) — run() takes it
+                                            // (and frees it) instead of uploading; reads.pos / flag / mapq are the host's, reads.cigar_off and reads.cigar null;
+                                            // seq, when given, is the SeqStore's device form over the same shard. OWNERSHIP passes with the struct: whoever
+                                            // receives it from ContigSource::next frees the shard (csvgpu_shard_free on a context of its device) — run() does,
+                                            // from the moment next() has returned, on every way out
     const SeqStore *seq = nullptr;
     uint32_t depth_len = 0;                 // contig length + 1
     const std::vector<std::string> *qnames = nullptr;   // [n_reads]; nullptr: this contig takes no part in the split-read pass
@@ -117,6 +127,10 @@ struct RunParams {
     bool unpack_on_device = false;          // runBam: every batch's records unpacked on the device (csvgpu_bam_unpack, BamReadOptions::device_unpack) on the reader's own
                                             // context — the inflate's when both are set — instead of by the host parser; a batch the device declines goes through
                                             // the host parser, so the records, and so the calls, do not depend on it
+    bool shard_on_device = false;           // runBam (implies unpack_on_device): every contig's resident shard is built on the device from the unpacked batches
+                                            // (BamReadOptions::device_shard) and handed to the run — no host arrays, no csvgpu_shard_upload; the 50-base ALT strings
+                                            // are cut from the shard's own sequences (csvgpu_alt_bases_resident), which are dropped afterwards; the calls do not
+                                            // depend on it
     bool overlap_split_prepare = true;      // runResident with lanes: the split-read pass's first half (qname map order on the device, survivors) beside the CIGAR pass
                                             // (false: after it — the big kernels then have the device to themselves: depth 0.53 of peak instead of 0.48, the step 10 % longer)
     int host_threads = 0;                   // host threads of the split-read and copy-number passes over contigs / regions (0: the hardware's); results do not depend on it
@@ -136,6 +150,8 @@ struct BamRunStats {
     // RunParams::unpack_on_device: batches the device unpacked / the host parser read, anchors given to the device, batches whose decoded
     // bytes never came to the host (BamReader::UnpackStats, summed over the contigs)
     uint64_t unpack_batches_device = 0, unpack_batches_host = 0, unpack_anchors = 0, unpack_batches_kept_on_device = 0;
+    // RunParams::shard_on_device: contigs that reached the run as resident shards; batches that went into them from the host parser's arrays
+    uint64_t contigs_resident = 0, unpack_batches_appended_host = 0;
 };
 
 // A SplitGroupSource that asks csvgpu_split_groups on `ctx` (SplitParams::device_groups); the caller keeps the context alive and uses it from the
@@ -219,6 +235,8 @@ public:
 
     // signature -> SVCall with the reference's field values (sv_caller.cpp:569-643)
     static SVCall toSVCall(const csv_sig &s, const SeqStore *seq);
+    // the ALT notes toSVCall left in `calls` for a SeqStore in its device form -> the bases, cut on the device from `shard`'s sequences
+    static void patchResidentAlts(csv_ctx *ctx, csv_shard *shard, std::vector<SVCall> &calls);
     static void mergeSignaturesWithLabels(const csv_sig *sig, const int32_t *labels, uint64_t n, const SeqStore *seq, std::vector<SVCall> &merged);
     // The host half of processChromosome on its own: ordered signatures (DEL block then INS block) + their labels -> merged calls.
     static void mergeOrdered(const csv_sig *sig, const int32_t *labels, uint64_t n_del, uint64_t n_ins, const SeqStore *seq, std::vector<SVCall> &chr_sv_calls, bool share_pool = true);

@@ -26,7 +26,8 @@ class chr_stats(C.Structure):
 class bam_stats(C.Structure):
     _fields_ = [("n_contigs", C.c_uint64), ("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("bam_bytes", C.c_uint64),
                 ("ms_decode", C.c_double), ("ms_total", C.c_double), ("unpack_batches_device", C.c_uint64), ("unpack_batches_host", C.c_uint64),
-                ("unpack_anchors", C.c_uint64), ("unpack_batches_kept_on_device", C.c_uint64)]
+                ("unpack_anchors", C.c_uint64), ("unpack_batches_kept_on_device", C.c_uint64), ("contigs_resident", C.c_uint64),
+                ("unpack_batches_appended_host", C.c_uint64)]
 
 
 class stage_times(C.Structure):
@@ -107,7 +108,11 @@ def load() -> C.CDLL:
     lib.csvhost_bam_set_device_inflate.argtypes = [_P, C.c_int]
     lib.csvhost_bam_set_device_unpack.argtypes = [_P, C.c_int]
     lib.csvhost_bam_unpack_stats.restype = None
-    lib.csvhost_bam_unpack_stats.argtypes = [_P, C.POINTER(C.c_uint64 * 6)]
+    lib.csvhost_bam_unpack_stats.argtypes = [_P, C.POINTER(C.c_uint64 * 9)]
+    lib.csvhost_bam_set_device_shard.restype = None
+    lib.csvhost_bam_set_device_shard.argtypes = [_P, C.c_int]
+    lib.csvhost_bam_shard_take_resident.restype = _P
+    lib.csvhost_bam_shard_take_resident.argtypes = [_P, C.c_int, C.POINTER(C.c_uint64)]
     lib.csvhost_bgzf_inflate_file.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     lib.csvhost_bam_shard.argtypes = [_P, C.c_int, C.POINTER(_lib.csv_reads), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(_P), C.POINTER(_P)]
     lib.csvhost_bam_shard_qnames.restype = C.c_int64
@@ -153,6 +158,7 @@ def load() -> C.CDLL:
                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(stage_times), _P]
     lib.csvhost_sig_alts.argtypes = [_P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_process_resident_chromosome_alts.argtypes = [_P, _P, _P, _P, C.c_double, C.c_double, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.csvhost_process_resident_chromosome_alts_resident.argtypes = [_P, _P, C.c_double, C.c_double, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_par_selftest.argtypes = [C.c_int, C.c_int]
     lib.csvhost_string_hashes.argtypes = [C.c_char_p, C.c_uint64, _P]
     lib.csvhost_assign_shards.argtypes = [_P, C.c_uint64, C.c_int, _P]
@@ -382,15 +388,21 @@ def sig_alts(sig: np.ndarray, seq_off=None, seq=None):
     return buf.raw[: ln.value].decode().split("\n")[:-1]
 
 
-def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off=None, seq=None):
-    """processChromosome on a resident shard -> [(start, end, ALT)] of the merged calls."""
+def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off=None, seq=None, resident_seq: bool = False):
+    """processChromosome on a resident shard -> [(start, end, ALT)] of the merged calls. resident_seq: the 50-base ALT strings are cut on the
+    device from the sequences the shard itself holds (a shard built with _lib.SB_SEQ) instead of from seq_off / seq."""
     so = np.ascontiguousarray(seq_off, np.uint64) if seq_off is not None else None
     sq = np.ascontiguousarray(seq, np.uint8) if seq is not None else None
     cap = 1 << 22
     buf = C.create_string_buffer(cap)
     ln = C.c_uint64(0)
-    _check(load().csvhost_process_resident_chromosome_alts(ctx.h, shard.h, so.ctypes.data if so is not None else None,
-                                                           sq.ctypes.data if sq is not None else None, eps, min_pts_pct, buf, cap, C.byref(ln)))
+    if resident_seq:
+        if so is not None or sq is not None:
+            raise ValueError("process_resident_chromosome_alts: resident_seq takes the shard's own sequences, not seq_off / seq")
+        _check(load().csvhost_process_resident_chromosome_alts_resident(ctx.h, shard.h, eps, min_pts_pct, buf, cap, C.byref(ln)))
+    else:
+        _check(load().csvhost_process_resident_chromosome_alts(ctx.h, shard.h, so.ctypes.data if so is not None else None,
+                                                               sq.ctypes.data if sq is not None else None, eps, min_pts_pct, buf, cap, C.byref(ln)))
     out = []
     for line in buf.raw[: ln.value].decode().split("\n")[:-1]:
         a, b, alt = line.split("\t")
@@ -746,6 +758,7 @@ class BamFile:
     def __init__(self, path: str, load_index: bool = True):
         self._inflate_device = -1
         self._unpack_device = -1
+        self._shard_ctx = {}                  # device -> Context the shards of read_contig(shard_on_device=True) are handed out on
         self.h = load().csvhost_bam_open(os.fsencode(path), int(load_index))
         if not self.h:
             raise RuntimeError((load().csvhost_last_error() or b"cannot open BAM").decode())
@@ -760,11 +773,14 @@ class BamFile:
         if self.h:
             load().csvhost_bam_close(self.h)
         self.h = None
+        for c in getattr(self, "_shard_ctx", {}).values():      # (shards handed out on them must have been freed by now)
+            c.close()
+        self._shard_ctx = {}
 
     def __del__(self):
         self.close()
 
-    def _shard(self, i, want_seq, want_qnames):
+    def _shard(self, i, want_seq, want_qnames, resident=False):
         lib = load()
         rs, tid, tl, so, sq = _lib.csv_reads(), C.c_int32(0), C.c_uint32(0), C.c_void_p(), C.c_void_p()
         lib.csvhost_bam_shard(self.h, i, C.byref(rs), C.byref(tid), C.byref(tl), C.byref(so), C.byref(sq))
@@ -772,7 +788,10 @@ class BamFile:
         addr = lambda p: C.cast(p, C.c_void_p).value
         reads = Reads.__new__(Reads)
         reads.pos, reads.flag, reads.mapq, reads.tid = _np_from(addr(rs.pos), n, np.int32), _np_from(addr(rs.flag), n, np.uint16), _np_from(addr(rs.mapq), n, np.uint8), None
-        reads.cigar_off, reads.cigar = _np_from(addr(rs.cigar_off), n + 1, np.uint64), _np_from(addr(rs.cigar), m, np.uint32)
+        if resident:                          # (the CIGAR arrays are in the resident shard: the host's are empty)
+            reads.cigar_off, reads.cigar = np.zeros(1, np.uint64), np.zeros(0, np.uint32)
+        else:
+            reads.cigar_off, reads.cigar = _np_from(addr(rs.cigar_off), n + 1, np.uint64), _np_from(addr(rs.cigar), m, np.uint32)
         out = {"tid": tid.value, "name": self.names[tid.value], "target_len": tl.value, "reads": reads}
         if want_seq:
             out["seq_off"] = _np_from(so.value, n + 1, np.uint64)
@@ -805,17 +824,37 @@ class BamFile:
     def unpack_stats(self) -> dict:
         """what unpack_on_device did in the last read_contig: batches the device unpacked / the host parser read (declined, or not given),
         anchors handed to the device, records it wrote, batches whose decoded bytes never came to the host, batches brought down after all"""
-        v = (C.c_uint64 * 6)()
+        v = (C.c_uint64 * 9)()
         load().csvhost_bam_unpack_stats(self.h, C.byref(v))
-        return dict(zip(("batches_device", "batches_host", "anchors", "records", "batches_kept_on_device", "batches_downloaded"), (int(x) for x in v)))
+        return dict(zip(("batches_device", "batches_host", "anchors", "records", "batches_kept_on_device", "batches_downloaded", "shard_resident",
+                         "batches_appended_host", "cigar_words_downloaded"), (int(x) for x in v)))
 
-    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0, unpack_on_device=False):
+    def read_contig(self, chr: str, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0, unpack_on_device=False,
+                    shard_on_device=False, ctx: "Context | None" = None):
+        """shard_on_device (implies unpack_on_device): the contig's records are appended on the device into a resident shard, batch by batch
+        (csvgpu_shard_builder_*), instead of coming down: the dict then holds that `shard` (a Shard on `ctx`, or on a context this BamFile
+        keeps for the purpose; the caller frees it) beside the small arrays — reads.pos / flag / mapq and the query names; reads.cigar_off,
+        reads.cigar and seq stay empty, the sequences are inside the shard (Context.alt_bases). `shard` is None for a contig without records."""
+        unpack_on_device = unpack_on_device or shard_on_device
         self._inflate_on(inflate_on_device, device)
         self._unpack_on(unpack_on_device, device)
+        load().csvhost_bam_set_device_shard(self.h, int(bool(shard_on_device)))
         k = load().csvhost_bam_read(self.h, chr.encode(), int(want_seq), int(want_qnames), threads, window_blocks, None)
         if k < 0:
             raise RuntimeError((load().csvhost_last_error() or b"BAM read failed").decode())
-        return self._shard(0, want_seq, want_qnames)
+        if not shard_on_device:
+            return self._shard(0, want_seq, want_qnames)
+        m = C.c_uint64(0)
+        handle = load().csvhost_bam_shard_take_resident(self.h, 0, C.byref(m))
+        if not handle:
+            return dict(self._shard(0, want_seq, want_qnames), shard=None)
+        out = self._shard(0, False, want_qnames, resident=True)
+        if ctx is None:
+            ctx = self._shard_ctx.get(device)
+            if ctx is None:
+                ctx = self._shard_ctx[device] = Context(device)
+        out["shard"] = Shard(ctx, handle, out["reads"].n_reads, out["target_len"] + 1)
+        return out
 
     def read_all(self, want_seq=False, want_qnames=False, threads=8, window_blocks=0, inflate_on_device=False, device=0):
         self._inflate_on(inflate_on_device, device)
@@ -853,14 +892,17 @@ def write_bam(path: str, ref_names, ref_lens, tid, reads: Reads, qnames, seq_off
 def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, save_cnv=False,
             genome: ReferenceGenome | None = None, vcf_dir=None, gap_path=None, file_date=None, capacity: int = 1 << 20,
             snp_vcf=None, pfb_table=None, ethnicity="", inflate_on_device: bool = False, split_groups_on_device: bool = False, split_fits_on_device: bool = False,
-            split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False):
+            split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False, shard_on_device: bool = False):
     """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict).
+    shard_on_device (implies unpack_on_device): every contig's resident shard is built on the device from the unpacked batches and handed to
+    the run — no host arrays, no upload; the 50-base ALT strings are cut from the shard's own sequences on the device.
     unpack_on_device: the records of every batch are unpacked on ctx's device (csvgpu_bam_unpack, on the reader's own context) instead of
     by the host parser; a batch the device declines is parsed on the host.
     inflate_on_device: the BAM's BGZF blocks are inflated on ctx's device (csvgpu_bgzf_inflate, on a context of the reader's own) instead of
     on the host's threads; the other switches as in run(). None of them changes the calls."""
     opt_in = (int(bool(split_groups_on_device)) << 9) | (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | \
-             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | (int(bool(unpack_on_device)) << 14) | ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
+             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | (int(bool(unpack_on_device or shard_on_device)) << 14) | (int(bool(shard_on_device)) << 15) | \
+             ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
     out = np.zeros(capacity, CALL_DTYPE)
     tid = np.zeros(capacity, np.int32)
     n = C.c_uint64(0)

@@ -620,9 +620,66 @@ int csvgpu_bam_unpack_dev(csv_ctx *ctx, const uint8_t *d_bytes, uint64_t len, co
 int csvgpu_bam_unpack(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
                       uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const csv_bam_out *out, csv_bam_counts *counts);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Resident shards built on the device from BAM batches (opt-in: the from-file path fills host arrays and uploads them by default) */
+/* A builder owns device arrays that grow: batches are appended behind its tail, and csvgpu_shard_builder_finish hands the arrays to a
+ * csv_shard of the kind csvgpu_shard_upload makes (padded CIGAR array, sortedness known) — without the host arrays of the reader's BamShard
+ * (host/bam_io.cpp readContig) and their upload (host/sv_caller.cpp run). `want`: what is kept beside the reads — the 4-bit packed
+ * sequences (for csvgpu_alt_bases_resident), the query names (for the split-read pass, which fetches them), their hashes (what
+ * csvgpu_shard_set_qname_hash would upload). One builder is used from one host thread at a time, on contexts of one device. */
+typedef struct csv_shard_builder csv_shard_builder;
+enum { CSV_SB_SEQ = 1, CSV_SB_NAMES = 2, CSV_SB_NAME_HASH = 4 };
+typedef struct csv_shard_sizes { uint64_t n_reads, n_cigar, n_seq, n_name; } csv_shard_sizes;   /* records, CIGAR words, sequence bytes, name bytes */
+
+/* reserve (may be NULL or zeros): room allocated now, as readContig sizes its arrays from the compressed span. NULL on failure. */
+csv_shard_builder *csvgpu_shard_builder_create(csv_ctx *ctx, uint32_t want, const csv_shard_sizes *reserve);
+/* csvgpu_bam_unpack_dev writing at the builder's tail (BamReader::append per record, host/bam_io.cpp): a sizing pass gives the exact counts,
+ * every array that is too small grows (a new block of at least 1.5x the old size, a device-to-device copy, the old block freed), a second
+ * pass writes in place with the builder's totals as cigar_base / seq_base / name_base. d_bytes, anchors, tid, end, counts and the return
+ * values are that function's: CSV_OK; 1 = declined, NOTHING appended, the builder's sizes unchanged, counts->status says why (the caller
+ * parses the bytes itself and appends them with _append_host); CSV_E*. CSV_ECAPACITY never leaves this function; after CSV_ENOMEM (a
+ * failed growth) the builder is valid with its old contents, and the same append may be tried again. The CIGAR array always keeps the
+ * pad words of an uploaded shard allocated behind its tail. Waits for its kernels. */
+int  csvgpu_shard_builder_append_bam(csv_ctx *ctx, csv_shard_builder *b, const uint8_t *d_bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors,
+                                     int32_t tid, int64_t end, csv_bam_counts *counts);
+/* A batch the host parser read (BamReader::append; a batch the device declined): HOST arrays, appended behind the tail. batch->cigar_off,
+ * seq_off and name_off are relative to the batch's own arrays (any first value; the span [off[0], off[n_reads]) is taken) and are rebased by
+ * the builder's totals. Arrays the builder does not want are ignored; CSV_EINVAL, nothing changed: a wanted one that is null, offsets not
+ * monotone, and what csvgpu_shard_upload refuses of a csv_reads. */
+int  csvgpu_shard_builder_append_host(csv_ctx *ctx, csv_shard_builder *b, const csv_reads *batch, const uint64_t *seq_off, const uint8_t *seq,
+                                      const uint64_t *name_off, const uint8_t *name, const uint64_t *name_hash);
+int  csvgpu_shard_builder_sizes(csv_ctx *ctx, const csv_shard_builder *b, csv_shard_sizes *out);
+/* The shard csvgpu_shard_upload would make of the appended records (with no record: of zero reads), the arrays handed over, not copied.
+ * Both appends keep "pos[i] < pos[i - 1]" in a device word (each batch's first record against the previous tail), so the shard's sortedness
+ * is known, as after an upload (the upload's loop over pos, api/shard.hip). With CSV_SB_NAME_HASH the hashes are in place as after
+ * csvgpu_shard_set_qname_hash. Consumes the builder, also on failure (NULL). The arrays are plain device memory: once this has returned the
+ * shard may be used and freed through another context of the same device, like an uploaded one. */
+csv_shard *csvgpu_shard_builder_finish(csv_ctx *ctx, csv_shard_builder *b, uint32_t depth_len);
+void csvgpu_shard_builder_destroy(csv_ctx *ctx, csv_shard_builder *b);
+
+/* What a resident shard holds, copied to the host (any shard; n_seq / n_name are 0 where it holds no sequences / names): the BamShard's
+ * pos / flag / mapq and query names for the split-read pass (host/split_caller.cpp), which are small. Any output may be NULL.
+ * fetch_names: CSV_EINVAL when name_off / name are asked of a shard without names, or name_hash of one without hashes. */
+int  csvgpu_shard_sizes(csv_ctx *ctx, const csv_shard *shard, csv_shard_sizes *out);
+int  csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *shard, int32_t *pos, uint16_t *flag, uint8_t *mapq, uint64_t *cigar_off, uint32_t *cigar);
+int  csvgpu_shard_fetch_names(csv_ctx *ctx, csv_shard *shard, uint64_t *name_off, uint8_t *name, uint64_t *name_hash);
+/* Frees the packed sequences of a built shard (the largest of its arrays: half a byte per base). csvgpu_alt_bases_resident returns
+ * CSV_EINVAL afterwards. CSV_OK also when there is none. */
+int  csvgpu_shard_drop_sequences(csv_ctx *ctx, csv_shard *shard);
+/* Replaces the base loop of SVCaller::toSVCall (host/sv_caller.cpp:47-62; the reference's sv_caller.cpp:572-590, :607-625) on the
+ * sequences a built shard holds: item i, len = out_off[i + 1] - out_off[i], writes len characters at out + out_off[i] — when
+ * ((uint64_t)qpos[i] + len + 1) / 2 <= the BYTES of record read[i]'s packed sequence, the bases from query offset qpos[i] on through the
+ * table "=ACMGRSVTWYHKDBN" with R Y K M S W B D H V turned into N (for an odd l_seq the last byte's pad nibble is inside the bound and
+ * decodes to whatever it holds, as on the host); otherwise len times N. out_off has n + 1 entries.
+ * CSV_EINVAL, nothing launched or written: read[i] >= the shard's records, out_off not non-decreasing, a shard without sequences (uploaded,
+ * wrapped, built without CSV_SB_SEQ, or dropped). Indices and offsets go up and the characters come back through the page-locked block;
+ * one launch, one wait. Timed under CSV_K_MISC. */
+int  csvgpu_alt_bases_resident(csv_ctx *ctx, csv_shard *shard, const uint32_t *read, const uint32_t *qpos, const uint64_t *out_off, uint64_t n, char *out);
+
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
- * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster). */
+ * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster and of the
+ * array growth in csvgpu_shard_builder_append_bam). */
 void csvgpu_test_fail_next_alloc(int n);
 
 /* Test build only: the device primitives under every kernel chain (kernels/sort.hip, launch_prefix_max of kernels/depth.hip), called
