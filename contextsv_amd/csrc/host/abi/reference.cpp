@@ -1,0 +1,87 @@
+// reference.cpp — reference genome + VCF writer (fasta_query.cpp, saveToVCF)
+#include <fstream>
+
+#include "abi.hpp"
+
+extern "C" {
+
+csvhost_fasta *csvhost_fasta_open(const char *path)
+{
+    try {
+        csvhost_fasta *h = new csvhost_fasta();
+        if (h->g.setFilepath(path ? path : "") != 0) { delete h; set_error("No FASTA filepath provided"); return nullptr; }
+        return h;
+    } catch (const std::exception &e) { set_error(e.what()); return nullptr; }
+}
+void csvhost_fasta_free(csvhost_fasta *h) { delete h; }
+
+// length of the view, -1 on error (unknown contig); at most cap bytes are copied to buf
+int64_t csvhost_fasta_query(const csvhost_fasta *h, const char *chr, uint32_t pos_start, uint32_t pos_end, char *buf, uint64_t cap)
+{
+    try {
+        std::string_view v = h->g.query(chr, pos_start, pos_end);
+        if (buf && cap) memcpy(buf, v.data(), (size_t)std::min<uint64_t>(cap, v.size()));
+        return (int64_t)v.size();
+    } catch (const std::exception &e) { set_error(e.what()); return -1; }
+}
+int csvhost_fasta_compare(const csvhost_fasta *h, const char *chr, uint32_t pos_start, uint32_t pos_end, const char *seq, float threshold)
+{
+    try { return h->g.compare(chr, pos_start, pos_end, seq, threshold) ? 1 : 0; } catch (const std::exception &e) { set_error(e.what()); return -1; }
+}
+uint32_t csvhost_fasta_length(const csvhost_fasta *h, const char *chr) { return h->g.getChromosomeLength(chr); }
+// contig header and the sorted contig list ('\n'-joined) as text; returns the full length
+int64_t csvhost_fasta_contig_header(const csvhost_fasta *h, char *buf, uint64_t cap) { return (int64_t)copy_text(h->g.getContigHeader(), buf, cap); }
+int64_t csvhost_fasta_chromosomes(const csvhost_fasta *h, char *buf, uint64_t cap)
+{
+    std::string s;
+    for (const std::string &c : h->g.getChromosomes()) { if (!s.empty()) s += '\n'; s += c; }
+    return (int64_t)copy_text(s, buf, cap);
+}
+
+// Calls of contig t = calls[call_off[t] .. call_off[t+1]) with ALT strings alts[i]. Depth comes from resident shards
+// (shards != nullptr, ShardDepthSource) or from host arrays depth[t][0..depth_len[t]) (a null depth[t] = contig without a map).
+// map_order != 0 goes through saveToVCF's unordered_map iteration; otherwise contigs are written in the order given.
+// counts = {total, unclassified, assembly-gap filtered}.
+int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fasta, const char *gap_path, const char *file_date, int n_contigs,
+                     const char *const *chr_names, const uint64_t *call_off, const csvhost_call *calls, const char *const *alts,
+                     csv_shard *const *shards, const uint32_t *const *depth, const uint64_t *depth_len, int map_order, int32_t *counts)
+{
+    GUARD({
+        std::vector<std::pair<std::string, std::vector<SVCall>>> per((size_t)n_contigs);
+        std::unordered_map<std::string, std::vector<uint32_t>> host_depth;
+        ShardDepthSource shard_src(ctx);
+        for (int t = 0; t < n_contigs; t++) {
+            per[t].first = chr_names[t];
+            for (uint64_t i = call_off[t]; i < call_off[t + 1]; i++) {
+                SVCall c = from_pod(calls[i]);
+                c.alt_allele = alts[i];
+                per[t].second.push_back(c);
+            }
+            if (shards) { if (shards[t]) shard_src.add(chr_names[t], shards[t]); }
+            else if (depth[t]) host_depth[chr_names[t]].assign(depth[t], depth[t] + depth_len[t]);
+        }
+        HostDepthSource host_src(host_depth);
+        const DepthSource &src = shards ? (const DepthSource &)shard_src : (const DepthSource &)host_src;
+        VCFOptions opt;
+        opt.assembly_gaps = gap_path ? gap_path : "";
+        opt.output_dir = out_dir;
+        opt.file_date = file_date ? file_date : "";
+        VCFCounts c;
+        if (map_order) {
+            std::unordered_map<std::string, std::vector<SVCall>> m;
+            for (auto &e : per) m[e.first] = e.second;
+            if (!saveToVCF(m, opt, fasta->g, src, &c)) throw std::runtime_error("saveToVCF returned early");
+        } else {
+            std::unordered_map<std::string, std::vector<std::pair<uint32_t, uint32_t>>> gaps;
+            if (!opt.assembly_gaps.empty() && !loadAssemblyGaps(opt.assembly_gaps, gaps)) throw std::runtime_error("cannot open assembly gap file");
+            std::ofstream f(opt.output_dir + "/output.vcf");
+            if (!f.is_open()) throw std::runtime_error("cannot open output.vcf");
+            std::vector<std::pair<std::string, const std::vector<SVCall> *>> order;
+            for (auto &e : per) order.emplace_back(e.first, &e.second);
+            c = writeVCF(f, order, opt, gaps, fasta->g, src);
+        }
+        if (counts) { counts[0] = c.total; counts[1] = c.unclassified; counts[2] = c.assembly_gap_filtered; }
+    })
+}
+
+}  // extern "C"

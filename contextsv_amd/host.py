@@ -13,8 +13,18 @@ from .context import Context, Reads, Shard
 # CONTEXTSV_HOST_LIB: another build of the host mirror (tests: the AddressSanitizer build, csrc/_obj/libcontextsv_host_asan.so)
 HOST_LIB_PATH = os.environ.get("CONTEXTSV_HOST_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcontextsv_host.so")
 
+# the structs below are the twins of csrc/host/abi/csvhost_abi.h (tests/test_run_options.py holds the two together)
 CALL_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("sv_type", "<i4"), ("cluster_size", "<i4"), ("hmm_likelihood", "<f8"),
                        ("id", "<i8"), ("aln_flags", "<u4"), ("genotype", "<i4"), ("cn_state", "<i4"), ("aln_offset", "<i4")])
+
+
+class run_options(C.Structure):
+    """csvhost_run_options: what a caller may set of a run, one field per RunParams / RunSchedule field (same name, same sense)."""
+    _fields_ = [("size", C.c_uint32), ("dbscan_epsilon", C.c_double), ("dbscan_min_pts_pct", C.c_double)] + \
+               [(k, C.c_int32) for k in ("sample_size", "min_cnv_length", "host_threads", "cigar_cn", "split_svs", "merge_split_svs", "merge_final_svs",
+                                         "split_order_on_device", "overlap_split_prepare", "split_groups_on_device", "split_fits_on_device",
+                                         "split_tables_on_device", "cn_observations_on_device", "inflate_on_device", "inflate_device", "unpack_on_device",
+                                         "shard_on_device", "save_cnv", "early_batches", "split_beside_pass", "split_order_self", "prepare_delay_ms")]
 
 
 class chr_stats(C.Structure):
@@ -76,8 +86,10 @@ def load() -> C.CDLL:
     lib.csvhost_split_fits_host.argtypes = [_P, C.POINTER(_lib.csv_split_tables), _P, C.c_uint64, _P, _P, _P, C.c_double, C.c_int, _P]
     lib.csvhost_split_refs.argtypes = [C.c_uint64, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint64, _P]
     lib.csvhost_split_groups_host.argtypes = [_P, _P, _P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]
-    lib.csvhost_run.argtypes = [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_lib.csv_hmm), C.c_double, C.c_double,
-                                C.c_int, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_char_p, C.c_char_p, _P, C.c_uint64, _P, C.c_int]
+    lib.csvhost_run_options_init.restype = None
+    lib.csvhost_run_options_init.argtypes = [C.POINTER(run_options)]
+    lib.csvhost_run.argtypes = [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_lib.csv_hmm), C.POINTER(run_options),
+                                _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_char_p, C.c_char_p, _P, C.c_uint64, _P]
     lib.csvhost_read_chmm.argtypes = [C.c_char_p, C.POINTER(_lib.csv_hmm), C.POINTER(C.c_int32)]
     lib.csvhost_sort_select_check.argtypes = [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.csvhost_partition_check.argtypes = [_P, C.c_uint64, C.POINTER(C.c_int)]
@@ -120,7 +132,7 @@ def load() -> C.CDLL:
     lib.csvhost_bam_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, C.c_char_p, _P, _P, _P,
                                       C.c_int, C.c_int]
     lib.csvhost_synth_write_bam.argtypes = [_P, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
-    lib.csvhost_run_bam.argtypes = [_P, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(_lib.csv_hmm), C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_int,
+    lib.csvhost_run_bam.argtypes = [_P, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(_lib.csv_hmm), C.POINTER(run_options),
                                     _P, C.c_char_p, C.c_char_p, C.c_char_p, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(bam_stats),
                                     C.c_char_p, C.c_char_p, C.c_char_p]
     lib.csvhost_snp_open.restype = _P
@@ -154,7 +166,7 @@ def load() -> C.CDLL:
     lib.csvhost_genome_n_contigs.restype = C.c_uint64
     lib.csvhost_genome_n_contigs.argtypes = [_P]
     lib.csvhost_genome_contig_info.argtypes = [_P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(_P)]
-    lib.csvhost_genome_run.argtypes = [_P, _P, C.c_int, _P, C.POINTER(_lib.csv_hmm), C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_int, C.c_int, _P, _P,
+    lib.csvhost_genome_run.argtypes = [_P, _P, C.c_int, _P, C.POINTER(_lib.csv_hmm), C.POINTER(run_options), _P, _P,
                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(stage_times), _P]
     lib.csvhost_sig_alts.argtypes = [_P, C.c_uint64, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_process_resident_chromosome_alts.argtypes = [_P, _P, _P, _P, C.c_double, C.c_double, _P, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -265,6 +277,34 @@ class SynthShard:
 
 
 _EARLY_BATCHES = {"timed": 0, "none": 1, "all": 2, "every3": 3}          # RunSchedule::EarlyBatches
+# keywords of Genome.run / run / run_bam whose run_options field has another name (the others are called what their field is called)
+_OPTION_OF = {"eps": "dbscan_epsilon", "min_pts_pct": "dbscan_min_pts_pct", "min_cnv": "min_cnv_length", "overlap_split": "overlap_split_prepare"}
+_OPTION_TYPES = dict(run_options._fields_[1:])
+
+
+def _run_options(**keywords) -> run_options:
+    """The library's defaults (csvhost_run_options_init: RunParams' own) with the fields set that the keywords name."""
+    o = run_options()
+    load().csvhost_run_options_init(C.byref(o))
+    for key, value in keywords.items():
+        if key == "early_batches":
+            if value not in _EARLY_BATCHES:
+                raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {value!r}")
+            o.early_batches = _EARLY_BATCHES[value]
+        elif key == "merges":
+            o.merge_split_svs = o.merge_final_svs = int(bool(value))
+        elif key == "host_split_order":
+            o.split_order_on_device = int(not value)
+        else:
+            field = _OPTION_OF.get(key, key)
+            if field not in _OPTION_TYPES:
+                raise TypeError(f"{key!r} is no run option")
+            if field == "prepare_delay_ms" and not 0 <= int(value) < 1 << 31:
+                raise ValueError(f"prepare_delay_ms must be in [0, {(1 << 31) - 1}], not {value!r}")
+            setattr(o, field, value if _OPTION_TYPES[field] is C.c_double else int(value))
+    if o.shard_on_device:
+        o.unpack_on_device = 1
+    return o
 
 
 class Genome:
@@ -316,13 +356,11 @@ class Genome:
         whatever the two other switches say; the calls are the same. cn_observations_on_device: the observation vectors of both copy-number
         passes built on the device from the window kernel's output and decoded there (csvgpu_cn_decode_resident_many) instead of windows back,
         the vectors assembled on the host pool and sent up again; the calls are the same."""
-        if early_batches not in _EARLY_BATCHES:
-            raise ValueError(f"early_batches must be one of {sorted(_EARLY_BATCHES)}, not {early_batches!r}")
-        if not 0 <= int(prepare_delay_ms) < 1 << 15:
-            raise ValueError(f"prepare_delay_ms must be in [0, 32767], not {prepare_delay_ms!r}")
-        passes = int(split_svs) | (int(cigar_cn) << 1) | (int(merges) << 2) | (int(host_split_order) << 3) | (int(not overlap_split) << 4) | \
-            (_EARLY_BATCHES[early_batches] << 5) | (int(not split_beside_pass) << 7) | (int(not split_order_self) << 8) | (int(bool(split_groups_on_device)) << 9) | \
-            (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | (int(bool(cn_observations_on_device)) << 12) | (int(prepare_delay_ms) << 16)
+        opt = _run_options(eps=eps, min_pts_pct=min_pts_pct, sample_size=sample_size, min_cnv=min_cnv, split_svs=split_svs, cigar_cn=cigar_cn, merges=merges,
+                           host_threads=host_threads, host_split_order=host_split_order, overlap_split=overlap_split, early_batches=early_batches,
+                           split_beside_pass=split_beside_pass, split_order_self=split_order_self, prepare_delay_ms=prepare_delay_ms,
+                           split_groups_on_device=split_groups_on_device, split_fits_on_device=split_fits_on_device,
+                           split_tables_on_device=split_tables_on_device, cn_observations_on_device=cn_observations_on_device)
         n = len(self)
         if getattr(self, "_cap", 0) < capacity:              # result buffers live with the genome (tens of megabytes of page faults per call otherwise)
             self._bufs = [(np.empty(capacity, CALL_DTYPE), np.empty(capacity, np.int32)) for _ in range(2)]
@@ -334,8 +372,7 @@ class Genome:
         cs = (chr_stats * max(n, 1))()
         lanes = lanes or []
         lp = (C.c_void_p * max(len(lanes), 1))(*[c.h for c in lanes])
-        _check(load().csvhost_genome_run(self.h, ctx.h, len(lanes), lp, C.byref(hmm), eps, min_pts_pct, sample_size, min_cnv, passes, host_threads,
-                                         out.ctypes.data, tid.ctypes.data, capacity, C.byref(k), C.byref(st), cs))
+        _check(load().csvhost_genome_run(self.h, ctx.h, len(lanes), lp, C.byref(hmm), C.byref(opt), out.ctypes.data, tid.ctypes.data, capacity, C.byref(k), C.byref(st), cs))
         if k.value > capacity:
             raise RuntimeError("Genome.run: capacity too small")
         if copy:
@@ -603,7 +640,8 @@ def run(ctx: Context, contigs: list, hmm, eps=0.1, min_pts_pct=0.1, sample_size=
     """SVCaller::run mirror. contigs: list of dicts {reads: Reads, depth_len, qname_id: uint32[n], snps: dict}; contig t is named
     "contig<t>". With genome (ReferenceGenome) and vcf_dir the run ends by writing <vcf_dir>/output.vcf.
     -> (merged calls, contig id per call[, ALT strings])."""
-    read_off = np.zeros(len(contigs) + 1, np.uint64)
+    opt = _run_options(eps=eps, min_pts_pct=min_pts_pct, sample_size=sample_size, min_cnv=min_cnv, save_cnv=save_cnv)
+    read_off =np.zeros(len(contigs) + 1, np.uint64)
     read_off[1:] = np.cumsum([c["reads"].n_reads for c in contigs])
     cig_base = np.concatenate([[0], np.cumsum([c["reads"].n_cigar for c in contigs])]).astype(np.uint64)
     pos = np.ascontiguousarray(np.concatenate([c["reads"].pos for c in contigs]), np.int32)
@@ -628,11 +666,10 @@ def run(ctx: Context, contigs: list, hmm, eps=0.1, min_pts_pct=0.1, sample_size=
     alt_off = np.zeros(cap + 1, np.uint64)
     _check(load().csvhost_run(ctx.h, len(contigs), read_off.ctypes.data, dl.ctypes.data, pos.ctypes.data, flag.ctypes.data, mapq.ctypes.data,
                               coff.ctypes.data, cigar.ctypes.data, qid.ctypes.data, snp_off.ctypes.data, sp.ctypes.data, sb.ctypes.data,
-                              sf.ctypes.data, sh.ctypes.data, C.byref(hmm), eps, min_pts_pct, sample_size, min_cnv, out.ctypes.data,
-                              tid.ctypes.data, cap, C.byref(n),
+                              sf.ctypes.data, sh.ctypes.data, C.byref(hmm), C.byref(opt), out.ctypes.data, tid.ctypes.data, cap, C.byref(n),
                               genome.h if genome is not None and vcf_dir else None, os.fsencode(vcf_dir) if vcf_dir else None,
                               os.fsencode(gap_path) if gap_path else None, file_date.encode() if file_date else None,
-                              alt_buf.ctypes.data if want_alts else None, alt_cap, alt_off.ctypes.data if want_alts else None, int(save_cnv)))
+                              alt_buf.ctypes.data if want_alts else None, alt_cap, alt_off.ctypes.data if want_alts else None))
     if want_alts:
         raw = alt_buf.tobytes()
         alts = [raw[int(alt_off[i]):int(alt_off[i + 1])] for i in range(n.value)]
@@ -900,15 +937,16 @@ def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0
     by the host parser; a batch the device declines is parsed on the host.
     inflate_on_device: the BAM's BGZF blocks are inflated on ctx's device (csvgpu_bgzf_inflate, on a context of the reader's own) instead of
     on the host's threads; the other switches as in run(). None of them changes the calls."""
-    opt_in = (int(bool(split_groups_on_device)) << 9) | (int(bool(split_fits_on_device)) << 10) | (int(bool(split_tables_on_device)) << 11) | \
-             (int(bool(cn_observations_on_device)) << 12) | (int(bool(inflate_on_device)) << 13) | (int(bool(unpack_on_device or shard_on_device)) << 14) | (int(bool(shard_on_device)) << 15) | \
-             ((int(getattr(ctx, "device", 0)) & 0x7f) << 24)
+    opt = _run_options(eps=eps, min_pts_pct=min_pts_pct, sample_size=sample_size, min_cnv=min_cnv, split_svs=split_svs, cigar_cn=cigar_cn, save_cnv=save_cnv,
+                       inflate_on_device=inflate_on_device, inflate_device=getattr(ctx, "device", 0), split_groups_on_device=split_groups_on_device,
+                       split_fits_on_device=split_fits_on_device, split_tables_on_device=split_tables_on_device,
+                       cn_observations_on_device=cn_observations_on_device, unpack_on_device=unpack_on_device, shard_on_device=shard_on_device)
     out = np.zeros(capacity, CALL_DTYPE)
     tid = np.zeros(capacity, np.int32)
     n = C.c_uint64(0)
     st = bam_stats()
-    _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm), eps,
-                                  min_pts_pct, sample_size, min_cnv, int(split_svs) | (int(cigar_cn) << 1) | (int(save_cnv) << 2) | opt_in, genome.h if genome is not None and vcf_dir else None,
+    _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm),
+                                  C.byref(opt), genome.h if genome is not None and vcf_dir else None,
                                   os.fsencode(vcf_dir) if vcf_dir else None, os.fsencode(gap_path) if gap_path else None,
                                   file_date.encode() if file_date else None, out.ctypes.data, tid.ctypes.data, capacity, C.byref(n), C.byref(st),
                                   os.fsencode(snp_vcf) if snp_vcf else None, os.fsencode(pfb_table) if pfb_table else None, ethnicity.encode()))
