@@ -87,6 +87,20 @@ class csv_bam_counts(C.Structure):
                 ("n_name", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint64), ("stopped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class csv_vcf_out(C.Structure):
+    _fields_ = [("line_off", C.c_void_p), ("chrom_len", C.c_void_p), ("pos", C.c_void_p), ("value", C.c_void_p), ("defer_off", C.c_void_p),
+                ("cap", C.c_uint64), ("cap_defer", C.c_uint64)]
+
+
+class csv_vcf_counts(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_kept", C.c_uint64), ("n_deferred", C.c_uint64), ("stop_off", C.c_uint64), ("status", C.c_uint64)]
+
+
+VCF_TILE_BYTES = 4096    # include/csvgpu.h CSV_VCF_TILE_BYTES
+VCF_HEADER_LINE = 1      # csv_vcf_counts::status reason
+VCF_NO_STOP = (1 << 64) - 1
+
+
 class csv_shard_sizes(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq", C.c_uint64), ("n_name", C.c_uint64)]
 
@@ -163,6 +177,12 @@ ABI = {
                                     C.POINTER(csv_bam_counts)]),
     "csvgpu_bam_unpack_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(csv_bam_out),
                                         C.POINTER(csv_bam_counts)]),
+    "csvgpu_vcf_snp_parse": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_vcf_out), C.POINTER(csv_vcf_counts)]),
+    "csvgpu_vcf_snp_parse_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_vcf_out), C.POINTER(csv_vcf_counts)]),
+    "csvgpu_vcf_af_parse": (C.c_int, [_P, _P, C.c_uint64, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, _P, C.c_uint64, C.POINTER(csv_vcf_out),
+                                      C.POINTER(csv_vcf_counts)]),
+    "csvgpu_vcf_af_parse_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, _P, C.c_uint64, C.POINTER(csv_vcf_out),
+                                          C.POINTER(csv_vcf_counts)]),
     "csvgpu_shard_builder_create": (_P, [_P, C.c_uint32, C.POINTER(csv_shard_sizes)]),
     "csvgpu_shard_builder_append_bam": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.POINTER(csv_bam_counts)]),
     "csvgpu_shard_builder_append_host": (C.c_int, [_P, _P, C.POINTER(csv_reads), _P, _P, _P, _P, _P]),

@@ -552,6 +552,114 @@ class Context:
         o = self._bam_out(out, address, lambda t: int(t.numel()), "bam_unpack_dev")
         return self._bam_call(self.lib.csvgpu_bam_unpack_dev, d_bytes.data_ptr(), int(d_bytes.numel()), anchors, tid, end, bases, o)
 
+    # -------------------------------------------------------------------------------- VCF lines
+    _VCF_DTYPES = dict(line_off=np.uint32, chrom_len=np.uint32, pos=np.uint32, value=np.float64, defer_off=np.uint32)
+
+    @staticmethod
+    def _vcf_out(arrays, address, numel, af, what):
+        """csv_vcf_out over the caller's arrays (numpy or torch, by the two accessors): the capacities are what the arrays hold."""
+        o = _lib.csv_vcf_out()
+        per_record = ["line_off", "pos", "value"] + ([] if af else ["chrom_len"])
+        for k in per_record + ["defer_off"]:
+            if arrays.get(k) is None:
+                raise ValueError(f"{what}: array '{k}' is required")
+            setattr(o, k, address(arrays[k], k))
+        o.cap = min(numel(arrays[k]) for k in per_record)
+        o.cap_defer = numel(arrays["defer_off"])
+        return o
+
+    @staticmethod
+    def _vcf_counts(c) -> dict:
+        d = {k: int(getattr(c, k)) for k in ("n_lines", "n_kept", "n_deferred", "stop_off", "status")}
+        d["reason"], d["offset"] = d["status"] & 0xFF, d["status"] >> 8
+        return d
+
+    def _vcf_call(self, dev, text_ptr, length, o, af_args):
+        c = _lib.csv_vcf_counts()
+        if af_args[0] == "snp":
+            fn = self.lib.csvgpu_vcf_snp_parse_dev if dev else self.lib.csvgpu_vcf_snp_parse
+            rc = fn(self.h, text_ptr, length, int(bool(af_args[1])), int(bool(af_args[2])), C.byref(o), C.byref(c))
+        else:
+            _, contig, needle, pos_ptr, n = af_args
+            contig, needle = (x.encode() if isinstance(x, str) else bytes(x) for x in (contig, needle))
+            fn = self.lib.csvgpu_vcf_af_parse_dev if dev else self.lib.csvgpu_vcf_af_parse
+            rc = fn(self.h, text_ptr, length, contig, len(contig), needle, len(needle), pos_ptr, n, C.byref(o), C.byref(c))
+        if rc < 0 and rc != _lib.CSV_ECAPACITY:
+            self._check(rc)
+        return rc, self._vcf_counts(c)
+
+    def _vcf_host(self, text, out, af, form):
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+
+        def address(a, k):
+            if a.dtype != self._VCF_DTYPES[k] or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise ValueError(f"vcf_parse: '{k}' must be a writeable contiguous {np.dtype(self._VCF_DTYPES[k]).name} array")
+            return a.ctypes.data
+        o = self._vcf_out(out, address, len, af, "vcf_parse")
+        return self._vcf_call(False, ptr(text), len(text), o, form)
+
+    def _vcf_sized(self, into, af):
+        """a sizing call (CSV_ECAPACITY carries the exact counts), then the call into arrays of exactly those sizes"""
+        def alloc(n, d):
+            a = dict(line_off=np.zeros(max(n, 1), np.uint32)[:n], pos=np.zeros(max(n, 1), np.uint32)[:n], value=np.zeros(max(n, 1), np.float64)[:n],
+                     defer_off=np.zeros(max(d, 1), np.uint32)[:d])
+            if not af:
+                a["chrom_len"] = np.zeros(max(n, 1), np.uint32)[:n]
+            return a
+        arrays = alloc(0, 0)
+        rc, c = into(arrays)
+        if rc == _lib.CSV_ECAPACITY:
+            arrays = alloc(c["n_kept"], c["n_deferred"])
+            rc, c = into(arrays)
+            if rc < 0:
+                self._check(rc)
+        c["declined"] = rc == 1
+        if rc == 0:
+            c.update(arrays)
+        return c
+
+    def vcf_snp_parse_into(self, text, out: dict, dp_int: bool = True, ad_int: bool = True):
+        """csvgpu_vcf_snp_parse: the lines of `text` (uint8: whole VCF data lines, no header) decided on the device by the rules of
+        SNPFile::load into the caller's numpy arrays `out` (line_off, chrom_len, pos uint32; value float64: the BAF; defer_off uint32: the
+        lines the caller parses itself); the capacities are the arrays' lengths. -> (rc, counts): rc 0 written, 1 declined
+        (counts['reason'] at counts['offset']), CSV_ECAPACITY with the exact counts."""
+        return self._vcf_host(text, out, False, ("snp", dp_int, ad_int))
+
+    def vcf_snp_parse(self, text, dp_int: bool = True, ad_int: bool = True) -> dict:
+        """The same into arrays of exactly the kept and deferred counts -> dict of the counts, 'declined', and (unless declined) the arrays."""
+        return self._vcf_sized(lambda a: self.vcf_snp_parse_into(text, a, dp_int, ad_int), False)
+
+    def vcf_af_parse_into(self, text, contig, needle, sorted_pos, out: dict):
+        """csvgpu_vcf_af_parse: the population file's lines by the rules of SNPFile::table — the records of `contig` at one of the
+        ascending `sorted_pos` whose INFO holds `needle` ("AF=" / "AF_<ethnicity>="); value: the frequency; counts['stop_off']: the first
+        line behind the last position (VCF_NO_STOP if none). -> (rc, counts) as vcf_snp_parse_into."""
+        sorted_pos = np.ascontiguousarray(sorted_pos, np.uint32)
+        return self._vcf_host(text, out, True, ("af", contig, needle, ptr(sorted_pos), len(sorted_pos)))
+
+    def vcf_af_parse(self, text, contig, needle, sorted_pos) -> dict:
+        return self._vcf_sized(lambda a: self.vcf_af_parse_into(text, contig, needle, sorted_pos, a), True)
+
+    def _vcf_dev(self, d_text, out, af, form):
+        def address(t, k):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != np.dtype(self._VCF_DTYPES[k]).itemsize:
+                raise ValueError(f"vcf_parse_dev: '{k}' must be a contiguous device tensor of {np.dtype(self._VCF_DTYPES[k]).itemsize}-byte elements")
+            return t.data_ptr()
+        if not d_text.is_cuda or not d_text.is_contiguous() or d_text.element_size() != 1:
+            raise ValueError("vcf_parse_dev: contiguous uint8 device tensor expected")
+        o = self._vcf_out(out, address, lambda t: int(t.numel()), af, "vcf_parse_dev")
+        return self._vcf_call(True, d_text.data_ptr(), int(d_text.numel()), o, form)
+
+    def vcf_snp_parse_dev(self, d_text, out: dict, dp_int: bool = True, ad_int: bool = True):
+        """csvgpu_vcf_snp_parse_dev: the same with the text (at any alignment: what bgzf_inflate_dev left) and the outputs as torch tensors
+        on this context's device (4-byte elements; value 8-byte). -> (rc, counts) as vcf_snp_parse_into."""
+        return self._vcf_dev(d_text, out, False, ("snp", dp_int, ad_int))
+
+    def vcf_af_parse_dev(self, d_text, contig, needle, d_sorted_pos, out: dict):
+        """csvgpu_vcf_af_parse_dev: d_sorted_pos a device tensor of 4-byte elements, ascending (not checked)."""
+        if not d_sorted_pos.is_cuda or not d_sorted_pos.is_contiguous() or d_sorted_pos.element_size() != 4:
+            raise ValueError("vcf_af_parse_dev: sorted_pos must be a contiguous device tensor of 4-byte elements")
+        return self._vcf_dev(d_text, out, True, ("af", contig, needle, d_sorted_pos.data_ptr(), int(d_sorted_pos.numel())))
+
     # -------------------------------------------------------------------------------- timing
     def synchronize(self):
         self._check(self.lib.csvgpu_synchronize(self.h))

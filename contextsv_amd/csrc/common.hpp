@@ -417,6 +417,38 @@ void launch_bam_fields(hipStream_t s, const uint8_t *bytes, uint32_t n_rec, int3
 // the outputs, after the caller has held the counts against its capacities
 void launch_bam_emit(hipStream_t s, const uint8_t *bytes, uint32_t first, uint32_t n_kept, uint32_t n_cigar, uint32_t n_seq, uint32_t n_name,
                      uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const BamUnpackWs &w, const BamUnpackOut &out);
+// vcfparse.hip — VCF text lines in HBM to the kept records and the deferred lines' offsets; csvgpu_vcf_snp_parse / _af_parse / _dev
+struct VcfHead {                             // one slice, preset by launch_vcf_count, copied back whole
+    uint32_t n_lines;                        // non-empty lines in front of stop_off
+    uint32_t stop_off;                       // lowest offset of a STOP line (all-ones: none)
+    unsigned long long hash_off;             // lowest offset of a line that begins with '#' (all-ones: none)
+    uint32_t n_kept, n_defer;                // the two sums' totals (launch_vcf_flags)
+};
+struct VcfOut { uint32_t *line_off, *chrom_len, *pos; double *value; uint32_t *defer_off; };
+struct VcfParseArgs {                        // what the per-line kernel is told; contig / needle / sorted_pos on the device (AF form)
+    bool af, dp_int, ad_int;
+    const uint8_t *contig, *needle; uint32_t contig_len, needle_len;
+    const uint32_t *sorted_pos; uint64_t n_sorted;
+};
+struct VcfWs {
+    VcfHead *head = nullptr;
+    uint32_t *tile_cnt = nullptr; void *es_tmp = nullptr;          // [n_tiles + 1] line ends per tile, then their exclusive sum
+    uint8_t *strings = nullptr;                                    // contig | needle (AF form)
+    // per line slot (n_slots = line ends + 1), carved once the line ends are counted
+    uint32_t *line_start = nullptr, *kept = nullptr, *defer = nullptr, *pos = nullptr, *chrom_len = nullptr; double *value = nullptr; uint8_t *code = nullptr;
+    void *es_tmp2 = nullptr;
+    VcfOut out{};                                                  // the host-pointer form alone: the outputs staged on the device
+};
+struct VcfTextWs { uint8_t *text = nullptr; uint32_t *sorted_pos = nullptr; };       // the host-pointer form's inputs, staged
+static inline uint32_t vcf_tiles(const uint8_t *text, uint64_t len) { return (uint32_t)((((uintptr_t)text & 15) + len + CSV_VCF_TILE_BYTES - 1) / CSV_VCF_TILE_BYTES); }
+// line ends per tile and their exclusive sum: tile_cnt[n_tiles] = the text's line ends; presets the head
+void launch_vcf_count(hipStream_t s, const uint8_t *text, uint32_t len, const VcfWs &w);
+// line_start[0 .. n_slots); n_slots = tile_cnt[n_tiles] + 1
+void launch_vcf_starts(hipStream_t s, const uint8_t *text, uint32_t len, const VcfWs &w);
+// every line decided by a group of `width` lanes (8, 16 or 64; 0: chosen from the mean line length), flags, sums, the head's counts
+void launch_vcf_parse(hipStream_t s, const uint8_t *text, uint32_t len, uint32_t n_slots, const VcfParseArgs &a, int width, const VcfWs &w);
+// the outputs, after the caller has held the counts against its capacities
+void launch_vcf_emit(hipStream_t s, uint32_t n_slots, bool af, const VcfWs &w, const VcfOut &out);
 // shardbuild.hip — a resident shard built on the device (csvgpu_shard_builder_*), and the ALT strings cut from its sequences
 // *unsorted |= pos[i] < pos[i - 1] for the records [first, first + n) (the first one against its predecessor, if there is one)
 void launch_sb_unsorted(hipStream_t s, const int32_t *pos, uint64_t first, uint64_t n, uint32_t *unsorted);

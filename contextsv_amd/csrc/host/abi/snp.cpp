@@ -4,7 +4,11 @@
 
 extern "C" {
 
-struct csvhost_snp { SNPFile f; };
+struct csvhost_snp {
+    SNPFile f;
+    SNPDeviceOptions dev;                                // ctx null: the host parser
+    const SNPDeviceOptions *device() const { return dev.ctx ? &dev : nullptr; }
+};
 
 csvhost_snp *csvhost_snp_open(const char *snp_vcf, int threads)
 {
@@ -13,7 +17,37 @@ csvhost_snp *csvhost_snp_open(const char *snp_vcf, int threads)
     if (!h->f.load(snp_vcf ? snp_vcf : "", threads, &e)) { set_error(e); delete h; return nullptr; }
     return h;
 }
+// The same with every chunk's data lines decided on the device (csvgpu_vcf_snp_parse on ctx; the population files of later queries through
+// csvgpu_vcf_af_parse); window_blocks: BGZF members per batch, 0 = the default. The tables are those of csvhost_snp_open.
+csvhost_snp *csvhost_snp_open_device(const char *snp_vcf, int threads, csv_ctx *ctx, uint32_t window_blocks)
+{
+    if (!ctx) { set_error("csvhost_snp_open_device: no context"); return nullptr; }
+    csvhost_snp *h = new csvhost_snp();
+    h->dev.ctx = ctx; h->dev.window_blocks = window_blocks;
+    std::string e;
+    if (!h->f.load(snp_vcf ? snp_vcf : "", threads, &e, h->device())) { set_error(e); delete h; return nullptr; }
+    return h;
+}
 void csvhost_snp_free(csvhost_snp *h) { delete h; }
+// out[4]: lines the device examined, records it kept, lines it deferred to the host parser, batches it declined
+void csvhost_snp_device_stats(const csvhost_snp *h, uint64_t *out)
+{
+    const SNPDeviceStats &s = h->f.device_stats();
+    out[0] = s.lines; out[1] = s.kept; out[2] = s.deferred; out[3] = s.declined_batches;
+}
+// A contig's whole table (population hits attached as by csvhost_snp_query): n[0] positions / BAFs, n[1] population records, all in file
+// order. Arrays may be null or short: the counts are always filled in, the arrays only when both capacities suffice. Returns 0, or 1 when
+// nothing was copied.
+int csvhost_snp_table(csvhost_snp *h, const char *chr, const char *pfb_vcf, const char *ethnicity, int threads, uint32_t *pos, double *baf, uint64_t cap,
+                      uint32_t *af_pos, double *af, uint64_t af_cap, uint64_t *n)
+{
+    const SNPFileTable &t = h->f.table(chr, pfb_vcf ? pfb_vcf : "", ethnicity ? ethnicity : "", threads, h->device());
+    n[0] = t.pos.size(); n[1] = t.af_pos.size();
+    if (n[0] > cap || n[1] > af_cap) return 1;
+    for (size_t i = 0; i < t.pos.size(); i++) { pos[i] = t.pos[i]; baf[i] = t.baf[i]; }
+    for (size_t i = 0; i < t.af_pos.size(); i++) { af_pos[i] = t.af_pos[i]; af[i] = t.af[i]; }
+    return 0;
+}
 uint64_t csvhost_snp_kept(const csvhost_snp *h) { return h->f.records_kept(); }
 
 // readSNPAlleleFrequencies for one region from the loaded tables. Returns the number of positions (file order), -1 when cap is too
@@ -21,7 +55,7 @@ uint64_t csvhost_snp_kept(const csvhost_snp *h) { return h->f.records_kept(); }
 int64_t csvhost_snp_query(csvhost_snp *h, const char *chr, const char *pfb_vcf, const char *ethnicity, uint32_t start_pos, uint32_t end_pos,
                           uint32_t *pos_out, double *baf_out, uint64_t cap, int *has_pfb, uint32_t *pfb_pos, double *pfb_val, int threads)
 {
-    const SNPFileTable &t = h->f.table(chr, pfb_vcf ? pfb_vcf : "", ethnicity ? ethnicity : "", threads);
+    const SNPFileTable &t = h->f.table(chr, pfb_vcf ? pfb_vcf : "", ethnicity ? ethnicity : "", threads, h->device());
     std::vector<uint32_t> pos;
     std::unordered_map<uint32_t, double> baf, pfb;
     t.query(start_pos, end_pos, pos, baf, pfb);

@@ -9,6 +9,7 @@
 #include <limits>
 #include <sstream>
 
+#include "../../../include/csvgpu.h"
 #include "log.h"
 
 namespace {
@@ -171,14 +172,14 @@ bool TextFile::open(const std::string &path, std::string *err)
     return true;
 }
 
-bool TextFile::forEachChunk(int threads, const std::function<bool(std::string_view)> &on_lines, std::string *err)
+bool TextFile::forEachChunk(int threads, const std::function<bool(std::string_view)> &on_lines, std::string *err, size_t window_blocks)
 {
     if (!is_bgzf) {                                       // plain text: one chunk
         if (file.size()) on_lines(sv((const char *)file.data(), file.size()));
         return true;
     }
     struct Batch { std::vector<bgzf::Block> blocks; HugeVec<uint8_t> data; bool ok = true; std::string err; uint64_t next = 0; };
-    const size_t kHead = 1 << 20, W = 1024;
+    const size_t kHead = 1 << 20, W = window_blocks ? window_blocks : 1024;
     auto load = [&](uint64_t coff, Batch &b) {
         b.blocks.clear(); b.ok = true;
         uint64_t total = 0;
@@ -265,6 +266,73 @@ std::string gnomadContigName(const std::string &chr, const std::string &pfb_file
     return g;
 }
 
+// ---- one data line ----------------------------------------------------------------------------------------------
+namespace {
+// (dp, ad: the caller's scratch, so that a file's lines share two allocations)
+inline bool snp_record_impl(sv line, bool dp_int, bool ad_int, std::vector<int32_t> &dp, std::vector<int32_t> &ad, SnpLineRecord &rec)
+{
+    Fields f;
+    if (!split_fields(line, f) || f.n < 9) return false;                     // no FORMAT / sample columns: DP lookup fails (:696-701)
+    if (!is_snp(f.f[3], f.f[4])) return false;                                // :679-683
+    if (f.f[5] == ".") return false;                                          // QUAL missing (:686)
+    const float qual = (float)strtod(std::string(f.f[5]).c_str(), nullptr);
+    if (qual <= 30) return false;
+    if (!dp_int || !format_ints(f.f[8], f.samples, "DP", dp) || dp[0] <= 10) return false;    // :693-701 (missing = INT32_MIN)
+    if (f.f[6] != "." && f.f[6] != "PASS") {                                 // bcf_has_filter(.., "PASS") (:704-707)
+        bool pass = false;
+        size_t a = 0;
+        for (;;) {
+            const size_t c = f.f[6].find(';', a);
+            if (f.f[6].substr(a, c == sv::npos ? sv::npos : c - a) == "PASS") pass = true;
+            if (c == sv::npos) break;
+            a = c + 1;
+        }
+        if (!pass) return false;
+    }
+    if (!ad_int || !format_ints(f.f[8], f.samples, "AD", ad) || ad.size() < 2) return false;  // :710-717
+    rec.baf = (double)ad[1] / (double)(int32_t)((uint32_t)ad[0] + (uint32_t)ad[1]);           // :720
+    rec.chrom = f.f[0];
+    rec.pos = (uint32_t)strtol(std::string(f.f[1]).c_str(), nullptr, 10);
+    return true;
+}
+
+inline AfLine af_record_impl(sv line, sv contig, sv needle, const std::vector<uint32_t> &sorted, uint32_t last_pos, uint32_t &pos, double &af)
+{
+    Fields f;
+    if (!split_fields(line, f)) return AfLine::Skip;
+    if (f.f[0] != contig) return AfLine::Skip;
+    const uint32_t p = (uint32_t)strtol(std::string(f.f[1]).c_str(), nullptr, 10);
+    if (p > last_pos) return AfLine::Stop;
+    if (!std::binary_search(sorted.begin(), sorted.end(), p)) return AfLine::Skip;   // :782-786
+    if (!is_snp(f.f[3], f.f[4])) return AfLine::Skip;                        // :775-779
+    // INFO key at the start of the field or behind ';'
+    sv info = f.f[7];
+    size_t k = info.find(needle);
+    while (k != sv::npos && k != 0 && info[k - 1] != ';') k = info.find(needle, k + 1);
+    if (k == sv::npos) return AfLine::Skip;                                  // status < 0
+    const size_t e = info.find_first_of(";,", k + needle.size());
+    const sv val = info.substr(k + needle.size(), e == sv::npos ? sv::npos : e - k - needle.size());
+    if (val.empty()) return AfLine::Skip;                                    // count == 0
+    const double v = val == "." ? std::nan("") : (double)(float)strtod(std::string(val).c_str(), nullptr);
+    if (v <= kMinPfb || v >= kMaxPfb) return AfLine::Skip;                   // :795-799 (NaN passes, as there)
+    pos = p;
+    af = v;
+    return AfLine::Keep;
+}
+}  // namespace
+
+bool snp_record_of_line(std::string_view line, bool dp_int, bool ad_int, SnpLineRecord &rec)
+{
+    static thread_local std::vector<int32_t> dp, ad;
+    return snp_record_impl(line, dp_int, ad_int, dp, ad, rec);
+}
+
+AfLine af_record_of_line(std::string_view line, std::string_view contig, std::string_view needle, const std::vector<uint32_t> &sorted, uint32_t last_pos,
+                         uint32_t &pos, double &af)
+{
+    return af_record_impl(line, contig, needle, sorted, last_pos, pos, af);
+}
+
 // ---- tables -----------------------------------------------------------------------------------------------------
 void SNPFileTable::query(uint32_t start_pos, uint32_t end_pos, std::vector<uint32_t> &snp_pos, std::unordered_map<uint32_t, double> &snp_baf,
                          std::unordered_map<uint32_t, double> &snp_pfb) const
@@ -284,7 +352,70 @@ void SNPFileTable::query(uint32_t start_pos, uint32_t end_pos, std::vector<uint3
     if (g < af_pos.size() && af_pos[g] <= hi) snp_pfb[af_pos[g]] = af[g];     // first acceptable record, then the reference breaks (:800-801)
 }
 
-bool SNPFile::load(const std::string &snp_vcf, int threads, std::string *err)
+// ---- a chunk's data lines on the device ---------------------------------------------------------------------------
+namespace {
+// the line that starts at chunk[off]
+sv line_at(sv chunk, size_t off)
+{
+    size_t e = chunk.find('\n', off);
+    if (e == sv::npos) e = chunk.size();
+    sv line = chunk.substr(off, e - off);
+    if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+    return line;
+}
+
+// The header lines in front of a chunk's first data line go to on_header; -> the first data line's offset (chunk.size() if there is none)
+template <class F>
+size_t leading_header(sv chunk, F on_header)
+{
+    size_t a = 0;
+    while (a < chunk.size()) {
+        size_t e = chunk.find('\n', a);
+        if (e == sv::npos) e = chunk.size();
+        sv line = chunk.substr(a, e - a);
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        if (!line.empty()) {
+            if (line[0] != '#') return a;
+            on_header(line);
+        }
+        a = e + 1;
+    }
+    return chunk.size();
+}
+
+// One chunk of data lines through csvgpu_vcf_*_parse: a sizing call where the arrays are too small, then the kept records and the
+// deferred lines' offsets in `o`. -> CSV_OK, 1 (declined: the caller parses the chunk), or a CSV_E* with *err set.
+struct DeviceLines {
+    std::vector<uint32_t> line_off, chrom_len, pos, defer_off;
+    std::vector<double> value;
+    csv_vcf_counts counts{};
+    // room for `n` kept records before the first call (a guess from the chunk's size spares most chunks the sizing call)
+    void expect(size_t n)
+    {
+        if (n > line_off.size()) { line_off.resize(n); chrom_len.resize(n); pos.resize(n); value.resize(n); }
+        if (defer_off.size() < 4096) defer_off.resize(4096);
+    }
+    template <class Call>
+    int run(csv_ctx *ctx, bool af, Call call, std::string *err)
+    {
+        for (int pass = 0; pass < 2; pass++) {
+            csv_vcf_out o{};
+            o.line_off = line_off.data(); o.chrom_len = af ? nullptr : chrom_len.data(); o.pos = pos.data(); o.value = value.data(); o.defer_off = defer_off.data();
+            o.cap = line_off.size(); o.cap_defer = defer_off.size();
+            const int rc = call(&o, &counts);
+            if (rc != CSV_ECAPACITY || pass) {
+                if (rc < 0 && err) *err = std::string("device VCF parser: ") + csvgpu_last_error(ctx);
+                return rc;
+            }
+            if (counts.n_kept > line_off.size()) { const size_t n = counts.n_kept + counts.n_kept / 4; line_off.resize(n); chrom_len.resize(n); pos.resize(n); value.resize(n); }
+            if (counts.n_deferred > defer_off.size()) defer_off.resize(counts.n_deferred + counts.n_deferred / 4);
+        }
+        return CSV_EHIP;
+    }
+};
+}  // namespace
+
+bool SNPFile::load(const std::string &snp_vcf, int threads, std::string *err, const SNPDeviceOptions *dev)
 {
     if (snp_vcf.empty()) { if (err) *err = "ERROR: SNP file path is empty."; return false; }
     TextFile tf;
@@ -297,50 +428,75 @@ bool SNPFile::load(const std::string &snp_vcf, int threads, std::string *err)
     std::vector<int32_t> dp, ad;
     std::string last_chr;
     SNPFileTable *cur = nullptr;
+    auto on_header = [&](sv line) {
+        std::string id, type;
+        if (header_decl(line, "FORMAT", id, type)) {
+            if (id == "DP") dp_int = type == "Integer";
+            if (id == "AD") ad_int = type == "Integer";
+        }
+    };
+    auto keep = [&](sv chrom, uint32_t pos, double baf) {
+        if (cur == nullptr || chrom != last_chr) {
+            last_chr.assign(chrom);
+            cur = &tables[last_chr];
+        }
+        cur->pos.push_back(pos);
+        cur->baf.push_back(baf);
+        n_kept++;
+    };
+    auto on_line = [&](sv line) {
+        if (line[0] == '#') { on_header(line); return true; }
+        SnpLineRecord rec;
+        if (snp_record_impl(line, dp_int, ad_int, dp, ad, rec)) keep(rec.chrom, rec.pos, rec.baf);
+        return true;
+    };
+    if (dev == nullptr || dev->ctx == nullptr) return tf.forEachChunk(threads, [&](sv chunk) { return for_lines(chunk, on_line); }, err);
+
+    DeviceLines d;
+    bool failed = false;
     const bool ok = tf.forEachChunk(threads, [&](sv chunk) {
-        return for_lines(chunk, [&](sv line) {
-            if (line[0] == '#') {
-                std::string id, type;
-                if (header_decl(line, "FORMAT", id, type)) {
-                    if (id == "DP") dp_int = type == "Integer";
-                    if (id == "AD") ad_int = type == "Integer";
+        const size_t a = leading_header(chunk, on_header);
+        const sv rest = chunk.substr(a);
+        if (rest.empty()) return true;
+        if (rest.size() >= (1ull << 32)) return for_lines(rest, on_line);
+        d.expect(rest.size() / 64 + 16);                  // (a sample's data line is rarely shorter)
+        const int rc = d.run(dev->ctx, false, [&](const csv_vcf_out *o, csv_vcf_counts *c) {
+            return csvgpu_vcf_snp_parse(dev->ctx, (const uint8_t *)rest.data(), rest.size(), dp_int, ad_int, o, c);
+        }, err);
+        if (rc < 0) { failed = true; return false; }
+        if (rc == 1) { dev_stats.declined_batches++; return for_lines(rest, on_line); }       // (a header line behind data may change dp_int / ad_int)
+        dev_stats.lines += d.counts.n_lines; dev_stats.kept += d.counts.n_kept; dev_stats.deferred += d.counts.n_deferred;
+        // Kept records and deferred lines in file order. A run of records with one CHROM (length and bytes equal to the run's first: one
+        // short memcmp per record) goes straight into the run's table; the name becomes a string, and the table is looked up, once per run.
+        uint64_t k = 0, q = 0;
+        uint32_t run_len = UINT32_MAX;
+        const char *run_name = nullptr;
+        SNPFileTable *run_table = nullptr;
+        while (k < d.counts.n_kept || q < d.counts.n_deferred) {
+            if (q >= d.counts.n_deferred || (k < d.counts.n_kept && d.line_off[k] < d.defer_off[q])) {
+                const char *name = rest.data() + d.line_off[k];
+                if (run_table == nullptr || d.chrom_len[k] != run_len || memcmp(name, run_name, run_len) != 0) {
+                    run_len = d.chrom_len[k]; run_name = name;
+                    keep(sv(run_name, run_len), d.pos[k], d.value[k]);
+                    run_table = cur;
+                } else {
+                    run_table->pos.push_back(d.pos[k]);
+                    run_table->baf.push_back(d.value[k]);
+                    n_kept++;
                 }
-                return true;
+                k++;
+            } else {
+                SnpLineRecord rec;
+                if (snp_record_of_line(line_at(rest, d.defer_off[q]), dp_int, ad_int, rec)) { keep(rec.chrom, rec.pos, rec.baf); run_table = nullptr; }   // (it may have changed the contig)
+                q++;
             }
-            Fields f;
-            if (!split_fields(line, f) || f.n < 9) return true;                 // no FORMAT / sample columns: DP lookup fails (:696-701)
-            if (!is_snp(f.f[3], f.f[4])) return true;                            // :679-683
-            if (f.f[5] == ".") return true;                                      // QUAL missing (:686)
-            const float qual = (float)strtod(std::string(f.f[5]).c_str(), nullptr);
-            if (qual <= 30) return true;
-            if (!dp_int || !format_ints(f.f[8], f.samples, "DP", dp) || dp[0] <= 10) return true;    // :693-701 (missing = INT32_MIN)
-            if (f.f[6] != "." && f.f[6] != "PASS") {                             // bcf_has_filter(.., "PASS") (:704-707)
-                bool pass = false;
-                size_t a = 0;
-                for (;;) {
-                    const size_t c = f.f[6].find(';', a);
-                    if (f.f[6].substr(a, c == sv::npos ? sv::npos : c - a) == "PASS") pass = true;
-                    if (c == sv::npos) break;
-                    a = c + 1;
-                }
-                if (!pass) return true;
-            }
-            if (!ad_int || !format_ints(f.f[8], f.samples, "AD", ad) || ad.size() < 2) return true;  // :710-717
-            const double b = (double)ad[1] / (double)(int32_t)((uint32_t)ad[0] + (uint32_t)ad[1]);   // :720
-            if (cur == nullptr || f.f[0] != last_chr) {
-                last_chr.assign(f.f[0]);
-                cur = &tables[last_chr];
-            }
-            cur->pos.push_back((uint32_t)strtol(std::string(f.f[1]).c_str(), nullptr, 10));
-            cur->baf.push_back(b);
-            n_kept++;
-            return true;
-        });
-    }, err);
-    return ok;
+        }
+        return true;
+    }, err, dev->window_blocks);
+    return ok && !failed;
 }
 
-const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads)
+const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev)
 {
     auto it = tables.find(chr);
     if (it == tables.end()) return none;
@@ -361,35 +517,58 @@ const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pf
     const uint32_t last_pos = sorted.back();
     bool key_is_float = false;
     const std::string needle = key + "=";
+    auto on_header = [&](sv line) {
+        std::string id, type;
+        if (header_decl(line, "INFO", id, type) && id == key) key_is_float = type == "Float";
+    };
+    auto on_line = [&](sv line) {
+        if (line[0] == '#') { on_header(line); return true; }
+        if (!key_is_float) return false;                                     // bcf_get_info_float fails on every record (:789-793)
+        uint32_t p = 0;
+        double v = 0;
+        const AfLine what = af_record_impl(line, contig, needle, sorted, last_pos, p, v);
+        if (what == AfLine::Stop) return false;                              // sorted file: nothing further can match
+        if (what == AfLine::Skip) return true;
+        t.af_pos.push_back(p);
+        t.af.push_back(v);
+        return true;
+    };
+    if (dev == nullptr || dev->ctx == nullptr) {
+        tf.forEachChunk(threads, [&](sv chunk) { return for_lines(chunk, on_line); }, &err);
+        return t;
+    }
+    // table() has no way to report a failure (an unreadable population file is logged and leaves the table without hits): a device call that
+    // fails (CSV_E*: out of memory, a HIP error) is logged ONCE and the host parser reads that chunk and the rest of the file — the table is
+    // complete either way. load() has the caller's `err` and fails instead.
+    DeviceLines d;
+    bool device_failed = false;
     tf.forEachChunk(threads, [&](sv chunk) {
-        return for_lines(chunk, [&](sv line) {
-            if (line[0] == '#') {
-                std::string id, type;
-                if (header_decl(line, "INFO", id, type) && id == key) key_is_float = type == "Float";
-                return true;
+        const size_t a = leading_header(chunk, on_header);
+        const sv rest = chunk.substr(a);
+        if (rest.empty()) return true;
+        if (!key_is_float) return false;
+        if (device_failed || rest.size() >= (1ull << 32)) return for_lines(rest, on_line);
+        d.expect(std::min(rest.size() / 64, 2 * sorted.size()) + 16);
+        const int rc = d.run(dev->ctx, true, [&](const csv_vcf_out *o, csv_vcf_counts *c) {
+            return csvgpu_vcf_af_parse(dev->ctx, (const uint8_t *)rest.data(), rest.size(), contig.data(), (uint32_t)contig.size(), needle.data(),
+                                       (uint32_t)needle.size(), sorted.data(), sorted.size(), o, c);
+        }, &err);
+        if (rc < 0) { printError("ERROR: " + err + " (the host parser reads the rest of " + pfb_vcf + ")"); device_failed = true; return for_lines(rest, on_line); }
+        if (rc == 1) { dev_stats.declined_batches++; return for_lines(rest, on_line); }
+        dev_stats.lines += d.counts.n_lines; dev_stats.kept += d.counts.n_kept; dev_stats.deferred += d.counts.n_deferred;
+        // file order; the first STOP ends the file, whether the device found it (behind everything it reported) or a deferred line is one
+        uint64_t k = 0, q = 0;
+        while (k < d.counts.n_kept || q < d.counts.n_deferred) {
+            if (q >= d.counts.n_deferred || (k < d.counts.n_kept && d.line_off[k] < d.defer_off[q])) {
+                t.af_pos.push_back(d.pos[k]);
+                t.af.push_back(d.value[k]);
+                k++;
+            } else {
+                if (!on_line(line_at(rest, d.defer_off[q]))) return false;
+                q++;
             }
-            if (!key_is_float) return false;                                     // bcf_get_info_float fails on every record (:789-793)
-            Fields f;
-            if (!split_fields(line, f)) return true;
-            if (f.f[0] != contig) return true;
-            const uint32_t p = (uint32_t)strtol(std::string(f.f[1]).c_str(), nullptr, 10);
-            if (p > last_pos) return false;                                      // sorted file: nothing further can match
-            if (!std::binary_search(sorted.begin(), sorted.end(), p)) return true;   // :782-786
-            if (!is_snp(f.f[3], f.f[4])) return true;                            // :775-779
-            // INFO key at the start of the field or behind ';'
-            sv info = f.f[7];
-            size_t k = info.find(needle);
-            while (k != sv::npos && k != 0 && info[k - 1] != ';') k = info.find(needle, k + 1);
-            if (k == sv::npos) return true;                                      // status < 0
-            const size_t e = info.find_first_of(";,", k + needle.size());
-            const sv val = info.substr(k + needle.size(), e == sv::npos ? sv::npos : e - k - needle.size());
-            if (val.empty()) return true;                                        // count == 0
-            const double v = val == "." ? std::nan("") : (double)(float)strtod(std::string(val).c_str(), nullptr);
-            if (v <= kMinPfb || v >= kMaxPfb) return true;                       // :795-799 (NaN passes, as there)
-            t.af_pos.push_back(p);
-            t.af.push_back(v);
-            return true;
-        });
-    }, &err);
+        }
+        return d.counts.stop_off == UINT64_MAX;
+    }, &err, dev->window_blocks);
     return t;
 }

@@ -23,7 +23,8 @@ class TextFile {
 public:
     bool open(const std::string &path, std::string *err);
     // on_lines(chunk): chunk holds whole lines ('\n'-terminated except possibly the last of the file); return false to stop early.
-    bool forEachChunk(int threads, const std::function<bool(std::string_view)> &on_lines, std::string *err);
+    // window_blocks: BGZF members inflated per batch (a test makes lines straddle batches with a small one)
+    bool forEachChunk(int threads, const std::function<bool(std::string_view)> &on_lines, std::string *err, size_t window_blocks = 1024);
     bool compressed() const { return is_bgzf; }
 private:
     bgzf::MappedFile file;
@@ -41,6 +42,24 @@ private:
     std::unordered_map<std::string, std::string> paths;
 };
 
+// Opt-in: the data lines of every chunk decided on the device (csvgpu_vcf_snp_parse / csvgpu_vcf_af_parse on `ctx`); the lines it defers and
+// the batches it declines run through the two functions below, so the tables are the same byte for byte.
+struct csv_ctx;
+// A device call that fails outright (CSV_E*): load() fails with the message in `err`; table(), which has no error channel, logs it once and
+// lets the host parser read the rest of that population file.
+struct SNPDeviceOptions { csv_ctx *ctx = nullptr; size_t window_blocks = 0; };          // window_blocks 0: forEachChunk's default
+struct SNPDeviceStats { uint64_t lines = 0, kept = 0, deferred = 0, declined_batches = 0; };
+
+// One data line's decision, as SNPFile::load and SNPFile::table take it (the device parser's deferred lines and the stand-alone check of
+// vcf_record_core.hpp call the same two functions).
+struct SnpLineRecord { std::string_view chrom; uint32_t pos = 0; double baf = 0; };
+// false: the line is not kept. dp_int / ad_int: the header declared FORMAT/DP, FORMAT/AD as Integer.
+bool snp_record_of_line(std::string_view line, bool dp_int, bool ad_int, SnpLineRecord &rec);
+enum class AfLine { Skip, Keep, Stop };
+// `sorted`: the contig's kept SNP positions, ascending, not empty; last_pos = sorted.back(); needle = "<key>="
+AfLine af_record_of_line(std::string_view line, std::string_view contig, std::string_view needle, const std::vector<uint32_t> &sorted, uint32_t last_pos,
+                         uint32_t &pos, double &af);
+
 // One contig's SNPs and population-frequency hits.
 struct SNPFileTable : SNPSource {
     std::vector<uint32_t> pos;            // file order (coordinate-sorted files: ascending; duplicates kept)
@@ -57,16 +76,18 @@ public:
     // Streams the file once and keeps, per contig, the records that pass the reference's filters (SNP alleles only, QUAL > 30,
     // FORMAT/DP > 10, FILTER PASS or ".", FORMAT/AD with two values; cnv_caller.cpp:679-727). Like the reference's synced reader
     // it wants an index next to a compressed file (.tbi or .csi): without one, false.
-    bool load(const std::string &snp_vcf, int threads, std::string *err);
+    bool load(const std::string &snp_vcf, int threads, std::string *err, const SNPDeviceOptions *dev = nullptr);
     // The contig's table with gnomAD hits from `pfb_vcf` ("" = none) under INFO key AF[_<ethnicity>]; built on first use.
     // chr naming against the gnomAD file follows the reference's path heuristic (cnv_caller.cpp:624-640).
-    const SNPFileTable &table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads);
+    const SNPFileTable &table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev = nullptr);
     uint64_t records_kept() const { return n_kept; }
+    const SNPDeviceStats &device_stats() const { return dev_stats; }       // summed over load() and every table() that parsed on the device
 private:
     std::unordered_map<std::string, SNPFileTable> tables;
     std::unordered_map<std::string, bool> af_done;
     SNPFileTable none;
     uint64_t n_kept = 0;
+    SNPDeviceStats dev_stats;
 };
 
 // the gnomAD contig name for `chr` given the file path (cnv_caller.cpp:624-640)

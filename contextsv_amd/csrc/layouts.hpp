@@ -12,7 +12,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "bgzf", "bam_unpack", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "bgzf", "bam_unpack", "vcf", "vcf_text", "dbscan_tmp", "viterbi_tmp"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -269,7 +269,33 @@ static inline bool carve_bam_unpack(Arena &a, uint64_t len, uint64_t n_anchors, 
     return k;
 }
 
-// ---- the kernels' own temporaries (one opaque `tmp` to their callers) ----------------------------------------------------------------
+// VCF lines parsed on the device (csvgpu_vcf_*_parse / _dev). The workspace is carved twice over the same arena: first with n_slots = 0
+// (the head, the tiles' line-end counts, the AF form's strings: none of these moves when n_slots changes), then, once the line ends are
+// counted, with n_slots = line ends + 1 for the per-line arrays and (io: the host-pointer form) the staged outputs, which hold at most one
+// record per line and no more than the caller's capacities.
+static inline bool carve_vcf(Arena &a, uint64_t n_tiles, uint64_t n_strings, uint64_t n_slots, bool io, bool af, uint64_t cap, uint64_t cap_defer, VcfWs &w)
+{
+    char *head = nullptr;
+    const bool ok = take(a, head, 256) && take(a, w.tile_cnt, (n_tiles + 1) * 4) && take(a, w.es_tmp, exclusive_sum_tmp_bytes(n_tiles + 1)) && take(a, w.strings, n_strings);
+    if (!ok) return false;
+    w.head = (VcfHead *)head;
+    w.out = VcfOut{};
+    if (!n_slots) return true;
+    bool k = take(a, w.line_start, n_slots * 4) && take(a, w.kept, (n_slots + 1) * 4) && take(a, w.defer, (n_slots + 1) * 4) && take(a, w.pos, n_slots * 4) &&
+             take(a, w.chrom_len, n_slots * 4) && take(a, w.value, n_slots * 8) && take(a, w.code, n_slots) && take(a, w.es_tmp2, exclusive_sum_tmp_bytes(n_slots + 1));
+    if (!io) return k;
+    cap = std::min(cap, n_slots); cap_defer = std::min(cap_defer, n_slots);
+    k = k && take(a, w.out.line_off, cap * 4) && take(a, w.out.pos, cap * 4) && take(a, w.out.value, cap * 8) && take(a, w.out.defer_off, cap_defer * 4);
+    if (!af) k = k && take(a, w.out.chrom_len, cap * 4);
+    return k;
+}
+// the host-pointer form's inputs: the text (+ 16: the last aligned 16-byte piece) and the AF form's positions
+static inline bool carve_vcf_text(Arena &a, uint64_t len, uint64_t n_sorted, VcfTextWs &w)
+{
+    return take(a, w.text, len + 16) && take(a, w.sorted_pos, n_sorted * 4);
+}
+
+// ---- the kernels' own temporaries (one opaque `tmp` to their callers)----------------------------------------------------------------
 // dbscan.hip: core u8[n] | parent u32[n] | root_of u32[n] | is_root/cid u32[n+1] | scan tmp | tile counts, prefixes | ticket
 struct DbscanTmp {
     uint8_t *core; uint32_t *parent, *root_of, *cid; void *es_tmp;

@@ -138,6 +138,12 @@ def load() -> C.CDLL:
     lib.csvhost_snp_open.restype = _P
     lib.csvhost_snp_open.argtypes = [C.c_char_p, C.c_int]
     lib.csvhost_snp_free.argtypes = [_P]
+    lib.csvhost_snp_open_device.restype = _P
+    lib.csvhost_snp_open_device.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32]
+    lib.csvhost_snp_device_stats.restype = None
+    lib.csvhost_snp_device_stats.argtypes = [_P, _P]
+    lib.csvhost_snp_table.restype = C.c_int
+    lib.csvhost_snp_table.argtypes = [_P, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P]
     lib.csvhost_snp_kept.restype = C.c_uint64
     lib.csvhost_snp_kept.argtypes = [_P]
     lib.csvhost_snp_query.restype = C.c_int64
@@ -959,8 +965,17 @@ class SNPFile:
     """The sample's SNP VCF (.vcf or bgzipped + indexed .vcf.gz) parsed once with the reference's filters; query() gives what
     readSNPAlleleFrequencies returns for a region: (positions in file order, BAF at those positions, (pfb_pos, pfb) or None)."""
 
-    def __init__(self, snp_vcf: str, threads: int = 4):
-        self.h = load().csvhost_snp_open(os.fsencode(snp_vcf), threads)
+    def __init__(self, snp_vcf: str, threads: int = 4, parse_on_device: bool = False, ctx: Context | None = None, window_blocks: int = 0):
+        """parse_on_device (opt-in): the data lines of the file, and of the population files of later queries, are decided on `ctx`'s device
+        (Context.vcf_snp_parse / vcf_af_parse); the tables are the same. window_blocks: BGZF members per batch (0: the default)."""
+        self.h, self.ctx = None, None
+        if parse_on_device:
+            if ctx is None:
+                raise ValueError("SNPFile: parse_on_device needs a context")
+            self.ctx = ctx                               # kept alive as long as the file may parse on it
+            self.h = load().csvhost_snp_open_device(os.fsencode(snp_vcf), threads, ctx.h, window_blocks)
+        else:
+            self.h = load().csvhost_snp_open(os.fsencode(snp_vcf), threads)
         if not self.h:
             raise RuntimeError((load().csvhost_last_error() or b"cannot load SNP VCF").decode())
 
@@ -975,6 +990,25 @@ class SNPFile:
     @property
     def records_kept(self) -> int:
         return int(load().csvhost_snp_kept(self.h))
+
+    @property
+    def device_stats(self) -> dict:
+        """What the device parser did so far: lines it examined, records it kept, lines it deferred to the host parser, batches it declined."""
+        out = np.zeros(4, np.uint64)
+        load().csvhost_snp_device_stats(self.h, out.ctypes.data)
+        return dict(zip(("lines", "kept", "deferred", "declined_batches"), (int(x) for x in out)))
+
+    def table(self, chr: str, pfb_vcf: str | None = None, ethnicity: str = "", threads: int = 4):
+        """The contig's whole tables, file order: (pos, baf, af_pos, af) — the kept SNP records and the population records that can become
+        a region's hit (built from pfb_vcf on the contig's first use, as in query())."""
+        n = np.zeros(2, np.uint64)
+        args = (self.h, chr.encode(), os.fsencode(pfb_vcf) if pfb_vcf else None, ethnicity.encode(), threads)
+        load().csvhost_snp_table(*args, None, None, 0, None, None, 0, n.ctypes.data)
+        pos, baf = np.zeros(int(n[0]), np.uint32), np.zeros(int(n[0]), np.float64)
+        af_pos, af = np.zeros(int(n[1]), np.uint32), np.zeros(int(n[1]), np.float64)
+        if load().csvhost_snp_table(*args, pos.ctypes.data, baf.ctypes.data, len(pos), af_pos.ctypes.data, af.ctypes.data, len(af), n.ctypes.data) != 0:
+            raise RuntimeError("SNP table: the counts changed between two calls")
+        return pos, baf, af_pos, af
 
     def query(self, chr: str, start: int, end: int, pfb_vcf: str | None = None, ethnicity: str = "", threads: int = 4, cap: int = 1 << 20):
         pos, baf = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)

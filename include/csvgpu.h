@@ -621,6 +621,50 @@ int csvgpu_bam_unpack(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const ui
                       uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const csv_bam_out *out, csv_bam_counts *counts);
 
 /* ------------------------------------------------------------------------------------------ */
+/* SNP and population-frequency VCF records parsed on the device (opt-in: the host reader parses every line itself by default) */
+/* Replaces, with kernels/vcfparse.hip, the per-line work of SNPFile::load and SNPFile::table (host/snp_io.cpp: snp_record_of_line,
+ * af_record_of_line) on one batch of whole text lines. The rules of one line are csrc/vcf_record_core.hpp; a line whose decision hangs on
+ * a number that the device cannot convert with libc's exact result, or that has more than one sample column, is not decided here but
+ * DEFERRED: its offset comes back and the caller parses it with the host function. Kept records and deferred offsets are in file order,
+ * duplicates kept. */
+#define CSV_VCF_TILE_BYTES 4096u   /* the text is searched for line ends in 16-byte-aligned tiles of this many bytes */
+typedef struct csv_vcf_out {
+    uint32_t *line_off;      /* [cap] offset of the kept record's line (CHROM starts there) */
+    uint32_t *chrom_len;     /* [cap] SNP form only; NULL for the AF form */
+    uint32_t *pos;           /* [cap] */
+    double   *value;         /* [cap] baf (SNP form) or af (AF form) */
+    uint32_t *defer_off;     /* [cap_defer] offsets of the lines the caller parses itself, ascending */
+    uint64_t  cap, cap_defer;
+} csv_vcf_out;
+enum { CSV_VCF_HEADER_LINE = 1 };   /* reason in csv_vcf_counts::status (bits 0-7; bits 8-39: the line's offset): a '#' line */
+typedef struct csv_vcf_counts {
+    uint64_t n_lines;        /* non-empty lines in front of stop_off */
+    uint64_t n_kept, n_deferred;
+    uint64_t stop_off;       /* AF form: offset of the first line the device found to be behind the last position, UINT64_MAX if none */
+    uint64_t status;         /* 0, or (offset << 8) | reason when declined */
+} csv_vcf_counts;
+
+/* text[0 .. len): lines ended by '\n' (the last one may lack it); a '\r' in front of the '\n' is stripped, empty lines are skipped.
+ * snp: dp_int / ad_int say whether the header declared FORMAT/DP and FORMAT/AD as Integer. af: the records of `contig` whose POS is in
+ * sorted_pos[0 .. n) (ascending, duplicates allowed; n == 0 is taken as a last position of 0) and whose INFO holds needle (the key with its
+ * '=', at the field's start or behind ';'); the first line of the contig with POS beyond sorted_pos[n - 1] is the STOP line: its offset is
+ * counts->stop_off and nothing at or behind it is reported. A deferred line in front of it may be a STOP line too: the caller finds out.
+ * Header lines are the caller's to consume before the call: a line in front of stop_off that begins with '#' declines the batch.
+ * Returns CSV_OK; 1 = declined, outputs unspecified, counts->status says why and where; CSV_ECAPACITY = out->cap or out->cap_defer too
+ * small, the exact counts filled in, nothing written; CSV_EINVAL, nothing reaching the device: a null pointer, len >= 2^32, sorted_pos not
+ * ascending (host-pointer form; the _dev form trusts it), needle_len 0 or above 64, a needle with a tab or a line end in it. The AF form
+ * ignores out->chrom_len. len == 0: CSV_OK with zero counts. Whatever the bytes are, nothing outside [0, len) is read beyond the
+ * aligned 16-byte piece that holds a byte of it, and nothing is written outside the capacities. Timed under CSV_K_MISC.
+ * _dev: text, sorted_pos and the arrays of d_out are device pointers (text at any alignment: what csvgpu_bgzf_inflate_dev left); contig,
+ * needle and counts are the host's. Host pointers: the text goes up and the arrays come back through the page-locked block, in pieces. */
+int csvgpu_vcf_snp_parse(csv_ctx *ctx, const uint8_t *text, uint64_t len, int dp_int, int ad_int, const csv_vcf_out *out, csv_vcf_counts *counts);
+int csvgpu_vcf_snp_parse_dev(csv_ctx *ctx, const uint8_t *d_text, uint64_t len, int dp_int, int ad_int, const csv_vcf_out *d_out, csv_vcf_counts *counts);
+int csvgpu_vcf_af_parse(csv_ctx *ctx, const uint8_t *text, uint64_t len, const char *contig, uint32_t contig_len, const char *needle, uint32_t needle_len,
+                        const uint32_t *sorted_pos, uint64_t n, const csv_vcf_out *out, csv_vcf_counts *counts);
+int csvgpu_vcf_af_parse_dev(csv_ctx *ctx, const uint8_t *d_text, uint64_t len, const char *contig, uint32_t contig_len, const char *needle, uint32_t needle_len,
+                            const uint32_t *d_sorted_pos, uint64_t n, const csv_vcf_out *d_out, csv_vcf_counts *counts);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Resident shards built on the device from BAM batches (opt-in: the from-file path fills host arrays and uploads them by default) */
 /* A builder owns device arrays that grow: batches are appended behind its tail, and csvgpu_shard_builder_finish hands the arrays to a
  * csv_shard of the kind csvgpu_shard_upload makes (padded CIGAR array, sortedness known) — without the host arrays of the reader's BamShard

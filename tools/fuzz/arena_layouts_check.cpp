@@ -120,6 +120,18 @@ int main()
                                     (char *)w.status == (char *)w.res + 32 && ((uintptr_t)w.status & 7) == 0;
                          });
             }
+            for (int io : {0, 1}) {   // n tiles, m line slots (0: the first carve); strings, form and capacities run along. The second carve must leave the first one's slices where they were
+                VcfWs w, w0;
+                const bool af = (n + m) % 2 != 0;
+                Arena p0 = arena_plan();
+                (void)carve_vcf(p0, n, m % 90, 0, io != 0, af, n, m, w0);
+                run_case(tag("vcf", {n, m, (uint64_t)io}), [&](Arena &a) { return carve_vcf(a, n, m % 90, m, io != 0, af, (n + m) % 1009, n % 7, w); },
+                         [&](char *lo, char *) {
+                             return (char *)w.head == lo && (char *)w.tile_cnt - (char *)w.head == (char *)w0.tile_cnt - (char *)w0.head &&
+                                    (char *)w.strings - (char *)w.head == (char *)w0.strings - (char *)w0.head && sizeof(VcfHead) <= 256;
+                         });
+            }
+            { VcfTextWs w; run_case(tag("vcf_text", {n, m}), [&](Arena &a) { return carve_vcf_text(a, n, m, w); }); }
             { SplitTablesOut w; run_case(tag("sr_tables", {n, m}), [&](Arena &a) { return sr_carve(a, n, m, w); }); }
             for (int with : {0, 1}) { SplitFitsIn w; run_case(tag("sf_tables", {n, m, (uint64_t)with}), [&](Arena &a) { return carve_sf_tables(a, n, m, with != 0, w); }); }
             {   // n members in m segments; the block cleared by one memset holds six sub-slices
@@ -158,7 +170,7 @@ int main()
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
     const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
-                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"bgzf", 2}, {"bam_unpack", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
+                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
         const auto it = n_counts.find(kv.first);
