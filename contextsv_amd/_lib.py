@@ -105,6 +105,10 @@ class csv_shard_sizes(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq", C.c_uint64), ("n_name", C.c_uint64)]
 
 
+class csv_genome_counts(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_name_bytes", C.c_uint64), ("total_bases", C.c_uint64), ("n_text_bytes", C.c_uint64), ("n_lines", C.c_uint64)]
+
+
 # csv_shard_builder's `want` bits
 SB_SEQ, SB_NAMES, SB_NAME_HASH = 1, 2, 4
 
@@ -194,6 +198,14 @@ ABI = {
     "csvgpu_shard_fetch_names": (C.c_int, [_P, _P, _P, _P, _P]),
     "csvgpu_shard_drop_sequences": (C.c_int, [_P, _P]),
     "csvgpu_alt_bases_resident": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, _P]),
+    "csvgpu_genome_builder_create": (_P, [_P, C.c_uint64]),
+    "csvgpu_genome_builder_append": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "csvgpu_genome_builder_append_dev": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "csvgpu_genome_builder_finish": (_P, [_P, _P]),
+    "csvgpu_genome_builder_destroy": (None, [_P, _P]),
+    "csvgpu_genome_free": (None, [_P, _P]),
+    "csvgpu_genome_describe": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(csv_genome_counts)]),
+    "csvgpu_genome_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int, _P]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

@@ -718,6 +718,11 @@ class Context:
         SB_NAME_HASH; reserve: (n_reads, n_cigar, n_seq, n_name) allocated now, or None."""
         return ShardBuilder(self, want, reserve)
 
+    def genome_builder(self, reserve_bytes: int = 0) -> "GenomeBuilder":
+        """csvgpu_genome_builder_create: a reference genome that is built on the device from FASTA text. reserve_bytes: room allocated now
+        (the file's size: the array never grows then)."""
+        return GenomeBuilder(self, reserve_bytes)
+
     def alt_bases(self, shard: "Shard", read, qpos, lengths):
         """csvgpu_alt_bases_resident: for item i the `lengths[i]` bases from query offset qpos[i] of record read[i], cut from the packed
         sequences a built shard holds (ambiguity codes as N; all N where the bases leave the stored sequence) -> list of str."""
@@ -730,6 +735,123 @@ class Context:
         self._check(self.lib.csvgpu_alt_bases_resident(self.h, shard.h, ptr(read), ptr(qpos), ptr(off), len(read), ptr(out)))
         text = out.tobytes().decode("latin-1")
         return [text[int(off[i]): int(off[i + 1])] for i in range(len(read))]
+
+
+class GenomeBuilder:
+    """csv_genome_builder: FASTA text appended in pieces (cut anywhere) into one base array the library owns; finish() gives a Genome."""
+
+    def __init__(self, ctx: Context, reserve_bytes: int = 0):
+        self.ctx = ctx
+        self.h = ctx.lib.csvgpu_genome_builder_create(ctx.h, int(reserve_bytes))
+        if not self.h:
+            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+
+    def _live(self):
+        if not self.h:
+            raise ValueError("GenomeBuilder: already finished or destroyed")
+
+    def append(self, text):
+        """csvgpu_genome_builder_append: the next bytes of the text (bytes or a uint8 numpy array), through the page-locked block."""
+        self._live()
+        data = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        self.ctx._check(self.ctx.lib.csvgpu_genome_builder_append(self.ctx.h, self.h, ptr(data) if len(data) else None, len(data)))
+
+    def append_dev(self, d_text):
+        """csvgpu_genome_builder_append_dev: the same for a uint8 torch tensor on the context's device, at any alignment."""
+        self._live()
+        if not d_text.is_cuda or not d_text.is_contiguous() or d_text.element_size() != 1:
+            raise ValueError("append_dev: contiguous uint8 device tensor expected")
+        self.append_ptr(d_text.data_ptr(), int(d_text.numel()))
+
+    def append_ptr(self, dev_ptr: int, length: int):
+        """The same for `length` bytes at a device address."""
+        self._live()
+        self.ctx._check(self.ctx.lib.csvgpu_genome_builder_append_dev(self.ctx.h, self.h, dev_ptr if length else None, int(length)))
+
+    def finish(self) -> "Genome":
+        """csvgpu_genome_builder_finish: the builder's array becomes a Genome (the builder is consumed, also on failure)."""
+        self._live()
+        h, self.h = self.ctx.lib.csvgpu_genome_builder_finish(self.ctx.h, self.h), None
+        if not h:
+            raise CsvError(_lib.CSV_EINVAL, (self.ctx.lib.csvgpu_last_error(self.ctx.h) or b"").decode())
+        return Genome(self.ctx, h)
+
+    def destroy(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.csvgpu_genome_builder_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    __del__ = destroy
+
+
+class Genome:
+    """csv_genome: a reference genome resident on the device. Records are the FASTA's named headers in file order."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx, self.h = ctx, handle
+        self._desc = None
+
+    def free(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.csvgpu_genome_free(self.ctx.h, self.h)
+        self.h = None
+
+    __del__ = free
+
+    def describe_raw(self, cap_records: int, cap_name_bytes: int):
+        """One csvgpu_genome_describe call with the given capacities -> (rc, counts dict, name_off, names, lengths)."""
+        name_off, names, lengths = np.zeros(cap_records + 1, np.uint64), np.zeros(max(cap_name_bytes, 1), np.uint8), np.zeros(max(cap_records, 1), np.uint32)
+        c = _lib.csv_genome_counts()
+        rc = self.ctx.lib.csvgpu_genome_describe(self.ctx.h, self.h, cap_records, cap_name_bytes, ptr(name_off), ptr(names), ptr(lengths), C.byref(c))
+        counts = {k: int(getattr(c, k)) for k in ("n_records", "n_name_bytes", "total_bases", "n_text_bytes", "n_lines")}
+        return rc, counts, name_off, names, lengths
+
+    def describe(self) -> dict:
+        """The records: names (bytes, file order, duplicates kept), lengths, and the counts (two calls: the first sizes the second)."""
+        if self._desc is None:
+            rc, counts, *_ = self.describe_raw(0, 0)
+            if rc not in (_lib.CSV_OK, _lib.CSV_ECAPACITY):
+                self.ctx._check(rc)
+            rc, counts, name_off, names, lengths = self.describe_raw(counts["n_records"], counts["n_name_bytes"])
+            self.ctx._check(rc)
+            raw, n = names.tobytes(), counts["n_records"]
+            self._desc = dict(counts, names=[raw[int(name_off[i]): int(name_off[i + 1])] for i in range(n)], lengths=lengths[:n].copy())
+        return self._desc
+
+    def record_of(self, name) -> int:
+        """The LAST record of that name (the host loader's map keeps the last one stored). KeyError when there is none."""
+        name = name.encode("latin-1") if isinstance(name, str) else bytes(name)
+        names = self.describe()["names"]
+        for i in range(len(names) - 1, -1, -1):
+            if names[i] == name:
+                return i
+        raise KeyError(name)
+
+    @staticmethod
+    def cut_len(length: int, pos_start: int, pos_end: int) -> int:
+        ps, pe = (pos_start - 1) & 0xFFFFFFFF, (pos_end - 1) & 0xFFFFFFFF
+        return 0 if pe >= length or ps > pe else pe - ps + 1
+
+    def fetch_raw(self, record, pos_start, pos_end, out_off, mask: bool, out) -> int:
+        """One csvgpu_genome_fetch call on the caller's arrays; out: a writeable uint8 array. -> rc."""
+        record, pos_start, pos_end = (np.ascontiguousarray(a, np.uint32) for a in (record, pos_start, pos_end))
+        out_off = np.ascontiguousarray(out_off, np.uint64)
+        if not (len(pos_start) == len(record) == len(pos_end) and len(out_off) == len(record) + 1):
+            raise ValueError("fetch: array lengths disagree")
+        return self.ctx.lib.csvgpu_genome_fetch(self.ctx.h, self.h, ptr(record), ptr(pos_start), ptr(pos_end), ptr(out_off), len(record), int(bool(mask)), ptr(out))
+
+    def fetch(self, record, pos_start, pos_end, mask: bool = False):
+        """The cuts [pos_start[i], pos_end[i]] (1-based inclusive, ReferenceGenome::query's rule) of records record[i] -> list of bytes."""
+        lengths = self.describe()["lengths"]
+        record = np.ascontiguousarray(record, np.uint32)
+        if len(record) and int(record.max()) >= len(lengths):
+            raise CsvError(_lib.CSV_EINVAL, "genome_fetch: record index beyond the genome")
+        off = np.zeros(len(record) + 1, np.uint64)
+        off[1:] = np.cumsum([self.cut_len(int(lengths[r]), int(s), int(e)) for r, s, e in zip(record, pos_start, pos_end)], dtype=np.uint64)
+        out = np.zeros(max(int(off[-1]), 1), np.uint8)
+        self.ctx._check(self.fetch_raw(record, pos_start, pos_end, off, mask, out))
+        raw = out.tobytes()
+        return [raw[int(off[i]): int(off[i + 1])] for i in range(len(record))]
 
 
 class ShardBuilder:

@@ -449,6 +449,32 @@ void launch_vcf_starts(hipStream_t s, const uint8_t *text, uint32_t len, const V
 void launch_vcf_parse(hipStream_t s, const uint8_t *text, uint32_t len, uint32_t n_slots, const VcfParseArgs &a, int width, const VcfWs &w);
 // the outputs, after the caller has held the counts against its capacities
 void launch_vcf_emit(hipStream_t s, uint32_t n_slots, bool af, const VcfWs &w, const VcfOut &out);
+// fasta.hip — a FASTA's text in HBM to the genome's base array (csvgpu_genome_builder_*), and cuts of it (csvgpu_genome_fetch)
+struct FastaCarry { uint8_t mid_line, kind; };        // the line the previous call's text left open, and its kind (fastacore::LINE_*)
+struct FastaHead {                           // one slice, copied back whole
+    uint32_t n_kept, n_hdr, n_name;          // the three sums' totals: residue bytes, header lines, name bytes
+    uint32_t tail_len, tail_kind;            // the text's last line slot: its bytes and its kind
+};
+struct FastaEvents {                         // the text's header lines in file order, [n_hdr] each
+    uint32_t *kept = nullptr;                // residue bytes of this text in front of the line
+    uint32_t *name_off = nullptr, *name_len = nullptr;   // its name's piece in names[]: up to the first blank or the line's end
+    uint8_t *blank = nullptr;                // a blank ended the piece
+    uint8_t *names = nullptr;                // [n_name]
+};
+struct FastaWs {
+    VcfWs vcf;                               // head, tile_cnt, es_tmp, line_start: what launch_vcf_count / _starts use
+    FastaHead *head = nullptr;
+    uint32_t *kept = nullptr, *hdr = nullptr, *nlen = nullptr;    // [n_slots + 1] per line, then their exclusive sums
+    uint8_t *blank = nullptr;                // [n_slots]
+    void *es_tmp = nullptr;
+    FastaEvents ev;                          // sized for n_slots lines and the text's bytes
+};
+// per line: kind, kept bytes, name span; the sums; the header events. line_start[] must be in place (launch_vcf_starts).
+void launch_fasta_lines(hipStream_t s, const uint8_t *text, uint32_t len, uint32_t n_slots, const FastaCarry &carry, const FastaWs &w);
+// the residue lines' bytes to dst[0 .. n_kept), in file order
+void launch_fasta_compact(hipStream_t s, const uint8_t *text, uint32_t len, const FastaWs &w, uint8_t *dst);
+// item i: out[out_off[i] .. out_off[i + 1]) = seq[src[i] ..), ambiguity codes as N if mask; out_off[0] = 0, out_off[n] = total; out 16-byte aligned
+void launch_fasta_cut(hipStream_t s, const uint8_t *seq, const uint64_t *src, const uint64_t *out_off, uint64_t n, uint64_t total, bool mask, uint8_t *out);
 // shardbuild.hip — a resident shard built on the device (csvgpu_shard_builder_*), and the ALT strings cut from its sequences
 // *unsorted |= pos[i] < pos[i - 1] for the records [first, first + n) (the first one against its predecessor, if there is one)
 void launch_sb_unsorted(hipStream_t s, const int32_t *pos, uint64_t first, uint64_t n, uint32_t *unsorted);

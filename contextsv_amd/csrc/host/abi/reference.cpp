@@ -13,6 +13,26 @@ csvhost_fasta *csvhost_fasta_open(const char *path)
         return h;
     } catch (const std::exception &e) { set_error(e.what()); return nullptr; }
 }
+// The same with the sequences on ctx's device (ReferenceGenome::setFilepath with FastaDeviceOptions): the file goes up in windows of
+// window_bytes (0 = the default), queries are fetches on ctx. The handle is what csvhost_fasta_open returns, for every function that takes one.
+csvhost_fasta *csvhost_fasta_open_device(const char *path, csv_ctx *ctx, uint64_t window_bytes)
+{
+    if (!ctx) { set_error("csvhost_fasta_open_device: no context"); return nullptr; }
+    try {
+        csvhost_fasta *h = new csvhost_fasta();
+        FastaDeviceOptions opt;
+        opt.ctx = ctx; opt.window_bytes = window_bytes;
+        if (h->g.setFilepath(path ? path : "", opt) != 0) { delete h; set_error("No FASTA filepath provided"); return nullptr; }
+        return h;
+    } catch (const std::exception &e) { set_error(e.what()); return nullptr; }
+}
+// out[8]: on the device (0 / 1), bytes uploaded, lines, records, bases, fetch calls, items fetched, fallback to the host loader (0 / 1)
+void csvhost_fasta_device_stats(const csvhost_fasta *h, uint64_t *out)
+{
+    const FastaDeviceStats s = h->g.deviceStats();
+    out[0] = h->g.onDevice() ? 1 : 0; out[1] = s.bytes_uploaded; out[2] = s.lines; out[3] = s.records; out[4] = s.bases;
+    out[5] = s.fetch_calls; out[6] = s.items_fetched; out[7] = s.fallback;
+}
 void csvhost_fasta_free(csvhost_fasta *h) { delete h; }
 
 // length of the view, -1 on error (unknown contig); at most cap bytes are copied to buf

@@ -123,12 +123,24 @@ VCFCounts writeVCF(std::ostream &out, const std::vector<std::pair<std::string, c
     std::vector<Record> recs;
     std::vector<uint32_t> positions;
     std::vector<int32_t> depths;
+    std::vector<ReferenceGenome::Cut> cuts;
+    std::vector<std::string> refs;
     for (const auto &entry : contigs) {
         const std::string &chr = entry.first;
         printMessage("Saving SV calls for " + chr + "...");
         recs.clear();
         positions.clear();
         const auto gap_it = gaps.find(chr);
+        // The contig's REF lookups in one call (one fetch where the genome lives on the device): the cuts of the calls that will ask for one,
+        // by the gating of the loop below, in its order. Unmasked: ALT takes its first base from REF before REF is masked.
+        cuts.clear();
+        for (const SVCall &sv : *entry.second) {
+            if (sv.sv_type == SVType::UNKNOWN || sv.sv_type == SVType::NEUTRAL) continue;
+            if (sv.sv_type == SVType::DEL) cuts.push_back({(uint32_t)std::max(1, (int)sv.start - 1), sv.end});
+            else if (sv.sv_type == SVType::INS && (int)sv.start > 1) cuts.push_back({sv.start - 1, sv.start - 1});
+        }
+        ref_genome.queryMany(chr, cuts, false, refs);
+        size_t next_ref = 0;
         for (const SVCall &sv : *entry.second) {
             uint32_t start = sv.start, end = sv.end;
             int sv_length = (int)(end - start + 1);
@@ -156,7 +168,7 @@ VCFCounts writeVCF(std::ostream &out, const std::vector<std::pair<std::string, c
             if (sv.sv_type == SVType::DEL) {
                 // REF = preceding base + deleted bases, ALT = preceding base, POS on the preceding base (:1242-1260)
                 const uint32_t preceding = (uint32_t)std::max(1, (int)start - 1);
-                ref_allele = ref_genome.query(chr, preceding, end);
+                ref_allele = refs[next_ref++];
                 if (ref_allele != "") {
                     alt_allele = ref_allele.substr(0, 1);
                 } else {
@@ -170,7 +182,7 @@ VCFCounts writeVCF(std::ostream &out, const std::vector<std::pair<std::string, c
                 // POS and END on the preceding base, its letter in front of a sequence ALT (:1265-1287)
                 if ((int)start > 1) {
                     start -= 1;
-                    ref_allele = ref_genome.query(chr, start, start);
+                    ref_allele = refs[next_ref++];
                     if (ref_allele != "") {
                         if (alt_allele != "<INS>") alt_allele.insert(0, ref_allele);
                     } else {

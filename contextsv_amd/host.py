@@ -95,6 +95,10 @@ def load() -> C.CDLL:
     lib.csvhost_partition_check.argtypes = [_P, C.c_uint64, C.POINTER(C.c_int)]
     lib.csvhost_fasta_open.restype = _P
     lib.csvhost_fasta_open.argtypes = [C.c_char_p]
+    lib.csvhost_fasta_open_device.restype = _P
+    lib.csvhost_fasta_open_device.argtypes = [C.c_char_p, _P, C.c_uint64]
+    lib.csvhost_fasta_device_stats.restype = None
+    lib.csvhost_fasta_device_stats.argtypes = [_P, _P]
     lib.csvhost_fasta_free.argtypes = [_P]
     lib.csvhost_fasta_query.restype = C.c_int64
     lib.csvhost_fasta_query.argtypes = [_P, C.c_char_p, C.c_uint32, C.c_uint32, _P, C.c_uint64]
@@ -709,11 +713,28 @@ def read_chmm(path: str):
 class ReferenceGenome:
     """ReferenceGenome of the host mirror (src/fasta_query.cpp): whole FASTA in memory, 1-based inclusive queries."""
 
-    def __init__(self, path: str):
-        self.path = path
-        self.h = load().csvhost_fasta_open(os.fsencode(path))
+    def __init__(self, path: str, load_on_device: bool = False, ctx: Context | None = None, window_bytes: int = 0):
+        """load_on_device (opt-in): the sequences are built and kept on `ctx`'s device (Context.genome_builder's entry points; the file goes
+        up in windows of window_bytes, 0: 256 MiB), no host copy exists, and query / compare / save_vcf fetch what they need. Every result is
+        the host backing's. A file the device builder refuses is loaded on the host, whole: device_stats['fallback']."""
+        self.path, self.ctx, self.h = path, None, None
+        if load_on_device:
+            if ctx is None:
+                raise ValueError("ReferenceGenome: load_on_device needs a context")
+            self.ctx = ctx                               # kept alive as long as the genome may fetch through it
+            self.h = load().csvhost_fasta_open_device(os.fsencode(path), ctx.h, int(window_bytes))
+        else:
+            self.h = load().csvhost_fasta_open(os.fsencode(path))
         if not self.h:
             raise RuntimeError((load().csvhost_last_error() or b"cannot open FASTA").decode())
+
+    @property
+    def device_stats(self) -> dict:
+        """Whether the sequences live on the device, what the builder took (bytes uploaded, line ends, records, bases), the fetches so far
+        (calls, items), and whether the host loader had to read the file instead (fallback)."""
+        out = np.zeros(8, np.uint64)
+        load().csvhost_fasta_device_stats(self.h, out.ctypes.data)
+        return dict(zip(("on_device", "bytes_uploaded", "lines", "records", "bases", "fetch_calls", "items_fetched", "fallback"), (int(x) for x in out)))
 
     def close(self):
         if self.h:

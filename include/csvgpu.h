@@ -720,6 +720,56 @@ int  csvgpu_shard_drop_sequences(csv_ctx *ctx, csv_shard *shard);
  * one launch, one wait. Timed under CSV_K_MISC. */
 int  csvgpu_alt_bases_resident(csv_ctx *ctx, csv_shard *shard, const uint32_t *read, const uint32_t *qpos, const uint64_t *out_off, uint64_t n, char *out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The reference genome loaded and queried on the device (opt-in: the host loader keeps every contig as a string by default) */
+/* Replaces, with kernels/fasta.hip, the line loop of ReferenceGenome::setFilepath and the cut of ::query (host/fasta_query.cpp). The rules
+ * are csrc/fasta_core.hpp: lines end at '\n' only (a '\r' stays), a non-empty line that begins with '>' is a header whose name runs to the
+ * first blank, every other line's bytes are kept in file order in ONE device array, and a record per named header owns the run of kept
+ * bytes that the host loader would store under it (residues in front of the first header or under an empty-named header fall to the next
+ * named one; kept bytes that no named header follows are dropped). Records are in file order, duplicates of a name kept: a lookup by name
+ * takes the LAST record of that name, as the loader's map does. One builder or genome is used from one host thread at a time, on
+ * contexts of one device. */
+typedef struct csv_genome_builder csv_genome_builder;
+typedef struct csv_genome csv_genome;
+typedef struct csv_genome_counts {
+    uint64_t n_records;      /* named headers */
+    uint64_t n_name_bytes;   /* their names, back to back */
+    uint64_t total_bases;    /* bytes that belong to a record */
+    uint64_t n_text_bytes;   /* what was appended */
+    uint64_t n_lines;        /* ... and its line ends */
+} csv_genome_counts;
+
+/* reserve_bytes: room for that many bases allocated now (the file's size: the array never grows then). NULL on failure. */
+csv_genome_builder *csvgpu_genome_builder_create(csv_ctx *ctx, uint64_t reserve_bytes);
+/* The next len < 2^32 bytes of the FASTA text. A call's text may be cut ANYWHERE — inside a header line, inside a name, between '\r' and
+ * '\n': what crosses the cut (whether the text is inside a line, that line's kind, the partial name, whether the open header is named)
+ * is carried by the builder. The array grows as csvgpu_shard_builder's do; after CSV_ENOMEM (a failed growth) or any other failure the
+ * builder is valid with its old contents and the same append may be tried again. CSV_EINVAL, nothing reaching the device: a null pointer,
+ * len >= 2^32, 2^32 line ends or more in one call. len == 0 does nothing. Whatever the bytes are, nothing outside [0, len) is read beyond
+ * the aligned 16-byte piece that holds a byte of it. Timed under CSV_K_MISC; waits for its kernels.
+ * _dev: text is a device pointer at any alignment (what csvgpu_bgzf_inflate_dev left). Host pointer: the text goes up through the
+ * page-locked block, in pieces. */
+int  csvgpu_genome_builder_append(csv_ctx *ctx, csv_genome_builder *b, const uint8_t *text, uint64_t len);
+int  csvgpu_genome_builder_append_dev(csv_ctx *ctx, csv_genome_builder *b, const uint8_t *d_text, uint64_t len);
+/* The text has ended (a final unterminated line counts). The array is handed over, not copied. Consumes the builder, also on failure
+ * (NULL): a contig of 2^32 bytes or more is refused, as the loader's uint32 length could not hold it. */
+csv_genome *csvgpu_genome_builder_finish(csv_ctx *ctx, csv_genome_builder *b);
+void csvgpu_genome_builder_destroy(csv_ctx *ctx, csv_genome_builder *b);
+void csvgpu_genome_free(csv_ctx *ctx, csv_genome *g);
+/* counts is always filled. Record i's name is names[name_off[i] .. name_off[i + 1]) (name_off [cap_records + 1], names [cap_name_bytes]),
+ * its bases length[i] (length [cap_records]). CSV_ECAPACITY, nothing written, when a capacity is too small: a first call with zero
+ * capacities sizes the second. */
+int  csvgpu_genome_describe(csv_ctx *ctx, const csv_genome *g, uint64_t cap_records, uint64_t cap_name_bytes, uint64_t *name_off, char *names, uint32_t *length,
+                            csv_genome_counts *counts);
+/* Item i: the cut [pos_start[i], pos_end[i]] of record record[i] (1-based inclusive, both decremented with uint32 wrap; empty when
+ * pos_end >= length or pos_start > pos_end — ReferenceGenome::query) written at out + out_off[i]; mask != 0 turns R Y K M S W B D H V of
+ * either case into N (the VCF writer's REF rule). out_off has n + 1 entries, and out_off[i + 1] - out_off[i] must be the cut's length, which
+ * the caller knows from the lengths. CSV_EINVAL, nothing launched or written: a record index beyond the genome, out_off decreasing, an
+ * item whose room is not its cut's length. Nothing outside the genome's array is read and nothing outside [out_off[0], out_off[n]) is
+ * written. Items and offsets go up and the bytes come back through the page-locked block; one launch, one wait. Timed under CSV_K_MISC. */
+int  csvgpu_genome_fetch(csv_ctx *ctx, const csv_genome *g, const uint32_t *record, const uint32_t *pos_start, const uint32_t *pos_end, const uint64_t *out_off,
+                         uint64_t n, int mask, char *out);
+
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
  * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster and of the
