@@ -11,6 +11,16 @@ from . import _lib
 from ._lib import SIG_DTYPE, CsvError, csv_chr_result, csv_hmm, csv_reads, csv_split_refs, csv_split_tables, ptr
 
 
+def _as_u8(x) -> np.ndarray:
+    """bytes-like or array-like -> contiguous uint8 array (no copy where there need be none)"""
+    return np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, np.uint8)
+
+
+def _is_dev(t, element_size: int) -> bool:
+    """a contiguous torch tensor on a device, of that element size"""
+    return t.is_cuda and t.is_contiguous() and t.element_size() == element_size
+
+
 @dataclass
 class SplitTables:
     """The members of a batch of contigs (primary alignments that have a supplementary record, map iteration order per segment) and
@@ -160,9 +170,12 @@ class Context:
     def __exit__(self, *a):
         self.close()
 
+    def _error(self, status: int) -> CsvError:
+        return CsvError(status, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+
     def _check(self, rc: int):
         if rc != 0:
-            raise CsvError(rc, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+            raise self._error(rc)
 
     # -------------------------------------------------------------------------------- host-pointer seams
     def cigar_scan(self, reads: Reads, depth_len: int, min_oplen: int = 50, min_mapq: int = 20, capacity: int | None = None):
@@ -401,7 +414,7 @@ class Context:
         n = C.c_uint64(cap)
         rc = self.lib.csvgpu_cn_observations_resident_many(self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n))
         if rc == _lib.CSV_ECAPACITY:
-            e = CsvError(rc, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+            e = self._error(rc)
             e.needed = int(n.value)
             raise e
         self._check(rc)
@@ -448,7 +461,7 @@ class Context:
         there. -> number of declined members."""
         blocks = np.ascontiguousarray(blocks, _lib.BGZF_BLOCK_DTYPE)
         for t in (d_comp, d_out, d_status):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 1:
+            if not _is_dev(t, 1):
                 raise ValueError("bgzf_inflate_dev: contiguous uint8 device tensors expected")
         if d_status.numel() < len(blocks):
             raise ValueError("bgzf_inflate_dev: status shorter than the member table")
@@ -503,7 +516,7 @@ class Context:
         (pos int32, flag uint16, mapq uint8, cigar_off uint64 [records + 1], cigar uint32; optional seq_off + seq, name_off + name,
         name_hash); the capacities are the arrays' lengths. anchors: ascending offsets of record starts, anchors[0] the first record's.
         -> (rc, counts): rc 0 written, 1 declined (counts['reason'] at counts['offset']), CSV_ECAPACITY with the exact counts."""
-        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        data = _as_u8(data)
 
         def address(a, k):
             if a.dtype != self._BAM_DTYPES[k] or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
@@ -544,10 +557,10 @@ class Context:
         numpy form: int32 / int16 / uint8 / int64 / int32 bit patterns) — behind bgzf_inflate_dev the bytes never leave the device, and
         pos / flag / mapq / cigar_off / cigar are what wrap_device takes. -> (rc, counts) as bam_unpack_into."""
         def address(t, k):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != self._BAM_SIZES[k]:
+            if not _is_dev(t, self._BAM_SIZES[k]):
                 raise ValueError(f"bam_unpack_dev: '{k}' must be a contiguous device tensor of {self._BAM_SIZES[k]}-byte elements")
             return t.data_ptr()
-        if not d_bytes.is_cuda or not d_bytes.is_contiguous() or d_bytes.element_size() != 1:
+        if not _is_dev(d_bytes, 1):
             raise ValueError("bam_unpack_dev: contiguous uint8 device tensor expected")
         o = self._bam_out(out, address, lambda t: int(t.numel()), "bam_unpack_dev")
         return self._bam_call(self.lib.csvgpu_bam_unpack_dev, d_bytes.data_ptr(), int(d_bytes.numel()), anchors, tid, end, bases, o)
@@ -589,7 +602,7 @@ class Context:
         return rc, self._vcf_counts(c)
 
     def _vcf_host(self, text, out, af, form):
-        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        text = _as_u8(text)
 
         def address(a, k):
             if a.dtype != self._VCF_DTYPES[k] or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
@@ -641,10 +654,10 @@ class Context:
 
     def _vcf_dev(self, d_text, out, af, form):
         def address(t, k):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != np.dtype(self._VCF_DTYPES[k]).itemsize:
+            if not _is_dev(t, np.dtype(self._VCF_DTYPES[k]).itemsize):
                 raise ValueError(f"vcf_parse_dev: '{k}' must be a contiguous device tensor of {np.dtype(self._VCF_DTYPES[k]).itemsize}-byte elements")
             return t.data_ptr()
-        if not d_text.is_cuda or not d_text.is_contiguous() or d_text.element_size() != 1:
+        if not _is_dev(d_text, 1):
             raise ValueError("vcf_parse_dev: contiguous uint8 device tensor expected")
         o = self._vcf_out(out, address, lambda t: int(t.numel()), af, "vcf_parse_dev")
         return self._vcf_call(True, d_text.data_ptr(), int(d_text.numel()), o, form)
@@ -656,7 +669,7 @@ class Context:
 
     def vcf_af_parse_dev(self, d_text, contig, needle, d_sorted_pos, out: dict):
         """csvgpu_vcf_af_parse_dev: d_sorted_pos a device tensor of 4-byte elements, ascending (not checked)."""
-        if not d_sorted_pos.is_cuda or not d_sorted_pos.is_contiguous() or d_sorted_pos.element_size() != 4:
+        if not _is_dev(d_sorted_pos, 4):
             raise ValueError("vcf_af_parse_dev: sorted_pos must be a contiguous device tensor of 4-byte elements")
         return self._vcf_dev(d_text, out, True, ("af", contig, needle, d_sorted_pos.data_ptr(), int(d_sorted_pos.numel())))
 
@@ -684,7 +697,7 @@ class Context:
         rs = reads.c_struct()
         h = self.lib.csvgpu_shard_upload(self.h, C.byref(rs), depth_len)
         if not h:
-            raise CsvError(_lib.CSV_ENOMEM, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+            raise self._error(_lib.CSV_ENOMEM)
         return Shard(self, h, reads.n_reads, depth_len)
 
     def wrap_device_ptrs(self, n_reads: int, n_cigar: int, pos: int, flag: int, mapq: int, cigar_off: int, cigar: int, depth_len: int, keep=None) -> "Shard":
@@ -695,7 +708,7 @@ class Context:
         r.pos, r.flag, r.mapq, r.tid, r.cigar_off, r.cigar = pos, flag, mapq, None, cigar_off, cigar       # (void * fields)
         h = self.lib.csvgpu_shard_wrap_dev(self.h, C.byref(r), depth_len)
         if not h:
-            raise CsvError(_lib.CSV_EINVAL, (self.lib.csvgpu_last_error(self.h) or b"").decode())
+            raise self._error(_lib.CSV_EINVAL)
         sh = Shard(self, h, n_reads, depth_len)
         sh._keep = keep
         return sh
@@ -706,7 +719,7 @@ class Context:
         if not (flag.numel() == n and mapq.numel() == n and cigar_off.numel() == n + 1):
             raise ValueError("wrap_device: array lengths disagree")
         for t, size in ((pos, 4), (flag, 2), (mapq, 1), (cigar_off, 8), (cigar, 4)):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            if not _is_dev(t, size):
                 raise ValueError("wrap_device: tensors must be contiguous device tensors of the csv_reads element sizes")
         return self.wrap_device_ptrs(n, m, pos.data_ptr(), flag.data_ptr(), mapq.data_ptr(), cigar_off.data_ptr(), cigar.data_ptr(), depth_len,
                                      keep=(pos, flag, mapq, cigar_off, cigar))
@@ -744,7 +757,7 @@ class GenomeBuilder:
         self.ctx = ctx
         self.h = ctx.lib.csvgpu_genome_builder_create(ctx.h, int(reserve_bytes))
         if not self.h:
-            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+            raise ctx._error(_lib.CSV_ENOMEM)
 
     def _live(self):
         if not self.h:
@@ -753,13 +766,13 @@ class GenomeBuilder:
     def append(self, text):
         """csvgpu_genome_builder_append: the next bytes of the text (bytes or a uint8 numpy array), through the page-locked block."""
         self._live()
-        data = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        data = _as_u8(text)
         self.ctx._check(self.ctx.lib.csvgpu_genome_builder_append(self.ctx.h, self.h, ptr(data) if len(data) else None, len(data)))
 
     def append_dev(self, d_text):
         """csvgpu_genome_builder_append_dev: the same for a uint8 torch tensor on the context's device, at any alignment."""
         self._live()
-        if not d_text.is_cuda or not d_text.is_contiguous() or d_text.element_size() != 1:
+        if not _is_dev(d_text, 1):
             raise ValueError("append_dev: contiguous uint8 device tensor expected")
         self.append_ptr(d_text.data_ptr(), int(d_text.numel()))
 
@@ -773,7 +786,7 @@ class GenomeBuilder:
         self._live()
         h, self.h = self.ctx.lib.csvgpu_genome_builder_finish(self.ctx.h, self.h), None
         if not h:
-            raise CsvError(_lib.CSV_EINVAL, (self.ctx.lib.csvgpu_last_error(self.ctx.h) or b"").decode())
+            raise self.ctx._error(_lib.CSV_EINVAL)
         return Genome(self.ctx, h)
 
     def destroy(self):
@@ -862,7 +875,7 @@ class ShardBuilder:
         r = _lib.csv_shard_sizes(*[int(x) for x in reserve]) if reserve is not None else None
         self.h = ctx.lib.csvgpu_shard_builder_create(ctx.h, self.want, C.byref(r) if r is not None else None)
         if not self.h:
-            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+            raise ctx._error(_lib.CSV_ENOMEM)
 
     def _live(self):
         if not self.h:
@@ -876,14 +889,14 @@ class ShardBuilder:
         ctx = self.ctx
         if hasattr(stream_or_dev, "data_ptr"):
             t = stream_or_dev
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 1:
+            if not _is_dev(t, 1):
                 raise ValueError("append_bam: contiguous uint8 device tensor expected")
             return self.append_bam_ptr(t.data_ptr(), int(t.numel()), anchors, tid, end)
         data = stream_or_dev
-        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        data = _as_u8(data)
         dev = ctx.lib.csvgpu_dev_alloc(ctx.h, max(len(data), 1))
         if not dev:
-            raise CsvError(_lib.CSV_ENOMEM, (ctx.lib.csvgpu_last_error(ctx.h) or b"").decode())
+            raise ctx._error(_lib.CSV_ENOMEM)
         try:
             ctx._check(ctx.lib.csvgpu_upload(ctx.h, dev, ptr(data), len(data)))
             return self.append_bam_ptr(dev, len(data), anchors, tid, end)
@@ -921,7 +934,7 @@ class ShardBuilder:
         n = self.sizes()["n_reads"]
         h, self.h = self.ctx.lib.csvgpu_shard_builder_finish(self.ctx.h, self.h, depth_len), None
         if not h:
-            raise CsvError(_lib.CSV_ENOMEM, (self.ctx.lib.csvgpu_last_error(self.ctx.h) or b"").decode())
+            raise self.ctx._error(_lib.CSV_ENOMEM)
         return Shard(self.ctx, h, n, depth_len)
 
     def destroy(self):

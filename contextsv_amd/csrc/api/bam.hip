@@ -1,6 +1,6 @@
 // bam.hip — BAM records unpacked on the device (kernels/bamunpack.hip): the checks of the anchors and of the output struct, the two
 // read-backs (records in the stream; the kept records' counts, held against the caller's capacities before anything is written), and for the
-// host-pointer form the pieced copies through the page-locked block (bgzf.hip's, through glue.hpp). Replaces, with the kernels, what the host
+// host-pointer form the pieced copies through the page-locked block (a Transfer, glue.hpp). Replaces, with the kernels, what the host
 // reader does per record with bam1_core_t's fields, bam_get_cigar / bam_get_qname / bam_get_seq and bam_tag2cigar (host/bam_io.cpp).
 #include "glue.hpp"
 
@@ -29,37 +29,26 @@ int check_args(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const uint32_t 
 struct Head { uint32_t res[BU_RES_WORDS]; unsigned long long status; uint32_t bounds[2]; };
 static_assert(sizeof(Head) <= BU_HEAD_BYTES, "the head is one slice");
 
-// the head to the host through the page-locked block's first bytes (behind whatever is queued on the stream); waits
-int read_head(csv_ctx *ctx, const BamUnpackWs &w, Head &h)
-{
-    CSV_HIP(ctx, hipGetLastError());
-    CSV_HIP(ctx, hipMemcpyAsync(ctx->pinned, w.res, sizeof(Head), hipMemcpyDeviceToHost, ctx->stream));
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    memcpy(&h, ctx->pinned, sizeof(Head));
-    return CSV_OK;
-}
-
 // What both entry points share: anchors up, chain, counts, capacities, outputs. d_out: the device arrays; caps: the caller's struct.
-// Returns CSV_OK / 1 (declined) / CSV_E*; everything queued has been waited for unless a HIP call failed.
-int run_unpack(csv_ctx *ctx, const BamUnpackWs &w, const uint8_t *d_bytes, uint32_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
-               uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const BamUnpackOut &d_out, const csv_bam_out &caps, csv_bam_counts &c,
-               hipEvent_t ev[2], size_t &piece_no)
+// Returns CSV_OK (the last kernel queued, not waited for) / 1 (declined) / CSV_E*.
+int run_unpack(csv_ctx *ctx, Transfer &t, const BamUnpackWs &w, const uint8_t *d_bytes, uint32_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid,
+               int64_t end, uint64_t cigar_base, uint64_t seq_base, uint64_t name_base, const BamUnpackOut &d_out, const csv_bam_out &caps, csv_bam_counts &c)
 {
     hipStream_t s = ctx->stream;
-    int rc = copy_up(ctx, w.anchors, anchors, (size_t)n_anchors * 4, ev, piece_no);
+    int rc = t.up(w.anchors, anchors, (size_t)n_anchors * 4);
     if (rc) return rc;
     CSV_HIP(ctx, hipMemsetAsync(w.res, 0xff, BU_HEAD_BYTES, s));          // status: none; bounds: beyond every record
     Head h;
     TimerScope ts(ctx, CSV_K_MISC);
     launch_bam_chain(s, d_bytes, len, n_anchors, w);
-    if ((rc = read_head(ctx, w, h))) return rc;
+    if ((rc = t.peek(&h, w.res, sizeof(Head)))) return rc;
     // (the kernels order a missed anchor in front of anything else at its offset by giving it reason 0)
     auto declined = [&](unsigned long long status) { c = csv_bam_counts{}; c.status = (status & 0xff) ? status : (status | CSV_BAM_ANCHOR); return 1; };
     if (h.status != BU_STATUS_NONE) return declined(h.status);
     const uint32_t n_rec = h.res[BU_RES_NREC], consumed = h.res[BU_RES_CONSUMED];
     if (n_rec > w.rec_cap || consumed > len) { ctx->err = "bam_unpack: the chain's counts leave the stream"; return CSV_EHIP; }
     launch_bam_fields(s, d_bytes, n_rec, tid, end, w);
-    if ((rc = read_head(ctx, w, h))) return rc;
+    if ((rc = t.peek(&h, w.res, sizeof(Head)))) return rc;
     if (h.status != BU_STATUS_NONE) return declined(h.status);
     const uint32_t n_kept = h.res[BU_RES_NKEPT], first = h.res[BU_RES_FIRST], n_cigar = h.res[BU_RES_NCIGAR], n_seq = h.res[BU_RES_NSEQ], n_name = h.res[BU_RES_NNAME];
     if ((uint64_t)first + n_kept > n_rec || n_cigar > len / 4 || n_seq > len || n_name > len) { ctx->err = "bam_unpack: the kept records' counts leave the stream"; return CSV_EHIP; }
@@ -90,14 +79,10 @@ int csvgpu_bam_unpack_dev(csv_ctx *ctx, const uint8_t *d_bytes, uint64_t len, co
     (void)hipSetDevice(ctx->device);
     BamUnpackWs w;
     if ((rc = arena_reserve_for(ctx, ctx->work, "bam_unpack", [&](Arena &a) { return carve_bam_unpack(a, len, n_anchors, false, 0, 0, 0, 0, false, w); }))) return rc;
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "bam_unpack: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
-    rc = run_unpack(ctx, w, d_bytes, (uint32_t)len, anchors, n_anchors, tid, end, cigar_base, seq_base, name_base, dev_out(*d_out), *d_out, *counts, e.ev, piece_no);
-    if (rc == CSV_OK) { CSV_HIP(ctx, wait_stream(ctx->stream)); }
-    if (rc == CSV_OK || rc == 1 || rc == CSV_ECAPACITY) e.done = true;          // (those ways out end behind a wait)
-    return rc;
+    Transfer t(ctx);
+    if ((rc = t.open("bam_unpack"))) return rc;
+    rc = run_unpack(ctx, t, w, d_bytes, (uint32_t)len, anchors, n_anchors, tid, end, cigar_base, seq_base, name_base, dev_out(*d_out), *d_out, *counts);
+    return rc == CSV_OK ? t.wait() : rc;                                  // (the caller's device arrays are complete on return)
 }
 
 int csvgpu_bam_unpack(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const uint32_t *anchors, uint32_t n_anchors, int32_t tid, int64_t end,
@@ -113,24 +98,17 @@ int csvgpu_bam_unpack(csv_ctx *ctx, const uint8_t *bytes, uint64_t len, const ui
             return carve_bam_unpack(a, len, n_anchors, true, out->cap_records, out->cap_cigar, out->seq ? std::max<uint64_t>(out->cap_seq, 1) : 0,
                                     out->name ? std::max<uint64_t>(out->cap_name, 1) : 0, out->name_hash != nullptr, w);
         }))) return rc;
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "bam_unpack: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
-    if ((rc = copy_up(ctx, w.bytes, bytes, len, e.ev, piece_no))) return rc;
+    Transfer t(ctx);
+    if ((rc = t.open("bam_unpack"))) return rc;
+    if ((rc = t.up(w.bytes, bytes, len))) return rc;
     // The staged arrays hold min(capacity, what the stream can hold): a count beyond the capacity is CSV_ECAPACITY before anything is
     // written, a count within it is within the staged array.
-    rc = run_unpack(ctx, w, w.bytes, (uint32_t)len, anchors, n_anchors, tid, end, cigar_base, seq_base, name_base, w.out, *out, *counts, e.ev, piece_no);
-    if (rc == 1 || rc == CSV_ECAPACITY) e.done = true;
-    if (rc != CSV_OK) return rc;
+    if ((rc = run_unpack(ctx, t, w, w.bytes, (uint32_t)len, anchors, n_anchors, tid, end, cigar_base, seq_base, name_base, w.out, *out, *counts))) return rc;
     const csv_bam_counts &c = *counts;
-    auto down = [&](void *dst, const void *src, size_t n) { return n ? copy_down(ctx, dst, src, n, e.ev, Runs{{0, n}}) : (int)CSV_OK; };
-    if ((rc = down(out->pos, w.out.pos, c.n_kept * 4)) || (rc = down(out->flag, w.out.flag, c.n_kept * 2)) || (rc = down(out->mapq, w.out.mapq, c.n_kept)) ||
-        (rc = down(out->cigar_off, w.out.cigar_off, (c.n_kept + 1) * 8)) || (rc = down(out->cigar, w.out.cigar, c.n_cigar * 4))) return rc;
-    if (out->seq && ((rc = down(out->seq_off, w.out.seq_off, (c.n_kept + 1) * 8)) || (rc = down(out->seq, w.out.seq, c.n_seq)))) return rc;
-    if (out->name && ((rc = down(out->name_off, w.out.name_off, (c.n_kept + 1) * 8)) || (rc = down(out->name, w.out.name, c.n_name)))) return rc;
-    if (out->name_hash && (rc = down(out->name_hash, w.out.name_hash, c.n_kept * 8))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    e.done = true;
-    return CSV_OK;
+    if ((rc = t.down(out->pos, w.out.pos, c.n_kept * 4)) || (rc = t.down(out->flag, w.out.flag, c.n_kept * 2)) || (rc = t.down(out->mapq, w.out.mapq, c.n_kept)) ||
+        (rc = t.down(out->cigar_off, w.out.cigar_off, (c.n_kept + 1) * 8)) || (rc = t.down(out->cigar, w.out.cigar, c.n_cigar * 4))) return rc;
+    if (out->seq && ((rc = t.down(out->seq_off, w.out.seq_off, (c.n_kept + 1) * 8)) || (rc = t.down(out->seq, w.out.seq, c.n_seq)))) return rc;
+    if (out->name && ((rc = t.down(out->name_off, w.out.name_off, (c.n_kept + 1) * 8)) || (rc = t.down(out->name, w.out.name, c.n_name)))) return rc;
+    if (out->name_hash && (rc = t.down(out->name_hash, w.out.name_hash, c.n_kept * 8))) return rc;
+    return t.wait();
 }

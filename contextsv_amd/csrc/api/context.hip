@@ -1,6 +1,6 @@
-// context.hip — the context of the C-ABI in include/csvgpu.h: create / destroy, tuning, the arenas and the page-locked block, the timers and
-// their event pool, the gate, the caller's page-locked blocks. No CPU fallback lives in the glue: every result is produced by the kernels
-// under kernels/.
+// context.hip — the context of the C-ABI in include/csvgpu.h: create / destroy, tuning, the arenas, the page-locked block and the builders'
+// growing arrays (DevBuf), the timers and their event pool, the gate, the caller's page-locked blocks. No CPU fallback lives in the glue:
+// every result is produced by the kernels under kernels/.
 #include <new>
 
 #include "glue.hpp"
@@ -35,6 +35,21 @@ int ensure_pinned(csv_ctx *ctx, size_t bytes)
     ctx->pinned = nullptr; ctx->pinned_cap = 0;
     CSV_HIP(ctx, hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault));
     ctx->pinned_cap = bytes;
+    return CSV_OK;
+}
+
+int devbuf_ensure(csv_ctx *ctx, DevBuf &b, uint64_t used, uint64_t need, const char *what)
+{
+    if (need <= b.cap) return CSV_OK;
+    const uint64_t cap = std::max(need, b.cap + b.cap / 2);
+    char *p = nullptr;
+    if (test_fail_alloc() || hipMalloc((void **)&p, cap) != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipMalloc failed (") + what + " growth)"; return CSV_ENOMEM; }
+    // (a new shard builder's offset arrays count their first entry as used before they exist: nothing to copy from then)
+    hipError_t e = used && b.p ? hipMemcpyAsync(p, b.p, std::min(used, b.cap), hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(p); ctx->err = std::string(what) + " growth: " + hipGetErrorString(e); return CSV_EHIP; }
+    (void)hipFree(b.p);
+    b.p = p; b.cap = cap;
     return CSV_OK;
 }
 
@@ -199,15 +214,10 @@ int csvgpu_upload(csv_ctx *ctx, void *dev_dst, const void *host_src, size_t byte
     if (!ctx || (bytes && (!dev_dst || !host_src))) return CSV_EINVAL;
     if (!bytes) return CSV_OK;
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_pinned(ctx, 2 * kPiece);
-    if (rc) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "csvgpu_upload: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
-    if ((rc = copy_up(ctx, dev_dst, host_src, bytes, e.ev, piece_no))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    e.done = true;
-    return CSV_OK;
+    Transfer t(ctx);
+    int rc = t.open("csvgpu_upload");
+    if (rc || (rc = t.up(dev_dst, host_src, bytes))) return rc;
+    return t.wait();
 }
 
 int csvgpu_download(csv_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes)

@@ -1,6 +1,7 @@
 // fasta.hip — the reference genome loaded and queried on the device: the builder (one base array that grows, FASTA text appended in pieces
 // cut anywhere), its hand-over to a csv_genome, the genome's description and the cuts of it (kernels/fasta.hip). The rules are
-// fasta_core.hpp. Replaces the line loop of ReferenceGenome::setFilepath and the substr of ::query (host/fasta_query.cpp), and the
+// fasta_core.hpp; the text and the header lines' events travel through a Transfer, the array grows as a DevBuf, and the line ends are counted
+// by vcf.hip's count_lines (all glue.hpp). Replaces the line loop of ReferenceGenome::setFilepath and the substr of ::query (host/fasta_query.cpp), and the
 // ambiguity masking of the VCF writer's REF lookups (host/vcf_writer.cpp).
 #include <new>
 
@@ -21,8 +22,8 @@ struct Rec { uint64_t start; uint32_t len; uint64_t name_off; uint32_t name_len;
 
 struct csv_genome_builder {
     int device = 0;
-    char *seq = nullptr;                             // the kept residue bytes, in file order
-    uint64_t cap = 0, n_kept = 0;
+    DevBuf seq;                                      // the kept residue bytes, in file order
+    uint64_t n_kept = 0;
     uint64_t n_text = 0, n_lines = 0;                // what was appended: bytes, line ends
     Assembler a;                                     // the records so far, and what crosses the cut between two appends
 };
@@ -40,26 +41,10 @@ namespace {
 
 int bad(csv_ctx *ctx, const char *msg) { ctx->err = msg; return CSV_EINVAL; }
 
-// `need` bytes in the builder's array, of which the first n_kept are kept: shard_build.hip's growth (a new block of at least 1.5x the old
-// one through the guarded allocation, a copy on the device, the old block freed). CSV_ENOMEM leaves the builder as it was.
-int ensure(csv_ctx *ctx, csv_genome_builder *b, uint64_t need)
-{
-    if (need <= b->cap) return CSV_OK;
-    const uint64_t cap = std::max(need, b->cap + b->cap / 2);
-    char *p = nullptr;
-    if (test_fail_alloc() || hipMalloc((void **)&p, cap) != hipSuccess) { (void)hipGetLastError(); ctx->err = "hipMalloc failed (genome builder growth)"; return CSV_ENOMEM; }
-    hipError_t e = b->n_kept && b->seq ? hipMemcpyAsync(p, b->seq, b->n_kept, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(p); ctx->err = std::string("genome builder growth: ") + hipGetErrorString(e); return CSV_EHIP; }
-    (void)hipFree(b->seq);
-    b->seq = p; b->cap = cap;
-    return CSV_OK;
-}
-
 void builder_release(csv_genome_builder *b)
 {
     if (!b) return;
-    (void)hipFree(b->seq);
+    (void)hipFree(b->seq.p);
     delete b;
 }
 
@@ -76,56 +61,38 @@ bool carve_fasta(Arena &a, uint64_t n_tiles, uint64_t n_slots, uint64_t len, Fas
            take(a, w.ev.name_off, n_slots * 4) && take(a, w.ev.name_len, n_slots * 4) && take(a, w.ev.blank, n_slots) && take(a, w.ev.names, len);
 }
 
-// `bytes` from the device to the host through the page-locked block's first bytes (behind whatever is queued on the stream); waits
-int read_back(csv_ctx *ctx, void *dst, const void *d_src, size_t bytes)
-{
-    CSV_HIP(ctx, hipGetLastError());
-    CSV_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    memcpy(dst, ctx->pinned, bytes);
-    return CSV_OK;
-}
-
 // One piece of the text, on the device. The builder changes only once everything has come back: a failure leaves it as it was (bytes
-// written behind its tail are not part of it).
-int run_append(csv_ctx *ctx, csv_genome_builder *b, const uint8_t *d_text, uint32_t len, hipEvent_t ev[2])
+// written behind its tail are not part of it). Everything queued has come back on CSV_OK.
+int run_append(csv_ctx *ctx, Transfer &t, csv_genome_builder *b, const uint8_t *d_text, uint32_t len)
 {
     hipStream_t s = ctx->stream;
     int rc;
-    if ((rc = ensure(ctx, b, b->n_kept + len + kSlack))) return rc;
+    if ((rc = devbuf_ensure(ctx, b->seq, b->n_kept, b->n_kept + len + kSlack, "genome builder"))) return rc;
     const uint32_t n_tiles = vcf_tiles(d_text, len);
     FastaWs w;
-    auto first_pass = [&]() {                             // the line ends counted (the timer around the launches alone)
-        TimerScope ts(ctx, CSV_K_MISC);
-        launch_vcf_count(s, d_text, len, w.vcf);
-    };
-    if ((rc = arena_reserve_for(ctx, ctx->work, "genome_append", [&](Arena &a) { return carve_fasta(a, n_tiles, 0, len, w); }))) return rc;
-    first_pass();
-    uint32_t n_ends = 0;
-    if ((rc = read_back(ctx, &n_ends, w.vcf.tile_cnt + n_tiles, 4))) return rc;
-    if (n_ends > len) { ctx->err = "genome_append: the line ends' count leaves the text"; return CSV_EHIP; }
-    if (n_ends == UINT32_MAX) return bad(ctx, "genome_append: 2^32 lines or more in one call");
-    const uint32_t n_slots = n_ends + 1;
-    // (as api/vcf.hip: a grown arena is a new allocation, and the count runs again)
-    const size_t cap_before = ctx->work.cap;
-    if ((rc = arena_reserve_for(ctx, ctx->work, "genome_append", [&](Arena &a) { return carve_fasta(a, n_tiles, n_slots, len, w); }))) return rc;
-    if (ctx->work.cap != cap_before) first_pass();
+    uint32_t n_slots = 0;
+    if ((rc = count_lines(ctx, t, "genome_append", "genome_append: 2^32 lines or more in one call", d_text, len, w.vcf,
+                          [&](Arena &a, uint64_t slots) { return carve_fasta(a, n_tiles, slots, len, w); },
+                          [&]() -> int {                 // the line ends counted (the timer around the launch alone)
+                              TimerScope ts(ctx, CSV_K_MISC);
+                              launch_vcf_count(s, d_text, len, w.vcf);
+                              return CSV_OK;
+                          }, n_slots))) return rc;
     const FastaCarry carry{(uint8_t)b->a.mid_line, b->a.kind};
     {
         TimerScope ts(ctx, CSV_K_MISC);
         launch_vcf_starts(s, d_text, len, w.vcf);
         launch_fasta_lines(s, d_text, len, n_slots, carry, w);
-        launch_fasta_compact(s, d_text, len, w, (uint8_t *)b->seq + b->n_kept);
+        launch_fasta_compact(s, d_text, len, w, (uint8_t *)b->seq.p + b->n_kept);
     }
     FastaHead h;
-    if ((rc = read_back(ctx, &h, w.head, sizeof(FastaHead)))) return rc;
+    if ((rc = t.peek(&h, w.head, sizeof(FastaHead)))) return rc;
     if (h.n_kept > len || h.n_hdr > n_slots || h.n_name > len || h.tail_len > len) { ctx->err = "genome_append: the counts leave the text"; return CSV_EHIP; }
     const uint32_t nh = h.n_hdr;
     std::vector<uint32_t> kept(nh), name_off(nh), name_len(nh);
     std::vector<uint8_t> blank(nh), names(h.n_name);
-    auto down = [&](void *dst, const void *src, size_t n) { return n ? copy_down(ctx, dst, src, n, ev, Runs{{0, n}}) : (int)CSV_OK; };
-    if ((rc = down(kept.data(), w.ev.kept, (size_t)nh * 4)) || (rc = down(name_off.data(), w.ev.name_off, (size_t)nh * 4)) ||
-        (rc = down(name_len.data(), w.ev.name_len, (size_t)nh * 4)) || (rc = down(blank.data(), w.ev.blank, nh)) || (rc = down(names.data(), w.ev.names, h.n_name))) return rc;
+    if ((rc = t.down(kept.data(), w.ev.kept, (size_t)nh * 4)) || (rc = t.down(name_off.data(), w.ev.name_off, (size_t)nh * 4)) ||
+        (rc = t.down(name_len.data(), w.ev.name_len, (size_t)nh * 4)) || (rc = t.down(blank.data(), w.ev.blank, nh)) || (rc = t.down(names.data(), w.ev.names, h.n_name))) return rc;
     for (uint32_t i = 0; i < nh; i++)
         if ((uint64_t)name_off[i] + name_len[i] > h.n_name || kept[i] > h.n_kept) { ctx->err = "genome_append: a header line's event leaves the text"; return CSV_EHIP; }
     // the header lines, in file order, to the records (fasta_core.hpp: the same function the CPU check feeds)
@@ -135,7 +102,7 @@ int run_append(csv_ctx *ctx, csv_genome_builder *b, const uint8_t *d_text, uint3
     fastacore::apply_piece(b->a, b->n_kept, e);
     b->n_kept += h.n_kept;
     b->n_text += len;
-    b->n_lines += n_ends;
+    b->n_lines += n_slots - 1;                           // the line ends
     return CSV_OK;
 }
 
@@ -157,7 +124,7 @@ csv_genome_builder *csvgpu_genome_builder_create(csv_ctx *ctx, uint64_t reserve_
     csv_genome_builder *b = new (std::nothrow) csv_genome_builder();
     if (!b) { ctx->err = "out of host memory"; return nullptr; }
     b->device = ctx->device;
-    if (ensure(ctx, b, reserve_bytes + kSlack) != CSV_OK) { builder_release(b); return nullptr; }
+    if (devbuf_ensure(ctx, b->seq, 0, reserve_bytes + kSlack, "genome builder") != CSV_OK) { builder_release(b); return nullptr; }
     return b;
 }
 
@@ -174,12 +141,9 @@ int csvgpu_genome_builder_append_dev(csv_ctx *ctx, csv_genome_builder *b, const 
     int rc = check_append(ctx, b, d_text, len);
     if (rc || len == 0) return rc;
     (void)hipSetDevice(ctx->device);
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "genome_builder_append: no event"; return CSV_EHIP; }
-    rc = run_append(ctx, b, d_text, (uint32_t)len, e.ev);
-    if (rc == CSV_OK) e.done = true;
-    return rc;
+    Transfer t(ctx);
+    if ((rc = t.open("genome_builder_append"))) return rc;
+    return run_append(ctx, t, b, d_text, (uint32_t)len);
 }
 
 int csvgpu_genome_builder_append(csv_ctx *ctx, csv_genome_builder *b, const uint8_t *text, uint64_t len)
@@ -189,14 +153,10 @@ int csvgpu_genome_builder_append(csv_ctx *ctx, csv_genome_builder *b, const uint
     (void)hipSetDevice(ctx->device);
     uint8_t *d_text = nullptr;
     if ((rc = arena_reserve_for(ctx, ctx->arena, "genome_append", [&](Arena &a) { return take(a, d_text, len + 16); }))) return rc;
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "genome_builder_append: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
-    if ((rc = copy_up(ctx, d_text, text, len, e.ev, piece_no))) return rc;
-    rc = run_append(ctx, b, d_text, (uint32_t)len, e.ev);
-    if (rc == CSV_OK) e.done = true;
-    return rc;
+    Transfer t(ctx);
+    if ((rc = t.open("genome_builder_append"))) return rc;
+    if ((rc = t.up(d_text, text, len))) return rc;
+    return run_append(ctx, t, b, d_text, (uint32_t)len);
 }
 
 csv_genome *csvgpu_genome_builder_finish(csv_ctx *ctx, csv_genome_builder *b)
@@ -218,8 +178,8 @@ csv_genome *csvgpu_genome_builder_finish(csv_ctx *ctx, csv_genome_builder *b)
         g->rec.push_back(Rec{r.start, (uint32_t)(r.end - r.start), g->names.size(), (uint32_t)r.name.size()});
         g->names += r.name;
     }
-    g->seq = b->seq;                                     // the array changes hands
-    b->seq = nullptr;
+    g->seq = b->seq.p;                                   // the array changes hands
+    b->seq.p = nullptr;
     builder_release(b);
     return g;
 }

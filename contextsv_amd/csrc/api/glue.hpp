@@ -1,10 +1,12 @@
 // glue.hpp — what more than one file of the C-ABI glue (api/*.hip) needs: the reservations of the arenas and of the page-locked block,
-// the short waits, and the chains one concern's entry points borrow from another's. Not part of the ABI.
+// the short waits, the transfer session of the pieced copies (Transfer), the device array that grows (DevBuf), and the chains one concern's
+// entry points borrow from another's. Not part of the ABI.
 #pragma once
 #include <string.h>
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -108,25 +110,46 @@ static inline const uint32_t *sorted_perm(csv_ctx *ctx, const int32_t *keys, uin
 }
 
 // ---- defined in one file, used by others ----
-// bgzf.hip: pieced copies between pageable host memory and the device through the two halves of the page-locked block
-constexpr size_t kPiece = (size_t)4 << 20;               // bytes per copy: the page-locked block holds two pieces (ensure_pinned(2 * kPiece)), one in flight, one being filled / emptied
+// transfer.hip: one entry point's copies between pageable host memory and the device through the page-locked block, in pieces
+constexpr size_t kPiece = (size_t)4 << 20;               // bytes per copy: the page-locked block holds two pieces, one in flight, one being filled / emptied
 typedef std::vector<std::pair<uint64_t, uint64_t>> Runs;
-int copy_up(csv_ctx *ctx, void *d_dst, const void *h_src, size_t bytes, hipEvent_t ev[2], size_t &piece_no);
-int copy_down(csv_ctx *ctx, void *h_dst, const void *d_src, size_t bytes, hipEvent_t ev[2], const Runs &runs);
-struct Events {                                           // two events of the context's pool, returned to it
+// Holds two events of the context's pool from open() until it goes out of scope. It knows whether a copy it queued may still be in flight
+// (up() and a failed member leave one; a wait that succeeded leaves none) and drains the stream on its way out then, and only then: the
+// events and the block's halves never change hands under a copy. The entry point's kernels go between the calls, on ctx->stream.
+struct Transfer {
+    explicit Transfer(csv_ctx *c) : ctx(c) {}
+    Transfer(const Transfer &) = delete;
+    Transfer &operator=(const Transfer &) = delete;
+    ~Transfer();
+    int open(const char *who);                            // ensure_pinned(2 * kPiece), the events; "<who>: no event" without them
+    // host -> device, queued: the last pieces may still be in flight on return (the stream orders them in front of the kernel). The
+    // pieces are counted across calls, so consecutive arrays alternate the halves like one long one.
+    int up(void *d_dst, const void *h_src, size_t bytes);
+    // device -> host, complete on return; piece k + 1 travels while piece k is copied out of the block. Only the bytes inside `runs`
+    // (ascending, disjoint [first, second) offsets into the range) reach the caller's memory: the rest is not the library's to write.
+    int down(void *h_dst, const void *d_src, size_t bytes, const Runs &runs);
+    int down(void *h_dst, const void *d_src, size_t bytes);   // the whole range; nothing to do for no bytes or a null h_dst
+    // `bytes` (at most kPinScalars) through the block's first bytes, behind whatever is queued on the stream; waits
+    int peek(void *dst, const void *d_src, size_t bytes);
+    int wait();                                           // wait_stream(ctx->stream)
+private:
     csv_ctx *ctx;
-    hipEvent_t ev[2];
-    bool done = false;                                    // set by the entry point on its way out with everything waited for
-    explicit Events(csv_ctx *c) : ctx(c) { ev[0] = get_event(c); ev[1] = get_event(c); }
-    // An early return (a HIP error part-way through the pieces) may leave copies queued that read or write the page-locked halves and events
-    // recorded but not waited for: the stream is drained before the events go back to the pool and the block to its next user.
-    ~Events()
-    {
-        if (!done) (void)hipStreamSynchronize(ctx->stream);
-        for (hipEvent_t e : ev) if (e) ctx->event_pool.push_back(e);
-    }
-    bool ok() const { return ev[0] && ev[1]; }
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    size_t n_up = 0;                                      // pieces sent up so far: the next one's half, and from the third on a wait for that half's last copy
+    bool pending = false;                                 // a copy of this session may be in flight
 };
+// context.hip: one device array that grows. `need` bytes in `b`, of which the first `used` are kept: a new block of at least 1.5x the old one
+// through the guarded allocation, a copy on the device, the old block freed. CSV_ENOMEM leaves `b` as it was. `what`: whose, for the texts.
+struct DevBuf {
+    char *p = nullptr;
+    uint64_t cap = 0;                                     // bytes allocated; the owner's counts say how many are in use
+};
+int devbuf_ensure(csv_ctx *ctx, DevBuf &b, uint64_t used, uint64_t need, const char *what);
+// vcf.hip: the line ends of a text counted (kernels/vcfparse.hip) and the per-line workspace sized by them. carve(a, 0) lays out what the
+// count needs, carve(a, n_slots) the per-line arrays behind it; first_pass queues the count (and whatever must be in place again once the
+// arena has grown: it runs a second time then). w: the count's slices, as the carve set them. n_slots: the lines, a last open one included.
+int count_lines(csv_ctx *ctx, Transfer &t, const char *what, const char *too_many, const uint8_t *d_text, uint32_t len, const VcfWs &w,
+                const std::function<bool(Arena &, uint64_t)> &carve, const std::function<int()> &first_pass, uint32_t &n_slots);
 // reads.hip
 int check_reads(csv_ctx *ctx, const csv_reads *r);           // host arrays
 int check_reads_dev(csv_ctx *ctx, const csv_reads *r);       // arrays in HBM: one small kernel

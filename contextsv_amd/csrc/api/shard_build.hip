@@ -10,11 +10,6 @@ using namespace csv;
 
 namespace {
 
-// one device array of the builder: `cap` bytes allocated, of which the builder's counts say how many are in use
-struct Buf {
-    char *p = nullptr;
-    uint64_t cap = 0;
-};
 constexpr uint64_t kSlack = 16;                      // bytes kept behind every array's last element, as csvgpu_shard_upload allocates them
 
 }  // namespace
@@ -22,7 +17,7 @@ constexpr uint64_t kSlack = 16;                      // bytes kept behind every 
 struct csv_shard_builder {
     uint32_t want = 0;
     int device = 0;
-    Buf pos, flag, mapq, cigar_off, cigar, seq_off, seq, name_off, name, name_hash;
+    DevBuf pos, flag, mapq, cigar_off, cigar, seq_off, seq, name_off, name, name_hash;
     csv_shard_sizes n{0, 0, 0, 0};
     uint32_t *unsorted = nullptr;                    // device word: some appended pos[i] < pos[i - 1]
 };
@@ -31,22 +26,8 @@ namespace {
 
 bool wants(const csv_shard_builder *b, uint32_t what) { return (b->want & what) != 0; }
 
-// `need` bytes in `b`, of which the first `used` are kept: a new block of at least 1.5x the old one through the guarded allocation, a copy on
-// the device, the old block freed. CSV_ENOMEM leaves `b` as it was.
-int ensure(csv_ctx *ctx, Buf &b, uint64_t used, uint64_t need)
-{
-    if (need <= b.cap) return CSV_OK;
-    const uint64_t cap = std::max(need, b.cap + b.cap / 2);
-    char *p = nullptr;
-    if (test_fail_alloc() || hipMalloc((void **)&p, cap) != hipSuccess) { (void)hipGetLastError(); ctx->err = "hipMalloc failed (shard builder growth)"; return CSV_ENOMEM; }
-    // (a new builder's offset arrays count their first entry as used before they exist: nothing to copy from then)
-    hipError_t e = used && b.p ? hipMemcpyAsync(p, b.p, std::min(used, b.cap), hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(p); ctx->err = std::string("shard builder growth: ") + hipGetErrorString(e); return CSV_EHIP; }
-    (void)hipFree(b.p);
-    b.p = p; b.cap = cap;
-    return CSV_OK;
-}
+// (the growth of glue.hpp, with the builder's name in its texts)
+int ensure(csv_ctx *ctx, DevBuf &b, uint64_t used, uint64_t need) { return devbuf_ensure(ctx, b, used, need, "shard builder"); }
 
 // room for `add` more behind the builder's totals in every array it keeps
 int ensure_all(csv_ctx *ctx, csv_shard_builder *b, const csv_shard_sizes &add)
@@ -68,7 +49,7 @@ int ensure_all(csv_ctx *ctx, csv_shard_builder *b, const csv_shard_sizes &add)
 void builder_release(csv_shard_builder *b)
 {
     if (!b) return;
-    for (Buf *x : {&b->pos, &b->flag, &b->mapq, &b->cigar_off, &b->cigar, &b->seq_off, &b->seq, &b->name_off, &b->name, &b->name_hash}) (void)hipFree(x->p);
+    for (DevBuf *x : {&b->pos, &b->flag, &b->mapq, &b->cigar_off, &b->cigar, &b->seq_off, &b->seq, &b->name_off, &b->name, &b->name_hash}) (void)hipFree(x->p);
     (void)hipFree(b->unsorted);
     delete b;
 }
@@ -87,12 +68,11 @@ csv_bam_out tail_out(const csv_shard_builder *b, const csv_shard_sizes &cap)
     return o;
 }
 
-// the sortedness of the records [first, first + n) into the builder's word, behind whatever wrote them; waits
+// the sortedness of the records [first, first + n) into the builder's word, queued behind whatever wrote them: the caller waits
 int note_order(csv_ctx *ctx, csv_shard_builder *b, uint64_t first, uint64_t n)
 {
     launch_sb_unsorted(ctx->stream, (const int32_t *)b->pos.p, first, n, b->unsorted);
     CSV_HIP(ctx, hipGetLastError());
-    CSV_HIP(ctx, wait_stream(ctx->stream));
     return CSV_OK;
 }
 
@@ -115,7 +95,7 @@ csv_shard_builder *csvgpu_shard_builder_create(csv_ctx *ctx, uint32_t want, cons
         CSV_HIP(ctx, hipMemsetAsync(b->unsorted, 0, 4, ctx->stream));
         const int rc = ensure_all(ctx, b, reserve ? *reserve : csv_shard_sizes{0, 0, 0, 0});
         if (rc) return rc;
-        for (Buf *x : {&b->cigar_off, &b->seq_off, &b->name_off}) if (x->p) CSV_HIP(ctx, hipMemsetAsync(x->p, 0, 8, ctx->stream));
+        for (DevBuf *x : {&b->cigar_off, &b->seq_off, &b->name_off}) if (x->p) CSV_HIP(ctx, hipMemsetAsync(x->p, 0, 8, ctx->stream));
         CSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CSV_OK;
     };
@@ -161,6 +141,7 @@ int csvgpu_shard_builder_append_bam(csv_ctx *ctx, csv_shard_builder *b, const ui
     if (rc == CSV_ECAPACITY || rc == 1) { ctx->err = "shard_builder_append_bam: the second pass disagrees with the sizing pass"; return CSV_EHIP; }
     if (rc) return rc;
     if ((rc = note_order(ctx, b, b->n.n_reads, add.n_reads))) return rc;
+    CSV_HIP(ctx, wait_stream(ctx->stream));
     b->n.n_reads += add.n_reads; b->n.n_cigar += add.n_cigar; b->n.n_seq += add.n_seq; b->n.n_name += add.n_name;
     return CSV_OK;
 }
@@ -187,26 +168,22 @@ int csvgpu_shard_builder_append_host(csv_ctx *ctx, csv_shard_builder *b, const c
     if (b->n.n_reads + k >= 0xffffffffull) return bad(ctx, "shard_builder_append_host: more than 2^32-2 reads in one shard");
     (void)hipSetDevice(ctx->device);
     if ((rc = ensure_all(ctx, b, add))) return rc;
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "shard_builder_append_host: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
+    Transfer t(ctx);
+    if ((rc = t.open("shard_builder_append_host"))) return rc;
     const csv_bam_out o = tail_out(b, add);
     hipStream_t s = ctx->stream;
     // an offset array goes up as it is and is rebased where it lies: + the builder's total, - the batch's own first offset
     auto offsets = [&](uint64_t *d_off, const uint64_t *h_off, uint64_t total) {
-        const int rc2 = copy_up(ctx, d_off, h_off, (k + 1) * 8, e.ev, piece_no);
+        const int rc2 = t.up(d_off, h_off, (k + 1) * 8);
         if (rc2 == CSV_OK) launch_sb_add(s, d_off, k + 1, total - h_off[0]);
         return rc2;
     };
-    if ((rc = copy_up(ctx, o.pos, r->pos, k * 4, e.ev, piece_no)) || (rc = copy_up(ctx, o.flag, r->flag, k * 2, e.ev, piece_no)) ||
-        (rc = copy_up(ctx, o.mapq, r->mapq, k, e.ev, piece_no)) || (rc = offsets(o.cigar_off, r->cigar_off, b->n.n_cigar)) ||
-        (rc = copy_up(ctx, o.cigar, r->cigar ? r->cigar + r->cigar_off[0] : nullptr, add.n_cigar * 4, e.ev, piece_no))) return rc;
-    if (wants(b, CSV_SB_SEQ) && ((rc = offsets(o.seq_off, seq_off, b->n.n_seq)) || (rc = copy_up(ctx, o.seq, seq ? seq + seq_off[0] : nullptr, add.n_seq, e.ev, piece_no)))) return rc;
-    if (wants(b, CSV_SB_NAMES) && ((rc = offsets(o.name_off, name_off, b->n.n_name)) || (rc = copy_up(ctx, o.name, name ? name + name_off[0] : nullptr, add.n_name, e.ev, piece_no)))) return rc;
-    if (wants(b, CSV_SB_NAME_HASH) && (rc = copy_up(ctx, o.name_hash, name_hash, k * 8, e.ev, piece_no))) return rc;
-    if ((rc = note_order(ctx, b, b->n.n_reads, k))) return rc;
-    e.done = true;
+    if ((rc = t.up(o.pos, r->pos, k * 4)) || (rc = t.up(o.flag, r->flag, k * 2)) || (rc = t.up(o.mapq, r->mapq, k)) || (rc = offsets(o.cigar_off, r->cigar_off, b->n.n_cigar)) ||
+        (rc = t.up(o.cigar, r->cigar ? r->cigar + r->cigar_off[0] : nullptr, add.n_cigar * 4))) return rc;
+    if (wants(b, CSV_SB_SEQ) && ((rc = offsets(o.seq_off, seq_off, b->n.n_seq)) || (rc = t.up(o.seq, seq ? seq + seq_off[0] : nullptr, add.n_seq)))) return rc;
+    if (wants(b, CSV_SB_NAMES) && ((rc = offsets(o.name_off, name_off, b->n.n_name)) || (rc = t.up(o.name, name ? name + name_off[0] : nullptr, add.n_name)))) return rc;
+    if (wants(b, CSV_SB_NAME_HASH) && (rc = t.up(o.name_hash, name_hash, k * 8))) return rc;
+    if ((rc = note_order(ctx, b, b->n.n_reads, k)) || (rc = t.wait())) return rc;
     b->n.n_reads += k; b->n.n_cigar += add.n_cigar; b->n.n_seq += add.n_seq; b->n.n_name += add.n_name;
     return CSV_OK;
 }
@@ -245,32 +222,18 @@ int csvgpu_shard_sizes(csv_ctx *ctx, const csv_shard *sh, csv_shard_sizes *out)
     return CSV_OK;
 }
 
-namespace {
-
-// device -> pageable host memory through the page-locked block, in pieces
-struct Fetch {
-    csv_ctx *ctx;
-    Events e;
-    explicit Fetch(csv_ctx *c) : ctx(c), e(c) {}
-    int operator()(void *dst, const void *src, size_t bytes) { return dst && bytes ? copy_down(ctx, dst, src, bytes, e.ev, Runs{{0, bytes}}) : (int)CSV_OK; }
-};
-
-}  // namespace
-
+// (the fetches: an array the caller passes null for is skipped)
 int csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *sh, int32_t *pos, uint16_t *flag, uint8_t *mapq, uint64_t *cigar_off, uint32_t *cigar)
 {
     if (!ctx || !sh) return CSV_EINVAL;
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_pinned(ctx, 2 * kPiece);
+    Transfer t(ctx);
+    int rc = t.open("shard_fetch_reads");
     if (rc) return rc;
-    Fetch f(ctx);
-    if (!f.e.ok()) { ctx->err = "shard_fetch_reads: no event"; return CSV_EHIP; }
     const uint64_t n = sh->d.n_reads;
-    if ((rc = f(pos, sh->d.pos, n * 4)) || (rc = f(flag, sh->d.flag, n * 2)) || (rc = f(mapq, sh->d.mapq, n)) || (rc = f(cigar_off, sh->d.cigar_off, (n + 1) * 8)) ||
-        (rc = f(cigar, sh->d.cigar, sh->d.n_cigar * 4))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    f.e.done = true;
-    return CSV_OK;
+    if ((rc = t.down(pos, sh->d.pos, n * 4)) || (rc = t.down(flag, sh->d.flag, n * 2)) || (rc = t.down(mapq, sh->d.mapq, n)) ||
+        (rc = t.down(cigar_off, sh->d.cigar_off, (n + 1) * 8)) || (rc = t.down(cigar, sh->d.cigar, sh->d.n_cigar * 4))) return rc;
+    return t.wait();
 }
 
 int csvgpu_shard_fetch_names(csv_ctx *ctx, csv_shard *sh, uint64_t *name_off, uint8_t *name, uint64_t *name_hash)
@@ -279,15 +242,12 @@ int csvgpu_shard_fetch_names(csv_ctx *ctx, csv_shard *sh, uint64_t *name_off, ui
     if ((name_off || name) && !sh->name_off) return bad(ctx, "shard_fetch_names: the shard holds no names");
     if (name_hash && !sh->qhash) return bad(ctx, "shard_fetch_names: the shard holds no name hashes");
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_pinned(ctx, 2 * kPiece);
+    Transfer t(ctx);
+    int rc = t.open("shard_fetch_names");
     if (rc) return rc;
-    Fetch f(ctx);
-    if (!f.e.ok()) { ctx->err = "shard_fetch_names: no event"; return CSV_EHIP; }
     const uint64_t n = sh->d.n_reads;
-    if ((rc = f(name_off, sh->name_off, (n + 1) * 8)) || (rc = f(name, sh->name, sh->n_name)) || (rc = f(name_hash, sh->qhash, n * 8))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    f.e.done = true;
-    return CSV_OK;
+    if ((rc = t.down(name_off, sh->name_off, (n + 1) * 8)) || (rc = t.down(name, sh->name, sh->n_name)) || (rc = t.down(name_hash, sh->qhash, n * 8))) return rc;
+    return t.wait();
 }
 
 int csvgpu_shard_drop_sequences(csv_ctx *ctx, csv_shard *sh)

@@ -1,7 +1,8 @@
 // vcf.hip — VCF text lines parsed on the device (kernels/vcfparse.hip): the checks of the arguments, the two read-backs (the text's line
 // ends, which size the per-line workspace; the counts, held against the caller's capacities before anything is written), and for the
-// host-pointer form the pieced copies through the page-locked block (bgzf.hip's, through glue.hpp). Replaces, with the kernels, what the host
-// reader does per line in SNPFile::load and SNPFile::table (host/snp_io.cpp: snp_record_of_line, af_record_of_line).
+// host-pointer form the pieced copies through the page-locked block (a Transfer, glue.hpp). The count of the line ends (count_lines) also
+// serves fasta.hip. Replaces, with the kernels, what the host reader does per line in SNPFile::load and SNPFile::table (host/snp_io.cpp:
+// snp_record_of_line, af_record_of_line).
 #include "glue.hpp"
 
 using namespace csv;
@@ -34,20 +35,37 @@ int check_args(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, c
     return CSV_OK;
 }
 
-// `bytes` from the device to the host through the page-locked block's first bytes (behind whatever is queued on the stream); waits
-int read_back(csv_ctx *ctx, void *dst, const void *d_src, size_t bytes)
+}  // namespace
+
+namespace csv {
+
+int count_lines(csv_ctx *ctx, Transfer &t, const char *what, const char *too_many, const uint8_t *d_text, uint32_t len, const VcfWs &w,
+                const std::function<bool(Arena &, uint64_t)> &carve, const std::function<int()> &first_pass, uint32_t &n_slots)
 {
-    CSV_HIP(ctx, hipGetLastError());
-    CSV_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    memcpy(dst, ctx->pinned, bytes);
-    return CSV_OK;
+    const uint32_t n_tiles = vcf_tiles(d_text, len);
+    int rc;
+    if ((rc = arena_reserve_for(ctx, ctx->work, what, [&](Arena &a) { return carve(a, 0); }))) return rc;
+    if ((rc = first_pass())) return rc;
+    uint32_t n_ends = 0;
+    if ((rc = t.peek(&n_ends, w.tile_cnt + n_tiles, 4))) return rc;
+    if (n_ends > len) { ctx->err = std::string(what) + ": the line ends' count leaves the text"; return CSV_EHIP; }
+    if (n_ends == UINT32_MAX) { ctx->err = too_many; return CSV_EINVAL; }
+    n_slots = n_ends + 1;
+    // The per-line arrays behind the first carve's slices, which keep their contents unless the arena had to grow: a grown arena is a new
+    // allocation (possibly at the old address, so the pointer says nothing; the capacity rises with every growth) and they are made again.
+    const size_t cap_before = ctx->work.cap;
+    if ((rc = arena_reserve_for(ctx, ctx->work, what, [&](Arena &a) { return carve(a, n_slots); }))) return rc;
+    return ctx->work.cap != cap_before ? first_pass() : (int)CSV_OK;
 }
 
+}  // namespace csv
+
+namespace {
+
 // What the entry points share. d_text / d_sorted: on the device; d_out: the caller's device arrays, or null for the workspace's staged ones
-// (io). Returns CSV_OK / 1 (declined) / CSV_E*; everything queued has been waited for unless a HIP call failed. w: the carved workspace.
-int run_parse(csv_ctx *ctx, const uint8_t *d_text, uint32_t len, const Call &c, const uint32_t *d_sorted, const VcfOut *d_out, const csv_vcf_out &caps,
-              csv_vcf_counts &cnt, VcfWs &w, hipEvent_t ev[2], size_t &piece_no)
+// (io). Returns CSV_OK (the last kernel queued, not waited for) / 1 (declined) / CSV_E*. w: the carved workspace.
+int run_parse(csv_ctx *ctx, Transfer &t, const uint8_t *d_text, uint32_t len, const Call &c, const uint32_t *d_sorted, const VcfOut *d_out, const csv_vcf_out &caps,
+              csv_vcf_counts &cnt, VcfWs &w)
 {
     hipStream_t s = ctx->stream;
     const uint32_t n_tiles = vcf_tiles(d_text, len);
@@ -55,24 +73,16 @@ int run_parse(csv_ctx *ctx, const uint8_t *d_text, uint32_t len, const Call &c, 
     std::vector<uint8_t> strings(n_strings);
     if (c.af) { if (c.contig_len) memcpy(strings.data(), c.contig, c.contig_len); memcpy(strings.data() + c.contig_len, c.needle, c.needle_len); }
     int rc;
-    auto first_pass = [&]() -> int {                      // the strings up, the line ends counted (the timer around the launches alone)
-        if (n_strings && (rc = copy_up(ctx, w.strings, strings.data(), n_strings, ev, piece_no))) return rc;
-        TimerScope ts(ctx, CSV_K_MISC);
-        launch_vcf_count(s, d_text, len, w);
-        return CSV_OK;
-    };
-    if ((rc = arena_reserve_for(ctx, ctx->work, "vcf_parse", [&](Arena &a) { return carve_vcf(a, n_tiles, n_strings, 0, c.io, c.af, caps.cap, caps.cap_defer, w); }))) return rc;
-    if ((rc = first_pass())) return rc;
-    uint32_t n_ends = 0;
-    if ((rc = read_back(ctx, &n_ends, w.tile_cnt + n_tiles, 4))) return rc;
-    if (n_ends > len) { ctx->err = "vcf_parse: the line ends' count leaves the text"; return CSV_EHIP; }
-    if (n_ends == UINT32_MAX) return bad(ctx, "2^32 lines or more");
-    const uint32_t n_slots = n_ends + 1;
-    // The per-line arrays behind the first carve's slices, which keep their contents unless the arena had to grow: a grown arena is a new
-    // allocation (possibly at the old address, so the pointer says nothing; the capacity rises with every growth) and they are made again.
-    const size_t cap_before = ctx->work.cap;
-    if ((rc = arena_reserve_for(ctx, ctx->work, "vcf_parse", [&](Arena &a) { return carve_vcf(a, n_tiles, n_strings, n_slots, c.io, c.af, caps.cap, caps.cap_defer, w); }))) return rc;
-    if (ctx->work.cap != cap_before && (rc = first_pass())) return rc;
+    uint32_t n_slots = 0;
+    if ((rc = count_lines(ctx, t, "vcf_parse", "vcf_parse: 2^32 lines or more", d_text, len, w,
+                          [&](Arena &a, uint64_t slots) { return carve_vcf(a, n_tiles, n_strings, slots, c.io, c.af, caps.cap, caps.cap_defer, w); },
+                          [&]() -> int {                 // the strings up, the line ends counted (the timer around the launch alone)
+                              const int rc2 = n_strings ? t.up(w.strings, strings.data(), n_strings) : (int)CSV_OK;
+                              if (rc2) return rc2;
+                              TimerScope ts(ctx, CSV_K_MISC);
+                              launch_vcf_count(s, d_text, len, w);
+                              return CSV_OK;
+                          }, n_slots))) return rc;
     VcfParseArgs a{};
     a.af = c.af; a.dp_int = c.dp_int != 0; a.ad_int = c.ad_int != 0;
     a.contig = w.strings; a.needle = w.strings + c.contig_len; a.contig_len = c.contig_len; a.needle_len = c.needle_len;
@@ -83,7 +93,7 @@ int run_parse(csv_ctx *ctx, const uint8_t *d_text, uint32_t len, const Call &c, 
         launch_vcf_parse(s, d_text, len, n_slots, a, 0, w);
     }
     VcfHead h;
-    if ((rc = read_back(ctx, &h, w.head, sizeof(VcfHead)))) return rc;
+    if ((rc = t.peek(&h, w.head, sizeof(VcfHead)))) return rc;
     cnt = csv_vcf_counts{};
     if (h.hash_off < (unsigned long long)h.stop_off) { cnt.status = (h.hash_off << 8) | CSV_VCF_HEADER_LINE; return 1; }
     if (h.n_kept > n_slots || h.n_defer > n_slots || h.n_lines > n_slots) { ctx->err = "vcf_parse: the counts leave the text"; return CSV_EHIP; }
@@ -107,16 +117,12 @@ int parse_dev(csv_ctx *ctx, const uint8_t *d_text, uint64_t len, const Call &c, 
     counts->stop_off = UINT64_MAX;
     if (len == 0) return CSV_OK;
     (void)hipSetDevice(ctx->device);
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "vcf_parse: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
+    Transfer t(ctx);
+    if ((rc = t.open("vcf_parse"))) return rc;
     VcfWs w;
     const VcfOut o{d_out->line_off, d_out->chrom_len, d_out->pos, d_out->value, d_out->defer_off};
-    rc = run_parse(ctx, d_text, (uint32_t)len, c, c.sorted_pos, &o, *d_out, *counts, w, e.ev, piece_no);
-    if (rc == CSV_OK) { CSV_HIP(ctx, wait_stream(ctx->stream)); }
-    if (rc == CSV_OK || rc == 1 || rc == CSV_ECAPACITY) e.done = true;          // (those ways out end behind a wait)
-    return rc;
+    rc = run_parse(ctx, t, d_text, (uint32_t)len, c, c.sorted_pos, &o, *d_out, *counts, w);
+    return rc == CSV_OK ? t.wait() : rc;                                  // (the caller's device arrays are complete on return)
 }
 
 int parse_host(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, const csv_vcf_out *out, csv_vcf_counts *counts)
@@ -128,26 +134,19 @@ int parse_host(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, c
     counts->stop_off = UINT64_MAX;
     if (len == 0) return CSV_OK;
     (void)hipSetDevice(ctx->device);
-    VcfTextWs t;
-    if ((rc = arena_reserve_for(ctx, ctx->arena, "vcf_parse", [&](Arena &a) { return carve_vcf_text(a, len, c.n, t); }))) return rc;
-    if ((rc = ensure_pinned(ctx, 2 * kPiece))) return rc;
-    Events e(ctx);
-    if (!e.ok()) { ctx->err = "vcf_parse: no event"; return CSV_EHIP; }
-    size_t piece_no = 0;
-    if ((rc = copy_up(ctx, t.text, text, len, e.ev, piece_no))) return rc;
-    if (c.n && (rc = copy_up(ctx, t.sorted_pos, c.sorted_pos, c.n * 4, e.ev, piece_no))) return rc;
+    VcfTextWs tw;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "vcf_parse", [&](Arena &a) { return carve_vcf_text(a, len, c.n, tw); }))) return rc;
+    Transfer t(ctx);
+    if ((rc = t.open("vcf_parse"))) return rc;
+    if ((rc = t.up(tw.text, text, len))) return rc;
+    if (c.n && (rc = t.up(tw.sorted_pos, c.sorted_pos, c.n * 4))) return rc;
     VcfWs w;
-    rc = run_parse(ctx, t.text, (uint32_t)len, c, t.sorted_pos, nullptr, *out, *counts, w, e.ev, piece_no);
-    if (rc == 1 || rc == CSV_ECAPACITY) e.done = true;
-    if (rc != CSV_OK) return rc;
+    if ((rc = run_parse(ctx, t, tw.text, (uint32_t)len, c, tw.sorted_pos, nullptr, *out, *counts, w))) return rc;
     const uint64_t k = counts->n_kept, d = counts->n_deferred;
-    auto down = [&](void *dst, const void *src, size_t n) { return n ? copy_down(ctx, dst, src, n, e.ev, Runs{{0, n}}) : (int)CSV_OK; };
-    if ((rc = down(out->line_off, w.out.line_off, k * 4)) || (rc = down(out->pos, w.out.pos, k * 4)) || (rc = down(out->value, w.out.value, k * 8)) ||
-        (rc = down(out->defer_off, w.out.defer_off, d * 4))) return rc;
-    if (!c.af && (rc = down(out->chrom_len, w.out.chrom_len, k * 4))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    e.done = true;
-    return CSV_OK;
+    if ((rc = t.down(out->line_off, w.out.line_off, k * 4)) || (rc = t.down(out->pos, w.out.pos, k * 4)) || (rc = t.down(out->value, w.out.value, k * 8)) ||
+        (rc = t.down(out->defer_off, w.out.defer_off, d * 4))) return rc;
+    if (!c.af && (rc = t.down(out->chrom_len, w.out.chrom_len, k * 4))) return rc;
+    return t.wait();
 }
 
 Call snp_call(int dp_int, int ad_int, bool io) { Call c; c.io = io; c.dp_int = dp_int; c.ad_int = ad_int; return c; }
