@@ -124,6 +124,11 @@ class csv_cn_regions(C.Structure):
                 ("snp_pfb", C.c_void_p)]
 
 
+class csv_cn_table_regions(C.Structure):
+    _fields_ = [("n_shards", C.c_int32), ("shards", C.c_void_p), ("tables", C.c_void_p), ("mean_cov", C.c_void_p), ("reg_off", C.c_void_p),
+                ("region_start", C.c_void_p), ("region_end", C.c_void_p), ("sample_size", C.c_void_p)]
+
+
 # every symbol include/csvgpu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 ABI = {
@@ -175,6 +180,15 @@ ABI = {
     "csvgpu_split_resident_fits": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(csv_split_refs), _P, C.c_double, C.c_int32, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_cn_observations_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_cn_decode_resident_many": (C.c_int, [_P, C.POINTER(csv_cn_regions), C.POINTER(csv_hmm), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_snp_table_create": (_P, [_P, _P, _P, _P, _P, C.c_uint64]),
+    "csvgpu_snp_table_create_hits": (_P, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64]),
+    "csvgpu_snp_table_create_dev": (_P, [_P, _P, _P, _P, _P, C.c_uint64]),
+    "csvgpu_snp_table_create_hits_dev": (_P, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64]),
+    "csvgpu_snp_table_free": (None, [_P, _P]),
+    "csvgpu_snp_table_size": (C.c_uint64, [_P]),
+    "csvgpu_snp_table_query": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_cn_observations_tables_many": (C.c_int, [_P, C.POINTER(csv_cn_table_regions), _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_cn_decode_tables_many": (C.c_int, [_P, C.POINTER(csv_cn_table_regions), C.POINTER(csv_hmm), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_bgzf_inflate": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "csvgpu_bgzf_inflate_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "csvgpu_bam_unpack": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(csv_bam_out),

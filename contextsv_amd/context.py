@@ -442,6 +442,140 @@ class Context:
             out.update(baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
         return out
 
+    # -------------------------------------------------------------------------------- resident SNP tables
+    def _snp_table(self, what, arrays, counts):
+        """arrays: (name, value or None, dtype) in the creator's order; all numpy / array-likes (the host form) or all device tensors."""
+        given = [a for _, a, _ in arrays if a is not None]
+        dev = bool(given) and all(hasattr(a, "is_cuda") for a in given)
+        if dev:
+            for name, a, dt in arrays:
+                if a is not None and not _is_dev(a, np.dtype(dt).itemsize):
+                    raise ValueError(f"{what}: {name} must be a contiguous device tensor of {np.dtype(dt).itemsize}-byte elements")
+            ptrs = [None if a is None or a.numel() == 0 else a.data_ptr() for _, a, _ in arrays]
+            lens = [None if a is None else a.numel() for _, a, _ in arrays]
+            keep = None
+        else:
+            keep = [None if a is None else np.ascontiguousarray(a, dt) for _, a, dt in arrays]
+            ptrs = [ptr(a) for a in keep]
+            lens = [None if a is None else len(a) for a in keep]
+        for (name, _, _), ln, want in zip(arrays, lens, counts):
+            if ln is not None and ln != lens[want]:
+                raise ValueError(f"{what}: {name} has {ln} entries, {arrays[want][0]} has {lens[want]}")
+        return dev, ptrs, lens, keep
+
+    def snp_table(self, pos, baf, pfb=None, has_pfb=None) -> "SnpTable":
+        """csvgpu_snp_table_create (numpy arrays) / _create_dev (device tensors): one contig's SNP records resident on the device, the
+        per-record kind — every member of a run of equal positions answers with the run's last baf and with the pfb of the run's last
+        record that has one (has_pfb), else 0.0. pos ascending (uint32), baf / pfb float64, has_pfb uint8."""
+        arrays = (("pos", pos, np.uint32), ("baf", baf, np.float64), ("pfb", pfb, np.float64), ("has_pfb", has_pfb, np.uint8))
+        dev, p, lens, keep = self._snp_table("snp_table", arrays, (0, 0, 0, 0))
+        fn = self.lib.csvgpu_snp_table_create_dev if dev else self.lib.csvgpu_snp_table_create
+        h = fn(self.h, p[0], p[1], p[2], p[3], lens[0])
+        if not h:
+            raise self._error(_lib.CSV_EINVAL)
+        return SnpTable(self, h)
+
+    def snp_table_hits(self, pos, baf, af_pos, af) -> "SnpTable":
+        """csvgpu_snp_table_create_hits / _hits_dev: the first-hit kind — a region's pfb comes from the first population record (af_pos
+        ascending, af) inside the span of the region's own records, for the records at that position; 0.0 for every other record."""
+        arrays = (("pos", pos, np.uint32), ("baf", baf, np.float64), ("af_pos", af_pos, np.uint32), ("af", af, np.float64))
+        dev, p, lens, keep = self._snp_table("snp_table_hits", arrays, (0, 0, 2, 2))
+        fn = self.lib.csvgpu_snp_table_create_hits_dev if dev else self.lib.csvgpu_snp_table_create_hits
+        h = fn(self.h, p[0], p[1], p[2], p[3], lens[0], lens[2])
+        if not h:
+            raise self._error(_lib.CSV_EINVAL)
+        return SnpTable(self, h)
+
+    def snp_table_query_raw(self, table: "SnpTable", region_start, region_end, snp_off, pos, baf, pfb, capacity: int):
+        """csvgpu_snp_table_query into the caller's arrays -> (status, n)."""
+        rs, re = np.ascontiguousarray(region_start, np.uint32), np.ascontiguousarray(region_end, np.uint32)
+        if len(rs) != len(re):
+            raise ValueError("snp_table_query: region_start and region_end differ in length")
+        n = C.c_uint64(capacity)
+        rc = self.lib.csvgpu_snp_table_query(self.h, table.h, ptr(rs), ptr(re), len(rs), ptr(snp_off), ptr(pos), ptr(baf), ptr(pfb), C.byref(n))
+        return rc, int(n.value)
+
+    def snp_table_query(self, table: "SnpTable", region_start, region_end) -> dict:
+        """What SNPSource::queryFlat appends for each region, back to back -> dict(snp_off, pos, baf, pfb): a first call sizes the arrays."""
+        R = len(region_start)
+        off = np.zeros(R + 1, np.uint64)
+        rc, n = self.snp_table_query_raw(table, region_start, region_end, off, None, None, None, 0)
+        if rc == _lib.CSV_ECAPACITY:
+            pos, baf, pfb = np.zeros(n, np.uint32), np.zeros(n, np.float64), np.zeros(n, np.float64)
+            rc, n = self.snp_table_query_raw(table, region_start, region_end, off, pos, baf, pfb, n)
+        else:
+            pos, baf, pfb = np.zeros(0, np.uint32), np.zeros(0, np.float64), np.zeros(0, np.float64)
+        self._check(rc)
+        return dict(snp_off=off, pos=pos, baf=baf, pfb=pfb)
+
+    @staticmethod
+    def _cn_table_regions(shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, what):
+        """csv_cn_table_regions over these arrays -> (struct, keep-alive tuple, R)."""
+        reg_off = np.ascontiguousarray(reg_off, np.uint64)
+        if len(reg_off) != len(shards) + 1 or len(mean_cov) != len(shards) or len(tables) != len(shards):
+            raise ValueError(what + ": reg_off needs one entry more than there are shards, mean_cov and tables one per shard")
+        rs, re = np.ascontiguousarray(region_start, np.uint32), np.ascontiguousarray(region_end, np.uint32)
+        ss = np.ascontiguousarray(sample_size, np.int32)
+        R = len(rs)
+        if not (len(re) == R and len(ss) == R):
+            raise ValueError(what + ": array lengths disagree")
+        if len(reg_off) and int(reg_off[-1]) != R:
+            raise ValueError(what + ": reg_off must end at the number of regions")
+        hs = (C.c_void_p * max(len(shards), 1))(*[s.h for s in shards])
+        ts = (C.c_void_p * max(len(tables), 1))(*[None if t is None else t.h for t in tables])
+        mc = np.ascontiguousarray(mean_cov, np.float64)
+        t = _lib.csv_cn_table_regions(len(shards), C.cast(hs, C.c_void_p), C.cast(ts, C.c_void_p), ptr(mc), ptr(reg_off), ptr(rs), ptr(re), ptr(ss))
+        return t, (hs, ts, mc, reg_off, rs, re, ss), R
+
+    def _cn_tables_call(self, R, capacity, decode, want_observations, call):
+        """The capacity handshake of the two calls: capacity None starts from 0, takes the bound the library answers and calls again."""
+        cap = 0 if capacity is None else capacity
+        while True:
+            m = max(cap, 1)
+            off = np.zeros(R + 1, np.uint64)
+            pos = np.zeros(m, np.uint32)
+            states, ll = (np.zeros(m, np.int32), np.zeros(max(R, 1), np.float64)) if decode else (None, None)
+            baf, pfb, l2 = ((np.zeros(m, np.float64) if want_observations else None) for _ in range(3))
+            snp = np.zeros(m, np.uint8) if want_observations else None
+            n = C.c_uint64(cap)
+            rc = call(off, pos, states, ll, baf, pfb, l2, snp, n)
+            if rc == 1:
+                return None
+            if rc == _lib.CSV_ECAPACITY:
+                if capacity is None and int(n.value) > cap:
+                    cap = int(n.value)
+                    continue
+                e = self._error(rc)
+                e.needed = int(n.value)
+                raise e
+            self._check(rc)
+            k = int(n.value)
+            out = dict(obs_off=off, pos=pos[:k].copy())
+            if decode:
+                out.update(states=states[:k].copy(), loglik=ll[:R].copy())
+            if want_observations:
+                out.update(baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
+            return out
+
+    def cn_observations_tables(self, shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, capacity: int | None = None):
+        """csvgpu_cn_observations_tables_many: cn_observations with the SNP records looked up on the device in tables[c] (a SnpTable of this
+        device per shard, None: no SNPs); sample_size[r] is the floor of region r's window count. -> the same dict, byte for byte; None when
+        the library declines (a region whose records call for more than 5087 windows: `last_error()` says why). capacity given and below
+        the bound (windows + 3 records): CsvError(CSV_ECAPACITY) with that bound in `needed`."""
+        t, keep, R = self._cn_table_regions(shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, "cn_observations_tables")
+        return self._cn_tables_call(R, capacity, False, True, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_observations_tables_many(
+            self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
+
+    def cn_decode_tables(self, hmm: csv_hmm, shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, want_observations: bool = False,
+                         capacity: int | None = None):
+        """csvgpu_cn_decode_tables_many: cn_decode on resident SNP tables -> the same dict, bit for bit; None when the library declines."""
+        t, keep, R = self._cn_table_regions(shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, "cn_decode_tables")
+        return self._cn_tables_call(R, capacity, True, want_observations, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_decode_tables_many(
+            self.h, C.byref(t), C.byref(hmm), ptr(off), ptr(pos), ptr(st), ptr(ll), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
+
+    def last_error(self) -> str:
+        return (self.lib.csvgpu_last_error(self.h) or b"").decode(errors="replace")
+
     # -------------------------------------------------------------------------------- BGZF members
     def bgzf_inflate(self, comp, blocks, out):
         """csvgpu_bgzf_inflate: the members `blocks` (_lib.BGZF_BLOCK_DTYPE records) of the compressed bytes `comp` (uint8) inflated on the
@@ -748,6 +882,19 @@ class Context:
         self._check(self.lib.csvgpu_alt_bases_resident(self.h, shard.h, ptr(read), ptr(qpos), ptr(off), len(read), ptr(out)))
         text = out.tobytes().decode("latin-1")
         return [text[int(off[i]): int(off[i + 1])] for i in range(len(read))]
+
+
+class SnpTable:
+    """One contig's SNP records resident on the device (csv_snp_table): immutable, readable from every Context of its device."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx, self.h = ctx, handle
+        self.n = int(ctx.lib.csvgpu_snp_table_size(handle))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.csvgpu_snp_table_free(self.ctx.h, self.h)
+            self.h = None
 
 
 class GenomeBuilder:

@@ -332,6 +332,126 @@ int cn_run(csv_ctx *ctx, const char *what, const csv_cn_regions *in, bool decode
     return CSV_OK;
 }
 
+// cn_run fed by resident SNP tables (kernels/snptable.hip): the record ranges, the window counts, the offset tables, the lists and the compact
+// records are made on the device; one readback of the plan's head sizes the rest. CSV_OK / 1 (declined, the reason in ctx->err) / CSV_E*.
+int cn_tables_run(csv_ctx *ctx, const char *what, const csv_cn_table_regions *in, bool decode, bool want_baf, bool want_pfb, bool want_l2, bool want_snp,
+                  uint64_t *n_obs, CnCall &c)
+{
+    auto bad = [&](const char *msg) { ctx->err = std::string(what) + ": " + msg; return (int)CSV_EINVAL; };
+    if (!in || !n_obs) return bad("null argument");
+    if (ctx->split_state) return bad("a split order is pending on this context");
+    if (in->n_shards < 0) return bad("negative shard count");
+    if (in->n_shards && (!in->shards || !in->mean_cov || !in->tables)) return bad("null array");
+    if (!in->reg_off || in->reg_off[0] != 0) return bad("reg_off missing or not starting at 0");
+    for (int s = 0; s < in->n_shards; s++) {
+        if (in->reg_off[s + 1] < in->reg_off[s]) return bad("reg_off not ascending");
+        if (in->reg_off[s + 1] > in->reg_off[s] && !in->shards[s]) return bad("null shard");
+        if (in->tables[s] && in->tables[s]->device != ctx->device) return bad("a table of another device");
+    }
+    const uint64_t R = in->n_shards ? in->reg_off[in->n_shards] : 0;
+    c.R = R; c.cap = *n_obs;
+    if (R == 0) return CSV_OK;
+    if (R >= 0xffffffffull) return bad("2^32 - 1 or more regions");
+    if (!in->region_start || !in->region_end || !in->sample_size) return bad("null array");
+    for (uint64_t r = 0; r < R; r++) {
+        if (in->sample_size[r] <= 0) return bad("sample_size <= 0");
+        if (in->region_start[r] > in->region_end[r]) return bad("region start > end");
+        if (in->region_end[r] >= 0x7fffffffu) return bad("a window coordinate could reach 2^31");
+        if ((uint32_t)in->sample_size[r] > CN_MAX_WINDOWS) return bad("more than 5087 windows in a region");
+    }
+    CnEpochs ep;
+    if (!cn_epochs(ep)) { ctx->err = std::string(what) + ": this C++ library's hash table does not grow as the kernels assume"; return CSV_EHIP; }
+
+    (void)hipSetDevice(ctx->device);
+    const uint64_t n_sh = (uint64_t)in->n_shards;
+    const CnUpLayout L(R, n_sh);
+    const size_t head_bytes = CN_PLAN_HEAD_BYTES + (n_sh + 1) * 4;
+    CnTabWs w;
+    int rc;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, 0, 0, decode, w); }))) return rc;
+    hipStream_t st = ctx->stream;
+    // what goes up: the regions, each region's shard, the tables as the kernels see them, the shards' first regions
+    auto fill_up = [&](char *h_up) {
+        memcpy(h_up + L.rs, in->region_start, R * 4);
+        memcpy(h_up + L.re, in->region_end, R * 4);
+        memcpy(h_up + L.ssf, in->sample_size, R * 4);
+        uint32_t *rsh = (uint32_t *)(h_up + L.rsh), *roff = (uint32_t *)(h_up + L.roff);
+        SnpTabDev *tabs = (SnpTabDev *)(h_up + L.tabs);
+        for (uint64_t s = 0; s < n_sh; s++) {
+            for (uint64_t r = in->reg_off[s]; r < in->reg_off[s + 1]; r++) rsh[r] = (uint32_t)s;
+            tabs[s] = snp_table_dev(in->tables[s]); roff[s] = (uint32_t)in->reg_off[s];
+        }
+        roff[n_sh] = (uint32_t)R;
+    };
+    auto queue_plan = [&](const char *h_up) -> int {
+        CSV_HIP(ctx, hipMemcpyAsync(w.up, h_up, L.bytes, hipMemcpyHostToDevice, st));
+        TimerScope ts(ctx, CSV_K_WINDOW);
+        launch_cn_plan(st, w.p, (uint32_t)R, (uint32_t)n_sh);
+        return CSV_OK;
+    };
+    std::vector<char> head(head_bytes);
+    {
+        PinStage pin(ctx);
+        char *h_up = nullptr, *h_head = nullptr;
+        if ((rc = pin_reserve_for(ctx, pin, [&](PinStage &p) { h_head = (char *)p.slot(head_bytes); h_up = (char *)p.slot(L.bytes); }))) return rc;
+        fill_up(h_up);
+        if ((rc = queue_plan(h_up))) return rc;
+        CSV_HIP(ctx, hipMemcpyAsync(h_head, w.p.head, head_bytes, hipMemcpyDeviceToHost, st));
+        CSV_HIP(ctx, wait_stream(st));
+        memcpy(head.data(), h_head, head_bytes);
+    }
+    const CnPlanHead h = *(const CnPlanHead *)head.data();
+    const uint32_t *shard_w0 = (const uint32_t *)(head.data() + CN_PLAN_HEAD_BYTES);
+    if (h.flags & CN_PLAN_OVER_WINDOWS) { ctx->err = std::string(what) + ": declined: a region's SNP records call for more than 5087 windows"; return 1; }
+    if (h.W + 3 * h.S >= 0xffffffffull) { ctx->err = std::string(what) + ": declined: 2^32 - 1 or more windows, records or observations"; return 1; }
+    const uint64_t W = h.W, S = h.S;
+    if ((uint64_t)h.n_small + h.n_big != R || shard_w0[n_sh] != W || shard_w0[0] != 0) { ctx->err = std::string(what) + ": the plan's totals disagree"; return CSV_EHIP; }
+    c.W = W; c.S = S; c.bound = W + 3 * S;
+    if (c.cap < c.bound) { *n_obs = c.bound; ctx->err = std::string(what) + ": capacity too small"; return CSV_ECAPACITY; }
+
+    // (a grown arena is a new allocation, possibly at the old address: the pointer says nothing, the capacity rises with every growth)
+    const size_t cap_before = ctx->arena.cap;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, W, S, decode, w); }))) return rc;
+    const uint64_t room = c.bound;                            // what can come back
+    char *h_up = nullptr;
+    uint64_t *h_total = nullptr;
+    c.pin = PinStage(ctx);
+    if ((rc = pin_reserve_for(ctx, c.pin, [&](PinStage &p) {
+            h_total = (uint64_t *)p.slot(256); h_up = (char *)p.slot(L.bytes);
+            c.h_off = p.slot((R + 1) * 8); c.h_pos = p.slot(room * 4);
+            if (want_baf) c.h_baf = p.slot(room * 8);
+            if (want_pfb) c.h_pfb = p.slot(room * 8);
+            if (want_l2) c.h_l2 = p.slot(room * 8);
+            if (want_snp) c.h_snp = p.slot(room);
+            if (decode) { c.h_states = p.slot(room * 4); c.h_ll = p.slot(R * 8); }
+        }))) return rc;
+    if (ctx->arena.cap != cap_before) {                       // the arena grew: the plan again, into the new one
+        fill_up(h_up);
+        if ((rc = queue_plan(h_up))) return rc;
+    }
+    c.w.o = w.o; c.w.states = w.states; c.w.loglik = w.loglik;
+    CSV_HIP(ctx, hipMemsetAsync(w.sl.tot, 0, (R + 1) * 4, st));
+    {
+        TimerScope ts(ctx, CSV_K_WINDOW);
+        for (uint64_t s = 0; s < n_sh; s++) {
+            const uint64_t r0 = in->reg_off[s], nr = in->reg_off[s + 1] - r0;
+            if (!nr) continue;
+            const uint64_t w0 = shard_w0[s], nw = shard_w0[s + 1] - shard_w0[s];
+            launch_window_log2(st, in->shards[s]->depth, in->shards[s]->depth_len, w.p.rs + r0, w.p.re + r0, w.p.ss + r0, w.p.wo + r0 + s, nr, nw, in->mean_cov[s],
+                               w.l2 + w0, w.ws + w0, w.we + w0);
+        }
+        launch_snp_gather(st, w.p, (uint32_t)R, (uint32_t)S, w.spos, w.sbaf, w.spfb);
+        launch_cn_order(st, w.ws, w.we, w.p.wbase, w.p.soff, w.spos, w.p.small, h.n_small, w.p.big, h.n_big, ep, w.sl);
+        launch_exclusive_sum_u32(st, w.sl.tot, R + 1, w.p.es_tmp);
+        launch_cn_fill(st, w.sl, (uint32_t)W, (uint32_t)R, w.sl.tot, w.ws, w.we, w.l2, w.spos, (const double *)w.sbaf, (const double *)w.spfb, w.o);
+    }
+    CSV_HIP(ctx, hipMemcpyAsync(h_total, w.o.obs_off + R, 8, hipMemcpyDeviceToHost, st));
+    CSV_HIP(ctx, wait_stream(st));
+    c.total = *h_total;
+    if (c.total > c.bound) { ctx->err = std::string(what) + ": more observations than the bound"; return CSV_EHIP; }
+    return CSV_OK;
+}
+
 // the answer's arrays to the page-locked block (queued; the caller waits and finishes)
 int cn_download(csv_ctx *ctx, CnCall &c, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp)
 {
@@ -364,6 +484,49 @@ int csvgpu_cn_observations_resident_many(csv_ctx *ctx, const csv_cn_regions *in,
     if (c.total > c.cap) { ctx->err = std::string(what) + ": capacity too small"; return CSV_ECAPACITY; }
     if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
     CSV_HIP(ctx, wait_stream(ctx->stream));
+    c.pin.finish();
+    return CSV_OK;
+}
+
+int csvgpu_cn_observations_tables_many(csv_ctx *ctx, const csv_cn_table_regions *in, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb,
+                                       double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
+{
+    if (!ctx) return CSV_EINVAL;
+    const char *what = "cn_observations_tables";
+    if (!obs_off) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
+    if (n_obs && *n_obs && (!pos || !baf || !pfb || !log2_cov || !is_snp)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
+    CnCall c;
+    int rc = cn_tables_run(ctx, what, in, false, true, true, true, true, n_obs, c);
+    if (rc) return rc;
+    *n_obs = c.total;
+    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
+    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
+    CSV_HIP(ctx, wait_stream(ctx->stream));
+    c.pin.finish();
+    return CSV_OK;
+}
+
+int csvgpu_cn_decode_tables_many(csv_ctx *ctx, const csv_cn_table_regions *in, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos, int32_t *states,
+                                 double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
+{
+    if (!ctx) return CSV_EINVAL;
+    const char *what = "cn_decode_tables";
+    if (!hmm) { ctx->err = std::string(what) + ": null hmm"; return CSV_EINVAL; }
+    if (!obs_off || !loglik) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
+    if (n_obs && *n_obs && (!pos || !states)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
+    CnCall c;
+    int rc = cn_tables_run(ctx, what, in, true, baf != nullptr, pfb != nullptr, log2_cov != nullptr, is_snp != nullptr, n_obs, c);
+    if (rc) return rc;
+    *n_obs = c.total;
+    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
+    if ((rc = csvgpu_viterbi_dev(ctx, hmm, c.w.o.log2_cov, c.w.o.baf, c.w.o.pfb, c.w.o.obs_off, c.R, c.total, c.w.states, c.w.loglik))) return rc;
+    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
+    hipStream_t st = ctx->stream;
+    CSV_HIP(ctx, hipMemcpyAsync(c.h_states, c.w.states, c.total * 4, hipMemcpyDeviceToHost, st));
+    CSV_HIP(ctx, hipMemcpyAsync(c.h_ll, c.w.loglik, c.R * 8, hipMemcpyDeviceToHost, st));
+    c.pin.outs.push_back(PinStage::Out{states, c.h_states, c.total * 4});
+    c.pin.outs.push_back(PinStage::Out{loglik, c.h_ll, c.R * 8});
+    CSV_HIP(ctx, wait_stream(st));
     c.pin.finish();
     return CSV_OK;
 }

@@ -164,6 +164,8 @@ int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32
 // shard.hip
 void shard_release(csv_shard *sh);                            // frees what the shard owns, and the shard
 csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh);         // the side arrays and the scan's split of a shard whose reads are in place; releases it on failure
+// snp_table.hip
+SnpTabDev snp_table_dev(const csv_snp_table *t);              // the table as the kernels see it (NULL or no records: all zero)
 // cluster.hip
 int check_dbscan_args(csv_ctx *ctx, double eps, int32_t min_pts, bool interval);
 // split_order.hip

@@ -102,6 +102,17 @@ struct csv_shard {
     uint64_t  n_seq = 0, n_name = 0;
 };
 
+// one contig's SNP records in device memory (csvgpu_snp_table_*): immutable once created, readable from every context of its device.
+// One block: pos u32[n] | baf f64[n] | pfb f64[n] (per-record kind) | af_pos u32[n_af] | af f64[n_af] (first-hit kind), each 256-byte aligned.
+struct csv_snp_table {
+    int       device = 0;
+    bool      hits = false;        // the first-hit kind
+    uint64_t  n = 0, n_af = 0;
+    char     *block = nullptr;
+    const uint32_t *pos = nullptr, *af_pos = nullptr;
+    const uint64_t *baf = nullptr, *pfb = nullptr, *af = nullptr;      // values as their bits
+};
+
 namespace csv {
 
 // device scalars written by the scan / depth kernels, read back once per chromosome
@@ -384,6 +395,39 @@ void launch_cn_order(hipStream_t s, const uint32_t *ws, const uint32_t *we, cons
                      const uint32_t *regions_small, uint32_t n_small, const uint32_t *regions_big, uint32_t n_big, const CnEpochs &ep, const CnSlots &out);
 void launch_cn_fill(hipStream_t s, const CnSlots &sl, uint32_t n_slots, uint32_t n_regions, const uint32_t *obs_off32, const uint32_t *ws, const uint32_t *we,
                     const double *l2, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const CnObs &o);
+// snptable.hip — one contig's SNP records resident in HBM (csv_snp_table), and what the copy-number pass derives from the regions' record
+// counts, on the device (csvgpu_snp_table_* / csvgpu_cn_*_tables_many). The per-region rules are snp_table_core.hpp's.
+struct SnpTabDev {                           // a table as the kernels see it (all zero: no records). Values as their bits.
+    const uint32_t *pos; const uint64_t *baf;            // [n] ascending; baf resolved per run
+    const uint64_t *pfb;                                  // [n] resolved per run (per-record kind), or null (first-hit kind)
+    const uint32_t *af_pos; const uint64_t *af;           // [n_af] ascending (first-hit kind)
+    uint32_t n, n_af;
+};
+enum : uint32_t { CN_PLAN_OVER_WINDOWS = 1 };             // CnPlanHead::flags: a region needs more than CN_MAX_WINDOWS windows
+struct CnPlanHead { unsigned long long W, S; uint32_t flags, n_small, n_big, pad; };      // zeroed by the caller; [n_shards + 1] first windows follow at byte 64
+constexpr size_t CN_PLAN_HEAD_BYTES = 64;
+struct CnPlan {                              // device arrays of R regions on n_shards tables, passed to the kernels by value
+    const uint32_t *rs, *re;                 // [R] the regions
+    const int32_t *ssf;                      // [R] the window count's floor (null: 1)
+    const uint32_t *rsh;                     // [R] the region's table (null: 0)
+    const SnpTabDev *tabs;                   // [n_shards]
+    const uint32_t *reg_off;                 // [n_shards + 1]
+    int32_t *ss;                             // [R] windows per region
+    uint64_t *wo;                            // [R + n_shards] window offsets relative to the region's shard (launch_window_log2)
+    uint32_t *wbase, *soff;                  // [R + 1] first window / first record of each region in the flat arrays
+    uint32_t *sfirst, *hit;                  // [R] first record in the table; the first-hit kind's AF record (snpcore::NO_HIT: none)
+    uint32_t *small, *big;                   // [R] the regions by kernel form (launch_cn_order), in no particular order
+    CnPlanHead *head; uint32_t *shard_w0;    // the readback: totals, flags, list lengths; [n_shards + 1] = wbase[reg_off[s]]
+    void *es_tmp;                            // exclusive_sum_tmp_bytes(R + 1)
+};
+// baf_out[i] = baf[last of i's run]; pfb_out[i] = pfb of the run's last flagged member, else 0.0 (pfb_out null: not wanted; has_pfb null: none
+// flagged; pfb null: 0.0). marks, pm: [n] int32; pm_tmp: prefix_max_tmp_bytes(n). Nothing for n == 0.
+void launch_snp_resolve(hipStream_t s, const uint32_t *pos, const uint64_t *baf, const uint64_t *pfb, const uint8_t *has_pfb, uint32_t n, int32_t *marks, int32_t *pm,
+                        void *pm_tmp, uint64_t *baf_out, uint64_t *pfb_out);
+// ranges, hits, window counts, the two exclusive sums, the per-shard offsets, the lists and the head (zeroed here). R >= 1.
+void launch_cn_plan(hipStream_t s, const CnPlan &p, uint32_t R, uint32_t n_shards);
+// the regions' resolved records into the compact layout launch_cn_order / launch_cn_fill read: [soff[r], soff[r + 1]) for region r
+void launch_snp_gather(hipStream_t s, const CnPlan &p, uint32_t R, uint32_t S, uint32_t *spos, uint64_t *sbaf, uint64_t *spfb);
 // inflate.hip — BGZF members (raw DEFLATE + CRC-32), one wave per member: status[i] = 0 decoded and written, 1 declined (nothing written);
 // *n_declined (zeroed by the caller) counts the declined ones
 void launch_bgzf_inflate(hipStream_t s, const uint8_t *comp, const csv_bgzf_block *blocks, uint32_t n_blocks, uint8_t *out, uint8_t *status,

@@ -21,12 +21,13 @@ SNPTable snp_table(const uint32_t *pos, const double *baf, const double *pfb, co
 
 static int cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out, const csv_hmm *hmm,
                          double mean_cov, int sample_size, uint32_t min_cnv, const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb,
-                         const uint8_t *snp_has_pfb, uint64_t n_snp, bool observations_on_device)
+                         const uint8_t *snp_has_pfb, uint64_t n_snp, bool observations_on_device, csv_snp_table *table = nullptr)
 {
     GUARD({
         csvhost::set_context(ctx);
         CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.min_cnv_length = min_cnv; cnv.device_observations = observations_on_device;
         SNPTable t = snp_table(snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp);
+        t.resident = table;                                  // borrowed: the caller's table of the same records
         CHMM h = chmm_from_pod(hmm);
         std::vector<SVCall> v; v.reserve(n);
         for (uint64_t i = 0; i < n; i++) v.push_back(from_pod(calls[i]));
@@ -37,6 +38,32 @@ static int cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call
             // alt_allele carries the id for untouched calls; calls whose ALT was rewritten report id -1 (and a symbol ALT)
             calls[i] = to_pod(v[i]);
         }
+    })
+}
+
+static int query_snp_regions(csv_ctx *ctx, csv_shard *shard, uint64_t n_regions, const uint32_t *start, const uint32_t *end, double mean_cov, int sample_size,
+                             const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp, int on_device,
+                             csv_snp_table *table, uint64_t *obs_off, uint32_t *pos_out, double *baf_out, double *pfb_out, double *log2_out, uint8_t *is_snp_out,
+                             uint64_t cap, uint64_t *n_out)
+{
+    GUARD({
+        CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.device_observations = on_device != 0;
+        SNPTable t = snp_table(snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp);
+        t.resident = table;                                  // borrowed (or none)
+        std::vector<std::pair<uint32_t, uint32_t>> regions;
+        for (uint64_t i = 0; i < n_regions; i++) regions.emplace_back(start[i], end[i]);
+        std::vector<SNPData> d;
+        cnv.querySNPRegions(regions, shard, mean_cov, t, d);
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < n_regions; i++) { obs_off[i] = total; total += d[i].pos.size(); }
+        obs_off[n_regions] = total;
+        *n_out = total;
+        if (total <= cap)
+            for (uint64_t i = 0; i < n_regions; i++)
+                for (size_t k = 0; k < d[i].pos.size(); k++) {
+                    const uint64_t at = obs_off[i] + k;
+                    pos_out[at] = d[i].pos[k]; baf_out[at] = d[i].baf[k]; pfb_out[at] = d[i].pfb[k]; log2_out[at] = d[i].log2_cov[k]; is_snp_out[at] = d[i].is_snp[k];
+                }
     })
 }
 
@@ -66,24 +93,8 @@ int csvhost_query_snp_regions(csv_ctx *ctx, csv_shard *shard, uint64_t n_regions
                               const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp, int on_device,
                               uint64_t *obs_off, uint32_t *pos_out, double *baf_out, double *pfb_out, double *log2_out, uint8_t *is_snp_out, uint64_t cap, uint64_t *n_out)
 {
-    GUARD({
-        CNVCaller cnv(ctx); cnv.sample_size = sample_size; cnv.device_observations = on_device != 0;
-        SNPTable t = snp_table(snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp);
-        std::vector<std::pair<uint32_t, uint32_t>> regions;
-        for (uint64_t i = 0; i < n_regions; i++) regions.emplace_back(start[i], end[i]);
-        std::vector<SNPData> d;
-        cnv.querySNPRegions(regions, shard, mean_cov, t, d);
-        uint64_t total = 0;
-        for (uint64_t i = 0; i < n_regions; i++) { obs_off[i] = total; total += d[i].pos.size(); }
-        obs_off[n_regions] = total;
-        *n_out = total;
-        if (total <= cap)
-            for (uint64_t i = 0; i < n_regions; i++)
-                for (size_t k = 0; k < d[i].pos.size(); k++) {
-                    const uint64_t at = obs_off[i] + k;
-                    pos_out[at] = d[i].pos[k]; baf_out[at] = d[i].baf[k]; pfb_out[at] = d[i].pfb[k]; log2_out[at] = d[i].log2_cov[k]; is_snp_out[at] = d[i].is_snp[k];
-                }
-    })
+    return query_snp_regions(ctx, shard, n_regions, start, end, mean_cov, sample_size, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp, on_device, nullptr, obs_off,
+                             pos_out, baf_out, pfb_out, log2_out, is_snp_out, cap, n_out);
 }
 
 // csvhost_cn_prediction with the observation vectors built on the device (observations_on_device != 0: CNVCaller::device_observations)
@@ -102,6 +113,35 @@ int csvhost_cn_prediction(csv_ctx *ctx, csv_shard *shard, int split, csvhost_cal
                           const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp)
 {
     return cn_prediction(ctx, shard, split, calls, n, cap, n_out, hmm, mean_cov, sample_size, min_cnv, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp, false);
+}
+
+// csvhost_cn_prediction_device with the SNPs looked up in `table` on the device (a csv_snp_table of the same records, the caller's to free;
+// NULL: as csvhost_cn_prediction_device). The arrays stay the route of a batch the device declines.
+int csvhost_cn_prediction_table(csv_ctx *ctx, csv_shard *shard, int split, csvhost_call *calls, uint64_t n, uint64_t cap, uint64_t *n_out,
+                                const csv_hmm *hmm, double mean_cov, int sample_size, uint32_t min_cnv,
+                                const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp,
+                                int observations_on_device, csv_snp_table *table)
+{
+    return cn_prediction(ctx, shard, split, calls, n, cap, n_out, hmm, mean_cov, sample_size, min_cnv, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp,
+                         observations_on_device != 0, table);
+}
+
+// csvhost_query_snp_regions with the SNPs looked up in `table` on the device (NULL: as csvhost_query_snp_regions)
+int csvhost_query_snp_regions_table(csv_ctx *ctx, csv_shard *shard, uint64_t n_regions, const uint32_t *start, const uint32_t *end, double mean_cov, int sample_size,
+                                    const uint32_t *snp_pos, const double *snp_baf, const double *snp_pfb, const uint8_t *snp_has_pfb, uint64_t n_snp, int on_device,
+                                    csv_snp_table *table, uint64_t *obs_off, uint32_t *pos_out, double *baf_out, double *pfb_out, double *log2_out,
+                                    uint8_t *is_snp_out, uint64_t cap, uint64_t *n_out)
+{
+    return query_snp_regions(ctx, shard, n_regions, start, end, mean_cov, sample_size, snp_pos, snp_baf, snp_pfb, snp_has_pfb, n_snp, on_device, table, obs_off,
+                             pos_out, baf_out, pfb_out, log2_out, is_snp_out, cap, n_out);
+}
+
+// The first capacity the next table call of the mirror starts from (0: none remembered); forget != 0 clears it afterwards (tests, measurements)
+uint64_t csvhost_cn_table_capacity_hint(int forget)
+{
+    const uint64_t h = CNVCaller::tableCapacityHint();
+    if (forget) CNVCaller::forgetTableCapacityHint();
+    return h;
 }
 
 // ---- HMM file + Viterbi seam

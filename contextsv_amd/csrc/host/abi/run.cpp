@@ -93,7 +93,7 @@ struct csvhost_genome {
         SNPTable snps;
     };
     std::vector<std::unique_ptr<Contig>> contigs;
-    ~csvhost_genome() { for (auto &c : contigs) if (c->shard) csvgpu_shard_free(c->ctx, c->shard); }
+    ~csvhost_genome() { for (auto &c : contigs) { c->snps.dropResident(); if (c->shard) csvgpu_shard_free(c->ctx, c->shard); } }
 };
 
 csvhost_genome *csvhost_genome_create(void) { return new csvhost_genome(); }
@@ -150,6 +150,18 @@ int csvhost_genome_add_synth(csvhost_genome *g, csv_ctx *ctx, const char *name, 
     if (with_snps) synth_snps(snp_seed, sh.depth_len - 1, sp, sb);
     const csv_reads r = sh.view();
     return csvhost_genome_add(g, ctx, name, global_tid, &r, sh.depth_len, sh.qname_id.data(), 1, sp.data(), sb.data(), nullptr, nullptr, sp.size());
+}
+
+// Opt-in: every contig's SNP table resident on its own context's device (on != 0: created, a refusal leaves that contig host-only; 0: freed).
+// While they are there the copy-number passes of csvhost_genome_run look the SNPs up on the device. Returns the number of resident tables.
+int csvhost_genome_snp_tables_resident(csvhost_genome *g, int on)
+{
+    int n = 0;
+    for (auto &c : g->contigs) {
+        if (!on) c->snps.dropResident();
+        else if (c->snps.resident || c->snps.makeResident(c->ctx)) n++;
+    }
+    return n;
 }
 
 uint64_t csvhost_genome_n_contigs(const csvhost_genome *g) { return g->contigs.size(); }

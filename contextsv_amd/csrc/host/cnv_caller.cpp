@@ -8,8 +8,11 @@
 
 #include <charconv>
 
+#include <atomic>
+
 #include "log.h"
 #include "par.h"
+#include "snp_io.h"
 #include "umap_order.h"
 
 namespace {
@@ -259,17 +262,160 @@ struct CNVCaller::DeviceObs {
     }
 };
 
+// ---- resident SNP tables -------------------------------------------------------------------------------------------------------------------
+namespace {
+std::atomic<bool> g_resident_refusal_logged{false};
+// The largest capacity a table call has asked for so far (its bound, windows + 3 x records, set when CSV_ECAPACITY came back): the next call's
+// first capacity, what g_result_hint is to the signatures. Only ever raised, so two passes on two threads cannot lower each other's value.
+std::atomic<uint64_t> g_cn_table_hint{0};
+void note_cn_table_capacity(uint64_t n)
+{
+    uint64_t h = g_cn_table_hint.load(std::memory_order_relaxed);
+    while (n > h && !g_cn_table_hint.compare_exchange_weak(h, n, std::memory_order_relaxed)) {}
+}
+
+csv_snp_table *resident_or_log(csv_ctx *ctx, csv_snp_table *t)
+{
+    if (!t && !g_resident_refusal_logged.exchange(true))
+        printMessage(std::string("SNP table stays on the host: ") + csvgpu_last_error(ctx));
+    return t;
+}
+}  // namespace
+
+uint64_t CNVCaller::tableCapacityHint() { return g_cn_table_hint.load(std::memory_order_relaxed); }
+void CNVCaller::forgetTableCapacityHint() { g_cn_table_hint.store(0, std::memory_order_relaxed); }
+
+bool SNPTable::makeResident(csv_ctx *ctx)
+{
+    dropResident();
+    resident = resident_or_log(ctx, csvgpu_snp_table_create(ctx, pos.data(), baf.data(), pfb.empty() ? nullptr : pfb.data(), has_pfb.empty() ? nullptr : has_pfb.data(), pos.size()));
+    resident_ctx = resident ? ctx : nullptr;
+    return resident != nullptr;
+}
+void SNPTable::dropResident()
+{
+    if (resident) csvgpu_snp_table_free(resident_ctx, resident);
+    resident = nullptr; resident_ctx = nullptr;
+}
+
+bool SNPFileTable::makeResident(csv_ctx *ctx)
+{
+    dropResident();
+    resident = resident_or_log(ctx, csvgpu_snp_table_create_hits(ctx, pos.data(), baf.data(), af_pos.data(), af.data(), pos.size(), af_pos.size()));
+    resident_ctx = resident ? ctx : nullptr;
+    return resident != nullptr;
+}
+void SNPFileTable::dropResident()
+{
+    if (resident) csvgpu_snp_table_free(resident_ctx, resident);
+    resident = nullptr; resident_ctx = nullptr;
+}
+
+// The regions' rows without a look at their SNPs: what finishWindows does, less the window counts (the device derives them)
+void CNVCaller::filterRegions(RegionBatch &B, bool log) const
+{
+    const size_t n = B.regions.size();
+    B.slot.assign(n, SIZE_MAX);
+    B.r_start.clear(); B.r_end.clear();
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t start_pos = B.regions[i].first, end_pos = B.regions[i].second;
+        if (start_pos > end_pos) {
+            if (log) printError("ERROR: Invalid SNP region for copy number prediction: " + std::to_string((int)start_pos) + "-" + std::to_string((int)end_pos));
+            continue;
+        }
+        B.slot[i] = B.r_start.size();
+        B.r_start.push_back(start_pos); B.r_end.push_back(end_pos);
+    }
+}
+
+bool CNVCaller::allResident(const std::vector<ContigJob> &jobs, const std::vector<RegionBatch> &batches)
+{
+    bool any = false;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        if (batches[j].regions.empty()) continue;
+        if (!jobs[j].snps || !jobs[j].snps->residentTable()) return false;
+        any = true;
+    }
+    return any;
+}
+
+// The tables of csv_cn_table_regions for the valid regions of some batches (row = the batches' slots, batch after batch), and what the two
+// table calls return for them. No SNP array: the device looks the records up.
+struct CNVCaller::TableObs {
+    std::vector<csv_shard *> shards;
+    std::vector<const csv_snp_table *> tabs;
+    std::vector<double> mean;
+    std::vector<uint64_t> reg_off{0};
+    std::vector<uint32_t> rs, re;
+    std::vector<int32_t> ss;
+    DeviceObs out;                             // the answer's vectors, as the device-observations route leaves them
+
+    // false: outside the table call's domain as far as the host can see — the caller takes the existing route
+    bool add(const RegionBatch &B, csv_shard *shard, const csv_snp_table *table, double mean_chr_cov, int sample_size)
+    {
+        if (sample_size <= 0 || sample_size > 5087) return false;
+        for (size_t k = 0; k < B.r_start.size(); k++) {
+            if (B.r_end[k] >= 0x7fffffffu) return false;
+            rs.push_back(B.r_start[k]); re.push_back(B.r_end[k]); ss.push_back(sample_size);
+        }
+        shards.push_back(shard); tabs.push_back(table); mean.push_back(mean_chr_cov); reg_off.push_back(rs.size());
+        return true;
+    }
+    // one call, again with the capacity the library asks for when the remembered one is too small; false: declined
+    bool run(csv_ctx *ctx, const CHMM *hmm, bool want_arrays)
+    {
+        const csv_cn_table_regions t{(int32_t)shards.size(), shards.data(), tabs.data(), mean.data(), reg_off.data(), rs.data(), re.data(), ss.data()};
+        const size_t R = rs.size();
+        csv_hmm pod{};
+        if (hmm) pod = to_pod(*hmm);
+        uint64_t cap = std::max<uint64_t>(g_cn_table_hint.load(), 1);
+        for (int attempt = 0; attempt < 2; attempt++) {
+            out.obs_off.assign(R + 1, 0); out.pos.resize(cap);
+            if (hmm) { out.states.resize(cap); out.ll.assign(R, 0.0); }
+            if (want_arrays) { out.baf.resize(cap); out.pfb.resize(cap); out.l2.resize(cap); out.is_snp.resize(cap); }
+            uint64_t n = cap;
+            double *const baf = want_arrays ? out.baf.data() : nullptr, *const pfb = want_arrays ? out.pfb.data() : nullptr, *const l2 = want_arrays ? out.l2.data() : nullptr;
+            uint8_t *const is_snp = want_arrays ? out.is_snp.data() : nullptr;
+            const int rc = hmm ? csvgpu_cn_decode_tables_many(ctx, &t, &pod, out.obs_off.data(), out.pos.data(), out.states.data(), out.ll.data(), baf, pfb, l2, is_snp, &n)
+                               : csvgpu_cn_observations_tables_many(ctx, &t, out.obs_off.data(), out.pos.data(), baf, pfb, l2, is_snp, &n);
+            if (rc == 1) return false;
+            if (rc == CSV_ECAPACITY && attempt == 0) { cap = n; note_cn_table_capacity(n); continue; }
+            check(ctx, rc, "copy-number observations (resident SNP tables)");
+            return true;
+        }
+        return false;
+    }
+};
+
 // querySNPRegions and runViterbi of `regions` in one device call; false (nothing done) where the batch is outside its domain. data[i] is
 // filled only with want_arrays; predictions[i] always (an invalid region: empty path, as runViterbi gives it).
 bool CNVCaller::decodeRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov, const SNPSource &snps,
-                              const CHMM &hmm, bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions) const
+                              const CHMM &hmm, bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions,
+                              bool *table_declined) const
 {
     RegionBatch B;
     B.regions = regions;
-    prepareWindows(B, snps);
     DeviceObs D;
-    if (!D.add(B, shard, mean_chr_cov)) return false;
-    if (!D.rs.empty()) D.decode(ctx, hmm, want_arrays);
+    bool done = false;
+    if (const csv_snp_table *table = snps.residentTable()) {                 // the SNPs looked up on the device: no query here
+        TableObs T;
+        filterRegions(B, false);
+        if (T.add(B, shard, table, mean_chr_cov, sample_size) && (T.rs.empty() || T.run(ctx, &hmm, want_arrays))) {
+            filterRegions(B, true);
+            D = std::move(T.out);
+            done = true;
+        } else {
+            B = RegionBatch();
+            B.regions = regions;
+            if (table_declined) *table_declined = true;
+            if (!device_observations) return false;
+        }
+    }
+    if (!done) {
+        prepareWindows(B, snps);
+        if (!D.add(B, shard, mean_chr_cov)) return false;
+        if (!D.rs.empty()) D.decode(ctx, hmm, want_arrays);
+    }
     data.assign(regions.size(), SNPData());
     predictions.assign(regions.size(), std::make_pair(std::vector<int>(), -100000000000.0));      // T = 0: testVit_CHMM's -VITHUGE
     for (size_t i = 0; i < regions.size(); i++) {
@@ -282,10 +428,22 @@ bool CNVCaller::decodeRegions(const std::vector<std::pair<uint32_t, uint32_t>> &
 }
 
 void CNVCaller::querySNPRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov,
-                                const SNPSource &snps, std::vector<SNPData> &out) const
+                                const SNPSource &snps, std::vector<SNPData> &out, bool try_table) const
 {
     RegionBatch B;
     B.regions = regions;
+    if (const csv_snp_table *table = try_table ? snps.residentTable() : nullptr) {                 // the SNPs looked up on the device: no query here
+        TableObs T;
+        filterRegions(B, false);
+        if (T.add(B, shard, table, mean_chr_cov, sample_size) && (T.rs.empty() || T.run(ctx, nullptr, true))) {
+            filterRegions(B, true);
+            out.assign(regions.size(), SNPData());
+            for (size_t i = 0; i < regions.size(); i++) if (B.slot[i] != SIZE_MAX) T.out.toSNPData(B.slot[i], out[i]);
+            return;
+        }
+        B = RegionBatch();
+        B.regions = regions;
+    }
     prepareWindows(B, snps);
     if (device_observations) {
         DeviceObs D;
@@ -341,6 +499,29 @@ struct CNVCaller::GenomeObs {
 
 void CNVCaller::observeAndDecode(std::vector<RegionBatch> &batches, const std::vector<ContigJob> &jobs, const CHMM &hmm, GenomeObs &G) const
 {
+    if (allResident(jobs, batches)) {
+        // every job's SNPs are resident: one decode call looks them up on the device; row q of its tables is candidate q
+        csvhost::TraceScope tr("cn: decode on resident tables");
+        TableObs T;
+        bool ok = true;
+        for (size_t j = 0; j < jobs.size() && ok; j++) {
+            if (batches[j].regions.empty()) continue;
+            filterRegions(batches[j], false);
+            if (!batches[j].r_start.empty()) ok = T.add(batches[j], jobs[j].shard, jobs[j].snps->residentTable(), jobs[j].mean_chr_cov, sample_size);
+        }
+        const size_t nq = G.cands.size();
+        if (ok && T.rs.size() == nq && T.run(ctx, &hmm, false)) {
+            for (size_t j = 0; j < jobs.size(); j++) if (!batches[j].regions.empty()) filterRegions(batches[j], true);
+            G.chunks.assign((nq + kChunk - 1) / kChunk, ObsChunk());
+            G.on_device = true;
+            G.seq_off = std::move(T.out.obs_off); G.dev_pos = std::move(T.out.pos); G.ll = std::move(T.out.ll);
+            G.states.assign(T.out.states.begin(), T.out.states.begin() + (std::ptrdiff_t)G.seq_off[nq]);
+            for (size_t q = 0; q < nq; q++)
+                if (G.len(q) == 0) printError("ERROR: No SNP data found for Viterbi algorithm.");
+            return;
+        }
+        for (RegionBatch &B : batches) { B.r_start.clear(); B.r_end.clear(); B.slot.clear(); }      // declined: the whole batch takes the route below
+    }
     {
         csvhost::TraceScope tr("cn: snp queries");
         // the chunks of ALL contigs as one parallel section (24 sections of a few chunks each left most of the pool idle)
@@ -532,8 +713,9 @@ void CNVCaller::runCopyNumberPredictions(const std::string &chr, const CHMM &hmm
     }
     std::vector<SNPData> data;
     std::vector<std::pair<std::vector<int>, double>> pred;
-    if (!device_observations || !decodeRegions(batch, shard, mean_chr_cov, snps, hmm, save_cnv_data, data, pred)) {
-        querySNPRegions(batch, shard, mean_chr_cov, snps, data);
+    bool table_declined = false;                                          // (a declined batch is not offered to the device a second time)
+    if (!(device_observations || snps.residentTable()) || !decodeRegions(batch, shard, mean_chr_cov, snps, hmm, save_cnv_data, data, pred, &table_declined)) {
+        querySNPRegions(batch, shard, mean_chr_cov, snps, data, !table_declined);
         std::vector<SNPData> sv_data(data.begin(), data.begin() + (std::ptrdiff_t)nv);
         runViterbi(hmm, sv_data, pred);
     }

@@ -38,6 +38,9 @@ struct SNPSource {
     // value snp_baf[pos] / snp_pfb[pos] would hold after query() (pfb: 0.0 where the map has no entry). Default: through query().
     virtual void queryFlat(uint32_t start_pos, uint32_t end_pos, std::vector<uint32_t> &snp_pos, std::vector<double> &baf_at,
                            std::vector<double> &pfb_at) const;
+    // The same records resident on the device (csvgpu_snp_table_*), or nullptr: a source that has one lets CNVCaller look the SNPs up there
+    // (csvgpu_cn_decode_tables_many / csvgpu_cn_observations_tables_many) instead of running queryFlat per region.
+    virtual const csv_snp_table *residentTable() const { return nullptr; }
 };
 
 // SNPs of one chromosome held in sorted arrays (the one-time-per-chromosome load the reference lacks).
@@ -50,6 +53,13 @@ struct SNPTable : SNPSource {
                std::unordered_map<uint32_t, double> &snp_pfb) const override;
     void queryFlat(uint32_t start_pos, uint32_t end_pos, std::vector<uint32_t> &snp_pos, std::vector<double> &baf_at,
                    std::vector<double> &pfb_at) const override;
+    // Opt-in: the table on ctx's device (the per-record kind). A creation the device refuses (positions not ascending, no memory) leaves the
+    // source host-only: logged once, not an error -> false. The table is the owner's to drop: copies of this struct only borrow it.
+    bool makeResident(csv_ctx *ctx);
+    void dropResident();
+    const csv_snp_table *residentTable() const override { return resident; }
+    csv_snp_table *resident = nullptr;
+    csv_ctx *resident_ctx = nullptr;
 };
 
 class CNVCaller {
@@ -63,8 +73,9 @@ public:
     static Genotype getGenotypeFromCNState(int cn_state);   // cnv_caller.h:76-97 of the reference
 
     // querySNPRegion for many regions at once (one window launch); out[i] belongs to regions[i].
+    // try_table false: the source's resident table (below) is not used, e.g. for a batch the device has just declined
     void querySNPRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov,
-                         const SNPSource &snps, std::vector<SNPData> &out) const;
+                         const SNPSource &snps, std::vector<SNPData> &out, bool try_table = true) const;
 
     // runViterbi for many SNPData at once (one Viterbi launch)
     void runViterbi(const CHMM &hmm, const std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions) const;
@@ -105,6 +116,12 @@ public:
     // votes stay on the pool. A batch outside that call's domain (an unsorted SNPSource, a region of more than 5087 windows, an end at or
     // above 2^31 - 1) takes the host route, whole. Same results either way.
     bool device_observations = false;
+    // The first capacity of the next table call (process-wide: the largest bound a table call has asked for), and a way to forget it
+    static uint64_t tableCapacityHint();
+    static void forgetTableCapacityHint();
+    // Whatever device_observations says, a call in which every job that has regions also has a resident SNP table (SNPSource::residentTable)
+    // takes the table route: no SNP query on the host, one csvgpu_cn_*_tables_many call per batch. A batch the device declines (a region whose
+    // records call for more than 5087 windows) or the host can see to be outside that call's domain takes the route above, whole.
 
     // sv_caller.cpp:983-1064 — the five-way update / duplicate rule for split-read candidates
     void runSplitReadCopyNumberPredictions(const std::string &chr, std::vector<SVCall> &split_sv_calls, const CHMM &hmm,
@@ -117,8 +134,12 @@ private:
     struct ObsChunk;
     struct GenomeObs;
     struct DeviceObs;
+    struct TableObs;
+    static bool allResident(const std::vector<ContigJob> &jobs, const std::vector<RegionBatch> &batches);
+    void filterRegions(RegionBatch &B, bool log) const;
     bool decodeRegions(const std::vector<std::pair<uint32_t, uint32_t>> &regions, csv_shard *shard, double mean_chr_cov, const SNPSource &snps, const CHMM &hmm,
-                       bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions) const;
+                       bool want_arrays, std::vector<SNPData> &data, std::vector<std::pair<std::vector<int>, double>> &predictions,
+                       bool *table_declined = nullptr) const;
     void prepareWindows(RegionBatch &B, const SNPSource &snps) const;
     void queryChunk(RegionBatch &B, const SNPSource &snps, size_t c) const;
     void finishWindows(RegionBatch &B) const;

@@ -68,6 +68,12 @@ struct SNPFileTable : SNPSource {
     std::vector<double> af;
     void query(uint32_t start_pos, uint32_t end_pos, std::vector<uint32_t> &snp_pos, std::unordered_map<uint32_t, double> &snp_baf,
                std::unordered_map<uint32_t, double> &snp_pfb) const override;
+    // Opt-in: the table on ctx's device (the first-hit kind), as SNPTable::makeResident. Nothing in runBam creates one yet.
+    bool makeResident(csv_ctx *ctx);
+    void dropResident();
+    const csv_snp_table *residentTable() const override { return resident; }
+    csv_snp_table *resident = nullptr;
+    csv_ctx *resident_ctx = nullptr;
 };
 
 // The sample's SNP VCF parsed once for every contig; population frequencies attached per contig on request.

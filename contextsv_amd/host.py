@@ -80,6 +80,13 @@ def load() -> C.CDLL:
                                               _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_cn_prediction_device.argtypes = [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_lib.csv_hmm),
                                                  C.c_double, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_int]
+    lib.csvhost_cn_prediction_table.argtypes = [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(_lib.csv_hmm),
+                                                C.c_double, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_int, _P]
+    lib.csvhost_query_snp_regions_table.argtypes = [_P, _P, C.c_uint64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, C.c_uint64, C.c_int, _P,
+                                                    _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.csvhost_genome_snp_tables_resident.argtypes = [_P, C.c_int]
+    lib.csvhost_cn_table_capacity_hint.restype = C.c_uint64
+    lib.csvhost_cn_table_capacity_hint.argtypes = [C.c_int]
     lib.csvhost_split_signatures.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_opts.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_split_signatures_dev.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -389,6 +396,12 @@ class Genome:
             return out[: k.value].copy(), tid[: k.value].copy(), st, list(cs)[:n]
         return out[: k.value], tid[: k.value], st, list(cs)[:n]
 
+    def snp_tables_resident(self, on: bool = True) -> int:
+        """Opt-in: every staged contig's SNP table resident on its context's device (csvgpu_snp_table_create); run() then looks the SNPs of
+        the copy-number passes up there instead of querying them on the host — same calls. on=False frees the tables (free() does too).
+        -> the number of resident tables (a contig whose table the device refuses stays on the host route)."""
+        return int(load().csvhost_genome_snp_tables_resident(self.h, int(bool(on))))
+
     def free(self):
         if self.h:
             load().csvhost_genome_free(self.h)
@@ -517,11 +530,18 @@ def query_snp_region(ctx: Context, shard: Shard, start: int, end: int, mean_cov:
     return {"pos": o_pos[:k], "baf": o_baf[:k], "pfb": o_pfb[:k], "log2_cov": o_l2[:k], "is_snp": o_is[:k].astype(bool)}
 
 
+def cn_table_capacity_hint(forget: bool = False) -> int:
+    """The capacity the mirror's next resident-SNP-table call starts from (the largest bound a table call has asked for; 0: none yet).
+    forget=True clears it afterwards: the next call then finds its capacity with one CSV_ECAPACITY round."""
+    return int(load().csvhost_cn_table_capacity_hint(int(bool(forget))))
+
+
 def query_snp_regions(ctx: Context, shard: Shard, starts, ends, mean_cov: float, sample_size: int, snps: dict, on_device: bool = False,
-                      cap: int | None = None) -> dict:
+                      cap: int | None = None, snp_table=None) -> dict:
     """CNVCaller::querySNPRegions mirror: many regions of one shard in one batch -> dict(obs_off, pos, baf, pfb, log2_cov, is_snp), region i
     at [obs_off[i], obs_off[i + 1]). on_device: the observation vectors from csvgpu_cn_observations_resident_many instead of the window
-    launch and the host's assembly (same arrays; a batch outside that call's domain takes the host route)."""
+    launch and the host's assembly (same arrays; a batch outside that call's domain takes the host route). snp_table: a Context.snp_table of
+    the same records — the SNPs are then looked up on the device (csvgpu_cn_observations_tables_many), whatever on_device says."""
     pos, baf, pfb, has = _snp_arrays(snps)
     st, en = np.ascontiguousarray(starts, np.uint32), np.ascontiguousarray(ends, np.uint32)
     if len(st) != len(en):
@@ -532,27 +552,36 @@ def query_snp_regions(ctx: Context, shard: Shard, starts, ends, mean_cov: float,
     off = np.zeros(len(st) + 1, np.uint64)
     o_pos = np.zeros(cap, np.uint32); o_baf = np.zeros(cap); o_pfb = np.zeros(cap); o_l2 = np.zeros(cap); o_is = np.zeros(cap, np.uint8)
     n = C.c_uint64(0)
-    _check(load().csvhost_query_snp_regions(ctx.h, shard.h, len(st), st.ctypes.data, en.ctypes.data, mean_cov, sample_size, pos.ctypes.data, baf.ctypes.data,
-                                            pfb.ctypes.data, has.ctypes.data, len(pos), int(bool(on_device)), off.ctypes.data, o_pos.ctypes.data,
-                                            o_baf.ctypes.data, o_pfb.ctypes.data, o_l2.ctypes.data, o_is.ctypes.data, cap, C.byref(n)))
+    head = (ctx.h, shard.h, len(st), st.ctypes.data, en.ctypes.data, mean_cov, sample_size, pos.ctypes.data, baf.ctypes.data, pfb.ctypes.data, has.ctypes.data,
+            len(pos), int(bool(on_device)))
+    tail = (off.ctypes.data, o_pos.ctypes.data, o_baf.ctypes.data, o_pfb.ctypes.data, o_l2.ctypes.data, o_is.ctypes.data, cap, C.byref(n))
+    if snp_table is not None:
+        _check(load().csvhost_query_snp_regions_table(*head, snp_table.h, *tail))
+    else:
+        _check(load().csvhost_query_snp_regions(*head, *tail))
     k = n.value
     if k > cap:
-        return query_snp_regions(ctx, shard, starts, ends, mean_cov, sample_size, snps, on_device, cap=int(k))
+        return query_snp_regions(ctx, shard, starts, ends, mean_cov, sample_size, snps, on_device, cap=int(k), snp_table=snp_table)
     return {"obs_off": off, "pos": o_pos[:k].copy(), "baf": o_baf[:k].copy(), "pfb": o_pfb[:k].copy(), "log2_cov": o_l2[:k].copy(), "is_snp": o_is[:k].astype(bool)}
 
 
 def cn_prediction(ctx: Context, shard: Shard, calls: np.ndarray, hmm, mean_cov: float, snps: dict, split: bool, sample_size: int = 20,
-                  min_cnv: int = 2000, observations_on_device: bool = False) -> np.ndarray:
+                  min_cnv: int = 2000, observations_on_device: bool = False, snp_table=None) -> np.ndarray:
     """runCIGARCopyNumberPrediction (split=False) / runSplitReadCopyNumberPredictions (split=True) mirror. observations_on_device:
-    CNVCaller::device_observations (the observation vectors built and decoded on the device; same calls)."""
+    CNVCaller::device_observations (the observation vectors built and decoded on the device; same calls). snp_table: a Context.snp_table
+    of the same records — the SNPs are then looked up on the device (csvgpu_cn_decode_tables_many); a batch it declines takes the route the
+    other options select."""
     pos, baf, pfb, has = _snp_arrays(snps)
     cap = 2 * len(calls) + 16
     buf = np.zeros(cap, CALL_DTYPE)
     buf[: len(calls)] = np.ascontiguousarray(calls, CALL_DTYPE)
     n = C.c_uint64(0)
-    _check(load().csvhost_cn_prediction_device(ctx.h, shard.h, int(split), buf.ctypes.data, len(calls), cap, C.byref(n), C.byref(hmm), mean_cov,
-                                               sample_size, min_cnv, pos.ctypes.data, baf.ctypes.data, pfb.ctypes.data, has.ctypes.data, len(pos),
-                                               int(bool(observations_on_device))))
+    args = (ctx.h, shard.h, int(split), buf.ctypes.data, len(calls), cap, C.byref(n), C.byref(hmm), mean_cov, sample_size, min_cnv, pos.ctypes.data,
+            baf.ctypes.data, pfb.ctypes.data, has.ctypes.data, len(pos), int(bool(observations_on_device)))
+    if snp_table is not None:
+        _check(load().csvhost_cn_prediction_table(*args, snp_table.h))
+    else:
+        _check(load().csvhost_cn_prediction_device(*args))
     return buf[: n.value].copy()
 
 

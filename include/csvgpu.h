@@ -496,6 +496,64 @@ int csvgpu_cn_observations_resident_many(csv_ctx *ctx, const csv_cn_regions *reg
 int csvgpu_cn_decode_resident_many(csv_ctx *ctx, const csv_cn_regions *regions, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos,
                                    int32_t *states, double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Resident SNP tables (opt-in: the copy-number pass looks its SNPs up on the device; kernels/snptable.hip, the rules in
+ * contextsv_amd/csrc/snp_table_core.hpp). A csv_snp_table holds one contig's records in device memory. It is immutable once created; any
+ * context of the same device may read it, several at a time. The creators wait for their own kernels before they return; NULL on failure
+ * (csvgpu_last_error). Values are copied as bits: a NaN stays that NaN. n == 0 is a valid table.
+ * NULL with a message: positions not ascending (checked on the device; the host forms tolerate disorder by scanning, which is outside the
+ * device's domain), n or n_af at or above 2^32 - 1, a null array with a count, no memory.
+ * What a region [start, end] yields: the records from lower_bound(pos, start) up to the first pos > end, every member of a run of equal
+ * positions with the baf of the run's last member (SNPSource::queryFlat, the values the reference's hash maps hold). */
+typedef struct csv_snp_table csv_snp_table;
+/* The per-record kind (the host mirror's SNPTable): every member of a run carries the pfb of the run's last member with has_pfb, or 0.0 if
+ * the run has none. pfb NULL: 0.0 everywhere; has_pfb NULL: no record has one. */
+csv_snp_table *csvgpu_snp_table_create(csv_ctx *ctx, const uint32_t *pos, const double *baf, const double *pfb, const uint8_t *has_pfb, uint64_t n);
+/* The first-hit kind (the host mirror's SNPFileTable): pfb is decided per region. With lo / hi the first and last position of the region's
+ * records and g = lower_bound(af_pos, lo): if g < n_af and af_pos[g] <= hi, every record with pos == af_pos[g] gets af[g]; all others 0.0. */
+csv_snp_table *csvgpu_snp_table_create_hits(csv_ctx *ctx, const uint32_t *pos, const double *baf, const uint32_t *af_pos, const double *af,
+                                            uint64_t n, uint64_t n_af);
+/* The same from device arrays (what csvgpu_vcf_snp_parse_dev leaves, cut to one contig), copied device to device. */
+csv_snp_table *csvgpu_snp_table_create_dev(csv_ctx *ctx, const uint32_t *d_pos, const double *d_baf, const double *d_pfb, const uint8_t *d_has_pfb,
+                                           uint64_t n);
+csv_snp_table *csvgpu_snp_table_create_hits_dev(csv_ctx *ctx, const uint32_t *d_pos, const double *d_baf, const uint32_t *d_af_pos,
+                                                const double *d_af, uint64_t n, uint64_t n_af);
+/* Waits for ctx's stream, then frees; the caller sees to it that no other context still reads the table. */
+void csvgpu_snp_table_free(csv_ctx *ctx, csv_snp_table *table);
+uint64_t csvgpu_snp_table_size(const csv_snp_table *table);      /* n; 0 for NULL */
+/* The seam for tests and integrators: what queryFlat would append for each of R regions, back to back: region r at
+ * [snp_off[r], snp_off[r + 1]) of pos / baf / pfb; a region with start > end yields nothing. *n: in, the capacity of the three arrays in
+ * records; out, the exact count. CSV_ECAPACITY (*n set, nothing written, snp_off included): the capacity is too small. CSV_EINVAL: a null
+ * array, a table of another device, 2^32 - 1 or more regions or records. */
+int csvgpu_snp_table_query(csv_ctx *ctx, const csv_snp_table *table, const uint32_t *region_start, const uint32_t *region_end, uint64_t n_regions,
+                           uint64_t *snp_off, uint32_t *pos, double *baf, double *pfb, uint64_t *n);
+
+/* csv_cn_regions without the SNP arrays: tables[c] is shard c's table (NULL: no SNPs), sample_size[r] the floor of region r's window count
+ * (it has max(sample_size[r], its records) windows). */
+typedef struct csv_cn_table_regions {
+    int32_t n_shards;
+    csv_shard *const *shards;     /* [n_shards] */
+    const csv_snp_table *const *tables;          /* [n_shards] */
+    const double   *mean_cov;     /* [n_shards] */
+    const uint64_t *reg_off;      /* [n_shards + 1], reg_off[0] == 0; R = reg_off[n_shards] */
+    const uint32_t *region_start, *region_end;   /* [R] */
+    const int32_t  *sample_size;  /* [R] */
+} csv_cn_table_regions;
+/* The twins of csvgpu_cn_observations_resident_many / csvgpu_cn_decode_resident_many: byte for byte what those return when they are fed
+ * the host's queryFlat arrays for the same regions, with no SNP array going up. The record ranges, the window counts, every offset table,
+ * the lists of the two kernel forms and the regions' records in the compact layout are made on the device; one small readback (windows W,
+ * records S, per-shard window totals, the decline flag) sizes the workspace and the window launches.
+ * *n_obs: in, the capacity; out on CSV_OK, the exact count. A capacity below W + 3 S returns CSV_ECAPACITY right after that readback with
+ * *n_obs = W + 3 S, which is always enough, and nothing else is launched.
+ * Returns 1 = declined, nothing written, the reason in csvgpu_last_error — what only the device can know: a region whose records call for
+ * more than 5087 windows, 2^32 - 1 or more windows, records or observations in all. CSV_EINVAL as above for what the host can see (null
+ * arrays, reg_off, sample_size <= 0 or above 5087, start > end, an end at or above 2^31 - 1, a pending split order) and for a table of
+ * another device. */
+int csvgpu_cn_observations_tables_many(csv_ctx *ctx, const csv_cn_table_regions *regions, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb,
+                                       double *log2_cov, uint8_t *is_snp, uint64_t *n_obs);
+int csvgpu_cn_decode_tables_many(csv_ctx *ctx, const csv_cn_table_regions *regions, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos,
+                                 int32_t *states, double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs);
+
 /* depth_out[i] = depth[pos[i]] on the depth map resident in `shard`, or -1 where pos[i] >= depth_len: the VCF writer's
  * SUPPORT / DP lookups (SVCaller::getReadDepth, sv_caller.cpp:1332-1344, called at :1306) without moving the map. */
 int csvgpu_depth_lookup_resident(csv_ctx *ctx, csv_shard *shard, const uint32_t *pos, uint64_t n, int32_t *depth_out);

@@ -110,6 +110,20 @@ int main()
                     return true;
                 });
             }
+            for (int dec : {0, 1}) {   // n regions, m windows (0: the first carve); shards and SNP records run along. The second carve must leave the first one's slices where they were
+                CnTabWs w, w0;
+                const uint64_t n_sh = n % 5 + 1, S = m ? (n + m) % 1009 : 0;
+                Arena p0 = arena_plan();
+                (void)carve_cn_tables(p0, n, n_sh, 0, 0, dec != 0, w0);
+                run_case(tag("cn_tables", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_tables(a, n, n_sh, m, S, dec != 0, w); }, [&](char *lo, char *) {
+                    const CnUpLayout L(n, n_sh);
+                    const size_t at[] = {L.rs, L.re, L.ssf, L.rsh, L.tabs, L.roff, L.bytes};
+                    const size_t need[] = {n * 4, n * 4, n * 4, n * 4, n_sh * sizeof(SnpTabDev), (n_sh + 1) * 4};
+                    for (int i = 0; i < 6; i++) if (at[i] % 256 || at[i] + need[i] > at[i + 1]) return false;
+                    return w.up == lo && (char *)w.p.head - w.up == (char *)w0.p.head - w0.up && (char *)w.sl.tot - w.up == (char *)w0.sl.tot - w0.up &&
+                           (char *)w.p.shard_w0 == (char *)w.p.head + CN_PLAN_HEAD_BYTES && sizeof(CnPlanHead) <= CN_PLAN_HEAD_BYTES;
+                });
+            }
             for (int io : {0, 1}) { BgzfWs w; run_case(tag("bgzf", {n, m, (uint64_t)io}), [&](Arena &a) { return carve_bgzf(a, n, io != 0, m, (n + m) % 1009 * 65, w); }); }   // n members, m compressed bytes
             for (int io : {0, 1}) {   // a stream of n * 36 + m % 36 bytes (n records at most) cut at m anchors; the outputs' capacities run along
                 BamUnpackWs w;
@@ -170,7 +184,7 @@ int main()
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
     const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
-                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
+                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"cn_tables", 2},{"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
         const auto it = n_counts.find(kv.first);
