@@ -142,6 +142,7 @@ ABI = {
     "csvgpu_timing_reset": (C.c_int, [_P]),
     "csvgpu_timing_get": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "csvgpu_set_tuning": (C.c_int, [_P, C.POINTER(csv_tuning)]),
+    "csvgpu_set_cigar_packing": (C.c_int, [_P, C.c_int]),
     "csvgpu_cigar_scan": (C.c_int, [_P, C.POINTER(csv_reads), C.c_uint32, C.c_uint32, C.c_uint8, _P, C.POINTER(C.c_uint64)]),
     "csvgpu_aln_intervals": (C.c_int, [_P, C.POINTER(csv_reads), _P, _P, _P]),
     "csvgpu_depth": (C.c_int, [_P, C.POINTER(csv_reads), C.c_uint32, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
@@ -208,6 +209,7 @@ ABI = {
     "csvgpu_shard_builder_finish": (_P, [_P, _P, C.c_uint32]),
     "csvgpu_shard_builder_destroy": (None, [_P, _P]),
     "csvgpu_shard_sizes": (C.c_int, [_P, _P, C.POINTER(csv_shard_sizes)]),
+    "csvgpu_shard_cigar_bytes": (C.c_uint64, [_P]),
     "csvgpu_shard_fetch_reads": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_shard_fetch_names": (C.c_int, [_P, _P, _P, _P, _P]),
     "csvgpu_shard_drop_sequences": (C.c_int, [_P, _P]),

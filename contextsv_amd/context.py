@@ -162,6 +162,10 @@ class Context:
                             int(dbscan_all_pairs), int(split_chain_only))
         self._check(self.lib.csvgpu_set_tuning(self.h, C.byref(t)))
 
+    def set_cigar_packing(self, on: bool = True):
+        """csvgpu_set_cigar_packing: whether long-read shards uploaded from now on keep their CIGAR ops in 16 bits (the default) or in 32."""
+        self._check(self.lib.csvgpu_set_cigar_packing(self.h, int(on)))
+
     __del__ = close
 
     def __enter__(self):
@@ -1158,6 +1162,10 @@ class Shard:
         s = _lib.csv_shard_sizes()
         self.ctx._check(self.ctx.lib.csvgpu_shard_sizes(self.ctx.h, self.h, C.byref(s)))
         return dict(n_reads=s.n_reads, n_cigar=s.n_cigar, n_seq=s.n_seq, n_name=s.n_name)
+
+    def cigar_bytes(self) -> int:
+        """csvgpu_shard_cigar_bytes: device bytes of the shard's CIGAR array, padding and escape tables included."""
+        return int(self.ctx.lib.csvgpu_shard_cigar_bytes(self.h))
 
     def fetch_reads(self, want_cigar: bool = True) -> Reads:
         """csvgpu_shard_fetch_reads: the shard's reads copied to the host (want_cigar False: pos / flag / mapq only, the CIGAR arrays empty)."""

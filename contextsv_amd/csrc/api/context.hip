@@ -170,6 +170,15 @@ int csvgpu_set_tuning(csv_ctx *ctx, const csv_tuning *t)
     return CSV_OK;
 }
 
+int csvgpu_set_cigar_packing(csv_ctx *ctx, int on)
+{
+    if (!ctx) return CSV_EINVAL;
+    if (ctx->job_pin_busy || ctx->split_state) { ctx->err = "set_cigar_packing: a job or a split order is open on this context"; return CSV_EINVAL; }
+    if (on != 0 && on != 1) { ctx->err = "set_cigar_packing: on must be 0 or 1"; return CSV_EINVAL; }
+    ctx->cigar_packing = on;
+    return CSV_OK;
+}
+
 int csvgpu_timing_enable(csv_ctx *ctx, int on) { if (!ctx) return CSV_EINVAL; ctx->timing = on < 0 ? 0 : (on > 3 ? 1 : on); return CSV_OK; }
 
 int csvgpu_timing_reset(csv_ctx *ctx)

@@ -139,7 +139,7 @@ void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, uint32_t
 // depth chain on device arrays. pmax / ord / range scratch is `ws` (carve_depth); `ranges` != nullptr: the scan already produced the
 // tiles' candidate ranges (coordinate-sorted shard) and only the tile kernel remains.
 int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
-                uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges, uint32_t cigar_pad, void *items, int form)
+                uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges, uint32_t cigar_pad, void *items, int form, const CigarPack &pack)
 {
     const uint64_t n = d.n_reads;
     TimerScope ts(ctx, CSV_K_DEPTH);
@@ -148,7 +148,7 @@ int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32
         return CSV_OK;
     }
     if (ranges && !unsorted) {
-        launch_depth_tiles(ctx->stream, d, nullptr, ref_end, ckpt, depth_len, depth, cnt, ranges, cigar_pad, items, form);
+        launch_depth_tiles(ctx->stream, d, nullptr, ref_end, ckpt, depth_len, depth, cnt, ranges, cigar_pad, items, form, pack);
         return CSV_OK;
     }
     int32_t *pmax = ws.pmax;
@@ -167,7 +167,7 @@ int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32
     }
     launch_prefix_max(ctx->stream, end_s, pmax, n, ptmp);
     launch_depth_ranges(ctx->stream, pos_s, pmax, n, depth_len, ttmp);
-    launch_depth_tiles(ctx->stream, d, ord, ref_end, ckpt, depth_len, depth, cnt, ttmp, cigar_pad, items, form);
+    launch_depth_tiles(ctx->stream, d, ord, ref_end, ckpt, depth_len, depth, cnt, ttmp, cigar_pad, items, form, pack);
     return CSV_OK;
 }
 

@@ -2,8 +2,11 @@
 #include <new>
 
 #include "glue.hpp"
+#include "../cigar_pack_core.hpp"
 
 namespace csv {
+
+namespace cpk = cigar_pack_core;
 
 void shard_release(csv_shard *sh)
 {
@@ -13,6 +16,7 @@ void shard_release(csv_shard *sh)
         (void)hipFree((void *)sh->d.cigar_off); (void)hipFree((void *)sh->d.cigar);
     }
     (void)hipFree(sh->ref_end); (void)hipFree(sh->q_start); (void)hipFree(sh->q_end);
+    (void)hipFree(sh->cig_half); (void)hipFree(sh->esc_piece); (void)hipFree(sh->esc_tab);
     (void)hipFree(sh->ckpt);
     (void)hipFree(sh->depth_items);
     (void)hipFree(sh->scan_split);
@@ -44,6 +48,49 @@ csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh)
     launch_scan_split(ctx->stream, ctx->n_cu, sh->d, sh->scan_split, sh->form);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "scan split failed (shard)"; shard_release(sh); return nullptr; }
     return sh;
+}
+
+// The 16-bit form of a freshly uploaded wave-form shard (cigar_pack_core.hpp), made on the device from the 32-bit words: escapes counted per
+// 512-op piece, the exclusive sum, one read-back that sizes the table, the halfwords and the table written, the 32-bit array freed. A shard
+// with more escapes than 1 / 64 of its ops, or one whose halfword array cannot be had, stays at 32 bits. CSV_OK either way; CSV_EHIP on a
+// failed launch or copy.
+static int shard_pack_cigar(csv_ctx *ctx, csv_shard *sh)
+{
+    const uint64_t m = sh->d.n_cigar, np = cpk::n_pieces(m);
+    if (m == 0 || np + 1 >= 0xffffffffull) return CSV_OK;         // (the per-piece index counts in 32 bits: at most m / 64 escapes, m below 2^40)
+    hipStream_t s = ctx->stream;
+    int rc = ensure_pinned(ctx, kPinScalars);
+    if (rc) return rc;
+    uint32_t *piece = nullptr;
+    void *es_tmp = nullptr;
+    uint16_t *half = nullptr;
+    uint64_t *tab = nullptr;
+    auto drop = [&]() { (void)hipFree(piece); (void)hipFree(es_tmp); (void)hipFree(half); (void)hipFree(tab); (void)hipGetLastError(); };
+    if (hipMalloc((void **)&piece, (np + 1) * 4) != hipSuccess || hipMalloc(&es_tmp, exclusive_sum_tmp_bytes(np + 1) + 16) != hipSuccess) { drop(); return CSV_OK; }
+    launch_cigar_esc_count(s, sh->d.cigar, m, piece);
+    launch_exclusive_sum_u32(s, piece, np + 1, es_tmp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->pinned, piece + np, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { drop(); ctx->err = std::string("shard upload: counting the escapes failed: ") + hipGetErrorString(e); return CSV_EHIP; }
+    const uint64_t n_esc = *(const uint32_t *)ctx->pinned;
+    if (!cpk::packs(m, n_esc)) { drop(); return CSV_OK; }
+    // INVARIANT the two big kernels rely on: the halfword array is allocated (and, behind op m, zeroed) up to the end of its last 512-op piece
+    // plus CIGAR_PAD_WORDS halfwords. Every 1 KiB LDS-DMA piece of the scan starts at a multiple of 512 ops below m, so it ends at or in front of
+    // the last piece's end; every lane load of the depth walk starts below m rounded up to 4 ops and is at most 16 bytes long, so it ends in
+    // front of the pad's end. The table has one entry to spare behind its last.
+    const uint64_t n_half = np * cpk::PIECE_OPS + CIGAR_PAD_WORDS;
+    if (hipMalloc((void **)&half, n_half * 2) != hipSuccess || hipMalloc((void **)&tab, (n_esc + 1) * 8) != hipSuccess) { drop(); return CSV_OK; }
+    e = hipMemsetAsync(half + np * cpk::PIECE_OPS, 0, (size_t)CIGAR_PAD_WORDS * 2, s);
+    if (e == hipSuccess) e = hipMemsetAsync(tab + n_esc, 0, 8, s);
+    if (e == hipSuccess) { launch_cigar_pack(s, sh->d.cigar, m, piece, half, tab); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { drop(); ctx->err = std::string("shard upload: packing the CIGAR array failed: ") + hipGetErrorString(e); return CSV_EHIP; }
+    (void)hipFree(es_tmp);
+    (void)hipFree((void *)sh->d.cigar);
+    sh->d.cigar = nullptr;
+    sh->cig_half = half; sh->esc_piece = piece; sh->esc_tab = tab; sh->n_esc = n_esc;
+    return CSV_OK;
 }
 
 }  // namespace csv
@@ -81,6 +128,7 @@ csv_shard *csvgpu_shard_upload(csv_ctx *ctx, const csv_reads *r, uint32_t depth_
     cp &= hipMemsetAsync((void *)(sh->d.cigar + m), 0, (size_t)CIGAR_PAD_WORDS * 4, s) == hipSuccess;
     cp &= hipStreamSynchronize(s) == hipSuccess;
     if (!cp) { ctx->err = "H2D copy failed (shard upload)"; shard_release(sh); return nullptr; }
+    if (ctx->cigar_packing && scan_form(ctx, n, m) == SCAN_FORM_WAVE && shard_pack_cigar(ctx, sh)) { shard_release(sh); return nullptr; }
     return shard_common(ctx, sh);
 }
 
@@ -93,6 +141,14 @@ csv_shard *csvgpu_shard_wrap_dev(csv_ctx *ctx, const csv_reads *r, uint32_t dept
     if (!sh) { ctx->err = "out of host memory"; return nullptr; }
     sh->owned = false; sh->depth_len = depth_len; sh->d = *r;
     return shard_common(ctx, sh);
+}
+
+uint64_t csvgpu_shard_cigar_bytes(const csv_shard *sh)
+{
+    if (!sh) return 0;
+    if (!sh->cig_half) return 4 * (sh->d.n_cigar + (uint64_t)sh->cigar_pad);
+    const uint64_t np = cpk::n_pieces(sh->d.n_cigar);
+    return 2 * (np * cpk::PIECE_OPS + (uint64_t)sh->cigar_pad) + 4 * (np + 1) + 8 * (sh->n_esc + 1);
 }
 
 void csvgpu_shard_free(csv_ctx *ctx, csv_shard *sh)

@@ -70,6 +70,7 @@ struct csv_ctx {
     uint32_t     job_pin_busy = 0;          // bit i: slot i belongs to a job between begin and end / abort
     struct csv_split_state *split_state = nullptr;   // between csvgpu_split_order_begin and _finish
     csv_tuning   tuning = CSV_TUNING_DEFAULTS;      // csvgpu_set_tuning
+    int          cigar_packing = 1;                 // csvgpu_set_cigar_packing: read when a shard is uploaded
 };
 
 struct csv_shard {
@@ -77,6 +78,12 @@ struct csv_shard {
     uint32_t  depth_len = 0;
     bool      owned = false;       // true: arrays hipMalloc'd by csvgpu_shard_upload
     uint32_t  cigar_pad = 0;       // allocated (zeroed) words behind d.cigar[n_cigar]: CIGAR_PAD_WORDS for the library's own uploads, 0 for wrapped arrays
+    // The 16-bit form (cigar_pack_core.hpp) of an uploaded wave-form shard: then d.cigar is null and these hold the ops. half: the halfwords,
+    // allocated to the end of the last 512-op piece + CIGAR_PAD_WORDS zeroed halfwords; esc_piece [n_pieces + 1]; esc_tab [n_esc + 1].
+    uint16_t *cig_half = nullptr;
+    uint32_t *esc_piece = nullptr;
+    uint64_t *esc_tab = nullptr;
+    uint64_t  n_esc = 0;
     int       unsorted = -1;       // pos[] not non-decreasing: 1 / 0, or -1 while unknown (wrapped device arrays before their first scan)
     // per-read side arrays + per-chromosome outputs (device, owned by the shard)
     int32_t  *ref_end = nullptr, *q_start = nullptr, *q_end = nullptr, *pmax_end = nullptr;
@@ -174,12 +181,18 @@ struct ScanExtras {
 };
 // Forms of the scan (and of the depth pass's walk): a wave per read (long reads), or groups of 16 / 8 lanes per read (short reads)
 enum { SCAN_FORM_WAVE = CSV_FORM_WAVE, SCAN_FORM_ROWS16 = CSV_FORM_ROWS16, SCAN_FORM_ROWS8 = CSV_FORM_ROWS8, SCAN_FORM_LANES = CSV_FORM_LANES };      // (LANES: the scan walks a read per lane; the depth walk takes groups of 16)
+// the 16-bit form of a shard's CIGAR array as the two big kernels see it (null half: the shard is at 32 bits and d.cigar holds the words)
+struct CigarPack {
+    const uint16_t *half = nullptr;
+    const uint32_t *piece = nullptr;
+    const uint64_t *tab = nullptr;
+};
 int scan_form_for(uint64_t n_reads, uint64_t n_cigar);          // by mean CIGAR words per read: SCAN_FORM_WAVE or SCAN_FORM_ROWS16
 void launch_cigar_scan(hipStream_t s, int n_cu, const csv_reads &d, uint32_t depth_len, uint32_t min_oplen,
                        uint32_t min_mapq, int emit, csv_sig *sig_out, uint64_t sig_cap,
                        int32_t *ref_end, int32_t *q_start, int32_t *q_end, uint32_t *ckpt, ScanCounters *cnt, const ScanExtras &extras = ScanExtras(),
                        const uint64_t *split = nullptr /* launch_scan_split's table for the same n_cu, shard and form */, int form = SCAN_FORM_WAVE,
-                       uint32_t cigar_pad_words = 0 /* allocated words behind d.cigar[n_cigar] */);
+                       uint32_t cigar_pad_words = 0 /* allocated words behind d.cigar[n_cigar] */, const CigarPack &pack = CigarPack() /* wave form only */);
 size_t scan_split_bytes(int n_cu, uint64_t n_reads, int form);
 void launch_scan_split(hipStream_t s, int n_cu, const csv_reads &d, uint64_t *split, int form);      // once per resident shard
 void launch_validate_offsets(hipStream_t s, const uint64_t *cigar_off, uint64_t n_reads, uint64_t n_cigar, uint64_t max_words, uint32_t *bad /* zeroed; set to 1 */);
@@ -200,7 +213,12 @@ void launch_depth_ranges(hipStream_t s, const int32_t *pos_s, const int32_t *pma
 size_t depth_items_bytes(uint32_t depth_len);
 void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, const int32_t *ref_end, const uint32_t *ckpt,
                         uint32_t depth_len, uint32_t *depth, ScanCounters *cnt, const uint64_t *tile_range, uint32_t cigar_pad_words = 0,
-                        void *items = nullptr, int form = SCAN_FORM_WAVE /* how the tiles walk their items: SCAN_FORM_* */);
+                        void *items = nullptr, int form = SCAN_FORM_WAVE /* how the tiles walk their items: SCAN_FORM_* */,
+                        const CigarPack &pack = CigarPack() /* wave form only */);
+// cigarpack.hip: the 16-bit form made and undone on the device (cigar_pack_core.hpp has the rule)
+void launch_cigar_esc_count(hipStream_t s, const uint32_t *cigar, uint64_t n_cigar, uint32_t *piece /* [n_pieces + 1]: escapes per piece, 0 last */);
+void launch_cigar_pack(hipStream_t s, const uint32_t *cigar, uint64_t n_cigar, const uint32_t *piece /* exclusive sums */, uint16_t *half, uint64_t *tab);
+void launch_cigar_unpack(hipStream_t s, const CigarPack &pack, uint64_t first, uint64_t n, uint32_t *out);      // ops [first, first + n)
 // reference-offset checkpoints every CKPT_WORDS CIGAR words (scan.hip writes them, depth.hip starts its walks from them)
 constexpr int CKPT_SHIFT = 6, CKPT_WORDS = 1 << CKPT_SHIFT;
 static inline size_t ckpt_bytes(uint64_t n_cigar) { return ((n_cigar >> CKPT_SHIFT) + 2) * sizeof(uint32_t); }

@@ -25,7 +25,12 @@
 #include "../common.hpp"
 #include "../devutil.hpp"
 
+#define CPK_HD __host__ __device__
+#include "../cigar_pack_core.hpp"
+
 namespace csv {
+
+namespace cpk = cigar_pack_core;
 
 constexpr int DEPTH_THREADS = 1024;
 constexpr int DEPTH_WAVES = DEPTH_THREADS / WAVE;          // 8
@@ -33,6 +38,8 @@ constexpr int DEPTH_PER_WAVE = DEPTH_TILE / DEPTH_WAVES;   // entries scanned pe
 constexpr int DEPTH_ROUNDS = DEPTH_PER_WAVE / (4 * WAVE);  // rounds of 256 entries
 constexpr int WL_CAP = 512;                                // work-list items staged per batch (12 KiB of LDS)
 constexpr int WL_SPEC = 256;                               // list entries a tile requests before it knows how many it has
+constexpr int DEPTH_PACKED_WPL = 8;                        // ops per lane and visit of the walk over a 16-bit shard: one 16-byte load, 512 ops per visit. (4 — 8-byte loads, the
+                                                           // 32-bit walk's 256-op visits — was built too: depth 10.6 ms per genome step against 9.7 with 8 and 11.2 at 32 bits)
 constexpr int DEPTH_PF = 5;                                // a walk keeps DEPTH_PF + 1 chunks in flight ahead of the one being worked on (1 -> 4: -4 %)
 
 // ------------------------------------------------------------------------------- prefix max
@@ -314,7 +321,11 @@ extern "C" void csvgpu_debug_depth_phase(unsigned long long *out, int reset)
 // every chunk load is one unconditional 16-byte load per lane.
 // GL: lanes that walk one item together — 64 (a wave per item, the stream of 1 KiB chunks below: long reads) or 16 / 8 (short reads:
 // a (tile, read) item of a HiFi shard is 40 words, and a whole wave per item left 5 lanes in 6 idle; 64-word windows, see scan.hip).
-template <bool PADDED, int GL>
+// PACKED (DEPTH_PACKED_WPL, with PADDED and GL = 64 only; 0: the 32-bit words): `cigar` is the 16-bit form's halfword array (cigar_pack_core.hpp)
+// with its escape tables beside it, and a lane takes PACKED = 8 ops per visit: one 16-byte load, eight halfwords zero-extended where the 32-bit
+// walk has its four words, 512 ops per visit, the visit count taken from the item's op count (the item's own counts 256-op chunks). An escape is
+// replaced by the table's word behind a wave-uniform branch. Items and checkpoints count ops as before.
+template <bool PADDED, int GL, int PACKED = 0>
 __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
     uint64_t n_reads, uint64_t n_cigar, const int32_t *__restrict__ pos, const uint16_t *__restrict__ flag,
     const uint64_t *__restrict__ cigar_off, const uint32_t *__restrict__ cigar, int vec_ok, int dvec_ok,
@@ -322,8 +333,10 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
     const int32_t *__restrict__ ref_end, const uint64_t *tile_range,        // (written by atomics of the previous kernel: no __restrict__ / read-only path)
     const uint32_t *__restrict__ ckpt,       // reference offset of the owning read at every CKPT_WORDS-word boundary (scan.hip)
     uint32_t depth_len, uint32_t *__restrict__ depth, ScanCounters *__restrict__ cnt,
-    const DepthItem *__restrict__ items, const uint32_t *__restrict__ n_items_pre)      // depth_items_kernel's lists, or null
+    const DepthItem *__restrict__ items, const uint32_t *__restrict__ n_items_pre,      // depth_items_kernel's lists, or null
+    const uint32_t *__restrict__ esc_piece, const uint64_t *__restrict__ esc_tab)       // PACKED: the escapes' per-piece index and table
 {
+    static_assert(PACKED == 0 || (PACKED == 8 && PADDED && GL == WAVE), "only the padded wave-per-item walk reads the 16-bit form, 16 bytes per lane");
     __shared__ alignas(16) uint32_t diff[DEPTH_TILE + 4];
     __shared__ uint32_t wave_tot[DEPTH_WAVES];
     __shared__ unsigned long long blk_sum;
@@ -462,14 +475,16 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
             }
         } else if (n_items) {
             constexpr int WPL = 4;                                                   // CIGAR words per lane and chunk visit (one 16-byte load)
-            constexpr int NS = DEPTH_PF + 1;                                         // ring slots (chunks in flight)
-            constexpr uint32_t CW = (uint32_t)WPL * WAVE;                            // words per chunk (1 KiB)
-            uint32_t w[NS][WPL];
-            uint32_t m_o0[NS], m_nrem[NS], m_c0rel[NS];
+            constexpr int OPL = PACKED ? PACKED : WPL;                               // ... ops of a 16-bit shard (also one 16-byte load)
+            constexpr int RAW = PACKED ? OPL / 2 : OPL;                              // registers a lane's share of a chunk takes while in flight
+            constexpr int NS = PACKED ? 4 : DEPTH_PF + 1;                            // ring slots (chunks in flight; 16-bit: four slots of 512 ops — six spill 9 registers)
+            constexpr uint32_t CW = (uint32_t)OPL * WAVE;                            // words per chunk (1 KiB)
+            uint32_t w[NS][RAW];
+            uint32_t m_o0[NS], m_nrem[NS], m_c0rel[NS], m_b0[NS];
             int32_t m_start[NS];
             bool m_valid[NS], m_first[NS];
             uint64_t f_chunk0 = 0, f_addr = 0;
-            uint32_t f_n = 0, f_c = 0, f_nrem = 0, f_c0rel = 0, f_off = 0;
+            uint32_t f_n = 0, f_c = 0, f_nrem = 0, f_c0rel = 0, f_off = 0, f_b0 = 0;
             int32_t f_start = 0;
             bool f_done = false;
             uint32_t nxt_v = 0;                                                     // lane 0: the next item's index (an LDS atomic in flight)
@@ -479,33 +494,40 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                     const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)nxt_v);
                     if (it < n_items) {
                         const uint4 d = *reinterpret_cast<const uint4 *>(&wl[it]);      // {b0, nrem, pack, start}
-                        f_chunk0 = (uint64_t)uniform32(d.x) << CKPT_SHIFT;
+                        f_b0 = uniform32(d.x);
+                        f_chunk0 = (uint64_t)f_b0 << CKPT_SHIFT;
                         f_nrem = uniform32(d.y);
                         f_start = (int32_t)uniform32(d.w);
                         const uint32_t pk = uniform32(d.z);
-                        f_n = pk >> 6; f_c0rel = pk & 63u; f_c = 0;
+                        f_n = PACKED ? (f_nrem + CW - 1u) / CW : pk >> 6; f_c0rel = pk & 63u; f_c = 0;       // (the item counts 256-op chunks)
                         if (lane == 0) nxt_v = atomicAdd(&next_item, 1u);
                     } else f_done = true;
                 }
                 m_valid[j] = !f_done;
                 if (!f_done) {
-                    m_o0[j] = f_c * CW; m_nrem[j] = f_nrem; m_c0rel[j] = f_c0rel; m_start[j] = f_start; m_first[j] = f_c == 0;
+                    m_o0[j] = f_c * CW; m_nrem[j] = f_nrem; m_c0rel[j] = f_c0rel; m_start[j] = f_start; m_first[j] = f_c == 0; m_b0[j] = f_b0;
                     f_off = f_c * CW;
                     f_addr = f_chunk0 + (uint64_t)f_off;
                     f_c++;
                 }
-                if (PADDED) {
+                if constexpr (PACKED) {
+                    // (as below, in halfwords: the load starts below the item's last op rounded up to OPL and is 2 OPL bytes long, inside the
+                    // array's zeroed pad at the worst; the halfwords stay packed in the buffer until the visit that decodes them)
+                    const uint32_t lw = min((uint32_t)lane * OPL, (f_nrem - 1u - f_off) & ~(uint32_t)(OPL - 1));
+                    const uint4 v = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(cigar) + f_addr + lw);
+                    w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
+                } else if (PADDED) {
                     // lanes whose words all lie behind the item's last word repeat the last lane that has one: no cache line is fetched
                     // for them, and the load stays unconditional (the consumer masks those words anyway)
-                    const uint32_t lw = min((uint32_t)lane * WPL, (f_nrem - 1u - f_off) & ~(uint32_t)(WPL - 1));
+                    const uint32_t lw = min((uint32_t)lane * OPL, (f_nrem - 1u - f_off) & ~(uint32_t)(OPL - 1));
                     const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + lw);
                     w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
                 } else if (vec_ok && f_addr + CW <= n_cigar) {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + (uint64_t)lane * WPL);
+                    const uint4 v = *reinterpret_cast<const uint4 *>(cigar + f_addr + (uint64_t)lane * OPL);
                     w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
                 } else {
                     uint32_t t4[4];
-                    depth_load4(cigar, n_cigar, vec_ok, f_addr + (uint64_t)lane * WPL, t4);
+                    depth_load4(cigar, n_cigar, vec_ok, f_addr + (uint64_t)lane * OPL, t4);
                     w[j][0] = t4[0]; w[j][1] = t4[1]; w[j][2] = t4[2]; w[j][3] = t4[3];
                 }
             };
@@ -520,20 +542,39 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                     if (!m_valid[j]) { walking = false; break; }                    // the stream has run dry (buffers are consumed in fetch order)
                     const uint32_t o0 = m_o0[j], nrem = m_nrem[j], c0rel = m_c0rel[j];      // word offset of this chunk from the item's first chunk
                     if (m_first[j]) base_rel = m_start[j];
-                    uint32_t (&cur)[WPL] = w[j];
+                    uint32_t unp[OPL];
+                    if constexpr (PACKED) {
+#pragma unroll
+                        for (int k = 0; k < RAW; k++) { unp[2 * k] = w[j][k] & 0xffffu; unp[2 * k + 1] = w[j][k] >> 16; }
+                    }
+                    uint32_t (&cur)[OPL] = [&]() -> uint32_t (&)[OPL] { if constexpr (PACKED) return unp; else return w[j]; }();
                     // only the first and the last chunk of an item can hold words of a neighbouring read
                     if (!(o0 >= c0rel && o0 + CW <= nrem)) {
-                        const uint32_t t = o0 + (uint32_t)lane * WPL - c0rel, lim = nrem - c0rel;      // word o is the item's iff o - c0rel < nrem - c0rel (unsigned)
+                        const uint32_t t = o0 + (uint32_t)lane * OPL - c0rel, lim = nrem - c0rel;      // word o is the item's iff o - c0rel < nrem - c0rel (unsigned)
 #pragma unroll
-                        for (int k = 0; k < WPL; k++) if (!(t + k < lim)) cur[k] = (uint32_t)OP_P;
+                        for (int k = 0; k < OPL; k++) if (!(t + k < lim)) cur[k] = (uint32_t)OP_P;
+                    }
+                    if constexpr (PACKED) {
+                        // escapes (one op in 1e5 on an ONT shard): only the ops this visit keeps are looked up, behind a wave-uniform branch
+                        uint32_t top = cur[0];
+#pragma unroll
+                        for (int k = 1; k < OPL; k++) top = max(top, cur[k]);
+                        const bool esc = top >= cpk::ESC_MIN;
+                        if (__ballot(esc)) {
+                            if (esc) {
+                                const uint64_t i0 = ((uint64_t)m_b0[j] << CKPT_SHIFT) + o0 + (uint32_t)lane * OPL;      // this lane's first op in the array
+#pragma unroll
+                                for (int k = 0; k < OPL; k++) if (cpk::is_escape(cur[k])) cur[k] = cpk::lookup(esc_piece, esc_tab, i0 + k, cur[k]);
+                            }
+                        }
                     }
                     // depth = (reads whose reference span covers the position) - (their D / N gaps over it): the same number as counting the
                     // aligned bases of every M / = / X run (cnv_caller.cpp:498-520), with HALF the difference-array updates on an ONT CIGAR
                     // (a gap op is every fourth op, an aligned run every second) and none of the run-end arithmetic: a gap covers
                     // [cursor before it, cursor after it), so its two updates sit at cursor values the walk computes anyway.
-                    uint32_t rl[WPL], gp[WPL], lane_ref = 0;
+                    uint32_t rl[OPL], gp[OPL], lane_ref = 0;
 #pragma unroll
-                    for (int k = 0; k < WPL; k++) {
+                    for (int k = 0; k < OPL; k++) {
                         // v_bfe_i32 takes its bit offset from the word's low five bits (op + the length's lowest bit): op masks repeated at bit 16
                         const uint32_t len = cur[k] >> 4;
                         rl[k] = len & (uint32_t)__builtin_amdgcn_sbfe((int)(REF_OPS | (REF_OPS << 16)), cur[k], 1u);    // all-ones when the op consumes the reference
@@ -553,7 +594,7 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                         // the whole chunk lies inside the tile (most do: a tile is seven chunks wide): cursors as byte offsets, no clipping
                         uint32_t a4 = (uint32_t)rel0 << 2;
 #pragma unroll
-                        for (int k = 0; k < WPL; k++) {
+                        for (int k = 0; k < OPL; k++) {
                             const uint32_t n4 = lshl2_add(rl[k], a4);
                             if (gp[k]) {
                                 atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(diff) + a4), 0xffffffffu);
@@ -564,7 +605,7 @@ __global__ __launch_bounds__(DEPTH_THREADS, 8) void depth_tile_kernel(
                     } else {
                         int32_t rel = rel0, a = clamp0_i32(rel0, TW);
 #pragma unroll
-                        for (int k = 0; k < WPL; k++) {
+                        for (int k = 0; k < OPL; k++) {
                             rel += (int32_t)rl[k];
                             const int32_t b = clamp0_i32(rel, TW);
                             if (gp[k]) {                                       // (both ends clipped to the same edge cancel)
@@ -684,7 +725,8 @@ void launch_depth_ranges(hipStream_t s, const int32_t *pos_s, const int32_t *pma
 size_t depth_items_bytes(uint32_t depth_len) { return align_up((size_t)depth_n_tiles(depth_len) * (WL_CAP * sizeof(DepthItem) + sizeof(uint32_t)), 256); }
 
 void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, const int32_t *ref_end, const uint32_t *ckpt,
-                        uint32_t depth_len, uint32_t *depth, ScanCounters *cnt, const uint64_t *tile_range, uint32_t cigar_pad_words, void *items, int form)
+                        uint32_t depth_len, uint32_t *depth, ScanCounters *cnt, const uint64_t *tile_range, uint32_t cigar_pad_words, void *items, int form,
+                        const CigarPack &pack)
 {
     if (depth_len == 0) return;
     const unsigned tiles = depth_n_tiles(depth_len);
@@ -694,11 +736,20 @@ void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, 
     uint32_t *n_it = items ? (uint32_t *)(it + (size_t)tiles * WL_CAP) : nullptr;
     if (items)
         hipLaunchKernelGGL(depth_items_kernel, dim3(tiles), dim3(ITEMS_THREADS), 0, s, d.pos, d.flag, d.cigar_off, ord, ref_end, tile_range, ckpt, depth_len, it, n_it);
+    if (pack.half) {
+        // The 16-bit form (wave form only: shard.hip packs no other). A lane's load starts at an op below the item's last op rounded up to the
+        // DEPTH_PACKED_WPL ops it takes, so below n_cigar + DEPTH_PACKED_WPL - 1, and is as many ops long: inside the array's zeroed pad of
+        // CIGAR_PAD_WORDS halfwords behind its last piece.
+        static_assert(CIGAR_PAD_WORDS >= 2 * DEPTH_PACKED_WPL, "a lane's load may start DEPTH_PACKED_WPL - 1 ops behind the array's last op");
+        hipLaunchKernelGGL((depth_tile_kernel<true, WAVE, DEPTH_PACKED_WPL>), dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off,
+                           reinterpret_cast<const uint32_t *>(pack.half), 1, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it, pack.piece, pack.tab);
+        return;
+    }
     if (form != SCAN_FORM_WAVE && d.n_cigar >= 0xffffffffull) form = SCAN_FORM_WAVE;
     const bool padded = vec_ok && cigar_pad_words >= 4 * WAVE;
 #define CSV_TILE_LAUNCH(PAD, GL)                                                                                                                 \
     hipLaunchKernelGGL((depth_tile_kernel<PAD, GL>), dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off, d.cigar, \
-                       vec_ok, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it)
+                       vec_ok, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it, nullptr, nullptr)
     if (form == SCAN_FORM_ROWS16 || form == SCAN_FORM_LANES) { if (padded) CSV_TILE_LAUNCH(true, 16); else CSV_TILE_LAUNCH(false, 16); }
     else if (form == SCAN_FORM_ROWS8) { if (padded) CSV_TILE_LAUNCH(true, 8); else CSV_TILE_LAUNCH(false, 8); }
     else { if (padded) CSV_TILE_LAUNCH(true, WAVE); else CSV_TILE_LAUNCH(false, WAVE); }

@@ -18,14 +18,19 @@
 // a single hot global counter would otherwise serialise the chip. Emission order is arbitrary —
 // the ordering pass (sort.hip) reproduces the reference's addSVCall order afterwards.
 //
-// HBM traffic per read: 4*n_cigar + 23 B in (pos 4, flag 2, mapq 1, cigar_off 2x8 shared) and
+// HBM traffic per read: 4*n_cigar (2*n_cigar when the shard is in the 16-bit form, cigar_pack_core.hpp) + 23 B in (pos 4, flag 2, mapq 1, cigar_off 2x8 shared) and
 // 12 B out (ref_end, q_start, q_end) + 16 B per signature.
 #include <type_traits>
 
 #include "../common.hpp"
 #include "../devutil.hpp"
 
+#define CPK_HD __host__ __device__
+#include "../cigar_pack_core.hpp"
+
 namespace csv {
+
+namespace cpk = cigar_pack_core;
 
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_WAVES = SCAN_THREADS / WAVE;
@@ -52,8 +57,16 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(
 
 // Fill one ring slot with the chunk starting at word `base` (wave-uniform, multiple of 256). Only the last chunk of the whole
 // array can be partial (or the base pointer unaligned, never for our own uploads): those go through registers, padded with P ops.
+// PACKED: the slot takes a PIECE of 512 halfwords starting at op `base` (a multiple of 512): always one LDS-DMA, because a packed array
+// is the library's own, 16-byte aligned and allocated to the end of its last piece (shard.hip states the invariant).
+template <bool PACKED>
 __device__ __forceinline__ void ring_issue(uint32_t *slot, const uint32_t *__restrict__ cigar, uint64_t base, int lane, uint64_t n_cigar, int vec_ok)
 {
+    if constexpr (PACKED) {
+        glds16(reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint16_t *>(cigar) + base), (uint32_t)lane * 16u,
+               (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(slot)));
+        return;
+    }
     const uint64_t idx = base + (uint64_t)lane * 4;
     if (vec_ok && base + CHUNK_WORDS <= n_cigar) {
         glds16(cigar + base, (uint32_t)lane * 16u, (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(slot)));
@@ -106,6 +119,11 @@ __device__ __forceinline__ uint64_t bcast64(uint64_t v, uint32_t i)
     return ((uint64_t)bcast32((uint32_t)(v >> 32), i) << 32) | bcast32((uint32_t)v, i);
 }
 // 54 VGPRs; the LDS (ring + signature buffer) sets the occupancy
+// PACKED: `cigar` is the 16-bit form's halfword array (cigar_pack_core.hpp) with its escape tables beside it. An LDS-DMA piece is still
+// 1 KiB and then holds 512 ops, two chunks: chunk j of the wave's stream lives in piece j >> 1, half j & 1; the ring, its top-up and the
+// counted waits count pieces. A visit zero-extends its four halfwords into cur.w[] and replaces an escape by the table's word; the rest of
+// the visit is the 32-bit one's, instruction for instruction.
+template <bool PACKED>
 __global__ __launch_bounds__(SCAN_THREADS, SCAN_OCC) void cigar_scan_kernel(
     uint64_t n_reads, uint64_t n_cigar, const int32_t *__restrict__ pos, const uint16_t *__restrict__ flag,
     const uint8_t *__restrict__ mapq, const uint64_t *__restrict__ cigar_off, const uint32_t *__restrict__ cigar,
@@ -113,8 +131,11 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_OCC) void cigar_scan_kernel(
     csv_sig *__restrict__ sig_out, uint64_t sig_cap, int32_t *__restrict__ ref_end, int32_t *__restrict__ q_start,
     int32_t *__restrict__ q_end, uint32_t *__restrict__ ckpt, ScanCounters *__restrict__ cnt,
     unsigned long long *__restrict__ tile_range, uint32_t n_tiles, uint32_t *__restrict__ bucket_hist, int hist_type_pos, int hist_shift,
-    const uint64_t *__restrict__ split)      // scan_split_kernel's table for this grid (resident shards: first read and its first word per wave), or null
+    const uint64_t *__restrict__ split,      // scan_split_kernel's table for this grid (resident shards: first read and its first word per wave), or null
+    const uint32_t *__restrict__ esc_piece, const uint64_t *__restrict__ esc_tab)      // PACKED: the escapes' per-piece index and table
 {
+    constexpr uint32_t PIECE = PACKED ? 2u * CHUNK_WORDS : (uint32_t)CHUNK_WORDS;       // ops per ring slot
+    static_assert(!PACKED || PIECE == cpk::PIECE_OPS, "the escape index is per LDS-DMA piece");
     __shared__ csv_sig buf[SIG_BUF];
     __shared__ alignas(16) uint32_t ring[SCAN_WAVES][RING_D][CHUNK_WORDS];      // 16-byte aligned: LDS-DMA destination and ds_read_b128 source
     __shared__ uint32_t buf_n, blk_n_del, blk_overflow;
@@ -160,11 +181,12 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_OCC) void cigar_scan_kernel(
     // This wave's load stream: the chunks [ring_base, ring_base + 256 ring_total) cover its reads' words.
     const uint64_t w_begin = split ? uniform64(split_w[wave]) : uniform64(r_begin < r_end ? cigar_off[r_begin] : 0);
     const uint64_t w_end = split ? uniform64(split_w[wave + 1]) : uniform64(r_begin < r_end ? cigar_off[r_end] : 0);
-    const uint64_t ring_base = w_begin & ~(uint64_t)(CHUNK_WORDS - 1);
-    const uint32_t ring_total = r_begin < r_end ? (uint32_t)((w_end - ring_base + CHUNK_WORDS - 1) / CHUNK_WORDS) : 0u;
+    // (PACKED: in pieces of 512 ops; "chunk" below is a piece wherever the ring is meant)
+    const uint64_t ring_base = w_begin & ~(uint64_t)(PIECE - 1);
+    const uint32_t ring_total = r_begin < r_end ? (uint32_t)((w_end - ring_base + PIECE - 1) / PIECE) : 0u;
     uint32_t ring_ready = 0;              // chunks [0, ring_ready) have landed; chunks [ring_ready, ring_ready + RING_D - 1) are in flight
     for (uint32_t a = 0; a < (uint32_t)(RING_D - 1) && a < ring_total; a++)
-        ring_issue(ring[wave][a], cigar, ring_base + (uint64_t)a * CHUNK_WORDS, lane, n_cigar, vec_ok);
+        ring_issue<PACKED>(ring[wave][a], cigar, ring_base + (uint64_t)a * PIECE, lane, n_cigar, vec_ok);
 
     // Per-read metadata is loaded for 64 reads at a time, lane-parallel and coalesced (lane l <-> read rb + l), and handed to
     // the wave with readlane; a wave's whole share is usually one batch. Inside the read loop only the ring traffic remains.
@@ -213,18 +235,22 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_OCC) void cigar_scan_kernel(
         for (uint32_t t = 0; t < n_chunks; t++, rel += CHUNK_WORDS) {
             // chunk j of the stream: top the ring up (chunks before j are dead, so slots (j, j + RING_D) mod RING_D are free), wait for j
             const uint32_t j = j0 + t;
-            if (j == ring_ready) {                // first visit (chunks are visited in stream order; a boundary chunk is visited again by the next read)
-                const uint32_t ahead = j + (RING_D - 1);
+            const uint32_t pj = PACKED ? j >> 1 : j;      // its ring piece
+            if (pj == ring_ready) {               // first visit (chunks are visited in stream order; a boundary chunk is visited again by the next read)
+                const uint32_t ahead = pj + (RING_D - 1);
                 if (ahead < ring_total) {
-                    ring_issue(ring[wave][ahead % RING_D], cigar, ring_base + (uint64_t)ahead * CHUNK_WORDS, lane, n_cigar, vec_ok);
+                    ring_issue<PACKED>(ring[wave][ahead % RING_D], cigar, ring_base + (uint64_t)ahead * PIECE, lane, n_cigar, vec_ok);
                     ring_wait_steady();           // chunks j + 1 .. j + RING_D - 1 may still be in flight
                 } else {
                     ring_wait_all();
                 }
-                ring_ready = j + 1;
+                ring_ready = pj + 1;
             }
             Chunk cur;
-            {
+            if constexpr (PACKED) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(&ring[wave][pj % RING_D][(j & 1u) * (CHUNK_WORDS / 2) + lane * 2]);
+                cur.w[0] = v.x & 0xffffu; cur.w[1] = v.x >> 16; cur.w[2] = v.y & 0xffffu; cur.w[3] = v.y >> 16;
+            } else {
                 const uint4 v = *reinterpret_cast<const uint4 *>(&ring[wave][j % RING_D][lane * 4]);
                 cur.w[0] = v.x; cur.w[1] = v.y; cur.w[2] = v.z; cur.w[3] = v.w;
             }
@@ -234,6 +260,17 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_OCC) void cigar_scan_kernel(
             if (edge) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (!((uint32_t)(rel + k) < n_words)) cur.w[k] = (uint32_t)OP_P;   // also catches rel + k < 0
+            }
+            if constexpr (PACKED) {
+                // escapes (one op in 1e5 on an ONT shard): only the ops this visit keeps are looked up, behind a wave-uniform branch
+                const bool esc = max(max(cur.w[0], cur.w[1]), max(cur.w[2], cur.w[3])) >= cpk::ESC_MIN;
+                if (__ballot(esc)) {
+                    if (esc) {
+                        const uint64_t i0 = c0 + (uint64_t)(int64_t)rel;      // this lane's first op in the array (rel < 0 only where the words are masked)
+#pragma unroll
+                        for (int k = 0; k < 4; k++) if (cpk::is_escape(cur.w[k])) cur.w[k] = cpk::lookup(esc_piece, esc_tab, i0 + k, cur.w[k]);
+                    }
+                }
             }
             uint32_t len[4], op[4], rl[4], ql[4];
             uint32_t lane_ref = 0, lane_q = 0, trig = 0, qst = 0;
@@ -965,7 +1002,7 @@ static unsigned scan_grid(int n_cu, uint64_t n_reads, int form)
     if (blocks_per_cu[form] == 0) {
         int occ = 0;
         hipError_t e;
-        if (form == SCAN_FORM_WAVE) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cigar_scan_kernel, SCAN_THREADS, 0);
+        if (form == SCAN_FORM_WAVE) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cigar_scan_kernel<false>, SCAN_THREADS, 0);      // (both widths: same LDS, which sets it)
         else if (form == SCAN_FORM_ROWS16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cigar_scan_rows_kernel<16, true>, RS_THREADS, 0);
         else if (form == SCAN_FORM_ROWS8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cigar_scan_rows_kernel<8, true>, RS_THREADS, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cigar_scan_lanes_kernel<true>, LN_THREADS, 0);
@@ -1020,18 +1057,28 @@ void launch_scan_split(hipStream_t s, int n_cu, const csv_reads &d, uint64_t *sp
 void launch_cigar_scan(hipStream_t s, int n_cu, const csv_reads &d, uint32_t depth_len, uint32_t min_oplen,
                        uint32_t min_mapq, int emit, csv_sig *sig_out, uint64_t sig_cap,
                        int32_t *ref_end, int32_t *q_start, int32_t *q_end, uint32_t *ckpt, ScanCounters *cnt, const ScanExtras &x, const uint64_t *split,
-                       int form, uint32_t cigar_pad_words)
+                       int form, uint32_t cigar_pad_words, const CigarPack &pack)
 {
     if (d.n_reads == 0) return;
+    if (pack.half) {
+        // The 16-bit form (wave form only: shard.hip packs no other). The array is allocated to the end of its last 512-op piece (+ pad), and
+        // a wave's pieces are [ring_base, ring_base + 512 ring_total) with ring_base a multiple of 512 and the last piece the one that holds
+        // op n_cigar - 1 at the most: every 1 KiB LDS-DMA lies inside the allocation, with no bounds test in the kernel.
+        hipLaunchKernelGGL(cigar_scan_kernel<true>, dim3(scan_grid(n_cu, d.n_reads, SCAN_FORM_WAVE)), dim3(SCAN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag,
+                           d.mapq, d.cigar_off, reinterpret_cast<const uint32_t *>(pack.half), 1, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap,
+                           ref_end, q_start, q_end, ckpt, cnt, (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift,
+                           split, pack.piece, pack.tab);
+        return;
+    }
     static_assert(SCAN_WAVES == RS_WAVES, "one split table layout for both forms");
     if (form != SCAN_FORM_WAVE && d.n_cigar >= 0xffffffffull) { form = SCAN_FORM_WAVE; split = nullptr; }
     const unsigned grid = scan_grid(n_cu, d.n_reads, form);
     const int vec_ok = (((uintptr_t)d.cigar) & 15u) == 0;
     if (form == SCAN_FORM_WAVE) {
-        hipLaunchKernelGGL(cigar_scan_kernel, dim3(grid), dim3(SCAN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag,
+        hipLaunchKernelGGL(cigar_scan_kernel<false>, dim3(grid), dim3(SCAN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag,
                            d.mapq, d.cigar_off, d.cigar, vec_ok, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap,
                            ref_end, q_start, q_end, ckpt, cnt, (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift,
-                           split);
+                           split, nullptr, nullptr);
         return;
     }
     const bool padded = vec_ok && cigar_pad_words >= 128;

@@ -153,6 +153,12 @@ typedef struct csv_tuning {
  * and _finish. A resident shard keeps the scan form of the context that created it (csvgpu_shard_upload / _wrap_dev), on whichever context it is
  * run later; the host-pointer entry points take the form of the context they are called on. */
 int         csvgpu_set_tuning(csv_ctx *ctx, const csv_tuning *t);
+/* Whether csvgpu_shard_upload stores the CIGAR array of a long-read (CSV_FORM_WAVE) shard in 16 bits per op: 4 of op, 12 of length, the few
+ * longer ops in a side table. Half the bytes the two big kernels read per step and half the resident memory; every result is the same bit for
+ * bit, and csvgpu_shard_fetch_reads still returns the uploaded 32-bit words. on: 1 (the default) or 0. Read when a shard is uploaded: a shard
+ * keeps the form it was uploaded with. Shards of the short-read forms, wrapped device arrays, shards of csvgpu_shard_builder_* and shards with
+ * more than one op in 64 of length >= 4095 stay at 32 bits. CSV_EINVAL: on out of range, or a job or a split order open on the context. */
+int         csvgpu_set_cigar_packing(csv_ctx *ctx, int on);
 
 /* ------------------------------------------------------------------------------------------ */
 /* host-pointer entry points (the seams of SURVEY.md §8b)                                       */
@@ -763,6 +769,9 @@ void csvgpu_shard_builder_destroy(csv_ctx *ctx, csv_shard_builder *b);
  * pos / flag / mapq and query names for the split-read pass (host/split_caller.cpp), which are small. Any output may be NULL.
  * fetch_names: CSV_EINVAL when name_off / name are asked of a shard without names, or name_hash of one without hashes. */
 int  csvgpu_shard_sizes(csv_ctx *ctx, const csv_shard *shard, csv_shard_sizes *out);
+/* Bytes of device memory the shard's CIGAR array takes, padding and (16-bit form) the escape tables included: 4 (n_cigar + pad) at 32 bits;
+ * 2 (n_cigar rounded up to 512 + pad) + 4 (pieces + 1) + 8 (escapes + 1) at 16 bits. n_cigar of csvgpu_shard_sizes counts ops either way. */
+uint64_t csvgpu_shard_cigar_bytes(const csv_shard *shard);
 int  csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *shard, int32_t *pos, uint16_t *flag, uint8_t *mapq, uint64_t *cigar_off, uint32_t *cigar);
 int  csvgpu_shard_fetch_names(csv_ctx *ctx, csv_shard *shard, uint64_t *name_off, uint8_t *name, uint64_t *name_hash);
 /* Frees the packed sequences of a built shard (the largest of its arrays: half a byte per base). csvgpu_alt_bases_resident returns
