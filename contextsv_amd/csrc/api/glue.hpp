@@ -158,10 +158,13 @@ int read_counters(csv_ctx *ctx, const ScanCounters *d_cnt, ScanCounters &h);
 ScanExtras scan_extras(ScanCounters *cnt, uint32_t depth_len, bool with_type, uint64_t *tile_range);
 void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, uint32_t depth_len, uint32_t overflow, uint32_t max_bucket,
                       ScanCounters *cnt, bool with_type, SortWs &w, csv_sig *sig_sorted, uint32_t *start_out, uint32_t *end_out);
-int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
-                uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges = nullptr, uint32_t cigar_pad = 0, void *items = nullptr,
-                int form = SCAN_FORM_WAVE, const CigarPack &pack = CigarPack());
-static inline CigarPack shard_pack(const csv_shard *sh) { return CigarPack{sh->cig_half, sh->esc_piece, sh->esc_tab}; }
+int depth_chain(csv_ctx *ctx, const DepthWs &ws, const ReadsView &v, bool unsorted, DepthArgs a);      // (a.ord is the chain's to set)
+// a resident shard as the two big kernels read it: the one place that holds the shard's form, pad and 16-bit arrays together
+static inline ReadsView shard_view(const csv_shard *sh)
+{
+    return ReadsView{sh->d, CigarPack{sh->cig_half, sh->esc_piece, sh->esc_tab}, sh->cigar_pad, sh->form, sh->ref_end, sh->q_start, sh->q_end, sh->ckpt,
+                     (ScanCounters *)sh->counters};
+}
 // shard.hip
 void shard_release(csv_shard *sh);                            // frees what the shard owns, and the shard
 csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh);         // the side arrays and the scan's split of a shard whose reads are in place; releases it on failure

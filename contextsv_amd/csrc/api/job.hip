@@ -60,7 +60,8 @@ static int job_queue_front(csv_ctx *ctx, csv_job *job)
 {
     csv_shard *sh = job->sh;
     hipStream_t s = ctx->stream;
-    ScanCounters *cnt = (ScanCounters *)sh->counters;
+    const ReadsView view = shard_view(sh);
+    ScanCounters *cnt = view.cnt;
     int rc;
     const bool sorted = sh->unsorted == 0;
     if (!job->ev_scan) job->ev_scan = get_event(ctx);          // (handed to the timers by an earlier pass of this job)
@@ -100,8 +101,8 @@ static int job_queue_front(csv_ctx *ctx, csv_job *job)
         // coordinate-sorted shards only, so the tile ranges are asked for there as well
         std::optional<TimerScope> ts;
         if (big == s) ts.emplace(ctx, CSV_K_CIGAR_SCAN, big);
-        launch_cigar_scan(big, ctx->n_cu, sh->d, sh->depth_len, job->min_oplen, job->min_mapq, 1, sh->sig_raw, sh->sig_cap, sh->ref_end,
-                          sh->q_start, sh->q_end, sh->ckpt, cnt, scan_extras(cnt, sh->depth_len, true, sorted ? sh->tile_range : nullptr), sh->owned ? sh->scan_split : nullptr, sh->form, sh->cigar_pad, shard_pack(sh));
+        launch_cigar_scan(big, ctx->n_cu, view, ScanArgs{sh->depth_len, job->min_oplen, job->min_mapq, 1, sh->sig_raw, sh->sig_cap,
+                                                         scan_extras(cnt, sh->depth_len, true, sorted ? sh->tile_range : nullptr), sh->owned ? sh->scan_split : nullptr});
     }
     job->depth_queued = false;
     if (sh->unsorted >= 0) {
@@ -116,7 +117,7 @@ static int job_queue_front(csv_ctx *ctx, csv_job *job)
             // streams whose only work is to wait share the four hardware queues with everything else and stalled the caller's context.)
             CSV_HIP(ctx, hipMemcpyAsync(job->pin, cnt, sizeof(ScanCounters), hipMemcpyDeviceToHost, big));
             CSV_HIP(ctx, hipEventRecord(job->ev_scan, big));
-            launch_depth_tiles(big, sh->d, nullptr, sh->ref_end, sh->ckpt, sh->depth_len, sh->depth, cnt, sh->tile_range, sh->cigar_pad, sh->depth_items, sh->form, shard_pack(sh));
+            launch_depth_tiles(big, view, DepthArgs{sh->depth_len, sh->depth, nullptr, sh->tile_range, sh->depth_items});
             CSV_HIP(ctx, hipEventRecord(job->ev_depth, big));
             turn.unlock();
             job->t0 = pair_timers ? t0 : nullptr;            // (handed to the timers with ev_scan / ev_depth when the job ends)
@@ -130,8 +131,7 @@ static int job_queue_front(csv_ctx *ctx, csv_job *job)
             CSV_HIP(ctx, hipEventRecord(job->ev_mid, cs));
             DepthWs dw;
             if ((rc = depth_work(ctx, sh, &dw))) return rc;
-            if ((rc = depth_chain(ctx, dw, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt,
-                                  sorted ? sh->tile_range : nullptr, sh->cigar_pad, sh->depth_items, sh->form, shard_pack(sh)))) return rc;
+            if ((rc = depth_chain(ctx, dw, view, sh->unsorted != 0, DepthArgs{sh->depth_len, sh->depth, nullptr, sorted ? sh->tile_range : nullptr, sh->depth_items}))) return rc;
             launch_min_pts(s, cnt, job->min_pts_pct);
         }
         job->depth_queued = true;
@@ -234,7 +234,7 @@ int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host
     if (!job->depth_queued) {
         DepthWs dw;
         if ((rc = depth_work(ctx, sh, &dw))) return rc;
-        if ((rc = depth_chain(ctx, dw, sh->d, sh->ref_end, sh->ckpt, sh->unsorted != 0, sh->depth_len, sh->depth, cnt, nullptr, sh->cigar_pad, sh->depth_items, sh->form, shard_pack(sh)))) return rc;
+        if ((rc = depth_chain(ctx, dw, shard_view(sh), sh->unsorted != 0, DepthArgs{sh->depth_len, sh->depth, nullptr, nullptr, sh->depth_items}))) return rc;
         launch_min_pts(s, cnt, job->min_pts_pct);
     }
 

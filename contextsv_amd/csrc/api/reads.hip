@@ -4,19 +4,12 @@
 
 namespace csv {
 
-struct DevReads {
-    csv_reads d;
-    int32_t *ref_end, *q_start, *q_end;
-    uint32_t *ckpt;
-    ScanCounters *cnt;
-};
-
 static constexpr uint64_t kMaxReadWords = 0x7ffff000ull;       // exclusive bound on one read's CIGAR words
 static inline uint32_t *bucket_off(ScanCounters *cnt) { return (uint32_t *)((char *)cnt + 256); }
 static inline uint32_t *bucket_cur(ScanCounters *cnt) { return bucket_off(cnt) + BK_N; }
 
-// copy a host shard into its carved slices (carve_reads); returns device views
-static int stage_reads(csv_ctx *ctx, const csv_reads *r, const ReadsWs &w, DevReads &o)
+// copy a host shard into its carved slices (carve_reads); o: the view of them (32-bit words, no pad behind them, the form of this call)
+static int stage_reads(csv_ctx *ctx, const csv_reads *r, const ReadsWs &w, ReadsView &o)
 {
     const uint64_t n = r->n_reads, m = r->n_cigar;
     hipStream_t s = ctx->stream;
@@ -28,8 +21,7 @@ static int stage_reads(csv_ctx *ctx, const csv_reads *r, const ReadsWs &w, DevRe
     CSV_HIP(ctx, hipMemcpyAsync(w.coff, r->cigar_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
     if (m) CSV_HIP(ctx, hipMemcpyAsync(w.cig, r->cigar, m * 4, hipMemcpyHostToDevice, s));
     CSV_HIP(ctx, hipMemsetAsync(w.cnt, 0, kCntBytes, s));
-    o.ref_end = w.ref_end; o.q_start = w.q_start; o.q_end = w.q_end; o.cnt = w.cnt; o.ckpt = w.ckpt;
-    o.d = *r;
+    o = ReadsView{*r, CigarPack(), 0, scan_form(ctx, n, m), w.ref_end, w.q_start, w.q_end, w.ckpt, w.cnt};
     o.d.pos = w.pos; o.d.flag = w.flag; o.d.mapq = w.mapq; o.d.tid = nullptr; o.d.cigar_off = w.coff; o.d.cigar = w.cig;
     return CSV_OK;
 }
@@ -136,38 +128,39 @@ void order_signatures(csv_ctx *ctx, const csv_sig *sig_raw, uint64_t n, uint32_t
     launch_sig_fix_ties_gather(ctx->stream, sig_raw, in_out ? w.k1 : w.k0, in_out ? w.v1 : w.v0, n, sig_sorted, start_out, end_out);
 }
 
-// depth chain on device arrays. pmax / ord / range scratch is `ws` (carve_depth); `ranges` != nullptr: the scan already produced the
+// depth chain on device arrays. pmax / ord / range scratch is `ws` (carve_depth); a.tile_range != nullptr: the scan already produced the
 // tiles' candidate ranges (coordinate-sorted shard) and only the tile kernel remains.
-int depth_chain(csv_ctx *ctx, const DepthWs &ws, const csv_reads &d, const int32_t *ref_end, const uint32_t *ckpt, bool unsorted, uint32_t depth_len,
-                uint32_t *depth, ScanCounters *cnt, const uint64_t *ranges, uint32_t cigar_pad, void *items, int form, const CigarPack &pack)
+int depth_chain(csv_ctx *ctx, const DepthWs &ws, const ReadsView &v, bool unsorted, DepthArgs a)
 {
+    const csv_reads &d = v.d;
     const uint64_t n = d.n_reads;
     TimerScope ts(ctx, CSV_K_DEPTH);
-    if (n == 0 || depth_len == 0) {
-        if (depth && depth_len) CSV_HIP(ctx, hipMemsetAsync(depth, 0, (size_t)depth_len * 4, ctx->stream));
+    a.ord = nullptr;
+    if (n == 0 || a.depth_len == 0) {
+        if (a.depth && a.depth_len) CSV_HIP(ctx, hipMemsetAsync(a.depth, 0, (size_t)a.depth_len * 4, ctx->stream));
         return CSV_OK;
     }
-    if (ranges && !unsorted) {
-        launch_depth_tiles(ctx->stream, d, nullptr, ref_end, ckpt, depth_len, depth, cnt, ranges, cigar_pad, items, form, pack);
+    if (a.tile_range && !unsorted) {
+        launch_depth_tiles(ctx->stream, v, a);
         return CSV_OK;
     }
     int32_t *pmax = ws.pmax;
     void *ptmp = ws.ptmp;
     uint64_t *ttmp = ws.ttmp;
-    const uint32_t *ord = nullptr;
     const int32_t *pos_s = d.pos;
-    const int32_t *end_s = ref_end;
+    const int32_t *end_s = v.ref_end;
     if (unsorted) {
         // shard not coordinate-sorted: sort the read indices by pos on device and feed the tile search through `ord`
         uint32_t *pos_g = ws.pos_g, *end_g = ws.end_g;
         const uint32_t *perm = sorted_perm(ctx, d.pos, n, ws.w);
         launch_gather_u32(ctx->stream, (const uint32_t *)d.pos, perm, n, pos_g);
-        launch_gather_u32(ctx->stream, (const uint32_t *)ref_end, perm, n, end_g);
-        ord = perm; pos_s = (const int32_t *)pos_g; end_s = (const int32_t *)end_g;
+        launch_gather_u32(ctx->stream, (const uint32_t *)v.ref_end, perm, n, end_g);
+        a.ord = perm; pos_s = (const int32_t *)pos_g; end_s = (const int32_t *)end_g;
     }
     launch_prefix_max(ctx->stream, end_s, pmax, n, ptmp);
-    launch_depth_ranges(ctx->stream, pos_s, pmax, n, depth_len, ttmp);
-    launch_depth_tiles(ctx->stream, d, ord, ref_end, ckpt, depth_len, depth, cnt, ttmp, cigar_pad, items, form, pack);
+    launch_depth_ranges(ctx->stream, pos_s, pmax, n, a.depth_len, ttmp);
+    a.tile_range = ttmp;
+    launch_depth_tiles(ctx->stream, v, a);
     return CSV_OK;
 }
 
@@ -189,12 +182,11 @@ int csvgpu_cigar_scan(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, 
     if ((rc = arena_reserve_for(ctx, ctx->arena, "cigar_scan", [&](Arena &a) {
             return carve_reads(a, reads->n_reads, reads->n_cigar, rw) && take(a, sig_raw, cap * sizeof(csv_sig) + 16);
         }))) return rc;
-    DevReads dr;
+    ReadsView dr;
     if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
-        launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, min_oplen, min_mapq, 1, sig_raw, cap, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt,
-                          scan_extras(dr.cnt, depth_len, false, nullptr), nullptr, scan_form(ctx, reads->n_reads, reads->n_cigar));
+        launch_cigar_scan(ctx->stream, ctx->n_cu, dr, ScanArgs{depth_len, min_oplen, min_mapq, 1, sig_raw, cap, scan_extras(dr.cnt, depth_len, false, nullptr), nullptr});
     }
     ScanCounters h;
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
@@ -219,12 +211,11 @@ int csvgpu_aln_intervals(csv_ctx *ctx, const csv_reads *reads, int32_t *ref_end,
     (void)hipSetDevice(ctx->device);
     ReadsWs rw;
     if ((rc = arena_reserve_for(ctx, ctx->arena, "aln_intervals", [&](Arena &a) { return carve_reads(a, reads->n_reads, reads->n_cigar, rw); }))) return rc;
-    DevReads dr;
+    ReadsView dr;
     if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
-        launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, 0, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
-                          scan_form(ctx, reads->n_reads, reads->n_cigar));
+        launch_cigar_scan(ctx->stream, ctx->n_cu, dr, ScanArgs{0, 0, 0, 0, nullptr, 0, ScanExtras(), nullptr});
     }
     const uint64_t n = reads->n_reads;
     if (n) {
@@ -246,19 +237,17 @@ int csvgpu_depth(csv_ctx *ctx, const csv_reads *reads, uint32_t depth_len, uint3
     if ((rc = arena_reserve_for(ctx, ctx->arena, "depth", [&](Arena &a) {
             return carve_reads(a, reads->n_reads, reads->n_cigar, rw) && take(a, d_depth, (size_t)depth_len * 4 + 16);
         }))) return rc;
-    DevReads dr;
+    ReadsView dr;
     if ((rc = stage_reads(ctx, reads, rw, dr))) return rc;
     {
         TimerScope ts(ctx, CSV_K_CIGAR_SCAN);
-        launch_cigar_scan(ctx->stream, ctx->n_cu, dr.d, depth_len, 0, 0, 0, nullptr, 0, dr.ref_end, dr.q_start, dr.q_end, dr.ckpt, dr.cnt, ScanExtras(), nullptr,
-                          scan_form(ctx, reads->n_reads, reads->n_cigar));
+        launch_cigar_scan(ctx->stream, ctx->n_cu, dr, ScanArgs{depth_len, 0, 0, 0, nullptr, 0, ScanExtras(), nullptr});
     }
     ScanCounters h;
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
     DepthWs dw;
     if ((rc = arena_reserve_for(ctx, ctx->work, "depth chain", [&](Arena &a) { return carve_depth(a, reads->n_reads, depth_len, dw); }))) return rc;
-    if ((rc = depth_chain(ctx, dw, dr.d, dr.ref_end, dr.ckpt, h.unsorted != 0, depth_len, d_depth, dr.cnt, nullptr, 0, nullptr,
-                          scan_form(ctx, reads->n_reads, reads->n_cigar)))) return rc;
+    if ((rc = depth_chain(ctx, dw, dr, h.unsorted != 0, DepthArgs{depth_len, d_depth, nullptr, nullptr, nullptr}))) return rc;
     if (depth && depth_len) CSV_HIP(ctx, hipMemcpyAsync(depth, d_depth, (size_t)depth_len * 4, hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = read_counters(ctx, dr.cnt, h))) return rc;
     if (sum) *sum = h.depth_sum;

@@ -233,7 +233,8 @@ int csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *sh, int32_t *pos, uint16_t
     const uint64_t n = sh->d.n_reads;
     if ((rc = t.down(pos, sh->d.pos, n * 4)) || (rc = t.down(flag, sh->d.flag, n * 2)) || (rc = t.down(mapq, sh->d.mapq, n)) ||
         (rc = t.down(cigar_off, sh->d.cigar_off, (n + 1) * 8))) return rc;
-    if (!sh->cig_half) { if ((rc = t.down(cigar, sh->d.cigar, sh->d.n_cigar * 4))) return rc; }
+    const CigarPack pack = shard_view(sh).pack;
+    if (!pack.half) { if ((rc = t.down(cigar, sh->d.cigar, sh->d.n_cigar * 4))) return rc; }
     else if (cigar) {
         // a packed shard (shard.hip) gives the caller's 32-bit words back: unpacked on the device one piece of the transfer at a time
         uint32_t *stage = nullptr;
@@ -241,7 +242,7 @@ int csvgpu_shard_fetch_reads(csv_ctx *ctx, csv_shard *sh, int32_t *pos, uint16_t
         const uint64_t per = kPiece / 4;
         for (uint64_t o = 0; o < sh->d.n_cigar; o += per) {
             const uint64_t k = std::min(per, sh->d.n_cigar - o);
-            launch_cigar_unpack(ctx->stream, shard_pack(sh), o, k, stage);
+            launch_cigar_unpack(ctx->stream, pack, o, k, stage);
             CSV_HIP(ctx, hipGetLastError());
             if ((rc = t.down(cigar + o, stage, k * 4))) return rc;
         }

@@ -187,12 +187,41 @@ struct CigarPack {
     const uint32_t *piece = nullptr;
     const uint64_t *tab = nullptr;
 };
+// A set of reads on the device as the scan and the depth pass see it: what both kernels read of one shard, and how to read it. Made by
+// shard_view (a resident shard) and stage_reads (a host-pointer call's staged arrays), nowhere else. What the two launchers rely on:
+//  - form is what scan_form chose for (n_reads, n_cigar): with 2^32 - 1 ops or more that is SCAN_FORM_WAVE whatever was asked for (the
+//    short-read forms index words in 32 bits), so neither launcher tests n_cigar again; a scan's `split` was built for this form.
+//  - cigar_pad counts the zeroed elements allocated behind the op array, in that array's own unit, and means nothing without it.
+//  - pack.half != nullptr (the 16-bit form) means d.cigar == nullptr, form == SCAN_FORM_WAVE, and a pad of cigar_pad halfwords behind the
+//    END OF THE LAST 512-OP PIECE (the allocation and why it covers every load of both kernels: shard_pack_cigar in api/shard.hip);
+//    otherwise d.cigar holds the 32-bit words, with cigar_pad words behind d.cigar[n_cigar], and pack is all null.
+struct ReadsView {
+    csv_reads     d;                   // device pointers
+    CigarPack     pack;
+    uint32_t      cigar_pad = 0;
+    int           form = SCAN_FORM_WAVE;
+    int32_t      *ref_end = nullptr, *q_start = nullptr, *q_end = nullptr;      // per read: the scan writes them, the depth pass reads ref_end
+    uint32_t     *ckpt = nullptr;      // ckpt_bytes(n_cigar): the scan's reference-offset checkpoints, where the depth pass starts its walks
+    ScanCounters *cnt = nullptr;
+};
+// what varies from one launch to the next on the same view
+struct ScanArgs {
+    uint32_t        depth_len, min_oplen, min_mapq;
+    int             emit;              // 0: the per-read arrays and the checkpoints only
+    csv_sig        *sig_out;
+    uint64_t        sig_cap;
+    ScanExtras      extras;
+    const uint64_t *split;             // launch_scan_split's table for the same n_cu, shard and form, or null
+};
+struct DepthArgs {
+    uint32_t        depth_len;
+    uint32_t       *depth;
+    const uint32_t *ord;               // null: the reads are coordinate-sorted; otherwise the tile ranges index `ord`
+    const uint64_t *tile_range;
+    void           *items;             // depth_items_bytes(depth_len) of scratch for the tiles' work lists, or null: every tile builds its own
+};
 int scan_form_for(uint64_t n_reads, uint64_t n_cigar);          // by mean CIGAR words per read: SCAN_FORM_WAVE or SCAN_FORM_ROWS16
-void launch_cigar_scan(hipStream_t s, int n_cu, const csv_reads &d, uint32_t depth_len, uint32_t min_oplen,
-                       uint32_t min_mapq, int emit, csv_sig *sig_out, uint64_t sig_cap,
-                       int32_t *ref_end, int32_t *q_start, int32_t *q_end, uint32_t *ckpt, ScanCounters *cnt, const ScanExtras &extras = ScanExtras(),
-                       const uint64_t *split = nullptr /* launch_scan_split's table for the same n_cu, shard and form */, int form = SCAN_FORM_WAVE,
-                       uint32_t cigar_pad_words = 0 /* allocated words behind d.cigar[n_cigar] */, const CigarPack &pack = CigarPack() /* wave form only */);
+void launch_cigar_scan(hipStream_t s, int n_cu, const ReadsView &v, const ScanArgs &a);
 size_t scan_split_bytes(int n_cu, uint64_t n_reads, int form);
 void launch_scan_split(hipStream_t s, int n_cu, const csv_reads &d, uint64_t *split, int form);      // once per resident shard
 void launch_validate_offsets(hipStream_t s, const uint64_t *cigar_off, uint64_t n_reads, uint64_t n_cigar, uint64_t max_words, uint32_t *bad /* zeroed; set to 1 */);
@@ -208,13 +237,9 @@ static inline uint32_t depth_n_tiles(uint32_t depth_len) { return (uint32_t)(((u
 size_t depth_tiles_tmp_bytes(uint32_t depth_len);
 // ranges from a prefix maximum of the read ends, for shards whose ranges the scan did not produce (unsorted: in `ord` order)
 void launch_depth_ranges(hipStream_t s, const int32_t *pos_s, const int32_t *pmax_end, uint64_t n_reads, uint32_t depth_len, uint64_t *tile_range);
-// ord == nullptr: reads are coordinate-sorted; otherwise the tile ranges index `ord`.
-// ckpt: reference offset of the owning read at every CKPT_WORDS-word CIGAR boundary (written by launch_cigar_scan).
+// v.ckpt: reference offset of the owning read at every CKPT_WORDS-word CIGAR boundary (written by launch_cigar_scan); v.form: how the tiles walk their items
 size_t depth_items_bytes(uint32_t depth_len);
-void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, const int32_t *ref_end, const uint32_t *ckpt,
-                        uint32_t depth_len, uint32_t *depth, ScanCounters *cnt, const uint64_t *tile_range, uint32_t cigar_pad_words = 0,
-                        void *items = nullptr, int form = SCAN_FORM_WAVE /* how the tiles walk their items: SCAN_FORM_* */,
-                        const CigarPack &pack = CigarPack() /* wave form only */);
+void launch_depth_tiles(hipStream_t s, const ReadsView &v, const DepthArgs &a);
 // cigarpack.hip: the 16-bit form made and undone on the device (cigar_pack_core.hpp has the rule)
 void launch_cigar_esc_count(hipStream_t s, const uint32_t *cigar, uint64_t n_cigar, uint32_t *piece /* [n_pieces + 1]: escapes per piece, 0 last */);
 void launch_cigar_pack(hipStream_t s, const uint32_t *cigar, uint64_t n_cigar, const uint32_t *piece /* exclusive sums */, uint16_t *half, uint64_t *tab);

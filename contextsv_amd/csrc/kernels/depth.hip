@@ -724,36 +724,34 @@ void launch_depth_ranges(hipStream_t s, const int32_t *pos_s, const int32_t *pma
 // null: every tile builds its own list
 size_t depth_items_bytes(uint32_t depth_len) { return align_up((size_t)depth_n_tiles(depth_len) * (WL_CAP * sizeof(DepthItem) + sizeof(uint32_t)), 256); }
 
-void launch_depth_tiles(hipStream_t s, const csv_reads &d, const uint32_t *ord, const int32_t *ref_end, const uint32_t *ckpt,
-                        uint32_t depth_len, uint32_t *depth, ScanCounters *cnt, const uint64_t *tile_range, uint32_t cigar_pad_words, void *items, int form,
-                        const CigarPack &pack)
+void launch_depth_tiles(hipStream_t s, const ReadsView &v, const DepthArgs &a)
 {
-    if (depth_len == 0) return;
-    const unsigned tiles = depth_n_tiles(depth_len);
+    const csv_reads &d = v.d;
+    if (a.depth_len == 0) return;
+    const unsigned tiles = depth_n_tiles(a.depth_len);
     const int vec_ok = (((uintptr_t)d.cigar) & 15u) == 0;
-    const int dvec_ok = (((uintptr_t)depth) & 15u) == 0;
-    DepthItem *it = (DepthItem *)items;
-    uint32_t *n_it = items ? (uint32_t *)(it + (size_t)tiles * WL_CAP) : nullptr;
-    if (items)
-        hipLaunchKernelGGL(depth_items_kernel, dim3(tiles), dim3(ITEMS_THREADS), 0, s, d.pos, d.flag, d.cigar_off, ord, ref_end, tile_range, ckpt, depth_len, it, n_it);
-    if (pack.half) {
-        // The 16-bit form (wave form only: shard.hip packs no other). A lane's load starts at an op below the item's last op rounded up to the
-        // DEPTH_PACKED_WPL ops it takes, so below n_cigar + DEPTH_PACKED_WPL - 1, and is as many ops long: inside the array's zeroed pad of
-        // CIGAR_PAD_WORDS halfwords behind its last piece.
+    const int dvec_ok = (((uintptr_t)a.depth) & 15u) == 0;
+    DepthItem *it = (DepthItem *)a.items;
+    uint32_t *n_it = a.items ? (uint32_t *)(it + (size_t)tiles * WL_CAP) : nullptr;
+    if (a.items)
+        hipLaunchKernelGGL(depth_items_kernel, dim3(tiles), dim3(ITEMS_THREADS), 0, s, d.pos, d.flag, d.cigar_off, a.ord, v.ref_end, a.tile_range, v.ckpt, a.depth_len, it, n_it);
+    const auto launch = [&](auto kernel, const uint32_t *ops, int ops_vec_ok, const uint32_t *piece, const uint64_t *tab) {
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off, ops, ops_vec_ok, dvec_ok, a.ord, v.ref_end,
+                           a.tile_range, v.ckpt, a.depth_len, a.depth, v.cnt, it, n_it, piece, tab);
+    };
+    if (v.pack.half) {
+        // The 16-bit form. A lane's load starts at an op below the item's last op rounded up to the DEPTH_PACKED_WPL ops it takes, so below
+        // n_cigar + DEPTH_PACKED_WPL - 1, and is as many ops long: inside the pad behind the last piece (ReadsView).
         static_assert(CIGAR_PAD_WORDS >= 2 * DEPTH_PACKED_WPL, "a lane's load may start DEPTH_PACKED_WPL - 1 ops behind the array's last op");
-        hipLaunchKernelGGL((depth_tile_kernel<true, WAVE, DEPTH_PACKED_WPL>), dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off,
-                           reinterpret_cast<const uint32_t *>(pack.half), 1, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it, pack.piece, pack.tab);
+        launch(depth_tile_kernel<true, WAVE, DEPTH_PACKED_WPL>, reinterpret_cast<const uint32_t *>(v.pack.half), 1, v.pack.piece, v.pack.tab);
         return;
     }
-    if (form != SCAN_FORM_WAVE && d.n_cigar >= 0xffffffffull) form = SCAN_FORM_WAVE;
-    const bool padded = vec_ok && cigar_pad_words >= 4 * WAVE;
-#define CSV_TILE_LAUNCH(PAD, GL)                                                                                                                 \
-    hipLaunchKernelGGL((depth_tile_kernel<PAD, GL>), dim3(tiles), dim3(DEPTH_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.cigar_off, d.cigar, \
-                       vec_ok, dvec_ok, ord, ref_end, tile_range, ckpt, depth_len, depth, cnt, it, n_it, nullptr, nullptr)
-    if (form == SCAN_FORM_ROWS16 || form == SCAN_FORM_LANES) { if (padded) CSV_TILE_LAUNCH(true, 16); else CSV_TILE_LAUNCH(false, 16); }
-    else if (form == SCAN_FORM_ROWS8) { if (padded) CSV_TILE_LAUNCH(true, 8); else CSV_TILE_LAUNCH(false, 8); }
-    else { if (padded) CSV_TILE_LAUNCH(true, WAVE); else CSV_TILE_LAUNCH(false, WAVE); }
-#undef CSV_TILE_LAUNCH
+    const bool padded = vec_ok && v.cigar_pad >= 4 * WAVE;
+    const auto words = [&](auto kernel) { launch(kernel, d.cigar, vec_ok, nullptr, nullptr); };
+    if (v.form == SCAN_FORM_ROWS16 || v.form == SCAN_FORM_LANES) { if (padded) words(depth_tile_kernel<true, 16>); else words(depth_tile_kernel<false, 16>); }
+    else if (v.form == SCAN_FORM_ROWS8) { if (padded) words(depth_tile_kernel<true, 8>); else words(depth_tile_kernel<false, 8>); }
+    else if (padded) words(depth_tile_kernel<true, WAVE>);
+    else words(depth_tile_kernel<false, WAVE>);
 }
 
 // min_pts = (int)ceil(mean_cov * pct), or 5 when pct <= 0 (sv_caller.cpp:723-728); mean = sum / #non-zero

@@ -1054,50 +1054,30 @@ void launch_scan_split(hipStream_t s, int n_cu, const csv_reads &d, uint64_t *sp
     hipLaunchKernelGGL(scan_split_kernel, dim3((unsigned)((n_waves + 1 + 3) / 4)), dim3(256), 0, s, d.cigar_off, d.n_reads, d.n_cigar, n_waves, split);
 }
 
-void launch_cigar_scan(hipStream_t s, int n_cu, const csv_reads &d, uint32_t depth_len, uint32_t min_oplen,
-                       uint32_t min_mapq, int emit, csv_sig *sig_out, uint64_t sig_cap,
-                       int32_t *ref_end, int32_t *q_start, int32_t *q_end, uint32_t *ckpt, ScanCounters *cnt, const ScanExtras &x, const uint64_t *split,
-                       int form, uint32_t cigar_pad_words, const CigarPack &pack)
+void launch_cigar_scan(hipStream_t s, int n_cu, const ReadsView &v, const ScanArgs &a)
 {
+    const csv_reads &d = v.d;
+    const ScanExtras &x = a.extras;
     if (d.n_reads == 0) return;
-    if (pack.half) {
-        // The 16-bit form (wave form only: shard.hip packs no other). The array is allocated to the end of its last 512-op piece (+ pad), and
-        // a wave's pieces are [ring_base, ring_base + 512 ring_total) with ring_base a multiple of 512 and the last piece the one that holds
-        // op n_cigar - 1 at the most: every 1 KiB LDS-DMA lies inside the allocation, with no bounds test in the kernel.
-        hipLaunchKernelGGL(cigar_scan_kernel<true>, dim3(scan_grid(n_cu, d.n_reads, SCAN_FORM_WAVE)), dim3(SCAN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag,
-                           d.mapq, d.cigar_off, reinterpret_cast<const uint32_t *>(pack.half), 1, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap,
-                           ref_end, q_start, q_end, ckpt, cnt, (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift,
-                           split, pack.piece, pack.tab);
-        return;
-    }
-    static_assert(SCAN_WAVES == RS_WAVES, "one split table layout for both forms");
-    if (form != SCAN_FORM_WAVE && d.n_cigar >= 0xffffffffull) { form = SCAN_FORM_WAVE; split = nullptr; }
-    const unsigned grid = scan_grid(n_cu, d.n_reads, form);
+    static_assert(SCAN_WAVES == RS_WAVES && LN_WAVES == SCAN_WAVES, "one split table layout for every form");
+    const unsigned grid = scan_grid(n_cu, d.n_reads, v.form);
+    // every scan kernel takes this list; they differ in what they are told of the op array (`ops`) and in what follows `split` (`tail`)
+    const auto launch = [&](auto kernel, unsigned threads, auto... ops) {
+        return [&, kernel, threads, ops...](auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.mapq, d.cigar_off, ops..., a.depth_len,
+                               scan_start_limit(a.depth_len), a.min_oplen, a.min_mapq, a.emit, a.sig_out, a.sig_cap, v.ref_end, v.q_start, v.q_end, v.ckpt, v.cnt,
+                               (unsigned long long *)x.tile_range, x.n_tiles, a.emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift, a.split, tail...);
+        };
+    };
+    // the 16-bit form: 1 KiB LDS-DMA pieces with no bounds test (the allocation that covers them: ReadsView)
+    if (v.pack.half) { launch(cigar_scan_kernel<true>, SCAN_THREADS, reinterpret_cast<const uint32_t *>(v.pack.half), 1)(v.pack.piece, v.pack.tab); return; }
     const int vec_ok = (((uintptr_t)d.cigar) & 15u) == 0;
-    if (form == SCAN_FORM_WAVE) {
-        hipLaunchKernelGGL(cigar_scan_kernel<false>, dim3(grid), dim3(SCAN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag,
-                           d.mapq, d.cigar_off, d.cigar, vec_ok, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap,
-                           ref_end, q_start, q_end, ckpt, cnt, (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift,
-                           split, nullptr, nullptr);
-        return;
-    }
-    const bool padded = vec_ok && cigar_pad_words >= 128;
-#define CSV_ROWS_LAUNCH(GL, PAD)                                                                                                                       \
-    hipLaunchKernelGGL((cigar_scan_rows_kernel<GL, PAD>), dim3(grid), dim3(RS_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.mapq, d.cigar_off,   \
-                       d.cigar, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap, ref_end, q_start, q_end, ckpt, cnt,  \
-                       (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift, split)
-    if (form == SCAN_FORM_ROWS16) { if (padded) CSV_ROWS_LAUNCH(16, true); else CSV_ROWS_LAUNCH(16, false); }
-    else if (form == SCAN_FORM_ROWS8) { if (padded) CSV_ROWS_LAUNCH(8, true); else CSV_ROWS_LAUNCH(8, false); }
-    else {
-        static_assert(LN_WAVES == SCAN_WAVES, "one split table layout for every form");
-#define CSV_LANES_LAUNCH(PAD)                                                                                                                        \
-    hipLaunchKernelGGL((cigar_scan_lanes_kernel<PAD>), dim3(grid), dim3(LN_THREADS), 0, s, d.n_reads, d.n_cigar, d.pos, d.flag, d.mapq, d.cigar_off,   \
-                       d.cigar, depth_len, scan_start_limit(depth_len), min_oplen, min_mapq, emit, sig_out, sig_cap, ref_end, q_start, q_end, ckpt, cnt,  \
-                       (unsigned long long *)x.tile_range, x.n_tiles, emit ? x.bucket_hist : nullptr, x.type_pos, x.bucket_shift, split)
-        if (padded) CSV_LANES_LAUNCH(true); else CSV_LANES_LAUNCH(false);
-#undef CSV_LANES_LAUNCH
-    }
-#undef CSV_ROWS_LAUNCH
+    if (v.form == SCAN_FORM_WAVE) { launch(cigar_scan_kernel<false>, SCAN_THREADS, d.cigar, vec_ok)(nullptr, nullptr); return; }
+    const bool padded = vec_ok && v.cigar_pad >= 128;
+    if (v.form == SCAN_FORM_ROWS16) { if (padded) launch(cigar_scan_rows_kernel<16, true>, RS_THREADS, d.cigar)(); else launch(cigar_scan_rows_kernel<16, false>, RS_THREADS, d.cigar)(); }
+    else if (v.form == SCAN_FORM_ROWS8) { if (padded) launch(cigar_scan_rows_kernel<8, true>, RS_THREADS, d.cigar)(); else launch(cigar_scan_rows_kernel<8, false>, RS_THREADS, d.cigar)(); }
+    else if (padded) launch(cigar_scan_lanes_kernel<true>, LN_THREADS, d.cigar)();
+    else launch(cigar_scan_lanes_kernel<false>, LN_THREADS, d.cigar)();
 }
 
 // cigar_off of arrays that already live in HBM (csvgpu_shard_wrap_dev) gets the test the host arrays get in check_reads

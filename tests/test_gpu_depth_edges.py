@@ -8,12 +8,14 @@ Three ways in, every form of the walk (a wave per item; groups of 16 / 8 lanes; 
      tile ranges when the shard is coordinate-sorted;
   3. wrapped device arrays (twice: the first job does not know yet whether the shard is sorted), the CIGAR array at byte offsets 0, 4, 8
      and 12 of its buffer: offset 0 is unpadded with 16-byte loads allowed, the others are the kernels' vec_ok == 0 branches (dword loads).
+Ways 2 and 3 once more behind a gate, where the job launches scan and depth tiles itself on the gate's stream (test_behind_a_gate).
 Not covered, because no entry point reaches it: a depth OUTPUT that is not 16-byte aligned (dvec_ok == 0)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import contextsv_amd as cs
 import depth_edge_inputs as de
 
 pytestmark = pytest.mark.gpu
@@ -112,6 +114,29 @@ def test_host_and_resident(ctx, oracle, form, case):
 def test_wrapped_at_every_alignment(ctx, oracle, form, case):
     name, reads, depth_len = case
     _check(ctx, oracle, reads, depth_len, ("wrapped",))
+
+
+_GATED = [c for c in _WRAPPED if c[0] in ("A/len%d" % (2 * de.T + 5), "D/tail1")]
+
+
+@pytest.mark.parametrize("case", _GATED, ids=[c[0] for c in _GATED])
+def test_behind_a_gate(ctx, oracle, form, case):
+    """The job's other caller of the two launchers: behind a gate a coordinate-sorted shard's scan and depth tiles go straight onto the
+    gate's stream, with no chain between. Resident (padded; the wave form at 16 bits and, with packing off, at 32) and wrapped (unpadded,
+    every alignment; the first job of a wrapped shard does not know its order yet and still takes the chain)."""
+    name, reads, depth_len = case
+    assert np.all(np.diff(reads.pos.astype(np.int64)) >= 0)           # or the gate would not take it
+    gate = cs.Gate()
+    ctx.set_gate(gate)
+    try:
+        _check(ctx, oracle, reads, depth_len, ("resident", "wrapped"))
+        if form == 0:
+            ctx.set_cigar_packing(False)
+            _check(ctx, oracle, reads, depth_len, ("resident",))
+    finally:
+        ctx.set_cigar_packing(True)
+        ctx.set_gate(None)
+        gate.close()
 
 
 @pytest.mark.parametrize("scan_form", [0, 1], ids=["wave", "rows16"])
