@@ -16,6 +16,11 @@ def _as_u8(x) -> np.ndarray:
     return np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, np.uint8)
 
 
+def _handles(objs):
+    """the C handles of shards, tables, ... as a void* array for the C-ABI (None: a null handle; at least one element long)"""
+    return (C.c_void_p * max(len(objs), 1))(*[None if o is None else o.h for o in objs])
+
+
 def _is_dev(t, element_size: int) -> bool:
     """a contiguous torch tensor on a device, of that element size"""
     return t.is_cuda and t.is_contiguous() and t.element_size() == element_size
@@ -258,7 +263,7 @@ class Context:
         iteration order of the reference's qname map -> list of uint32 arrays."""
         supp_hash = np.ascontiguousarray(supp_hash, np.uint64)
         n = len(shards)
-        hs = (C.c_void_p * max(n, 1))(*[s.h for s in shards])
+        hs = _handles(shards)
         cap = capacity if capacity is not None else max(1024, 2 * len(supp_hash))
         out = np.zeros(max(cap, 1), np.uint32)
         off = np.zeros(n + 1, np.uint64)
@@ -273,7 +278,7 @@ class Context:
         `capacity` exercises the retry of _finish after CSV_ECAPACITY."""
         supp_hash = np.ascontiguousarray(supp_hash, np.uint64)
         n = len(shards)
-        hs = (C.c_void_p * max(n, 1))(*[s.h for s in shards])
+        hs = _handles(shards)
         self._check(self.lib.csvgpu_split_order_begin(self.h, n, hs, min_mapq))
         out = np.zeros(max(capacity, 1), np.uint32)
         off = np.zeros(n + 1, np.uint64)
@@ -289,7 +294,7 @@ class Context:
         """csvgpu_split_order_begin_self (the supplementary hashes are those of the same shards' supplementary records; the whole order is
         queued) + csvgpu_split_order_finish without hashes."""
         n = len(shards)
-        hs = (C.c_void_p * max(n, 1))(*[s.h for s in shards])
+        hs = _handles(shards)
         self._check(self.lib.csvgpu_split_order_begin_self(self.h, n, hs, min_mapq))
         out = np.zeros(max(capacity, 1), np.uint32)
         off = np.zeros(n + 1, np.uint64)
@@ -328,7 +333,7 @@ class Context:
         n_seg = len(seg_off) - 1
         if n_seg < 0 or len(shards) != n_seg:
             raise ValueError(what + ": seg_off must have one entry more than there are shards")
-        hs = (C.c_void_p * max(n_seg, 1))(*[s.h for s in shards])
+        hs = _handles(shards)
         return seg_off, n_seg, hs
 
     def split_tables_resident(self, shards, refs, seg_off) -> "SplitTables":
@@ -397,7 +402,7 @@ class Context:
             raise ValueError(what + ": array lengths disagree")
         if (len(reg_off) and int(reg_off[-1]) != R) or int(so[-1]) != len(sp):
             raise ValueError(what + ": reg_off must end at the number of regions, snp_off at the number of SNP records")
-        hs = (C.c_void_p * max(len(shards), 1))(*[s.h for s in shards])
+        hs = _handles(shards)
         mc = np.ascontiguousarray(mean_cov, np.float64)
         t = _lib.csv_cn_regions(len(shards), C.cast(hs, C.c_void_p), ptr(mc), ptr(reg_off), ptr(rs), ptr(re), ptr(ss), ptr(so), ptr(sp), ptr(sb), ptr(sf))
         return t, (hs, mc, reg_off, rs, re, ss, so, sp, sb, sf), R
@@ -411,19 +416,8 @@ class Context:
         with the exact count in the exception's `needed`."""
         t, keep, R = self._cn_regions(shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb, "cn_observations")
         cap = capacity if capacity is not None else int(np.maximum(keep[5], np.diff(keep[6]).astype(np.int64)).sum()) + 3 * len(keep[7])
-        off = np.zeros(R + 1, np.uint64)
-        pos = np.zeros(max(cap, 1), np.uint32)
-        baf, pfb, l2 = (np.zeros(max(cap, 1), np.float64) for _ in range(3))
-        snp = np.zeros(max(cap, 1), np.uint8)
-        n = C.c_uint64(cap)
-        rc = self.lib.csvgpu_cn_observations_resident_many(self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n))
-        if rc == _lib.CSV_ECAPACITY:
-            e = self._error(rc)
-            e.needed = int(n.value)
-            raise e
-        self._check(rc)
-        k = int(n.value)
-        return dict(obs_off=off, pos=pos[:k].copy(), baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
+        return self._cn_call(R, cap, False, False, True, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_observations_resident_many(
+            self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
 
     def cn_decode(self, hmm: csv_hmm, shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb,
                   want_observations: bool = False) -> dict:
@@ -431,20 +425,8 @@ class Context:
         -> dict(obs_off, pos, states, loglik), and baf / pfb / log2_cov / is_snp with want_observations."""
         t, keep, R = self._cn_regions(shards, mean_cov, reg_off, region_start, region_end, sample_size, snp_off, snp_pos, snp_baf, snp_pfb, "cn_decode")
         cap = int(np.maximum(keep[5], np.diff(keep[6]).astype(np.int64)).sum()) + 3 * len(keep[7])
-        off = np.zeros(R + 1, np.uint64)
-        pos = np.zeros(max(cap, 1), np.uint32)
-        states = np.zeros(max(cap, 1), np.int32)
-        ll = np.zeros(max(R, 1), np.float64)
-        baf, pfb, l2 = ((np.zeros(max(cap, 1), np.float64) if want_observations else None) for _ in range(3))
-        snp = np.zeros(max(cap, 1), np.uint8) if want_observations else None
-        n = C.c_uint64(cap)
-        self._check(self.lib.csvgpu_cn_decode_resident_many(self.h, C.byref(t), C.byref(hmm), ptr(off), ptr(pos), ptr(states), ptr(ll), ptr(baf), ptr(pfb),
-                                                            ptr(l2), ptr(snp), C.byref(n)))
-        k = int(n.value)
-        out = dict(obs_off=off, pos=pos[:k].copy(), states=states[:k].copy(), loglik=ll[:R].copy())
-        if want_observations:
-            out.update(baf=baf[:k].copy(), pfb=pfb[:k].copy(), log2_cov=l2[:k].copy(), is_snp=snp[:k].copy())
-        return out
+        return self._cn_call(R, cap, False, True, want_observations, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_decode_resident_many(
+            self.h, C.byref(t), C.byref(hmm), ptr(off), ptr(pos), ptr(st), ptr(ll), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
 
     # -------------------------------------------------------------------------------- resident SNP tables
     def _snp_table(self, what, arrays, counts):
@@ -525,15 +507,16 @@ class Context:
             raise ValueError(what + ": array lengths disagree")
         if len(reg_off) and int(reg_off[-1]) != R:
             raise ValueError(what + ": reg_off must end at the number of regions")
-        hs = (C.c_void_p * max(len(shards), 1))(*[s.h for s in shards])
-        ts = (C.c_void_p * max(len(tables), 1))(*[None if t is None else t.h for t in tables])
+        hs = _handles(shards)
+        ts = _handles(tables)
         mc = np.ascontiguousarray(mean_cov, np.float64)
         t = _lib.csv_cn_table_regions(len(shards), C.cast(hs, C.c_void_p), C.cast(ts, C.c_void_p), ptr(mc), ptr(reg_off), ptr(rs), ptr(re), ptr(ss))
         return t, (hs, ts, mc, reg_off, rs, re, ss), R
 
-    def _cn_tables_call(self, R, capacity, decode, want_observations, call):
-        """The capacity handshake of the two calls: capacity None starts from 0, takes the bound the library answers and calls again."""
-        cap = 0 if capacity is None else capacity
+    def _cn_call(self, R, cap, retry, decode, want_observations, call):
+        """The result handling of the four copy-number calls: the arrays for `cap` observations, the call, and the answer cut to its count.
+        None when the library declines; CSV_ECAPACITY: with `retry`, once more with the count the library answers, else CsvError with that
+        count in `needed`."""
         while True:
             m = max(cap, 1)
             off = np.zeros(R + 1, np.uint64)
@@ -546,7 +529,7 @@ class Context:
             if rc == 1:
                 return None
             if rc == _lib.CSV_ECAPACITY:
-                if capacity is None and int(n.value) > cap:
+                if retry and int(n.value) > cap:
                     cap = int(n.value)
                     continue
                 e = self._error(rc)
@@ -567,14 +550,14 @@ class Context:
         the library declines (a region whose records call for more than 5087 windows: `last_error()` says why). capacity given and below
         the bound (windows + 3 records): CsvError(CSV_ECAPACITY) with that bound in `needed`."""
         t, keep, R = self._cn_table_regions(shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, "cn_observations_tables")
-        return self._cn_tables_call(R, capacity, False, True, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_observations_tables_many(
+        return self._cn_call(R, capacity or 0, capacity is None, False, True, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_observations_tables_many(
             self.h, C.byref(t), ptr(off), ptr(pos), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
 
     def cn_decode_tables(self, hmm: csv_hmm, shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, want_observations: bool = False,
                          capacity: int | None = None):
         """csvgpu_cn_decode_tables_many: cn_decode on resident SNP tables -> the same dict, bit for bit; None when the library declines."""
         t, keep, R = self._cn_table_regions(shards, tables, mean_cov, reg_off, region_start, region_end, sample_size, "cn_decode_tables")
-        return self._cn_tables_call(R, capacity, True, want_observations, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_decode_tables_many(
+        return self._cn_call(R, capacity or 0, capacity is None, True, want_observations, lambda off, pos, st, ll, baf, pfb, l2, snp, n: self.lib.csvgpu_cn_decode_tables_many(
             self.h, C.byref(t), C.byref(hmm), ptr(off), ptr(pos), ptr(st), ptr(ll), ptr(baf), ptr(pfb), ptr(l2), ptr(snp), C.byref(n)))
 
     def last_error(self) -> str:

@@ -134,6 +134,19 @@ int csvgpu_viterbi(csv_ctx *ctx, const csv_hmm *hmm, const double *o1, const dou
     return CSV_OK;
 }
 
+// One window launch per shard that has regions. Shard s's regions are [r0, r0 + nr) of the device tables rs / re / ss, its window offsets (from
+// 0) are at wo + r0 + s, and its windows are [w0, w0 + nw) of l2 / ws / we.
+struct ShardSpan { uint64_t r0, nr, w0, nw; };
+static void launch_windows_per_shard(hipStream_t st, int n_shards, csv_shard *const *shards, const double *mean_cov, const ShardSpan *spans, const uint32_t *rs,
+                                     const uint32_t *re, const int32_t *ss, const uint64_t *wo, double *l2, uint32_t *ws, uint32_t *we)
+{
+    for (int s = 0; s < n_shards; s++) {
+        const ShardSpan &p = spans[s];
+        if (!p.nr) continue;
+        launch_window_log2(st, shards[s]->depth, shards[s]->depth_len, rs + p.r0, re + p.r0, ss + p.r0, wo + p.r0 + s, p.nr, p.nw, mean_cov[s], l2 + p.w0, ws + p.w0, we + p.w0);
+    }
+}
+
 int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *const *shards, const uint32_t *const *region_start,
                                      const uint32_t *const *region_end, const int32_t *const *sample_size, const uint64_t *const *win_off,
                                      const uint64_t *n_regions, const double *mean_cov, double *const *log2_cov, uint32_t *const *win_start,
@@ -164,6 +177,7 @@ int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *cons
     if ((rc = arena_reserve_for(ctx, ctx->arena, "window_log2_many", [&](Arena &a) { return take(a, d_in, in_bytes) && take(a, d_out, out_bytes); }))) return rc;
     const size_t o_rs = 0, o_re = align_up(R * 4, 8), o_ss = 2 * align_up(R * 4, 8), o_wo = 3 * align_up(R * 4, 8);
     const size_t o_l2 = 0, o_ws = W * 8, o_we = W * 8 + align_up(W * 4, 8);
+    std::vector<ShardSpan> spans(n_shards);
     uint64_t r0 = 0, w0 = 0;
     for (int c = 0; c < n_shards; c++) {
         const uint64_t nr = n_regions[c];
@@ -172,22 +186,15 @@ int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *cons
         memcpy(h_in + o_re + r0 * 4, region_end[c], nr * 4);
         memcpy(h_in + o_ss + r0 * 4, sample_size[c], nr * 4);
         memcpy(h_in + o_wo + (r0 + (uint64_t)c) * 8, win_off[c], (nr + 1) * 8);
-        r0 += nr;
+        spans[c] = ShardSpan{r0, nr, w0, win_off[c][nr]};
+        r0 += nr; w0 += win_off[c][nr];
     }
     hipStream_t s = ctx->stream;
     CSV_HIP(ctx, hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
     {
         TimerScope ts(ctx, CSV_K_WINDOW);
-        r0 = 0;
-        for (int c = 0; c < n_shards; c++) {
-            const uint64_t nr = n_regions[c];
-            if (!nr) continue;
-            const uint64_t nw = win_off[c][nr];
-            launch_window_log2(s, shards[c]->depth, shards[c]->depth_len, (const uint32_t *)(d_in + o_rs) + r0, (const uint32_t *)(d_in + o_re) + r0,
-                               (const int32_t *)(d_in + o_ss) + r0, (const uint64_t *)(d_in + o_wo) + r0 + c, nr, nw, mean_cov[c],
-                               (double *)(d_out + o_l2) + w0, (uint32_t *)(d_out + o_ws) + w0, (uint32_t *)(d_out + o_we) + w0);
-            r0 += nr; w0 += nw;
-        }
+        launch_windows_per_shard(s, n_shards, shards, mean_cov, spans.data(), (const uint32_t *)(d_in + o_rs), (const uint32_t *)(d_in + o_re), (const int32_t *)(d_in + o_ss),
+                                 (const uint64_t *)(d_in + o_wo), (double *)(d_out + o_l2), (uint32_t *)(d_out + o_ws), (uint32_t *)(d_out + o_we));
     }
     CSV_HIP(ctx, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
     CSV_HIP(ctx, wait_stream(s));
@@ -206,84 +213,168 @@ int csvgpu_window_log2_resident_many(csv_ctx *ctx, int n_shards, csv_shard *cons
 
 // ---- the copy-number observations (kernels/cnobs.hip) --------------------------------------------------------------------------------------
 namespace {
-// What the two entry points share: the checks, the tables' way up, windows -> order -> offsets -> fill, and the count's readback.
+// the caller's arrays (states / loglik: the decode calls'; baf / pfb / log2_cov / is_snp each optional there)
+struct CnOut { uint64_t *obs_off; uint32_t *pos; int32_t *states; double *loglik, *baf, *pfb, *log2_cov; uint8_t *is_snp; };
+
+// What the four entry points hold: the counts, the workspace's back half, the page-locked slots of what comes back.
 struct CnCall {
+    const char *what;                                         // the entry point, as the messages name it
+    const csv_hmm *hmm;                                       // the decode calls'
+    bool decode;
+    CnOut out;
     uint64_t R = 0, W = 0, S = 0, bound = 0, cap = 0, total = 0;
-    CnWs w;
-    PinStage pin;
+    CnBack b;
+    PinStage pin{};
     void *h_off = nullptr, *h_pos = nullptr, *h_baf = nullptr, *h_pfb = nullptr, *h_l2 = nullptr, *h_snp = nullptr, *h_states = nullptr, *h_ll = nullptr;
 };
 
-// the epochs a region of up to CN_MAX_WINDOWS nodes can reach, from the library's own policy; false if a bucket count does not fit its form
-bool cn_epochs(CnEpochs &ep)
+// what both routes' `in` say of the shards and their regions; own_*: the route's own per-shard / per-region arrays are there
+struct CnRegions {
+    int32_t n_shards; csv_shard *const *shards; const double *mean_cov; const uint64_t *reg_off;
+    const uint32_t *region_start, *region_end; const int32_t *sample_size;
+    bool own_shard_arrays, own_region_arrays;
+};
+
+// the tables and the compact SNP records on the device, as either route leaves them for the tail
+struct CnDev {
+    const uint32_t *rs, *re; const int32_t *ss; const uint64_t *wo;            // per shard (launch_window_log2): wo starts at 0 in every shard
+    const uint32_t *wbase, *soff, *small, *big; uint32_t n_small, n_big;        // flat (launch_cn_order)
+    uint32_t *spos; uint64_t *sbaf, *spfb;                                      // values as their bits
+    void *es_tmp;
+    const CnPlan *gather;                                                       // the table route: the records are gathered from the tables first
+};
+
+// the epochs a region of up to CN_MAX_WINDOWS nodes can reach, from the library's own policy; CSV_EHIP if a bucket count does not fit its form
+int cn_epochs(csv_ctx *ctx, const char *what, CnEpochs &ep)
 {
     std::vector<uint64_t> first, bkt;
     split_order_epochs(CN_MAX_WINDOWS, first, bkt);
     ep = CnEpochs();
+    bool ok = true;
     for (size_t k = 0; k < first.size() && first[k] < CN_MAX_WINDOWS; k++) {
-        if (ep.n == CN_MAX_EPOCHS || bkt[k] > (first[k] < CN_SMALL_MAX ? CN_SMALL_MAX : CN_MAX_WINDOWS)) return false;
+        if (ep.n == CN_MAX_EPOCHS || bkt[k] > (first[k] < CN_SMALL_MAX ? CN_SMALL_MAX : CN_MAX_WINDOWS)) { ok = false; break; }
         ep.first[ep.n] = (uint32_t)first[k]; ep.B[ep.n] = (uint32_t)bkt[k]; ep.n++;
     }
     ep.first[ep.n] = 0xffffffffu;
-    return ep.n > 0 && ep.first[0] == 0;
+    if (ok && ep.n > 0 && ep.first[0] == 0) return CSV_OK;
+    ctx->err = std::string(what) + ": this C++ library's hash table does not grow as the kernels assume";
+    return CSV_EHIP;
 }
 
-int cn_run(csv_ctx *ctx, const char *what, const csv_cn_regions *in, bool decode, bool want_baf, bool want_pfb, bool want_l2, bool want_snp,
-           const uint64_t *n_obs, CnCall &c)
+// Everything the host can see of the shards and the regions. own_shard(s) and own_region(r, windows) are the route's own checks of a shard and
+// of a region (a message, or null); the latter says how many windows the region has as far as the host knows. R == 0 on CSV_OK: nothing to do.
+template <class Shard, class Region>
+int cn_check_regions(csv_ctx *ctx, const char *what, const CnRegions &v, Shard own_shard, Region own_region, uint64_t &R, uint64_t &W)
 {
     auto bad = [&](const char *msg) { ctx->err = std::string(what) + ": " + msg; return (int)CSV_EINVAL; };
-    if (!in || !n_obs) return bad("null argument");
+    R = W = 0;
     if (ctx->split_state) return bad("a split order is pending on this context");
-    if (in->n_shards < 0) return bad("negative shard count");
-    if (in->n_shards && (!in->shards || !in->mean_cov)) return bad("null array");
-    if (!in->reg_off || in->reg_off[0] != 0) return bad("reg_off missing or not starting at 0");
-    for (int s = 0; s < in->n_shards; s++) {
-        if (in->reg_off[s + 1] < in->reg_off[s]) return bad("reg_off not ascending");
-        if (in->reg_off[s + 1] > in->reg_off[s] && !in->shards[s]) return bad("null shard");
+    if (v.n_shards < 0) return bad("negative shard count");
+    if (v.n_shards && (!v.shards || !v.mean_cov || !v.own_shard_arrays)) return bad("null array");
+    if (!v.reg_off || v.reg_off[0] != 0) return bad("reg_off missing or not starting at 0");
+    for (int s = 0; s < v.n_shards; s++) {
+        if (v.reg_off[s + 1] < v.reg_off[s]) return bad("reg_off not ascending");
+        if (v.reg_off[s + 1] > v.reg_off[s] && !v.shards[s]) return bad("null shard");
+        if (const char *msg = own_shard(s)) return bad(msg);
     }
-    const uint64_t R = in->n_shards ? in->reg_off[in->n_shards] : 0;
-    c.R = R; c.cap = *n_obs;
+    R = v.n_shards ? v.reg_off[v.n_shards] : 0;
     if (R == 0) return CSV_OK;
     if (R >= 0xffffffffull) return bad("2^32 - 1 or more regions");
-    if (!in->region_start || !in->region_end || !in->sample_size || !in->snp_off) return bad("null array");
-    if (in->snp_off[0] != 0) return bad("snp_off must start at 0");
-    uint64_t W = 0;
+    if (!v.region_start || !v.region_end || !v.sample_size || !v.own_region_arrays) return bad("null array");
     for (uint64_t r = 0; r < R; r++) {
-        if (in->snp_off[r + 1] < in->snp_off[r]) return bad("snp_off not ascending");
-        if (in->sample_size[r] <= 0) return bad("sample_size <= 0");
-        if (in->region_start[r] > in->region_end[r]) return bad("region start > end");
-        if (in->region_end[r] >= 0x7fffffffu) return bad("a window coordinate could reach 2^31");
-        const uint64_t ss = std::max<uint64_t>(in->snp_off[r + 1] - in->snp_off[r], (uint64_t)in->sample_size[r]);
-        if (ss > CN_MAX_WINDOWS) return bad("more than 5087 windows in a region");
-        W += ss;
+        uint64_t windows = 0;
+        if (const char *msg = own_region(r, windows)) return bad(msg);
+        if (v.sample_size[r] <= 0) return bad("sample_size <= 0");
+        if (v.region_start[r] > v.region_end[r]) return bad("region start > end");
+        if (v.region_end[r] >= 0x7fffffffu) return bad("a window coordinate could reach 2^31");
+        if (windows > CN_MAX_WINDOWS) return bad("more than 5087 windows in a region");
+        W += windows;
     }
-    const uint64_t S = in->snp_off[R];
+    return CSV_OK;
+}
+
+// the entry points' own checks of what the caller gave: the arrays for the answer, the regions (have_in), the capacity
+int cn_check_call(csv_ctx *ctx, CnCall &c, bool have_in, const uint64_t *n_obs)
+{
+    auto bad = [&](const char *msg) { ctx->err = std::string(c.what) + ": " + msg; return (int)CSV_EINVAL; };
+    const CnOut &o = c.out;
+    if (c.decode && !c.hmm) return bad("null hmm");
+    if (!o.obs_off || (c.decode && !o.loglik)) return bad("null array");
+    if (n_obs && *n_obs && (!o.pos || (c.decode ? !o.states : !o.baf || !o.pfb || !o.log2_cov || !o.is_snp))) return bad("null array with a capacity");
+    if (!have_in || !n_obs) return bad("null argument");
+    c.cap = *n_obs;
+    return CSV_OK;
+}
+
+// the page-locked slots of what comes back: `room` observations at the most, an optional array only where the caller gave one
+void cn_pin_outputs(PinStage &p, CnCall &c, uint64_t room)
+{
+    c.h_off = p.slot((c.R + 1) * 8); c.h_pos = p.slot(room * 4);
+    if (c.out.baf) c.h_baf = p.slot(room * 8);
+    if (c.out.pfb) c.h_pfb = p.slot(room * 8);
+    if (c.out.log2_cov) c.h_l2 = p.slot(room * 8);
+    if (c.out.is_snp) c.h_snp = p.slot(room);
+    if (c.decode) { c.h_states = p.slot(room * 4); c.h_ll = p.slot(c.R * 8); }
+}
+
+// memset -> windows -> (the table route's records) -> order -> offsets -> fill, and the count's readback through h_total
+int cn_tail(csv_ctx *ctx, const char *what, const CnRegions &v, const std::vector<ShardSpan> &spans, const CnDev &d, const CnEpochs &ep, uint64_t *h_total, CnCall &c)
+{
+    hipStream_t st = ctx->stream;
+    const CnBack &b = c.b;
+    CSV_HIP(ctx, hipMemsetAsync(b.sl.tot, 0, (c.R + 1) * 4, st));
+    {
+        TimerScope ts(ctx, CSV_K_WINDOW);
+        launch_windows_per_shard(st, v.n_shards, v.shards, v.mean_cov, spans.data(), d.rs, d.re, d.ss, d.wo, b.l2, b.ws, b.we);
+        if (d.gather) launch_snp_gather(st, *d.gather, (uint32_t)c.R, (uint32_t)c.S, d.spos, d.sbaf, d.spfb);
+        launch_cn_order(st, b.ws, b.we, d.wbase, d.soff, d.spos, d.small, d.n_small, d.big, d.n_big, ep, b.sl);
+        launch_exclusive_sum_u32(st, b.sl.tot, c.R + 1, d.es_tmp);
+        launch_cn_fill(st, b.sl, (uint32_t)c.W, (uint32_t)c.R, b.sl.tot, b.ws, b.we, b.l2, d.spos, (const double *)d.sbaf, (const double *)d.spfb, b.o);
+    }
+    CSV_HIP(ctx, hipMemcpyAsync(h_total, b.o.obs_off + c.R, 8, hipMemcpyDeviceToHost, st));
+    CSV_HIP(ctx, wait_stream(st));
+    c.total = *h_total;
+    if (c.total > c.bound) { ctx->err = std::string(what) + ": more observations than the bound"; return CSV_EHIP; }
+    return CSV_OK;
+}
+
+// The SNP records come from the host: the region tables are made here and go up in one copy.
+int cn_run(csv_ctx *ctx, const csv_cn_regions *in, const uint64_t *n_obs, CnCall &c)
+{
+    const char *what = c.what;
+    auto bad = [&](const char *msg) { ctx->err = std::string(what) + ": " + msg; return (int)CSV_EINVAL; };
+    int rc = cn_check_call(ctx, c, in != nullptr, n_obs);
+    if (rc) return rc;
+    const CnRegions v{in->n_shards, in->shards, in->mean_cov, in->reg_off, in->region_start, in->region_end, in->sample_size, true, in->snp_off != nullptr};
+    rc = cn_check_regions(ctx, what, v, [](int) { return (const char *)nullptr; }, [&](uint64_t r, uint64_t &windows) -> const char * {
+        if (r == 0 && in->snp_off[0] != 0) return "snp_off must start at 0";
+        if (in->snp_off[r + 1] < in->snp_off[r]) return "snp_off not ascending";
+        windows = std::max<uint64_t>(in->snp_off[r + 1] - in->snp_off[r], (uint64_t)in->sample_size[r]);
+        return nullptr;
+    }, c.R, c.W);
+    if (rc || c.R == 0) return rc;
+    const uint64_t R = c.R, W = c.W, S = in->snp_off[R];
     if (S && (!in->snp_pos || !in->snp_baf || !in->snp_pfb)) return bad("null array");
     for (uint64_t r = 0; r < R; r++)
         for (uint64_t k = in->snp_off[r] + 1; k < in->snp_off[r + 1]; k++)
             if (in->snp_pos[k] < in->snp_pos[k - 1]) return bad("SNP positions decrease inside a region");
     if (W + 3 * S >= 0xffffffffull) return bad("2^32 - 1 or more windows, records or observations");
-    c.W = W; c.S = S; c.bound = W + 3 * S;
+    c.S = S; c.bound = W + 3 * S;
     CnEpochs ep;
-    if (!cn_epochs(ep)) { ctx->err = std::string(what) + ": this C++ library's hash table does not grow as the kernels assume"; return CSV_EHIP; }
+    if ((rc = cn_epochs(ctx, what, ep))) return rc;
 
     (void)hipSetDevice(ctx->device);
     const uint64_t n_sh = (uint64_t)in->n_shards;
-    int rc;
-    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_obs(a, R, W, n_sh, S, decode, c.w); }))) return rc;
+    CnWs w;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_obs(a, R, W, n_sh, S, c.decode, w); }))) return rc;
+    c.b = w.b;
     const CnInLayout L(R, n_sh, S);
-    const uint64_t room = std::min(c.cap, c.bound);          // what can come back
     char *h_in = nullptr;
     uint64_t *h_total = nullptr;
     c.pin = PinStage(ctx);
     if ((rc = pin_reserve_for(ctx, c.pin, [&](PinStage &p) {
             h_total = (uint64_t *)p.slot(256); h_in = (char *)p.slot(L.bytes);
-            c.h_off = p.slot((R + 1) * 8); c.h_pos = p.slot(room * 4);
-            if (want_baf) c.h_baf = p.slot(room * 8);
-            if (want_pfb) c.h_pfb = p.slot(room * 8);
-            if (want_l2) c.h_l2 = p.slot(room * 8);
-            if (want_snp) c.h_snp = p.slot(room);
-            if (decode) { c.h_states = p.slot(room * 4); c.h_ll = p.slot(R * 8); }
+            cn_pin_outputs(p, c, std::min(c.cap, c.bound));
         }))) return rc;
     // the tables: per-shard window offsets for the window kernel (each shard's start at 0), flat ones for the order kernels
     memcpy(h_in + L.rs, in->region_start, R * 4);
@@ -291,6 +382,7 @@ int cn_run(csv_ctx *ctx, const char *what, const csv_cn_regions *in, bool decode
     int32_t *h_ss = (int32_t *)(h_in + L.ss);
     uint64_t *h_wo = (uint64_t *)(h_in + L.wo);
     uint32_t *h_wbase = (uint32_t *)(h_in + L.wbase), *h_soff = (uint32_t *)(h_in + L.soff), *h_small = (uint32_t *)(h_in + L.small), *h_big = (uint32_t *)(h_in + L.big);
+    std::vector<ShardSpan> spans(n_sh);
     uint64_t wflat = 0;
     uint32_t n_small = 0, n_big = 0;
     for (uint64_t s = 0; s < n_sh; s++) {
@@ -302,73 +394,40 @@ int cn_run(csv_ctx *ctx, const char *what, const csv_cn_regions *in, bool decode
             wrel += ss; wflat += ss;
         }
         h_wo[in->reg_off[s + 1] + s] = wrel;
+        spans[s] = ShardSpan{in->reg_off[s], in->reg_off[s + 1] - in->reg_off[s], wflat - wrel, wrel};
     }
     h_wbase[R] = (uint32_t)W; h_soff[R] = (uint32_t)S;
     if (S) { memcpy(h_in + L.spos, in->snp_pos, S * 4); memcpy(h_in + L.sbaf, in->snp_baf, S * 8); memcpy(h_in + L.spfb, in->snp_pfb, S * 8); }
 
-    hipStream_t st = ctx->stream;
-    char *d_in = c.w.in;
-    CSV_HIP(ctx, hipMemcpyAsync(d_in, h_in, L.bytes, hipMemcpyHostToDevice, st));
-    CSV_HIP(ctx, hipMemsetAsync(c.w.sl.tot, 0, (R + 1) * 4, st));
-    {
-        TimerScope ts(ctx, CSV_K_WINDOW);
-        for (uint64_t s = 0; s < n_sh; s++) {
-            const uint64_t r0 = in->reg_off[s], nr = in->reg_off[s + 1] - r0;
-            if (!nr) continue;
-            const uint64_t w0 = h_wbase[r0], nw = h_wo[r0 + nr + s];
-            launch_window_log2(st, in->shards[s]->depth, in->shards[s]->depth_len, (const uint32_t *)(d_in + L.rs) + r0, (const uint32_t *)(d_in + L.re) + r0,
-                               (const int32_t *)(d_in + L.ss) + r0, (const uint64_t *)(d_in + L.wo) + r0 + s, nr, nw, in->mean_cov[s], c.w.l2 + w0, c.w.ws + w0, c.w.we + w0);
-        }
-        launch_cn_order(st, c.w.ws, c.w.we, (const uint32_t *)(d_in + L.wbase), (const uint32_t *)(d_in + L.soff), (const uint32_t *)(d_in + L.spos),
-                        (const uint32_t *)(d_in + L.small), n_small, (const uint32_t *)(d_in + L.big), n_big, ep, c.w.sl);
-        launch_exclusive_sum_u32(st, c.w.sl.tot, R + 1, c.w.es_tmp);
-        launch_cn_fill(st, c.w.sl, (uint32_t)W, (uint32_t)R, c.w.sl.tot, c.w.ws, c.w.we, c.w.l2, (const uint32_t *)(d_in + L.spos), (const double *)(d_in + L.sbaf),
-                       (const double *)(d_in + L.spfb), c.w.o);
-    }
-    CSV_HIP(ctx, hipMemcpyAsync(h_total, c.w.o.obs_off + R, 8, hipMemcpyDeviceToHost, st));
-    CSV_HIP(ctx, wait_stream(st));
-    c.total = *h_total;
-    if (c.total > c.bound) { ctx->err = std::string(what) + ": more observations than the bound"; return CSV_EHIP; }
-    return CSV_OK;
+    char *d_in = w.in;
+    CSV_HIP(ctx, hipMemcpyAsync(d_in, h_in, L.bytes, hipMemcpyHostToDevice, ctx->stream));
+    const CnDev d{(const uint32_t *)(d_in + L.rs), (const uint32_t *)(d_in + L.re), (const int32_t *)(d_in + L.ss), (const uint64_t *)(d_in + L.wo),
+                  (const uint32_t *)(d_in + L.wbase), (const uint32_t *)(d_in + L.soff), (const uint32_t *)(d_in + L.small), (const uint32_t *)(d_in + L.big), n_small, n_big,
+                  (uint32_t *)(d_in + L.spos), (uint64_t *)(d_in + L.sbaf), (uint64_t *)(d_in + L.spfb), w.es_tmp, nullptr};
+    return cn_tail(ctx, what, v, spans, d, ep, h_total, c);
 }
 
 // cn_run fed by resident SNP tables (kernels/snptable.hip): the record ranges, the window counts, the offset tables, the lists and the compact
 // records are made on the device; one readback of the plan's head sizes the rest. CSV_OK / 1 (declined, the reason in ctx->err) / CSV_E*.
-int cn_tables_run(csv_ctx *ctx, const char *what, const csv_cn_table_regions *in, bool decode, bool want_baf, bool want_pfb, bool want_l2, bool want_snp,
-                  uint64_t *n_obs, CnCall &c)
+int cn_tables_run(csv_ctx *ctx, const csv_cn_table_regions *in, uint64_t *n_obs, CnCall &c)
 {
-    auto bad = [&](const char *msg) { ctx->err = std::string(what) + ": " + msg; return (int)CSV_EINVAL; };
-    if (!in || !n_obs) return bad("null argument");
-    if (ctx->split_state) return bad("a split order is pending on this context");
-    if (in->n_shards < 0) return bad("negative shard count");
-    if (in->n_shards && (!in->shards || !in->mean_cov || !in->tables)) return bad("null array");
-    if (!in->reg_off || in->reg_off[0] != 0) return bad("reg_off missing or not starting at 0");
-    for (int s = 0; s < in->n_shards; s++) {
-        if (in->reg_off[s + 1] < in->reg_off[s]) return bad("reg_off not ascending");
-        if (in->reg_off[s + 1] > in->reg_off[s] && !in->shards[s]) return bad("null shard");
-        if (in->tables[s] && in->tables[s]->device != ctx->device) return bad("a table of another device");
-    }
-    const uint64_t R = in->n_shards ? in->reg_off[in->n_shards] : 0;
-    c.R = R; c.cap = *n_obs;
-    if (R == 0) return CSV_OK;
-    if (R >= 0xffffffffull) return bad("2^32 - 1 or more regions");
-    if (!in->region_start || !in->region_end || !in->sample_size) return bad("null array");
-    for (uint64_t r = 0; r < R; r++) {
-        if (in->sample_size[r] <= 0) return bad("sample_size <= 0");
-        if (in->region_start[r] > in->region_end[r]) return bad("region start > end");
-        if (in->region_end[r] >= 0x7fffffffu) return bad("a window coordinate could reach 2^31");
-        if ((uint32_t)in->sample_size[r] > CN_MAX_WINDOWS) return bad("more than 5087 windows in a region");
-    }
+    const char *what = c.what;
+    int rc = cn_check_call(ctx, c, in != nullptr, n_obs);
+    if (rc) return rc;
+    const CnRegions v{in->n_shards, in->shards, in->mean_cov, in->reg_off, in->region_start, in->region_end, in->sample_size, in->tables != nullptr, true};
+    rc = cn_check_regions(ctx, what, v, [&](int s) { return in->tables[s] && in->tables[s]->device != ctx->device ? "a table of another device" : nullptr; },
+                          [&](uint64_t r, uint64_t &windows) -> const char * { windows = (uint32_t)in->sample_size[r]; return nullptr; }, c.R, c.W);      // (c.W: the floors' sum until the plan has counted)
+    if (rc || c.R == 0) return rc;
+    const uint64_t R = c.R;
     CnEpochs ep;
-    if (!cn_epochs(ep)) { ctx->err = std::string(what) + ": this C++ library's hash table does not grow as the kernels assume"; return CSV_EHIP; }
+    if ((rc = cn_epochs(ctx, what, ep))) return rc;
 
     (void)hipSetDevice(ctx->device);
     const uint64_t n_sh = (uint64_t)in->n_shards;
     const CnUpLayout L(R, n_sh);
     const size_t head_bytes = CN_PLAN_HEAD_BYTES + (n_sh + 1) * 4;
     CnTabWs w;
-    int rc;
-    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, 0, 0, decode, w); }))) return rc;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, 0, 0, c.decode, w); }))) return rc;
     hipStream_t st = ctx->stream;
     // what goes up: the regions, each region's shard, the tables as the kernels see them, the shards' first regions
     auto fill_up = [&](char *h_up) {
@@ -411,60 +470,48 @@ int cn_tables_run(csv_ctx *ctx, const char *what, const csv_cn_table_regions *in
 
     // (a grown arena is a new allocation, possibly at the old address: the pointer says nothing, the capacity rises with every growth)
     const size_t cap_before = ctx->arena.cap;
-    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, W, S, decode, w); }))) return rc;
-    const uint64_t room = c.bound;                            // what can come back
+    if ((rc = arena_reserve_for(ctx, ctx->arena, what, [&](Arena &a) { return carve_cn_tables(a, R, n_sh, W, S, c.decode, w); }))) return rc;
+    c.b = w.b;
     char *h_up = nullptr;
     uint64_t *h_total = nullptr;
     c.pin = PinStage(ctx);
     if ((rc = pin_reserve_for(ctx, c.pin, [&](PinStage &p) {
             h_total = (uint64_t *)p.slot(256); h_up = (char *)p.slot(L.bytes);
-            c.h_off = p.slot((R + 1) * 8); c.h_pos = p.slot(room * 4);
-            if (want_baf) c.h_baf = p.slot(room * 8);
-            if (want_pfb) c.h_pfb = p.slot(room * 8);
-            if (want_l2) c.h_l2 = p.slot(room * 8);
-            if (want_snp) c.h_snp = p.slot(room);
-            if (decode) { c.h_states = p.slot(room * 4); c.h_ll = p.slot(R * 8); }
+            cn_pin_outputs(p, c, c.bound);
         }))) return rc;
     if (ctx->arena.cap != cap_before) {                       // the arena grew: the plan again, into the new one
         fill_up(h_up);
         if ((rc = queue_plan(h_up))) return rc;
     }
-    c.w.o = w.o; c.w.states = w.states; c.w.loglik = w.loglik;
-    CSV_HIP(ctx, hipMemsetAsync(w.sl.tot, 0, (R + 1) * 4, st));
-    {
-        TimerScope ts(ctx, CSV_K_WINDOW);
-        for (uint64_t s = 0; s < n_sh; s++) {
-            const uint64_t r0 = in->reg_off[s], nr = in->reg_off[s + 1] - r0;
-            if (!nr) continue;
-            const uint64_t w0 = shard_w0[s], nw = shard_w0[s + 1] - shard_w0[s];
-            launch_window_log2(st, in->shards[s]->depth, in->shards[s]->depth_len, w.p.rs + r0, w.p.re + r0, w.p.ss + r0, w.p.wo + r0 + s, nr, nw, in->mean_cov[s],
-                               w.l2 + w0, w.ws + w0, w.we + w0);
-        }
-        launch_snp_gather(st, w.p, (uint32_t)R, (uint32_t)S, w.spos, w.sbaf, w.spfb);
-        launch_cn_order(st, w.ws, w.we, w.p.wbase, w.p.soff, w.spos, w.p.small, h.n_small, w.p.big, h.n_big, ep, w.sl);
-        launch_exclusive_sum_u32(st, w.sl.tot, R + 1, w.p.es_tmp);
-        launch_cn_fill(st, w.sl, (uint32_t)W, (uint32_t)R, w.sl.tot, w.ws, w.we, w.l2, w.spos, (const double *)w.sbaf, (const double *)w.spfb, w.o);
-    }
-    CSV_HIP(ctx, hipMemcpyAsync(h_total, w.o.obs_off + R, 8, hipMemcpyDeviceToHost, st));
-    CSV_HIP(ctx, wait_stream(st));
-    c.total = *h_total;
-    if (c.total > c.bound) { ctx->err = std::string(what) + ": more observations than the bound"; return CSV_EHIP; }
-    return CSV_OK;
+    std::vector<ShardSpan> spans(n_sh);
+    for (uint64_t s = 0; s < n_sh; s++) spans[s] = ShardSpan{in->reg_off[s], in->reg_off[s + 1] - in->reg_off[s], shard_w0[s], (uint64_t)shard_w0[s + 1] - shard_w0[s]};
+    const CnDev d{w.p.rs, w.p.re, w.p.ss, w.p.wo, w.p.wbase, w.p.soff, w.p.small, w.p.big, h.n_small, h.n_big, w.spos, w.sbaf, w.spfb, w.p.es_tmp, &w.p};
+    return cn_tail(ctx, what, v, spans, d, ep, h_total, c);
 }
 
-// the answer's arrays to the page-locked block (queued; the caller waits and finishes)
-int cn_download(csv_ctx *ctx, CnCall &c, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp)
+// after either run: the count, the capacity, the decoding where it is asked for, and the answer through the page-locked block to the caller's
+// arrays: each one the caller gave and that has a slot
+int cn_finish(csv_ctx *ctx, CnCall &c, uint64_t *n_obs)
 {
-    hipStream_t st = ctx->stream;
+    *n_obs = c.total;
+    if (c.R == 0) { c.out.obs_off[0] = 0; return CSV_OK; }
+    // (the table route has turned a capacity below the bound away before it ran)
+    if (c.total > c.cap) { ctx->err = std::string(c.what) + ": capacity too small"; return CSV_ECAPACITY; }
+    const CnObs &o = c.b.o;
     const uint64_t n = c.total;
+    int rc;
+    if (c.decode && (rc = csvgpu_viterbi_dev(ctx, c.hmm, o.log2_cov, o.baf, o.pfb, o.obs_off, c.R, n, c.b.states, c.b.loglik))) return rc;
     struct Down { void *dst, *pin; const void *src; size_t bytes; };
-    const Down down[] = {{obs_off, c.h_off, c.w.o.obs_off, (c.R + 1) * 8}, {pos, c.h_pos, c.w.o.pos, n * 4}, {baf, c.h_baf, c.w.o.baf, n * 8},
-                         {pfb, c.h_pfb, c.w.o.pfb, n * 8}, {log2_cov, c.h_l2, c.w.o.log2_cov, n * 8}, {is_snp, c.h_snp, c.w.o.is_snp, n}};
+    const Down down[] = {{c.out.obs_off, c.h_off, o.obs_off, (c.R + 1) * 8}, {c.out.pos, c.h_pos, o.pos, n * 4}, {c.out.baf, c.h_baf, o.baf, n * 8},
+                         {c.out.pfb, c.h_pfb, o.pfb, n * 8}, {c.out.log2_cov, c.h_l2, o.log2_cov, n * 8}, {c.out.is_snp, c.h_snp, o.is_snp, n},
+                         {c.out.states, c.h_states, c.b.states, n * 4}, {c.out.loglik, c.h_ll, c.b.loglik, c.R * 8}};
     for (const Down &d : down) {
         if (!d.dst || !d.pin) continue;
-        CSV_HIP(ctx, hipMemcpyAsync(d.pin, d.src, d.bytes, hipMemcpyDeviceToHost, st));
+        CSV_HIP(ctx, hipMemcpyAsync(d.pin, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream));
         c.pin.outs.push_back(PinStage::Out{d.dst, d.pin, d.bytes});
     }
+    CSV_HIP(ctx, wait_stream(ctx->stream));
+    c.pin.finish();
     return CSV_OK;
 }
 }  // namespace
@@ -473,86 +520,34 @@ int csvgpu_cn_observations_resident_many(csv_ctx *ctx, const csv_cn_regions *in,
                                          double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
 {
     if (!ctx) return CSV_EINVAL;
-    const char *what = "cn_observations";
-    if (!obs_off) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
-    if (n_obs && *n_obs && (!pos || !baf || !pfb || !log2_cov || !is_snp)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
-    CnCall c;
-    int rc = cn_run(ctx, what, in, false, true, true, true, true, n_obs, c);
-    if (rc) return rc;
-    *n_obs = c.total;
-    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
-    if (c.total > c.cap) { ctx->err = std::string(what) + ": capacity too small"; return CSV_ECAPACITY; }
-    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    c.pin.finish();
-    return CSV_OK;
+    CnCall c{"cn_observations", nullptr, false, {obs_off, pos, nullptr, nullptr, baf, pfb, log2_cov, is_snp}};
+    const int rc = cn_run(ctx, in, n_obs, c);
+    return rc ? rc : cn_finish(ctx, c, n_obs);
 }
 
 int csvgpu_cn_observations_tables_many(csv_ctx *ctx, const csv_cn_table_regions *in, uint64_t *obs_off, uint32_t *pos, double *baf, double *pfb,
                                        double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
 {
     if (!ctx) return CSV_EINVAL;
-    const char *what = "cn_observations_tables";
-    if (!obs_off) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
-    if (n_obs && *n_obs && (!pos || !baf || !pfb || !log2_cov || !is_snp)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
-    CnCall c;
-    int rc = cn_tables_run(ctx, what, in, false, true, true, true, true, n_obs, c);
-    if (rc) return rc;
-    *n_obs = c.total;
-    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
-    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
-    CSV_HIP(ctx, wait_stream(ctx->stream));
-    c.pin.finish();
-    return CSV_OK;
+    CnCall c{"cn_observations_tables", nullptr, false, {obs_off, pos, nullptr, nullptr, baf, pfb, log2_cov, is_snp}};
+    const int rc = cn_tables_run(ctx, in, n_obs, c);
+    return rc ? rc : cn_finish(ctx, c, n_obs);
 }
 
 int csvgpu_cn_decode_tables_many(csv_ctx *ctx, const csv_cn_table_regions *in, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos, int32_t *states,
                                  double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
 {
     if (!ctx) return CSV_EINVAL;
-    const char *what = "cn_decode_tables";
-    if (!hmm) { ctx->err = std::string(what) + ": null hmm"; return CSV_EINVAL; }
-    if (!obs_off || !loglik) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
-    if (n_obs && *n_obs && (!pos || !states)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
-    CnCall c;
-    int rc = cn_tables_run(ctx, what, in, true, baf != nullptr, pfb != nullptr, log2_cov != nullptr, is_snp != nullptr, n_obs, c);
-    if (rc) return rc;
-    *n_obs = c.total;
-    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
-    if ((rc = csvgpu_viterbi_dev(ctx, hmm, c.w.o.log2_cov, c.w.o.baf, c.w.o.pfb, c.w.o.obs_off, c.R, c.total, c.w.states, c.w.loglik))) return rc;
-    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
-    hipStream_t st = ctx->stream;
-    CSV_HIP(ctx, hipMemcpyAsync(c.h_states, c.w.states, c.total * 4, hipMemcpyDeviceToHost, st));
-    CSV_HIP(ctx, hipMemcpyAsync(c.h_ll, c.w.loglik, c.R * 8, hipMemcpyDeviceToHost, st));
-    c.pin.outs.push_back(PinStage::Out{states, c.h_states, c.total * 4});
-    c.pin.outs.push_back(PinStage::Out{loglik, c.h_ll, c.R * 8});
-    CSV_HIP(ctx, wait_stream(st));
-    c.pin.finish();
-    return CSV_OK;
+    CnCall c{"cn_decode_tables", hmm, true, {obs_off, pos, states, loglik, baf, pfb, log2_cov, is_snp}};
+    const int rc = cn_tables_run(ctx, in, n_obs, c);
+    return rc ? rc : cn_finish(ctx, c, n_obs);
 }
 
 int csvgpu_cn_decode_resident_many(csv_ctx *ctx, const csv_cn_regions *in, const csv_hmm *hmm, uint64_t *obs_off, uint32_t *pos, int32_t *states,
                                    double *loglik, double *baf, double *pfb, double *log2_cov, uint8_t *is_snp, uint64_t *n_obs)
 {
     if (!ctx) return CSV_EINVAL;
-    const char *what = "cn_decode";
-    if (!hmm) { ctx->err = std::string(what) + ": null hmm"; return CSV_EINVAL; }
-    if (!obs_off || !loglik) { ctx->err = std::string(what) + ": null array"; return CSV_EINVAL; }
-    if (n_obs && *n_obs && (!pos || !states)) { ctx->err = std::string(what) + ": null array with a capacity"; return CSV_EINVAL; }
-    CnCall c;
-    int rc = cn_run(ctx, what, in, true, baf != nullptr, pfb != nullptr, log2_cov != nullptr, is_snp != nullptr, n_obs, c);
-    if (rc) return rc;
-    *n_obs = c.total;
-    if (c.R == 0) { obs_off[0] = 0; return CSV_OK; }
-    if (c.total > c.cap) { ctx->err = std::string(what) + ": capacity too small"; return CSV_ECAPACITY; }
-    if ((rc = csvgpu_viterbi_dev(ctx, hmm, c.w.o.log2_cov, c.w.o.baf, c.w.o.pfb, c.w.o.obs_off, c.R, c.total, c.w.states, c.w.loglik))) return rc;
-    if ((rc = cn_download(ctx, c, obs_off, pos, baf, pfb, log2_cov, is_snp))) return rc;
-    hipStream_t st = ctx->stream;
-    CSV_HIP(ctx, hipMemcpyAsync(c.h_states, c.w.states, c.total * 4, hipMemcpyDeviceToHost, st));
-    CSV_HIP(ctx, hipMemcpyAsync(c.h_ll, c.w.loglik, c.R * 8, hipMemcpyDeviceToHost, st));
-    c.pin.outs.push_back(PinStage::Out{states, c.h_states, c.total * 4});
-    c.pin.outs.push_back(PinStage::Out{loglik, c.h_ll, c.R * 8});
-    CSV_HIP(ctx, wait_stream(st));
-    c.pin.finish();
-    return CSV_OK;
+    CnCall c{"cn_decode", hmm, true, {obs_off, pos, states, loglik, baf, pfb, log2_cov, is_snp}};
+    const int rc = cn_run(ctx, in, n_obs, c);
+    return rc ? rc : cn_finish(ctx, c, n_obs);
 }

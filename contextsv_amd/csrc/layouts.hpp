@@ -12,7 +12,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_obs", "cn_tables", "bgzf", "bam_unpack", "vcf", "vcf_text", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_back", "cn_obs", "cn_tables", "bgzf", "bam_unpack", "vcf", "vcf_text", "dbscan_tmp", "viterbi_tmp"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -197,10 +197,28 @@ static inline bool carve_window(Arena &a, uint64_t n_regions, uint64_t nw, Windo
            take(a, w.l2, nw * 8) && take(a, w.ws, nw * 4) && take(a, w.we, nw * 4);
 }
 
-// the copy-number observations of R regions with W windows and S SNP records in all (csvgpu_cn_observations_resident_many / _cn_decode_):
-// the tables as they come up (`in`: one slice, one copy; the sub-arrays at CnInLayout's offsets), the windows, the per-slot records, the
-// regions' totals, and the answer sized by its bound W + 3 S (a position lies in at most three distinct keys) plus, for the fused call, the
-// Viterbi outputs
+// What both copy-number routes carve behind their inputs, for R regions with W windows and S SNP records in all: the windows, the per-slot
+// records, the answer sized by its bound W + 3 S (a position lies in at most three distinct keys) and, for the fused call, the Viterbi
+// outputs. The regions' totals (sl.tot) are each route's own take, in front of this.
+struct CnBack {
+    double *l2 = nullptr; uint32_t *ws = nullptr, *we = nullptr;
+    CnSlots sl{};
+    CnObs o{};
+    int32_t *states = nullptr; double *loglik = nullptr;
+};
+static inline bool carve_cn_back(Arena &a, uint64_t R, uint64_t W, uint64_t S, bool decode, CnBack &b)
+{
+    const uint64_t bound = W + 3 * S;
+    const bool ok = take(a, b.l2, W * 8) && take(a, b.ws, W * 4) && take(a, b.we, W * 4) &&
+                    take(a, b.sl.fw, W * 4) && take(a, b.sl.lw, W * 4) && take(a, b.sl.lo, W * 4) && take(a, b.sl.cnt, W * 4) && take(a, b.sl.off, W * 4) &&
+                    take(a, b.sl.reg, W * 4) && take(a, b.o.obs_off, (R + 1) * 8) && take(a, b.o.pos, bound * 4) &&
+                    take(a, b.o.baf, bound * 8 + 8) && take(a, b.o.pfb, bound * 8 + 8) && take(a, b.o.log2_cov, bound * 8 + 8) && take(a, b.o.is_snp, bound);
+    if (!decode) return ok;
+    return ok && take(a, b.states, bound * 4 + 8) && take(a, b.loglik, R * 8);
+}
+
+// the copy-number observations fed from host arrays (csvgpu_cn_observations_resident_many / _cn_decode_): the tables as they come up (`in`:
+// one slice, one copy; the sub-arrays at CnInLayout's offsets), the regions' totals, and the back half
 struct CnInLayout {
     size_t rs, re, ss, wo, wbase, soff, spos, sbaf, spfb, small, big, bytes;
     CnInLayout(uint64_t R, uint64_t n_shards, uint64_t S)
@@ -214,28 +232,19 @@ struct CnInLayout {
 };
 struct CnWs {
     char *in = nullptr;
-    double *l2 = nullptr; uint32_t *ws = nullptr, *we = nullptr;
-    CnSlots sl{};
     void *es_tmp = nullptr;
-    CnObs o{};
-    int32_t *states = nullptr; double *loglik = nullptr;
+    CnBack b;
 };
 static inline bool carve_cn_obs(Arena &a, uint64_t R, uint64_t W, uint64_t n_shards, uint64_t S, bool decode, CnWs &w)
 {
-    const uint64_t bound = W + 3 * S;
-    const bool ok = take(a, w.in, CnInLayout(R, n_shards, S).bytes) && take(a, w.l2, W * 8) && take(a, w.ws, W * 4) && take(a, w.we, W * 4) &&
-                    take(a, w.sl.fw, W * 4) && take(a, w.sl.lw, W * 4) && take(a, w.sl.lo, W * 4) && take(a, w.sl.cnt, W * 4) && take(a, w.sl.off, W * 4) &&
-                    take(a, w.sl.reg, W * 4) && take(a, w.sl.tot, (R + 1) * 4) && take(a, w.es_tmp, exclusive_sum_tmp_bytes(R + 1)) &&
-                    take(a, w.o.obs_off, (R + 1) * 8) && take(a, w.o.pos, bound * 4) && take(a, w.o.baf, bound * 8 + 8) && take(a, w.o.pfb, bound * 8 + 8) &&
-                    take(a, w.o.log2_cov, bound * 8 + 8) && take(a, w.o.is_snp, bound);
-    if (!decode) return ok;
-    return ok && take(a, w.states, bound * 4 + 8) && take(a, w.loglik, R * 8);
+    return take(a, w.in, CnInLayout(R, n_shards, S).bytes) && take(a, w.b.sl.tot, (R + 1) * 4) && take(a, w.es_tmp, exclusive_sum_tmp_bytes(R + 1)) &&
+           carve_cn_back(a, R, W, S, decode, w.b);
 }
 
 // The same pass fed by resident SNP tables (csvgpu_cn_observations_tables_many / _cn_decode_tables_many). Carved twice over the same arena:
 // first with W = 0 for what the plan needs (sized by R and the shards alone: `up`, one slice and one copy with the sub-arrays at CnUpLayout's
-// offsets, and the plan's arrays), then, once the plan's totals are back, with W and S for the compact records, the windows, the slots and the
-// answer behind them. The first part does not move when W and S change.
+// offsets, the plan's arrays and the regions' totals), then, once the plan's totals are back, with W and S for the compact records and the
+// back half behind them. The first part does not move when W and S change.
 struct CnUpLayout {
     size_t rs, re, ssf, rsh, tabs, roff, bytes;
     CnUpLayout(uint64_t R, uint64_t n_shards)
@@ -250,30 +259,21 @@ struct CnTabWs {
     char *up = nullptr;
     CnPlan p{};
     uint32_t *spos = nullptr; uint64_t *sbaf = nullptr, *spfb = nullptr;
-    double *l2 = nullptr; uint32_t *ws = nullptr, *we = nullptr;
-    CnSlots sl{};
-    CnObs o{};
-    int32_t *states = nullptr; double *loglik = nullptr;
+    CnBack b;
 };
 static inline bool carve_cn_tables(Arena &a, uint64_t R, uint64_t n_shards, uint64_t W, uint64_t S, bool decode, CnTabWs &w)
 {
     char *head = nullptr;
     const CnUpLayout L(R, n_shards);
-    bool ok = take(a, w.up, L.bytes) && take(a, head, CN_PLAN_HEAD_BYTES + (n_shards + 1) * 4) && take(a, w.p.ss, R * 4) && take(a, w.p.wo, (R + n_shards) * 8) &&
-              take(a, w.p.wbase, (R + 1) * 4) && take(a, w.p.soff, (R + 1) * 4) && take(a, w.p.sfirst, R * 4) && take(a, w.p.hit, R * 4) &&
-              take(a, w.p.small, R * 4) && take(a, w.p.big, R * 4) && take(a, w.p.es_tmp, exclusive_sum_tmp_bytes(R + 1)) && take(a, w.sl.tot, (R + 1) * 4);
+    const bool ok = take(a, w.up, L.bytes) && take(a, head, CN_PLAN_HEAD_BYTES + (n_shards + 1) * 4) && take(a, w.p.ss, R * 4) && take(a, w.p.wo, (R + n_shards) * 8) &&
+                    take(a, w.p.wbase, (R + 1) * 4) && take(a, w.p.soff, (R + 1) * 4) && take(a, w.p.sfirst, R * 4) && take(a, w.p.hit, R * 4) &&
+                    take(a, w.p.small, R * 4) && take(a, w.p.big, R * 4) && take(a, w.p.es_tmp, exclusive_sum_tmp_bytes(R + 1)) && take(a, w.b.sl.tot, (R + 1) * 4);
     if (!ok) return false;
     w.p.rs = (const uint32_t *)(w.up + L.rs); w.p.re = (const uint32_t *)(w.up + L.re); w.p.ssf = (const int32_t *)(w.up + L.ssf);
     w.p.rsh = (const uint32_t *)(w.up + L.rsh); w.p.tabs = (const SnpTabDev *)(w.up + L.tabs); w.p.reg_off = (const uint32_t *)(w.up + L.roff);
     w.p.head = (CnPlanHead *)head; w.p.shard_w0 = (uint32_t *)(head + CN_PLAN_HEAD_BYTES);
     if (!W) return true;
-    const uint64_t bound = W + 3 * S;
-    ok = take(a, w.spos, S * 4) && take(a, w.sbaf, S * 8) && take(a, w.spfb, S * 8) && take(a, w.l2, W * 8) && take(a, w.ws, W * 4) && take(a, w.we, W * 4) &&
-         take(a, w.sl.fw, W * 4) && take(a, w.sl.lw, W * 4) && take(a, w.sl.lo, W * 4) && take(a, w.sl.cnt, W * 4) && take(a, w.sl.off, W * 4) && take(a, w.sl.reg, W * 4) &&
-         take(a, w.o.obs_off, (R + 1) * 8) && take(a, w.o.pos, bound * 4) && take(a, w.o.baf, bound * 8 + 8) && take(a, w.o.pfb, bound * 8 + 8) &&
-         take(a, w.o.log2_cov, bound * 8 + 8) && take(a, w.o.is_snp, bound);
-    if (!decode) return ok;
-    return ok && take(a, w.states, bound * 4 + 8) && take(a, w.loglik, R * 8);
+    return take(a, w.spos, S * 4) && take(a, w.sbaf, S * 8) && take(a, w.spfb, S * 8) && carve_cn_back(a, R, W, S, decode, w.b);
 }
 
 // BGZF members inflated on the device (csvgpu_bgzf_inflate / _dev): the member table and the count of declined members, and for the

@@ -237,3 +237,62 @@ def test_no_region_and_argument_errors(ctx, fam):
         ctx.cn_observations_tables(shards, dev, mean_cov, [0, 2, 1], [1000], [2000], [20])
     assert ei.value.status == _lib.CSV_EINVAL and "reg_off" in str(ei.value)
     _same(ctx.cn_observations_tables(shards, dev, mean_cov, t["reg_off"], t["region_start"], t["region_end"], t["sample_size"]), ref, "after the refusals")
+
+
+OPTIONAL = ("baf", "pfb", "log2_cov", "is_snp")
+
+
+def _family_regions(ctx, fam, route):
+    """The families as the C struct of either route -> (struct, keep-alive, R, the bound windows + 3 records)."""
+    shards, mean_cov, tables, t, ref, dev = fam
+    common = (mean_cov, t["reg_off"], t["region_start"], t["region_end"], t["sample_size"])
+    if route == "host":
+        reg, keep, R = ctx._cn_regions(shards, *common, t["snp_off"], t["snp_pos"], t["snp_baf"], t["snp_pfb"], "test")
+    else:
+        reg, keep, R = ctx._cn_table_regions(shards, dev, *common, "test")
+    n_snps = np.diff(t["snp_off"]).astype(np.int64)
+    return reg, keep, R, int(np.maximum(n_snps, t["sample_size"]).sum() + 3 * n_snps.sum())
+
+
+def _raw_decode(ctx, fam, route, want):
+    """csvgpu_cn_decode_resident_many ("host") / _tables_many ("tables") with the optional arrays in `want` and null for the others."""
+    reg, keep, R, bound = _family_regions(ctx, fam, route)
+    hmm = make_hmm(**WGS_HMM)
+    out = dict(obs_off=np.zeros(R + 1, np.uint64), pos=np.zeros(bound, np.uint32), states=np.zeros(bound, np.int32), loglik=np.zeros(R, np.float64))
+    out.update({f: np.zeros(bound, np.uint8 if f == "is_snp" else np.float64) for f in want})
+    n = C.c_uint64(bound)
+    fn = ctx.lib.csvgpu_cn_decode_resident_many if route == "host" else ctx.lib.csvgpu_cn_decode_tables_many
+    rc = fn(ctx.h, C.byref(reg), C.byref(hmm), *[_lib.ptr(out.get(f)) for f in ("obs_off", "pos", "states", "loglik") + OPTIONAL], C.byref(n))
+    assert rc == _lib.CSV_OK, (route, want, rc, ctx.last_error())
+    k = int(n.value)
+    return {f: (a if f in ("obs_off", "loglik") else a[:k]) for f, a in out.items()}
+
+
+def test_each_optional_array_alone(ctx, fam):
+    """The decode calls take each of baf / pfb / log2_cov / is_snp on its own: a null pointer gets no slot and no copy, and what is asked
+    for comes back as in the call that asks for all four. (The wrapper passes all four or none, hence the calls through ctypes.)"""
+    for route in ("host", "tables"):
+        full = _raw_decode(ctx, fam, route, OPTIONAL)
+        assert full["obs_off"].tobytes() == fam[4]["obs_off"].tobytes() and full["pos"].tobytes() == fam[4]["pos"].tobytes(), route
+        for f in OPTIONAL:
+            got = _raw_decode(ctx, fam, route, (f,))
+            assert set(got) == {"obs_off", "pos", "states", "loglik", f}
+            for name, a in got.items():
+                assert a.tobytes() == full[name].tobytes(), (route, f, name)
+
+
+def test_host_fed_capacity_leaves_the_arrays_untouched(ctx, fam):
+    """csvgpu_cn_observations_resident_many runs with any capacity and reports the exact count afterwards: one short of it is
+    CSV_ECAPACITY with that count in *n_obs and nothing written to obs_off or the five arrays; the context serves the next call."""
+    shards, mean_cov, tables, t, ref, dev = fam
+    reg, keep, R, bound = _family_regions(ctx, fam, "host")
+    total = len(ref["pos"])
+    cap = total - 1
+    arrays = [np.full(R + 1, 0xA5A5A5A5A5A5A5A5, np.uint64), np.full(cap, 0xA5A5A5A5, np.uint32)]
+    arrays += [np.frombuffer(b"\xa5" * (cap * 8), np.float64).copy() for _ in range(3)] + [np.full(cap, 0xA5, np.uint8)]
+    n = C.c_uint64(cap)
+    rc = ctx.lib.csvgpu_cn_observations_resident_many(ctx.h, C.byref(reg), *[_lib.ptr(a) for a in arrays], C.byref(n))
+    assert rc == _lib.CSV_ECAPACITY and int(n.value) == total, (rc, int(n.value), total)
+    assert all(a.tobytes() == b"\xa5" * a.nbytes for a in arrays), "written despite CSV_ECAPACITY"
+    again = ctx.cn_observations(shards, mean_cov, t["reg_off"], t["region_start"], t["region_end"], t["sample_size"], t["snp_off"], t["snp_pos"], t["snp_baf"], t["snp_pfb"])
+    _same(again, ref, "after CSV_ECAPACITY")

@@ -99,15 +99,18 @@ int main()
             { ReadsWs w; run_case(tag("reads", {n, m}), [&](Arena &a) { return carve_reads(a, n, m, w); }); }
             { SplitNodesWs w; run_case(tag("split_nodes", {n, m}), [&](Arena &a) { return carve_split_nodes(a, n, m, w); }); }
             { WindowWs w; run_case(tag("window", {n, m}), [&](Arena &a) { return carve_window(a, n, m, w); }); }
+            // (both copy-number routes end with the same back half: from its first slice to the reservation's end it is as large in either)
+            auto back_bytes = [&](uint64_t S, bool dec) { return arena_plan_bytes([&](Arena &a) { CnBack b; return carve_cn_back(a, n, m, S, dec, b); }); };
+            for (int dec : {0, 1}) { CnBack b; run_case(tag("cn_back", {n, m, (n + m) % 1009, (uint64_t)dec}), [&](Arena &a) { return carve_cn_back(a, n, m, (n + m) % 1009, dec != 0, b); }); }
             for (int dec : {0, 1}) {   // n regions, m windows; shards and SNP records run along
                 CnWs w;
                 const uint64_t n_sh = n % 5 + 1, S = (n + m) % 1009;
-                run_case(tag("cn_obs", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_obs(a, n, m, n_sh, S, dec != 0, w); }, [&](char *, char *) {
+                run_case(tag("cn_obs", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_obs(a, n, m, n_sh, S, dec != 0, w); }, [&](char *, char *hi) {
                     const CnInLayout L(n, n_sh, S);
                     const size_t at[] = {L.rs, L.re, L.ss, L.wo, L.wbase, L.soff, L.spos, L.sbaf, L.spfb, L.small, L.big, L.bytes};
                     const size_t need[] = {n * 4, n * 4, n * 4, (n + n_sh) * 8, (n + 1) * 4, (n + 1) * 4, S * 4, S * 8, S * 8, n * 4, n * 4};
                     for (int i = 0; i < 11; i++) if (at[i] % 256 || at[i] + need[i] > at[i + 1]) return false;
-                    return true;
+                    return (size_t)(hi - (char *)w.b.l2) == back_bytes(S, dec != 0);
                 });
             }
             for (int dec : {0, 1}) {   // n regions, m windows (0: the first carve); shards and SNP records run along. The second carve must leave the first one's slices where they were
@@ -115,12 +118,13 @@ int main()
                 const uint64_t n_sh = n % 5 + 1, S = m ? (n + m) % 1009 : 0;
                 Arena p0 = arena_plan();
                 (void)carve_cn_tables(p0, n, n_sh, 0, 0, dec != 0, w0);
-                run_case(tag("cn_tables", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_tables(a, n, n_sh, m, S, dec != 0, w); }, [&](char *lo, char *) {
+                run_case(tag("cn_tables", {n, m, n_sh, S, (uint64_t)dec}), [&](Arena &a) { return carve_cn_tables(a, n, n_sh, m, S, dec != 0, w); }, [&](char *lo, char *hi) {
                     const CnUpLayout L(n, n_sh);
                     const size_t at[] = {L.rs, L.re, L.ssf, L.rsh, L.tabs, L.roff, L.bytes};
                     const size_t need[] = {n * 4, n * 4, n * 4, n * 4, n_sh * sizeof(SnpTabDev), (n_sh + 1) * 4};
                     for (int i = 0; i < 6; i++) if (at[i] % 256 || at[i] + need[i] > at[i + 1]) return false;
-                    return w.up == lo && (char *)w.p.head - w.up == (char *)w0.p.head - w0.up && (char *)w.sl.tot - w.up == (char *)w0.sl.tot - w0.up &&
+                    if (m && (size_t)(hi - (char *)w.b.l2) != back_bytes(S, dec != 0)) return false;
+                    return w.up == lo && (char *)w.p.head - w.up == (char *)w0.p.head - w0.up && (char *)w.b.sl.tot - w.up == (char *)w0.b.sl.tot - w0.up &&
                            (char *)w.p.shard_w0 == (char *)w.p.head + CN_PLAN_HEAD_BYTES && sizeof(CnPlanHead) <= CN_PLAN_HEAD_BYTES;
                 });
             }
@@ -184,7 +188,7 @@ int main()
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
     const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
-                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_obs", 2}, {"cn_tables", 2},{"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
+                                                    {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_back", 2}, {"cn_obs", 2}, {"cn_tables", 2},{"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
         const auto it = n_counts.find(kv.first);
