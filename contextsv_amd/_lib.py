@@ -56,6 +56,22 @@ class csv_tuning(C.Structure):
                 ("split_chain_only", C.c_int32)]
 
 
+class csv_merge_counts(C.Structure):
+    _fields_ = [("n_rep", C.c_uint64 * 2), ("n_declined", C.c_uint64 * 2)]
+
+
+class csv_merge_rep(C.Structure):
+    _fields_ = [("sig", C.c_uint32 * 4), ("label", C.c_int32), ("cluster_size", C.c_uint32), ("status", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# csv_merge_rep as a numpy record: the chosen signature's four words, then the bucket's
+MERGE_REP_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("read", "<u4"), ("qpos_kind", "<u4"), ("label", "<i4"), ("cluster_size", "<u4"),
+                            ("status", "<u4"), ("reserved", "<u4")])
+REP_CHOSEN, REP_PASS_THROUGH, REP_DECLINED = 0, 1, 2
+SORT_SLOT_LDS_CAP = 4096      # contextsv_amd/csrc/sort_select_core.hpp LDS_CAP: the largest range a workgroup replays in LDS
+SORT_SLOT_NONE = 0xFFFFFFFF
+
+
 class csv_split_tables(C.Structure):
     _fields_ = [("n_members", C.c_uint64), ("n_supp", C.c_uint64), ("start", C.c_void_p), ("end", C.c_void_p), ("q_start", C.c_void_p),
                 ("q_end", C.c_void_p), ("reverse", C.c_void_p), ("supp_off", C.c_void_p), ("supp_start", C.c_void_p), ("supp_end", C.c_void_p),
@@ -156,6 +172,10 @@ ABI = {
     "csvgpu_shard_free": (None, [_P, _P]),
     "csvgpu_chr_pipeline_dev": (C.c_int, [_P, _P, C.c_uint32, C.c_uint8, C.c_double, C.c_double, C.POINTER(csv_chr_result)]),
     "csvgpu_chr_pipeline_fetch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint8, C.c_double, C.c_double, C.POINTER(csv_chr_result), _P, _P, C.c_uint64]),
+    "csvgpu_sort_slot": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, _P]),
+    "csvgpu_merge_select": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(csv_merge_counts)]),
+    "csvgpu_chr_merge_select": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), C.c_uint32, _P, C.c_uint64, C.POINTER(csv_merge_counts)]),
+    "csvgpu_chr_job_cluster_select": (C.c_int, [_P, _P, C.c_double, C.c_uint32, _P, C.c_uint64, _P]),
     "csvgpu_chr_job_begin": (_P, [_P, _P, C.c_uint32, C.c_uint8, C.c_double]),
     "csvgpu_chr_job_cluster": (C.c_int, [_P, _P, C.c_double, _P, _P, C.c_uint64]),
     "csvgpu_chr_job_end": (C.c_int, [_P, _P, C.POINTER(csv_chr_result)]),

@@ -233,6 +233,29 @@ class Context:
         self._check(self.lib.csvgpu_dbscan_1d(self.h, ptr(pts), ptr(seg_off), len(seg_off) - 1, eps, min_pts, ptr(labels)))
         return labels[: len(pts)]
 
+    def sort_slot(self, keys, seg_off, nth, max_partitions: int = 0):
+        """csvgpu_sort_slot: for every segment keys[seg_off[s]:seg_off[s + 1]] the index (inside the segment) of the element that libstdc++'s
+        std::sort by key descending leaves at slot nth[s] -> (idx uint32, declined bool). A segment whose chain of partitions exceeds
+        max_partitions (0: the library's own depth limit) is declined, idx = SORT_SLOT_NONE; so is idx of an empty segment (not declined)."""
+        keys = np.ascontiguousarray(keys, np.uint32)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        nth = np.ascontiguousarray(nth, np.uint64)
+        n_seg = len(seg_off) - 1
+        assert n_seg >= 0 and len(nth) == n_seg
+        idx = np.zeros(max(n_seg, 1), np.uint32)
+        declined = np.zeros(max(n_seg, 1), np.uint8)
+        self._check(self.lib.csvgpu_sort_slot(self.h, ptr(keys), ptr(seg_off), n_seg, ptr(nth), max_partitions, ptr(idx), ptr(declined)))
+        return idx[:n_seg], declined[:n_seg].astype(bool)
+
+    def merge_select(self, sig, labels, n_del: int, max_partitions: int = 0, capacity=None):
+        """csvgpu_merge_select: mergeSVs' representatives of one contig from host arrays — sig[SIG_DTYPE] with the n_del DEL signatures
+        first, labels as dbscan_iv gives them per type -> (records[MERGE_REP_DTYPE], counts dict). capacity None: always enough."""
+        sig = np.ascontiguousarray(sig, SIG_DTYPE)
+        labels = np.ascontiguousarray(labels, np.int32)
+        assert len(labels) == len(sig) and 0 <= n_del <= len(sig)
+        return _merge_records(self, capacity, len(sig), lambda rep, cap, cnt: self.lib.csvgpu_merge_select(
+            self.h, ptr(sig), ptr(labels), n_del, len(sig) - n_del, max_partitions, ptr(rep), cap, C.byref(cnt)))
+
     def window_log2(self, depth, region_start, region_end, sample_size, mean_cov: float):
         depth = np.ascontiguousarray(depth, np.uint32)
         rs = np.ascontiguousarray(region_start, np.uint32)
@@ -1124,6 +1147,21 @@ class ChrResult:
     raw: csv_chr_result
 
 
+def _merge_records(ctx, capacity, n_sig: int, call):
+    """One csvgpu_*merge_select call into a fresh record array; CsvError(CSV_ECAPACITY) carries the counts as .counts."""
+    cap = n_sig // 2 + 2 if capacity is None else capacity
+    rep = np.zeros(max(cap, 1), _lib.MERGE_REP_DTYPE)
+    cnt = _lib.csv_merge_counts()
+    rc = call(rep, cap, cnt)
+    counts = dict(n_rep=(int(cnt.n_rep[0]), int(cnt.n_rep[1])), n_declined=(int(cnt.n_declined[0]), int(cnt.n_declined[1])))
+    if rc == _lib.CSV_ECAPACITY:
+        e = ctx._error(rc)
+        e.counts = counts
+        raise e
+    ctx._check(rc)
+    return rep[: counts["n_rep"][0] + counts["n_rep"][1]].copy(), counts
+
+
 class Shard:
     """Reads resident in HBM + the per-chromosome device pipeline (csvgpu_chr_pipeline_dev)."""
 
@@ -1182,6 +1220,12 @@ class Shard:
         res = csv_chr_result()
         self.ctx._check(self.ctx.lib.csvgpu_chr_pipeline_dev(self.ctx.h, self.h, min_oplen, min_mapq, eps, min_pts_pct, C.byref(res)))
         return ChrResult(res.n_sig, res.n_del, res.n_ins, res.depth_sum, res.depth_nonzero, res.min_pts, res.mean_cov, res)
+
+    def merge_select(self, res: ChrResult, max_partitions: int = 0, capacity=None):
+        """csvgpu_chr_merge_select on the results of this shard's last pipeline: the representatives mergeSVs keeps, chosen on the device
+        -> (records[MERGE_REP_DTYPE], counts dict); signatures and labels stay where they are."""
+        return _merge_records(self.ctx, capacity, res.n_sig, lambda rep, cap, cnt: self.ctx.lib.csvgpu_chr_merge_select(
+            self.ctx.h, self.h, C.byref(res.raw), max_partitions, ptr(rep), cap, C.byref(cnt)))
 
     def fetch(self, res: ChrResult, want_depth: bool = False):
         """Copy the pipeline's device results to host numpy arrays (test / host-merge plumbing)."""

@@ -172,6 +172,11 @@ csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh);         // the side arrays
 SnpTabDev snp_table_dev(const csv_snp_table *t);              // the table as the kernels see it (NULL or no records: all zero)
 // cluster.hip
 int check_dbscan_args(csv_ctx *ctx, double eps, int32_t min_pts, bool interval);
+// merge_select.hip: both types' representatives of one contig queued on the context's stream, DEL records first — the kernels, and the
+// gave-up words on their way into w.back; nothing is waited for. sh: the shard whose select scratch is carved (it grows here if it must:
+// then, and only then, the device is waited for), or nullptr: the context's workspace. max_label[t]: a bound of type t's labels.
+int merge_select_queue(csv_ctx *ctx, csv_shard *sh, const csv_sig *d_sig_del, const int32_t *d_lab_del, uint64_t n_del, const csv_sig *d_sig_ins,
+                       const int32_t *d_lab_ins, uint64_t n_ins, const int64_t *max_label, uint32_t max_partitions, MergeRunWs &w);
 // split_order.hip
 void split_order_epochs(uint64_t n_max, std::vector<uint64_t> &first_node, std::vector<uint64_t> &buckets);
 void split_state_free(csv_ctx *ctx);

@@ -12,18 +12,23 @@ struct csv_job {
     uint32_t min_oplen = 50; uint8_t min_mapq = 20; double min_pts_pct = 0.1;
     hipEvent_t ev_zero = nullptr, ev_scan = nullptr, ev_depth = nullptr, ev_mid = nullptr, ev_done = nullptr, t0 = nullptr;
     bool on_gate = false;                // the pair runs on a gate's stream: this context's stream meets it only in job_cluster (ev_depth)
-    char *pin = nullptr;                 // 512 B page-locked: [0,256) counters behind the scan, [256,512) counters at the end
+    char *pin = nullptr;                 // 1 KiB page-locked: [0,256) counters behind the scan, [256,512) counters at the end, [512,576) the select's MergeBack
     bool depth_queued = false, clustered = false, copied = false;
     uint64_t n = 0, n_del = 0, capacity = 0;
     csv_sig *sig_sorted = nullptr;
     int32_t *labels = nullptr;
+    // csvgpu_chr_job_cluster_select: the select queued behind the DBSCAN
+    bool select = false;
+    csv_merge_counts *host_counts = nullptr;
+    uint64_t rep_capacity = 0, rep_bound = 0;
 };
 
 // CSV_MAX_JOBS rotating 512-byte page-locked slots per context; a slot belongs to its job from begin to end / abort, so a caller
 // that holds more than CSV_MAX_JOBS jobs open on one context is refused instead of aliasing another job's counters.
+constexpr size_t kJobPinSlot = 1024;
 static char *job_pin_slot(csv_ctx *ctx)
 {
-    constexpr size_t kSlots = CSV_MAX_JOBS, kSlot = 512;
+    constexpr size_t kSlots = CSV_MAX_JOBS, kSlot = kJobPinSlot;
     if (!ctx->job_pin && hipHostMalloc((void **)&ctx->job_pin, kSlots * kSlot, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     for (size_t k = 0; k < kSlots; k++) {
         const size_t i = (ctx->job_pin_next + k) % kSlots;
@@ -37,7 +42,7 @@ static char *job_pin_slot(csv_ctx *ctx)
 static void job_pin_release(csv_ctx *ctx, char *p)
 {
     if (!p || !ctx->job_pin) return;
-    ctx->job_pin_busy &= ~(1u << (size_t)((p - ctx->job_pin) / 512));
+    ctx->job_pin_busy &= ~(1u << (size_t)((p - ctx->job_pin) / kJobPinSlot));
 }
 
 // ctx->work for a shard's depth chain: reserved when the job begins (ws == nullptr), carved again — the same carve, the same arguments —
@@ -175,7 +180,10 @@ csv_job *csvgpu_chr_job_begin(csv_ctx *ctx, csv_shard *sh, uint32_t min_oplen, u
     return job;
 }
 
-int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host_sig, int32_t *host_labels, uint64_t capacity)
+// what csvgpu_chr_job_cluster_select asks for on top of the clustering (nullptr: nothing — the job's carve and launches are what they were)
+struct JobSelect { uint32_t max_partitions; csv_merge_rep *host_rep; uint64_t capacity; csv_merge_counts *host_counts; };
+
+static int job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host_sig, int32_t *host_labels, uint64_t capacity, const JobSelect *sel)
 {
     if (!ctx || !job || job->clustered) return CSV_EINVAL;
     if (!(eps >= 0.0) || !(eps < 1.0)) { ctx->err = "pipeline: eps must be in [0,1)"; return CSV_EINVAL; }
@@ -257,11 +265,38 @@ int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host
         CSV_HIP(ctx, hipMemcpyAsync(host_sig, sig_sorted, n * sizeof(csv_sig), hipMemcpyDeviceToHost, s));
         CSV_HIP(ctx, hipMemcpyAsync(host_labels, labels, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
+    if (sel && n) {
+        // the representatives behind the last clustering kernel: only the counts and the records ride home. How many records there are is
+        // known on the device alone, so min(capacity, bound) of them are copied; csvgpu_chr_job_end says whether that was all of them.
+        MergeRunWs mw;
+        const int64_t max_label[2] = {(int64_t)n_del, (int64_t)(n - n_del)};          // DBSCAN's cluster ids lie below the set's size
+        if ((rc = merge_select_queue(ctx, sh, sig_sorted, labels, n_del, sig_sorted + n_del, labels + n_del, n - n_del, max_label, sel->max_partitions, mw))) return rc;
+        job->rep_bound = merge_rep_bound(n_del, n - n_del);
+        const uint64_t n_copy = std::min(sel->capacity, job->rep_bound);
+        CSV_HIP(ctx, hipMemcpyAsync(job->pin + 512, mw.back, sizeof(MergeBack), hipMemcpyDeviceToHost, s));
+        if (n_copy) CSV_HIP(ctx, hipMemcpyAsync(sel->host_rep, mw.rep, n_copy * sizeof(csv_merge_rep), hipMemcpyDeviceToHost, s));
+    }
+    if (sel) { job->select = true; job->host_counts = sel->host_counts; job->rep_capacity = sel->capacity; }
     CSV_HIP(ctx, hipMemcpyAsync(job->pin + 256, cnt, sizeof(ScanCounters), hipMemcpyDeviceToHost, s));
     CSV_HIP(ctx, hipEventRecord(job->ev_done, s));
     job->n = n; job->n_del = n_del; job->capacity = capacity; job->sig_sorted = sig_sorted; job->labels = labels;
     job->clustered = true;
     return CSV_OK;
+}
+
+int csvgpu_chr_job_cluster(csv_ctx *ctx, csv_job *job, double eps, csv_sig *host_sig, int32_t *host_labels, uint64_t capacity)
+{
+    return job_cluster(ctx, job, eps, host_sig, host_labels, capacity, nullptr);
+}
+
+int csvgpu_chr_job_cluster_select(csv_ctx *ctx, csv_job *job, double eps, uint32_t max_partitions, csv_merge_rep *host_rep, uint64_t capacity,
+                                  csv_merge_counts *host_counts)
+{
+    if (!ctx || !job) return CSV_EINVAL;
+    if (!host_counts || (capacity && !host_rep)) { ctx->err = "job select: null output"; return CSV_EINVAL; }
+    if (ctx->split_state) { ctx->err = "job select: a split order is pending on this context"; return CSV_EINVAL; }
+    const JobSelect sel{max_partitions, host_rep, capacity, host_counts};
+    return job_cluster(ctx, job, eps, nullptr, nullptr, 0, &sel);
 }
 
 int csvgpu_chr_job_end(csv_ctx *ctx, csv_job *job, csv_chr_result *res)
@@ -281,6 +316,15 @@ int csvgpu_chr_job_end(csv_ctx *ctx, csv_job *job, csv_chr_result *res)
         res->label_del = job->labels; res->label_ins = job->labels + job->n_del;
         res->depth = sh->depth; res->ref_end = sh->ref_end; res->q_start = sh->q_start; res->q_end = sh->q_end;
         if (job->capacity && job->n > job->capacity) { ctx->err = "pipeline_fetch: host buffers too small"; rc = CSV_ECAPACITY; }
+    }
+    if (rc == CSV_OK && job->clustered && job->select) {
+        MergeBack mb;
+        memset(&mb, 0, sizeof(mb));
+        if (job->n) memcpy(&mb, job->pin + 512, sizeof(MergeBack));
+        *job->host_counts = mb.counts;
+        const uint64_t n_rep = mb.counts.n_rep[0] + mb.counts.n_rep[1];
+        if (mb.gave_up[0] || mb.gave_up[1] || n_rep > job->rep_bound) { ctx->err = "job select: a radix pass's look-back gave up"; rc = CSV_EHIP; }
+        else if (n_rep > job->rep_capacity) { ctx->err = "job select: host_rep too small"; rc = CSV_ECAPACITY; }
     }
     job_free(ctx, job);
     return rc;

@@ -18,6 +18,7 @@ void shard_release(csv_shard *sh)
     (void)hipFree(sh->ref_end); (void)hipFree(sh->q_start); (void)hipFree(sh->q_end);
     (void)hipFree(sh->cig_half); (void)hipFree(sh->esc_piece); (void)hipFree(sh->esc_tab);
     (void)hipFree(sh->ckpt);
+    (void)hipFree(sh->sel_scratch);
     (void)hipFree(sh->depth_items);
     (void)hipFree(sh->scan_split);
     (void)hipFree(sh->qhash);

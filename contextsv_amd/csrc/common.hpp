@@ -94,6 +94,7 @@ struct csv_shard {
     int32_t  *labels = nullptr;
     uint32_t *ord = nullptr;       // read permutation by pos when the shard is not coordinate-sorted
     char     *scratch = nullptr;   size_t scratch_cap = 0;   // sort / dbscan workspace
+    char     *sel_scratch = nullptr; size_t sel_cap = 0;     // the representative select's workspace (carve_merge_run; grow-only, allocated at its first use)
     uint64_t *counters = nullptr;  // device scalars (see ScanCounters) + bucket tables + the depth tiles' candidate ranges, zeroed together per chromosome
     uint64_t *tile_range = nullptr;   // inside `counters`
     uint64_t *scan_split = nullptr;   // the scan's work split for this device's grid (launch_scan_split, once per shard)
@@ -280,6 +281,36 @@ void launch_gather_u32(hipStream_t s, const uint32_t *src, const uint32_t *idx, 
 void launch_gather3_u32(hipStream_t s, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *idx, uint64_t n, uint32_t *da, uint32_t *db, uint32_t *dc);
 void launch_exclusive_sum_u32(hipStream_t s, uint32_t *data, uint64_t n, void *tmp);   // in place
 size_t exclusive_sum_tmp_bytes(uint64_t n);
+// mergeselect.hip — which element libstdc++'s std::sort by length descending leaves at a slot, for a batch of segments (sort_select_core.hpp)
+constexpr uint32_t SORT_SLOT_LDS_CAP = 4096;             // the largest range a workgroup replays in LDS
+struct SortSlotArgs {                                    // passed to the kernels by value
+    const uint32_t *off;        // [n_seg + 1] first entry of each segment
+    const uint32_t *n_seg;      // the segments, a device scalar (mergeSVs' buckets are counted on the device)
+    const uint32_t *nth;        // [n_seg] the slots, or nullptr: mergeSVs' slot of the segment's size, [max(1, (int)(sz * 0.2)) / 2]
+    uint64_t *ent;              // [n] (length << 32) | index, in segment order; permuted inside the segments
+    uint32_t *list;             // [n] scratch of the streamed rounds
+    uint32_t *mid, *big, *cnt;  // the segments that take a workgroup, by form (at most n / 17 each), and cnt[0], cnt[1] how many
+    uint32_t *idx;              // [n_seg] the chosen index; 0xffffffff for an empty or a declined segment
+    uint32_t *keep;             // [n_seg] 1 where the segment has two members or more, or nullptr
+    uint32_t max_partitions;    // 0: the library's own depth limit
+};
+// n: the entries in all, n_seg_bound: an upper bound of *b.n_seg (the grids are sized by them)
+void launch_sort_slot(hipStream_t s, const SortSlotArgs &b, uint64_t n, uint64_t n_seg_bound);
+struct MergeEmitArgs {
+    const uint32_t *off, *n_buckets;
+    const uint64_t *keys;       // sorted: slot = label + 2
+    const uint32_t *idx, *keep;
+    const csv_sig *sig;
+    int type;                   // 0 DEL, 1 INS: the INS records go behind counts->n_rep[0]
+    csv_merge_counts *counts;
+    csv_merge_rep *rep;
+    uint64_t capacity;
+};
+struct MergeSelectWs;
+// One type's representatives behind whatever is queued: buckets by label (one radix sort), the slot replay, one record per bucket of two or
+// more in slot order — or the type's 0 or 1 signatures passed through. key_bits: the bits of the largest slot (label + 2). *gave_up: the sort's flag to read back (radix_sort_gave_up), or nullptr.
+void launch_merge_select_type(hipStream_t s, const MergeSelectWs &w, const csv_sig *sig, const int32_t *label, uint64_t n, int type, int key_bits,
+                              uint32_t max_partitions, bool onesweep, csv_merge_counts *counts, csv_merge_rep *rep, uint64_t capacity, const uint32_t **gave_up);
 // dbscan.hip
 size_t dbscan_tmp_bytes(uint64_t n);
 // s,e sorted by start; oid = original index of each sorted position (nullptr: identity).

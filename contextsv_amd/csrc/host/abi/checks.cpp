@@ -44,6 +44,32 @@ int csvhost_partition_check(const uint32_t *keys, uint64_t n, int *differ)
     })
 }
 
+// How many partitions the library's chain for slot nth takes on `keys` (descending by key, ids in input order: the loop of std_sort_select
+// with the library's own partition, counted), or -1 where std::sort's depth limit runs out first and the library heap-sorts. The device's
+// slot replay (csvgpu_sort_slot) declines exactly the chains that need more than its bound: the GPU tests predict its declines with this.
+int64_t csvhost_sort_select_rounds(const uint32_t *keys, uint64_t n, uint64_t nth)
+{
+    try {
+        if (n == 0 || nth >= n) return 0;
+        std::vector<uint32_t> a(n);
+        for (uint64_t i = 0; i < n; i++) a[i] = (uint32_t)i;
+        auto cmp = [&](uint32_t x, uint32_t y) { return keys[x] > keys[y]; };
+        int depth_limit = 0;
+        for (uint64_t k = n; k > 1; k >>= 1) depth_limit++;
+        depth_limit *= 2;
+        uint32_t *lo = a.data(), *hi = a.data() + n, *target = a.data() + nth;
+        int64_t rounds = 0;
+        while (hi - lo > 16) {
+            if (depth_limit == 0) return -1;
+            --depth_limit; rounds++;
+            csvhost::lib_move_median_to_first(lo, lo + 1, lo + (hi - lo) / 2, hi - 1, cmp);
+            uint32_t *cut = csvhost::lib_unguarded_partition(lo + 1, hi, lo, cmp);
+            if (target >= cut) lo = cut; else hi = cut;
+        }
+        return rounds;
+    } catch (...) { return -2; }
+}
+
 // std::hash<std::string> of n '\n'-joined names (what the staging code attaches to a shard as its query-name column)
 int csvhost_string_hashes(const char *names, uint64_t n, uint64_t *out)
 {

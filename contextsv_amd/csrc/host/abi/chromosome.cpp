@@ -1,5 +1,12 @@
 // chromosome.cpp — the per-chromosome CIGAR path (SVCaller::processChromosome mirror) on resident shards
+#include <atomic>
+
 #include "abi.hpp"
+
+// csvhost_set_merge_on_device: what the SVCallers behind csvhost_process_resident_* take (SVCaller::merge_on_device, off by default)
+static std::atomic<int> g_merge_on_device{0};
+static std::atomic<uint32_t> g_merge_max_partitions{0};
+static void configure(SVCaller &c) { c.merge_on_device = g_merge_on_device.load() != 0; c.merge_max_partitions = g_merge_max_partitions.load(); }
 
 static SeqStore host_seqs(const uint64_t *seq_off, const uint8_t *seq) { SeqStore ss; ss.seq_off = seq_off; ss.seq = seq; return ss; }
 
@@ -16,6 +23,7 @@ static void flatten(const std::vector<SVCall> &calls, csvhost_call *out, uint8_t
 static void chromosome_alts(csv_ctx *ctx, csv_shard *shard, const SeqStore *ss, double eps, double min_pts_pct, char *buf, uint64_t cap, uint64_t *len)
 {
     SVCaller caller(ctx);
+    configure(caller);
     std::vector<SVCall> calls;
     ChrStats cs;
     caller.processResidentChromosome("chr", shard, ss, eps, min_pts_pct, calls, cs);
@@ -24,12 +32,23 @@ static void chromosome_alts(csv_ctx *ctx, csv_shard *shard, const SeqStore *ss, 
 
 extern "C" {
 
+// The switch of the SVCallers behind csvhost_process_resident_* (process-wide; off / 0 by default): SVCaller::merge_on_device, merge_max_partitions.
+void csvhost_set_merge_on_device(int on, uint32_t max_partitions) { g_merge_on_device = on != 0; g_merge_max_partitions = max_partitions; }
+// SVCaller::mergeRouteStats: out[0] contigs whose representatives the device chose, [1] contigs that took the host route for a declined bucket,
+// [2] for records that overflowed twice, [3] buckets the device declined; reset != 0 clears them.
+void csvhost_merge_route_stats(uint64_t *out, int reset)
+{
+    const SVCaller::MergeRouteStats r = SVCaller::mergeRouteStats(reset != 0);
+    out[0] = r.contigs_device; out[1] = r.contigs_host_declined; out[2] = r.contigs_host_overflow; out[3] = r.buckets_declined;
+}
+
 // Runs the whole path on a resident shard and writes the merged calls (POD) + alt_tag[i] (0 "<DEL>", 1 "<INS>", 2 literal sequence).
 int csvhost_process_resident_chromosome(csv_ctx *ctx, csv_shard *shard, const uint64_t *seq_off, const uint8_t *seq, double eps,
                                         double min_pts_pct, csvhost_call *out, uint8_t *alt_tag, uint64_t cap, csvhost_chr_stats *st)
 {
     GUARD({
         SVCaller caller(ctx);
+        configure(caller);
         const SeqStore ss = host_seqs(seq_off, seq);
         std::vector<SVCall> calls;
         ChrStats cs;
@@ -79,6 +98,7 @@ int csvhost_process_resident_pipelined(csv_ctx *ctx, csv_shard *shard, uint64_t 
 {
     GUARD({
         SVCaller caller(ctx);
+        configure(caller);
         const SeqStore ss = host_seqs(seq_off, seq);
         std::vector<csv_shard *> shards(n_steps, shard);
         std::vector<std::vector<SVCall>> calls;
@@ -106,7 +126,8 @@ int csvhost_process_resident_lanes(int n_lanes, csv_ctx *const *ctxs, csv_shard 
 {
     GUARD({
         std::vector<SVCaller::Lane> lanes((size_t)n_lanes);
-        for (int l = 0; l < n_lanes; l++) { lanes[l].ctx = ctxs[l]; lanes[l].shards.assign(steps[l], shards[l]); }
+        for (int l = 0; l < n_lanes; l++) { lanes[l].ctx = ctxs[l]; lanes[l].shards.assign(steps[l], shards[l]);
+                                           lanes[l].merge_on_device = g_merge_on_device.load() != 0; lanes[l].merge_max_partitions = g_merge_max_partitions.load(); }
         std::vector<std::vector<std::vector<SVCall>>> calls;
         std::vector<std::vector<ChrStats>> stats;
         const auto t0 = std::chrono::steady_clock::now();

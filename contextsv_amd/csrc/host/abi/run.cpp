@@ -80,6 +80,8 @@ int csvhost_run(csv_ctx *ctx, int n_contigs, const uint64_t *read_off, const uin
 
 // ---- a staged genome: contigs resident in HBM + the host arrays of the host-side passes (SVCaller::runResident) -----------
 struct csvhost_genome {
+    bool merge_on_device = false;               // csvhost_genome_merge_on_device
+    uint32_t merge_max_partitions = 0;
     struct Contig {
         std::string name;
         int32_t global_tid = 0;
@@ -164,6 +166,14 @@ int csvhost_genome_snp_tables_resident(csvhost_genome *g, int on)
     return n;
 }
 
+// Opt-in: the CIGAR merge's representatives of csvhost_genome_run chosen on the device (SVCaller::merge_on_device; max_partitions: the
+// device's bound per bucket, 0 = the library's). Same calls and statistics either way; csvhost_merge_route_stats says which route the contigs took.
+int csvhost_genome_merge_on_device(csvhost_genome *g, int on, uint32_t max_partitions)
+{
+    g->merge_on_device = on != 0; g->merge_max_partitions = max_partitions;
+    return 0;
+}
+
 uint64_t csvhost_genome_n_contigs(const csvhost_genome *g) { return g->contigs.size(); }
 void csvhost_genome_contig_info(const csvhost_genome *g, uint64_t i, uint64_t *n_reads, uint64_t *n_cigar, uint32_t *depth_len, int32_t *global_tid, csv_shard **shard)
 {
@@ -191,6 +201,7 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
         const RunParams P = run_params_from(*opt);
         std::vector<csv_ctx *> lanes(lane_ctxs, lane_ctxs + (n_lanes > 0 ? n_lanes : 0));
         SVCaller caller(ctx);
+        caller.merge_on_device = g->merge_on_device; caller.merge_max_partitions = g->merge_max_partitions;
         // the call map of a genome is 3e4 records with strings in them: it is torn down beside whatever the caller does next — the next run,
         // in a loop of runs: the previous run's teardown is waited for when this run hands over its own map, not before it starts
         static std::mutex teardown_mu;                                          // (runs of different genomes may come from different threads)

@@ -154,15 +154,77 @@ void SVCaller::DeviceOut::reserve(csv_ctx *c, uint64_t n)
     cap = want;
 }
 
+void SVCaller::DeviceOut::reserveRep(csv_ctx *c, uint64_t n)
+{
+    if (n <= rep_cap && c == rep_ctx && cnt) return;
+    releaseRep();
+    rep_ctx = c;
+    const uint64_t want = n + n / 4 + 4096;
+    rep = (csv_merge_rep *)csvgpu_host_alloc(c, want * sizeof(csv_merge_rep));
+    cnt = (csv_merge_counts *)csvgpu_host_alloc(c, sizeof(csv_merge_counts));
+    if (!rep || !cnt) { releaseRep(); throw std::runtime_error("cannot allocate page-locked record buffers"); }
+    memset(cnt, 0, sizeof(*cnt));
+    rep_cap = want;
+}
+
+namespace {
+std::atomic<uint64_t> g_route_device{0}, g_route_declined{0}, g_route_overflow{0}, g_buckets_declined{0};
+}
+SVCaller::MergeRouteStats SVCaller::mergeRouteStats(bool reset)
+{
+    MergeRouteStats r;
+    r.contigs_device = g_route_device.load(); r.contigs_host_declined = g_route_declined.load(); r.contigs_host_overflow = g_route_overflow.load();
+    r.buckets_declined = g_buckets_declined.load();
+    if (reset) { g_route_device = 0; g_route_declined = 0; g_route_overflow = 0; g_buckets_declined = 0; }
+    return r;
+}
+
+void SVCaller::finishSelect(csv_shard *shard, const csv_chr_result &res, int rc, DeviceOut &out)
+{
+    out.use_rep = false;
+    bool overflow = false;
+    if (rc == CSV_ECAPACITY) {                         // more records than room: once more with room for what the counts say
+        out.reserveRep(ctx, out.cnt->n_rep[0] + out.cnt->n_rep[1]);
+        rc = csvgpu_chr_merge_select(ctx, shard, &res, merge_max_partitions, out.rep, out.rep_cap, out.cnt);
+        if (rc == CSV_ECAPACITY) { overflow = true; rc = CSV_OK; }
+    }
+    check(ctx, rc, "processChromosome (select)");
+    const uint64_t declined = out.cnt->n_declined[0] + out.cnt->n_declined[1];
+    g_buckets_declined += declined;
+    if (overflow || declined) {                        // today's route for this contig: everything comes down, the host picks
+        out.reserve(ctx, res.n_sig);
+        check(ctx, csvgpu_chr_fetch(ctx, shard, &res, out.sig, out.lab), "processChromosome (fetch behind a declined select)");
+        (declined ? g_route_declined : g_route_overflow)++;
+        return;
+    }
+    out.n_rep = out.cnt->n_rep[0] + out.cnt->n_rep[1];
+    out.use_rep = true;
+    g_route_device++;
+}
+
 void SVCaller::runDeviceChain(const std::string &chr, csv_shard *shard, double eps, double pct, DeviceOut &out, ChrStats &st)
 {
     const double t0 = now_ms();
     csv_chr_result res;
-    if (!out.cap) out.reserve(ctx, result_capacity_hint(ctx));
-    int rc = csvgpu_chr_pipeline_fetch(ctx, shard, (uint32_t)min_oplen, (uint8_t)min_mapq, eps, pct, &res, out.sig, out.lab, out.cap);
-    if (rc == CSV_ECAPACITY) {                         // first contig of this size: grow the buffers, fetch what the device already holds
-        out.reserve(ctx, res.n_sig);
-        rc = csvgpu_chr_fetch(ctx, shard, &res, out.sig, out.lab);
+    int rc;
+    out.use_rep = false;
+    if (merge_on_device) {
+        if (!out.rep_cap) out.reserveRep(ctx, 1 << 14);
+        csv_job *job = csvgpu_chr_job_begin(ctx, shard, (uint32_t)min_oplen, (uint8_t)min_mapq, pct);
+        if (!job) throw std::runtime_error(std::string("processChromosome: ") + csvgpu_last_error(ctx));
+        rc = csvgpu_chr_job_cluster_select(ctx, job, eps, merge_max_partitions, out.rep, out.rep_cap, out.cnt);
+        if (rc) { csvgpu_chr_job_abort(ctx, job); check(ctx, rc, "processChromosome"); }
+        rc = csvgpu_chr_job_end(ctx, job, &res);
+        if (rc != CSV_ECAPACITY) check(ctx, rc, "processChromosome");
+        finishSelect(shard, res, rc, out);
+        rc = CSV_OK;
+    } else {
+        if (!out.cap) out.reserve(ctx, result_capacity_hint(ctx));
+        rc = csvgpu_chr_pipeline_fetch(ctx, shard, (uint32_t)min_oplen, (uint8_t)min_mapq, eps, pct, &res, out.sig, out.lab, out.cap);
+        if (rc == CSV_ECAPACITY) {                     // first contig of this size: grow the buffers, fetch what the device already holds
+            out.reserve(ctx, res.n_sig);
+            rc = csvgpu_chr_fetch(ctx, shard, &res, out.sig, out.lab);
+        }
     }
     check(ctx, rc, "processChromosome");
     note_result_size(ctx, res.n_sig);
@@ -284,7 +346,15 @@ void SVCaller::hostMerge(const std::string &chr, const DeviceOut &in, const SeqS
     const double t1 = now_ms();
     csvhost::TraceScope tr("lane: host merge");
     printMessage(chr + ": Merging CIGAR...");
-    mergeOrdered(in.sig, in.lab, in.n_del, in.n_ins, seq, chr_sv_calls, share_pool);
+    if (in.use_rep) {                                  // the device chose: the records' calls, DEL records first, as mergeOrdered orders them
+        chr_sv_calls.clear();
+        chr_sv_calls.reserve(in.n_rep);
+        for (uint64_t i = 0; i < in.n_rep; i++) {
+            SVCall c = toSVCall(in.rep[i].sig, seq);
+            if (in.rep[i].status == 0) c.cluster_size = (int)in.rep[i].cluster_size;      // (a pass-through record stays untouched)
+            chr_sv_calls.push_back(std::move(c));
+        }
+    } else mergeOrdered(in.sig, in.lab, in.n_del, in.n_ins, seq, chr_sv_calls, share_pool);
     st.ms_host_merge = now_ms() - t1;
     printMessage(chr + ": Found " + std::to_string(getSVCount(chr_sv_calls)) + " SV candidates in the CIGAR string");
 }
@@ -379,18 +449,25 @@ void SVCaller::processResidentChromosomesPipelined(const std::vector<csv_shard *
             const double t0 = now_ms();
             DeviceOut &out = slot[i % kSlots];
             ChrStats &st = stats[i];
-            if (!out.cap) out.reserve(ctx, result_capacity_hint(ctx));
+            if (merge_on_device) { if (!out.rep_cap) out.reserveRep(ctx, 1 << 14); }
+            else if (!out.cap) out.reserve(ctx, result_capacity_hint(ctx));
             if (ahead.empty()) top_up();                   // (a repeated shard: its next pass could not be queued ahead)
             csv_job *job = ahead.front();
             ahead.pop_front();
-            int rc = csvgpu_chr_job_cluster(ctx, job, eps, out.sig, out.lab, out.cap);
+            int rc = merge_on_device ? csvgpu_chr_job_cluster_select(ctx, job, eps, merge_max_partitions, out.rep, out.rep_cap, out.cnt)
+                                     : csvgpu_chr_job_cluster(ctx, job, eps, out.sig, out.lab, out.cap);
             if (rc) { csvgpu_chr_job_abort(ctx, job); check(ctx, rc, "processChromosome"); }      // abort keeps the failure's own message
             open_shards.erase(open_shards.begin());       // this shard's clustering is queued: a later pass over it may follow on the stream
             // more scan + depth passes go into the queue now, behind this shard's clustering and copies
             try { top_up(); } catch (...) { csvgpu_chr_job_abort(ctx, job); throw; }
             csv_chr_result res;
             rc = csvgpu_chr_job_end(ctx, job, &res);
-            if (rc == CSV_ECAPACITY) {                     // first contig of this size: grow the buffers, fetch what the device still holds
+            out.use_rep = false;
+            if (merge_on_device) {
+                if (rc != CSV_ECAPACITY) check(ctx, rc, "processChromosome");
+                finishSelect(shards[i], res, rc, out);
+                rc = CSV_OK;
+            } else if (rc == CSV_ECAPACITY) {              // first contig of this size: grow the buffers, fetch what the device still holds
                 out.reserve(ctx, res.n_sig);
                 rc = csvgpu_chr_fetch(ctx, shards[i], &res, out.sig, out.lab);
             }
@@ -446,6 +523,7 @@ void SVCaller::processResidentLanes(const std::vector<Lane> &lanes, const SeqSto
             try {
                 SVCaller caller(lanes[l].ctx);
                 caller.min_mapq = min_mapq; caller.min_oplen = min_oplen;
+                caller.merge_on_device = lanes[l].merge_on_device; caller.merge_max_partitions = lanes[l].merge_max_partitions;
                 if (on_merged) caller.on_merged = [&on_merged, l](size_t k) { on_merged(l, k); };
                 if (on_device) caller.on_device = [&on_device, l](size_t k) { on_device(l, k); };
                 if (!lanes[l].seqs.empty()) caller.processResidentChromosomesPipelined(lanes[l].shards, lanes[l].seqs, eps, pct, calls[l], stats[l]);
@@ -1022,7 +1100,7 @@ void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const 
     std::vector<std::vector<std::vector<SVCall>>> lane_calls;
     std::vector<std::vector<ChrStats>> lane_stats;
     if (P.cigar_svs && n) {
-        for (size_t l = 0; l < L; l++) lanes[l].ctx = lane_ctxs.empty() ? ctx : lane_ctxs[l];
+        for (size_t l = 0; l < L; l++) { lanes[l].ctx = lane_ctxs.empty() ? ctx : lane_ctxs[l]; lanes[l].merge_on_device = merge_on_device; lanes[l].merge_max_partitions = merge_max_partitions; }
         std::vector<size_t> order(n);
         for (size_t i = 0; i < n; i++) order[i] = i;
         std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return contigs[a].split.n != contigs[b].split.n ? contigs[a].split.n > contigs[b].split.n : contigs[a].depth_len != contigs[b].depth_len ? contigs[a].depth_len > contigs[b].depth_len : a < b; });
@@ -1043,6 +1121,7 @@ void SVCaller::runResident(const std::vector<ResidentContig> &contigs_in, const 
             lane_calls.resize(1); lane_stats.resize(1);
             SVCaller one(lanes[0].ctx);
             one.min_mapq = min_mapq; one.min_oplen = min_oplen;
+            one.merge_on_device = merge_on_device; one.merge_max_partitions = merge_max_partitions;
             one.processResidentChromosomesPipelined(lanes[0].shards, lanes[0].seqs, P.dbscan_epsilon, P.dbscan_min_pts_pct, lane_calls[0], lane_stats[0]);
         } else {
             std::function<void(size_t, size_t)> on_merged, on_device;

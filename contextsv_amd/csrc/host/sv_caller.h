@@ -164,6 +164,15 @@ class SVCaller {
 public:
     explicit SVCaller(csv_ctx *ctx) : ctx(ctx) {}
     int min_mapq = 20;       // sv_caller.h:72 of the reference
+    // Opt-in: the representative choice of the CIGAR merge made on the device (csvgpu_chr_job_cluster_select): only the representatives' records
+    // come back and the merge threads materialise SVCalls from them. A contig with a declined bucket, or whose records overflowed twice, takes
+    // the host route (csvgpu_chr_fetch + mergeOrdered): the call set is the same either way. merge_max_partitions: the device's bound on the
+    // partitions per bucket (0: the library's own depth limit).
+    bool merge_on_device = false;
+    uint32_t merge_max_partitions = 0;
+    // which route the contigs of this process took since the last reset (all callers, all lanes), and the buckets the device declined
+    struct MergeRouteStats { uint64_t contigs_device = 0, contigs_host_declined = 0, contigs_host_overflow = 0, buckets_declined = 0; };
+    static MergeRouteStats mergeRouteStats(bool reset = false);
     int min_oplen = 50;      // sv_caller.cpp:566
 
     // Depth pass + CIGAR pass + CIGAR merge of one chromosome. `reads` are host arrays; they are uploaded,
@@ -192,7 +201,10 @@ public:
 
     // Several chromosomes in flight on one GPU: every lane is a context of its own (own stream; attach one csv_gate to all of them so
     // that their scan + depth pairs run back to back on the gate's stream) and runs processResidentChromosomesPipelined on its shards in its own pair of threads.
-    struct Lane { csv_ctx *ctx; std::vector<csv_shard *> shards; std::vector<const SeqStore *> seqs; /* per shard, or empty */ };
+    struct Lane {
+        csv_ctx *ctx; std::vector<csv_shard *> shards; std::vector<const SeqStore *> seqs; /* per shard, or empty */
+        bool merge_on_device = false; uint32_t merge_max_partitions = 0;       // the lane's caller takes them
+    };
     // Which rank of `world` takes which shard: longest processing time first over the weights (read counts), ties by index — the partition
     // `contextsv_amd.parallel.assign_shards` makes for bench.py --gpus N (the reference runs the chromosomes as independent pool tasks,
     // sv_caller.cpp:827-863; a rank's shards are what it stages and passes to runResident, the merged calls are gathered once at the end).
@@ -255,13 +267,24 @@ private:
         csv_sig *sig = nullptr;
         int32_t *lab = nullptr;
         uint64_t cap = 0, n_del = 0, n_ins = 0;
+        // merge_on_device: the representatives' records and their counts (page-locked); use_rep: the merge reads them, not sig / lab
+        csv_merge_rep *rep = nullptr;
+        csv_merge_counts *cnt = nullptr;
+        uint64_t rep_cap = 0, n_rep = 0;
+        bool use_rep = false;
         DeviceOut() = default;
         DeviceOut(const DeviceOut &) = delete;
         DeviceOut &operator=(const DeviceOut &) = delete;
-        ~DeviceOut() { release(); }
+        ~DeviceOut() { release(); releaseRep(); }
         void release() { if (ctx) { csvgpu_host_free(ctx, sig); csvgpu_host_free(ctx, lab); } sig = nullptr; lab = nullptr; cap = 0; }
+        void releaseRep() { if (rep_ctx) { csvgpu_host_free(rep_ctx, rep); csvgpu_host_free(rep_ctx, cnt); } rep = nullptr; cnt = nullptr; rep_cap = 0; }
         void reserve(csv_ctx *c, uint64_t n);
+        void reserveRep(csv_ctx *c, uint64_t n);
+        csv_ctx *rep_ctx = nullptr;
     };
     void runDeviceChain(const std::string &chr, csv_shard *shard, double eps, double pct, DeviceOut &out, ChrStats &st);
+    // behind csvgpu_chr_job_end of a select job (rc: what it returned): the records are in place, or selected again with room, or — a declined
+    // bucket, a second overflow — the signatures and labels are fetched for the host merge
+    void finishSelect(csv_shard *shard, const csv_chr_result &res, int rc, DeviceOut &out);
     static void hostMerge(const std::string &chr, const DeviceOut &in, const SeqStore *seq, std::vector<SVCall> &chr_sv_calls, ChrStats &st, bool share_pool = true);
 };

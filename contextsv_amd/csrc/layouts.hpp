@@ -12,7 +12,7 @@ namespace csv {
 #ifdef CSV_ARENA_LOG               // (the check program's build alone)
 // the check program must cover exactly these (a carve function added here without a line there fails tests/test_arena_layouts.py)
 static const char *const kLayoutNames[] = {"reads", "sortws", "depth", "dbscan_iv", "dbscan1d", "split_nodes", "split_epochs", "split_groups",
-                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_back", "cn_obs", "cn_tables", "bgzf", "bam_unpack", "vcf", "vcf_text", "dbscan_tmp", "viterbi_tmp"};
+                                           "sf_tables", "sf_run", "sr_refs", "sr_tables", "job_scratch", "window", "cn_back", "cn_obs", "cn_tables", "bgzf", "bam_unpack", "vcf", "vcf_text", "dbscan_tmp", "viterbi_tmp", "sort_slot", "merge_select", "merge_run"};
 constexpr size_t kLayoutCount = sizeof(kLayoutNames) / sizeof(kLayoutNames[0]);
 #endif
 
@@ -187,6 +187,54 @@ static inline bool carve_job_scratch(Arena &a, uint64_t n, JobScratch &j)
     // + 16 on start / end / labels: the clustering kernels' 16-byte loads at the arrays' ends
     return take(a, j.sig_sorted, n * sizeof(csv_sig)) && take(a, j.st, n * 4 + 16) && take(a, j.en, n * 4 + 16) && take(a, j.labels, n * 4 + 16) &&
            sortws_carve(a, n, j.w) && take(a, j.db_tmp, dbscan_tmp_bytes(n));
+}
+
+// the slot replay of a batch (kernels/mergeselect.hip): n (length, index) entries in n_seg segments, the pair lists of the streamed rounds,
+// the segments' offsets and slots, the answers, the lists of the segments that take a workgroup (17 members or more: at most n / 17 of them)
+struct SortSlotWs {
+    uint64_t *ent = nullptr;
+    uint32_t *list = nullptr, *off = nullptr, *nth = nullptr, *idx = nullptr, *mid = nullptr, *big = nullptr;
+    uint32_t *cnt = nullptr;            // [0] segments of the LDS form, [1] of the streaming form, [2] the segments in all
+};
+static inline bool carve_sort_slot(Arena &a, uint64_t n, uint64_t n_seg, SortSlotWs &w)
+{
+    const uint64_t wg = std::min(n_seg, n / 17);
+    return take(a, w.ent, n * 8) && take(a, w.list, n * 4) && take(a, w.off, (n_seg + 1) * 4) && take(a, w.nth, n_seg * 4) && take(a, w.idx, n_seg * 4) &&
+           take(a, w.mid, wg * 4) && take(a, w.big, wg * 4) && take(a, w.cnt, 256);
+}
+
+// mergeSVs' representatives of ONE type with n signatures (csvgpu_merge_select and its kin run it once per type over the same slices):
+// the bucket sort, the head marks and the kept-bucket marks with their sums, and the slot replay of up to n buckets
+struct MergeSelectWs {
+    SortWs sw;
+    SortSlotWs ss;
+    uint32_t *head = nullptr, *keep = nullptr;
+    void *es_tmp = nullptr;
+};
+static inline bool carve_merge_select(Arena &a, uint64_t n, MergeSelectWs &w)
+{
+    return sortws_carve(a, n, w.sw) && carve_sort_slot(a, n, n, w.ss) && take(a, w.head, (n + 1) * 4) && take(a, w.keep, (n + 1) * 4) &&
+           take(a, w.es_tmp, exclusive_sum_tmp_bytes(n + 1));
+}
+
+// One contig's select, both types over the same slices: what the call reads back behind its kernels (the counts and the two bucket sorts'
+// gave-up words: each sort reuses the other's workspace, so the words are copied here before the next sort clears them) and the records.
+// This is the carve of a shard's select scratch (csv_shard::sel_scratch) and, for the host-fed call, of the context's workspace.
+struct MergeBack {
+    csv_merge_counts counts;
+    uint32_t gave_up[2];
+    uint32_t pad[6];
+};
+struct MergeRunWs {
+    MergeSelectWs ms;
+    MergeBack *back = nullptr;
+    csv_merge_rep *rep = nullptr;
+};
+// records never exceed this: one per bucket of two or more, or a type's single signature passed through
+static inline uint64_t merge_rep_bound(uint64_t n_del, uint64_t n_ins) { return (n_del < 2 ? n_del : n_del / 2) + (n_ins < 2 ? n_ins : n_ins / 2); }
+static inline bool carve_merge_run(Arena &a, uint64_t n_del, uint64_t n_ins, MergeRunWs &w)
+{
+    return carve_merge_select(a, std::max(n_del, n_ins), w.ms) && take(a, w.back, 256) && take(a, w.rep, merge_rep_bound(n_del, n_ins) * sizeof(csv_merge_rep));
 }
 
 // region tables in, windows out (csvgpu_window_log2*)

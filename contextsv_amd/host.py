@@ -85,6 +85,11 @@ def load() -> C.CDLL:
     lib.csvhost_query_snp_regions_table.argtypes = [_P, _P, C.c_uint64, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P, C.c_uint64, C.c_int, _P,
                                                     _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.csvhost_genome_snp_tables_resident.argtypes = [_P, C.c_int]
+    lib.csvhost_genome_merge_on_device.argtypes = [_P, C.c_int, C.c_uint32]
+    lib.csvhost_set_merge_on_device.restype = None
+    lib.csvhost_set_merge_on_device.argtypes = [C.c_int, C.c_uint32]
+    lib.csvhost_merge_route_stats.restype = None
+    lib.csvhost_merge_route_stats.argtypes = [_P, C.c_int]
     lib.csvhost_cn_table_capacity_hint.restype = C.c_uint64
     lib.csvhost_cn_table_capacity_hint.argtypes = [C.c_int]
     lib.csvhost_split_signatures.argtypes = [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -100,6 +105,8 @@ def load() -> C.CDLL:
     lib.csvhost_read_chmm.argtypes = [C.c_char_p, C.POINTER(_lib.csv_hmm), C.POINTER(C.c_int32)]
     lib.csvhost_sort_select_check.argtypes = [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.csvhost_partition_check.argtypes = [_P, C.c_uint64, C.POINTER(C.c_int)]
+    lib.csvhost_sort_select_rounds.restype = C.c_int64
+    lib.csvhost_sort_select_rounds.argtypes = [_P, C.c_uint64, C.c_uint64]
     lib.csvhost_fasta_open.restype = _P
     lib.csvhost_fasta_open.argtypes = [C.c_char_p]
     lib.csvhost_fasta_open_device.restype = _P
@@ -402,6 +409,12 @@ class Genome:
         -> the number of resident tables (a contig whose table the device refuses stays on the host route)."""
         return int(load().csvhost_genome_snp_tables_resident(self.h, int(bool(on))))
 
+    def merge_on_device(self, on: bool = True, max_partitions: int = 0):
+        """Opt-in: run() has the CIGAR merge's representatives chosen on the device (csvgpu_chr_job_cluster_select): only their records come
+        back instead of every signature and label. Same calls and statistics; a contig with a bucket the device declines (max_partitions bounds
+        the partitions per bucket, 0 = the library's own limit) takes the host route — merge_route_stats() says how many did."""
+        _check(load().csvhost_genome_merge_on_device(self.h, int(bool(on)), int(max_partitions)))
+
     def free(self):
         if self.h:
             load().csvhost_genome_free(self.h)
@@ -448,7 +461,44 @@ def sig_alts(sig: np.ndarray, seq_off=None, seq=None):
     return buf.raw[: ln.value].decode().split("\n")[:-1]
 
 
-def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off=None, seq=None, resident_seq: bool = False):
+def merge_ordered(sig: np.ndarray, labels: np.ndarray, n_del: int, reps: int = 1):
+    """SVCaller::mergeOrdered alone (no device): ordered signatures + labels -> (merged calls, mean ms of one of `reps` repetitions)."""
+    sig = np.ascontiguousarray(sig, _lib.SIG_DTYPE)
+    labels = np.ascontiguousarray(labels, np.int32)
+    cap = len(sig) // 2 + 4
+    out = np.zeros(cap, CALL_DTYPE)
+    n, ms = C.c_uint64(0), C.c_double(0)
+    lib = load()
+    lib.csvhost_merge_ordered.argtypes = [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    _check(lib.csvhost_merge_ordered(sig.ctypes.data, labels.ctypes.data, n_del, len(sig) - n_del, reps, out.ctypes.data, cap, C.byref(n), C.byref(ms)))
+    return out[: min(n.value, cap)].copy(), ms.value
+
+
+def merge_route_stats(reset: bool = False) -> dict:
+    """Which route the contigs of this process took since the last reset (SVCaller::mergeRouteStats): device = the representatives came from
+    the device; host_declined / host_overflow = fetched and merged on the host because a bucket was declined / the records overflowed twice;
+    buckets_declined = buckets the device declined in all."""
+    out = np.zeros(4, np.uint64)
+    load().csvhost_merge_route_stats(out.ctypes.data, int(bool(reset)))
+    return dict(device=int(out[0]), host_declined=int(out[1]), host_overflow=int(out[2]), buckets_declined=int(out[3]))
+
+
+class _merge_switch:
+    """SVCaller::merge_on_device for the callers behind the process_resident_* functions, for the length of one call"""
+    def __init__(self, on, max_partitions):
+        self.on, self.mp = bool(on), int(max_partitions)
+
+    def __enter__(self):
+        if self.on:
+            load().csvhost_set_merge_on_device(1, self.mp)
+
+    def __exit__(self, *a):
+        if self.on:
+            load().csvhost_set_merge_on_device(0, 0)
+
+
+def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off=None, seq=None, resident_seq: bool = False,
+                                     merge_on_device: bool = False, merge_max_partitions: int = 0):
     """processChromosome on a resident shard -> [(start, end, ALT)] of the merged calls. resident_seq: the 50-base ALT strings are cut on the
     device from the sequences the shard itself holds (a shard built with _lib.SB_SEQ) instead of from seq_off / seq."""
     so = np.ascontiguousarray(seq_off, np.uint64) if seq_off is not None else None
@@ -456,13 +506,14 @@ def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min
     cap = 1 << 22
     buf = C.create_string_buffer(cap)
     ln = C.c_uint64(0)
-    if resident_seq:
-        if so is not None or sq is not None:
-            raise ValueError("process_resident_chromosome_alts: resident_seq takes the shard's own sequences, not seq_off / seq")
-        _check(load().csvhost_process_resident_chromosome_alts_resident(ctx.h, shard.h, eps, min_pts_pct, buf, cap, C.byref(ln)))
-    else:
-        _check(load().csvhost_process_resident_chromosome_alts(ctx.h, shard.h, so.ctypes.data if so is not None else None,
-                                                               sq.ctypes.data if sq is not None else None, eps, min_pts_pct, buf, cap, C.byref(ln)))
+    if resident_seq and (so is not None or sq is not None):
+        raise ValueError("process_resident_chromosome_alts: resident_seq takes the shard's own sequences, not seq_off / seq")
+    with _merge_switch(merge_on_device, merge_max_partitions):
+        if resident_seq:
+            _check(load().csvhost_process_resident_chromosome_alts_resident(ctx.h, shard.h, eps, min_pts_pct, buf, cap, C.byref(ln)))
+        else:
+            _check(load().csvhost_process_resident_chromosome_alts(ctx.h, shard.h, so.ctypes.data if so is not None else None,
+                                                                   sq.ctypes.data if sq is not None else None, eps, min_pts_pct, buf, cap, C.byref(ln)))
     out = []
     for line in buf.raw[: ln.value].decode().split("\n")[:-1]:
         a, b, alt = line.split("\t")
@@ -470,32 +521,36 @@ def process_resident_chromosome_alts(ctx: Context, shard: Shard, eps: float, min
     return out
 
 
-def process_resident_chromosome(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off_ptr=None, seq_ptr=None, capacity: int = 1 << 20):
+def process_resident_chromosome(ctx: Context, shard: Shard, eps: float, min_pts_pct: float, seq_off_ptr=None, seq_ptr=None, capacity: int = 1 << 20,
+                                merge_on_device: bool = False, merge_max_partitions: int = 0):
     """SVCaller::processChromosome mirror on a resident shard -> (merged calls, alt tags, stats)."""
     out = np.zeros(capacity, CALL_DTYPE)
     tag = np.zeros(capacity, np.uint8)
     st = chr_stats()
-    _check(load().csvhost_process_resident_chromosome(ctx.h, shard.h, seq_off_ptr, seq_ptr, eps, min_pts_pct, out.ctypes.data, tag.ctypes.data,
-                                                      capacity, C.byref(st)))
+    with _merge_switch(merge_on_device, merge_max_partitions):
+        _check(load().csvhost_process_resident_chromosome(ctx.h, shard.h, seq_off_ptr, seq_ptr, eps, min_pts_pct, out.ctypes.data, tag.ctypes.data,
+                                                          capacity, C.byref(st)))
     n = min(st.n_calls, capacity)
     return out[:n].copy(), tag[:n].copy(), st
 
 
 def process_resident_pipelined(ctx: Context, shard: Shard, n_steps: int, eps: float, min_pts_pct: float, seq_off_ptr=None, seq_ptr=None,
-                               capacity: int = 1 << 20):
+                               capacity: int = 1 << 20, merge_on_device: bool = False, merge_max_partitions: int = 0):
     """n_steps pipelined passes over one resident shard (device chain of step i+1 overlaps the host merge of step i).
     -> (merged calls of the last step, alt tags, stats averaged over steps, wall ms, total merged calls)."""
     out = np.zeros(capacity, CALL_DTYPE)
     tag = np.zeros(capacity, np.uint8)
     st = chr_stats()
     ms, tot = C.c_double(0), C.c_uint64(0)
-    _check(load().csvhost_process_resident_pipelined(ctx.h, shard.h, n_steps, seq_off_ptr, seq_ptr, eps, min_pts_pct, out.ctypes.data,
-                                                     tag.ctypes.data, capacity, C.byref(st), C.byref(ms), C.byref(tot)))
+    with _merge_switch(merge_on_device, merge_max_partitions):
+        _check(load().csvhost_process_resident_pipelined(ctx.h, shard.h, n_steps, seq_off_ptr, seq_ptr, eps, min_pts_pct, out.ctypes.data,
+                                                         tag.ctypes.data, capacity, C.byref(st), C.byref(ms), C.byref(tot)))
     n = min(st.n_calls, capacity)
     return out[:n].copy(), tag[:n].copy(), st, ms.value, tot.value
 
 
-def process_resident_lanes(ctxs, shards, steps, eps: float, min_pts_pct: float, capacity: int = 1 << 20):
+def process_resident_lanes(ctxs, shards, steps, eps: float, min_pts_pct: float, capacity: int = 1 << 20, merge_on_device: bool = False,
+                           merge_max_partitions: int = 0):
     """Several contexts of one GPU, lane l doing steps[l] pipelined passes over shards[l] at the same time (attach one Gate to all
     contexts first). -> (lane 0's last merged calls, stats averaged over all steps, wall ms, total merged calls)."""
     n = len(ctxs)
@@ -505,8 +560,9 @@ def process_resident_lanes(ctxs, shards, steps, eps: float, min_pts_pct: float, 
     out = np.zeros(capacity, CALL_DTYPE)
     st = chr_stats()
     ms, tot = C.c_double(0), C.c_uint64(0)
-    _check(load().csvhost_process_resident_lanes(n, cp, sp, st_n.ctypes.data, eps, min_pts_pct, out.ctypes.data, capacity, C.byref(st), C.byref(ms),
-                                                 C.byref(tot)))
+    with _merge_switch(merge_on_device, merge_max_partitions):
+        _check(load().csvhost_process_resident_lanes(n, cp, sp, st_n.ctypes.data, eps, min_pts_pct, out.ctypes.data, capacity, C.byref(st), C.byref(ms),
+                                                     C.byref(tot)))
     return out[: min(st.n_calls, capacity)].copy(), st, ms.value, tot.value
 
 
@@ -722,6 +778,16 @@ def sort_select_check(keys: np.ndarray, nth: int):
     a, b = C.c_int64(-1), C.c_int64(-1)
     _check(load().csvhost_sort_select_check(keys.ctypes.data, len(keys), nth, C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def sort_select_rounds(keys: np.ndarray, nth: int) -> int:
+    """How many partitions libstdc++'s std::sort (descending by key) runs on the ranges that hold slot nth, or -1 where its depth limit runs
+    out first (it heap-sorts there). Context.sort_slot declines the segments whose count exceeds its bound, and those of -1 always."""
+    keys = np.ascontiguousarray(keys, np.uint32)
+    r = load().csvhost_sort_select_rounds(keys.ctypes.data, len(keys), nth)
+    if r < -1:
+        raise RuntimeError("csvhost_sort_select_rounds failed")
+    return int(r)
 
 
 def partition_check(keys: np.ndarray) -> bool:

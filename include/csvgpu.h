@@ -266,7 +266,8 @@ typedef struct csv_chr_result {
 /* The whole per-chromosome device path of SVCaller::processChromosome up to cluster labels
  * (sv_caller.cpp:692-745 with cnv_caller.cpp:488-543 in front): CIGAR scan -> depth map and mean
  * coverage -> min_pts -> ordering -> per-type interval DBSCAN. Representative selection of
- * mergeSVs (sv_object.cpp:121-244) is host code above this ABI.
+ * mergeSVs (sv_object.cpp:121-244) is host code above this ABI. (Opt-in, that choice has a device form too: csvgpu_chr_merge_select below
+ * works on what this call leaves on the shard.)
  * min_pts_pct <= 0 selects the fixed min_pts = 5 (sv_caller.cpp:724-727). */
 int csvgpu_chr_pipeline_dev(csv_ctx *ctx, csv_shard *shard, uint32_t min_oplen, uint8_t min_mapq,
                             double eps, double min_pts_pct, csv_chr_result *result);
@@ -302,6 +303,56 @@ int csvgpu_chr_job_end(csv_ctx *ctx, csv_job *job, csv_chr_result *result);
 /* Give up a job after csvgpu_chr_job_cluster (or anything between begin and end) failed: waits for what the job queued, frees it,
  * and leaves csvgpu_last_error() as the failure left it (csvgpu_chr_job_end on an unclustered job would overwrite it). */
 int csvgpu_chr_job_abort(csv_ctx *ctx, csv_job *job);
+
+/* ---- mergeSVs' representatives on the device (opt-in; kernels/mergeselect.hip, the rule in contextsv_amd/csrc/sort_select_core.hpp) ----
+ * mergeSVs keeps one member of every cluster (and of the noise bucket): with the members sorted by length descending through an UNSTABLE
+ * std::sort, the one at slot [max(1, (int)(size * 0.2)) / 2] (sv_object.cpp:190-230). With length ties that member is whatever libstdc++'s
+ * introsort leaves there; the device replays the chain of partitions that decides the slot, exactly. What it does not replay is the
+ * library's heap-sort fallback (the depth limit 2 floor(log2 size) running out): such a bucket is DECLINED, never answered wrong, and the
+ * caller takes the host route (csvgpu_chr_fetch and the host merge) for that contig. Timed under CSV_K_MISC. */
+
+/* The primitive on its own, batched: idx_out[s] = the index inside segment s = keys[seg_off[s] .. seg_off[s + 1]) of the element that
+ * libstdc++'s std::sort by key DESCENDING leaves at slot nth[s] of that segment. max_partitions == 0: the library's own depth limit; a
+ * smaller positive value is the caller's bound on the partitions per segment. A segment whose chain needs more partitions than the bound is
+ * declined: idx_out[s] = UINT32_MAX, declined_out[s] = 1 (declined_out may be NULL). Segments of up to 16 elements need no partition and
+ * are never declined. An empty segment: idx_out[s] = UINT32_MAX, declined_out[s] = 0, nth[s] not read. seg_off[0] == 0.
+ * CSV_EINVAL: a null array, offsets not ascending, nth[s] beyond its segment, 2^31 or more keys or segments, a split order pending on the
+ * context. n_seg == 0 is valid. */
+int csvgpu_sort_slot(csv_ctx *ctx, const uint32_t *keys, const uint64_t *seg_off, uint64_t n_seg, const uint64_t *nth, uint32_t max_partitions,
+                     uint32_t *idx_out, uint8_t *declined_out);
+
+typedef struct csv_merge_rep {      /* 32 bytes */
+    csv_sig  sig;                   /* the chosen member, untouched (read and qpos included: the host cuts the ALT from them) */
+    int32_t  label;                 /* the bucket's DBSCAN label; -2 for a pass-through record */
+    uint32_t cluster_size;          /* bucket size; 0 for a pass-through record */
+    uint32_t status;                /* 0 chosen, 1 pass-through (its type has < 2 signatures: sv_object.cpp:85-92), 2 declined (sig undefined) */
+    uint32_t reserved;              /* 0 */
+} csv_merge_rep;
+typedef struct csv_merge_counts { uint64_t n_rep[2]; uint64_t n_declined[2]; } csv_merge_counts;   /* [0] DEL, [1] INS */
+
+/* One contig's representatives from host arrays (the seam for tests and other callers): sig / labels [n_del + n_ins], the DEL signatures
+ * first, each type in chr_sv_calls order with its labels as csvgpu_dbscan_iv gives them (-2 noise, 0 .. k - 1). Per type: buckets by label,
+ * ascending, -2 first, members in input order; one record per bucket of two or more members, in bucket order; a type with fewer than two
+ * signatures passes them through (status 1; its labels are neither read nor copied). DEL records come first. counts->n_rep: records per type;
+ * n_declined: how many of them have status 2.
+ * CSV_ECAPACITY: n_rep[0] + n_rep[1] > capacity; counts is valid and nothing is written to rep_out. n_sig / 2 + 2 records always suffice.
+ * CSV_EINVAL: a null array, a label below -2 or above 2^31 - 17, 2^31 or more signatures of a type, a split order pending on the context.
+ * CSV_EHIP also when a bounded device loop (a radix pass's look-back) gave up. */
+int csvgpu_merge_select(csv_ctx *ctx, const csv_sig *sig, const int32_t *labels, uint64_t n_del, uint64_t n_ins, uint32_t max_partitions,
+                        csv_merge_rep *rep_out, uint64_t capacity, csv_merge_counts *counts);
+/* The same on the still-valid results of the last pipeline on `shard` (csvgpu_chr_pipeline_dev / _fetch, csvgpu_chr_job_end): the signatures
+ * and labels stay on the device, 32 bytes per counts and 32 per representative come back. After CSV_ECAPACITY the caller calls again with
+ * room, or fetches (csvgpu_chr_fetch) and merges on the host — as it does for a contig with a declined bucket. */
+int csvgpu_chr_merge_select(csv_ctx *ctx, csv_shard *shard, const csv_chr_result *result, uint32_t max_partitions, csv_merge_rep *host_rep,
+                            uint64_t capacity, csv_merge_counts *counts);
+
+/* csvgpu_chr_job_cluster with the select queued behind the DBSCAN: nothing of the signatures or labels is copied; min(capacity, n_sig / 2 + 2)
+ * records and the counts ride behind the last kernel into host_rep / host_counts (page-locked memory from csvgpu_host_alloc), valid once
+ * csvgpu_chr_job_end has returned. csvgpu_chr_job_end is called as before: CSV_ECAPACITY when there are more records than `capacity`
+ * (host_counts valid; *result valid: csvgpu_chr_merge_select with room, or csvgpu_chr_fetch), CSV_EHIP when a radix pass gave up. The
+ * select's workspace is the shard's own (allocated at its first use, grow-only): nothing a job queued ahead uses is touched. */
+int csvgpu_chr_job_cluster_select(csv_ctx *ctx, csv_job *job, double eps, uint32_t max_partitions, csv_merge_rep *host_rep, uint64_t capacity,
+                                  csv_merge_counts *host_counts);
 
 /* Several chromosomes in flight on one GPU: several contexts (one per host thread, each with its own stream) that share a gate.
  * They queue the scan + depth pair of their jobs onto the gate's ONE stream — so the bandwidth-bound kernels of all lanes run back

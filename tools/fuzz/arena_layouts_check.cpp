@@ -91,6 +91,7 @@ int main()
         { SortWs w; run_case(tag("sortws", {n}), [&](Arena &a) { return sortws_carve(a, n, w); }, [&](char *, char *) { return sort_adjacent(w, n); }); }
         { DbscanIvWs w; run_case(tag("dbscan_iv", {n}), [&](Arena &a) { return carve_dbscan_iv(a, n, w); }, [&](char *, char *) { return sort_adjacent(w.w, n); }); }
         { JobScratch w; run_case(tag("job_scratch", {n}), [&](Arena &a) { return carve_job_scratch(a, n, w); }, [&](char *, char *) { return sort_adjacent(w.w, n); }); }
+        { MergeSelectWs w; run_case(tag("merge_select", {n}), [&](Arena &a) { return carve_merge_select(a, n, w); }, [&](char *, char *) { return sort_adjacent(w.sw, n); }); }
         { DbscanTmp w; run_case(tag("dbscan_tmp", {n}), [&](Arena &a) { return carve_dbscan_tmp(a, n, kUfTile, w); }); }
         { ViterbiTmp w; run_case(tag("viterbi_tmp", {n}), [&](Arena &a) { return carve_viterbi_tmp(a, n, 1000, w); }); }
         for (uint32_t dl : depth_lens) { DepthWs w; run_case(tag("depth", {n, dl}), [&](Arena &a) { return carve_depth(a, n, dl, w); }, [&](char *, char *) { return sort_adjacent(w.w, n); }); }
@@ -98,6 +99,8 @@ int main()
         for (uint64_t m : counts) {
             { ReadsWs w; run_case(tag("reads", {n, m}), [&](Arena &a) { return carve_reads(a, n, m, w); }); }
             { SplitNodesWs w; run_case(tag("split_nodes", {n, m}), [&](Arena &a) { return carve_split_nodes(a, n, m, w); }); }
+            { MergeRunWs w; run_case(tag("merge_run", {n, m}), [&](Arena &a) { return carve_merge_run(a, n, m, w); }, [&](char *, char *) { return sort_adjacent(w.ms.sw, std::max(n, m)); }); }
+            { SortSlotWs w; run_case(tag("sort_slot", {n, m}), [&](Arena &a) { return carve_sort_slot(a, n, m, w); }); }
             { WindowWs w; run_case(tag("window", {n, m}), [&](Arena &a) { return carve_window(a, n, m, w); }); }
             // (both copy-number routes end with the same back half: from its first slice to the reservation's end it is as large in either)
             auto back_bytes = [&](uint64_t S, bool dec) { return arena_plan_bytes([&](Arena &a) { CnBack b; return carve_cn_back(a, n, m, S, dec, b); }); };
@@ -187,7 +190,7 @@ int main()
     }
 
     // every count of a layout (n, n_seg, G, nm, ns: its leading arguments) has taken every value of the list
-    const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
+    const std::map<std::string, size_t> n_counts = {{"sortws", 1}, {"merge_select", 1}, {"sort_slot", 2}, {"merge_run", 2}, {"dbscan_iv", 1}, {"job_scratch", 1}, {"dbscan_tmp", 1}, {"viterbi_tmp", 1}, {"depth", 1}, {"sf_run", 1},
                                                     {"reads", 2}, {"split_nodes", 2}, {"window", 2}, {"cn_back", 2}, {"cn_obs", 2}, {"cn_tables", 2},{"bgzf", 2}, {"bam_unpack", 2}, {"vcf", 2}, {"vcf_text", 2}, {"sr_tables", 2}, {"sf_tables", 2}, {"split_groups", 2},
                                                     {"split_epochs", 2}, {"sr_refs", 3}, {"dbscan1d", 0}};
     for (const auto &kv : args) {
