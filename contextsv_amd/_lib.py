@@ -112,6 +112,16 @@ class csv_vcf_counts(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("n_kept", C.c_uint64), ("n_deferred", C.c_uint64), ("stop_off", C.c_uint64), ("status", C.c_uint64)]
 
 
+class csv_snp_runs(C.Structure):
+    _fields_ = [("run_first", C.c_void_p), ("run_line_off", C.c_void_p), ("run_chrom_len", C.c_void_p), ("defer_off", C.c_void_p),
+                ("cap_runs", C.c_uint64), ("cap_defer", C.c_uint64)]
+
+
+class csv_snp_append_counts(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_kept", C.c_uint64), ("n_deferred", C.c_uint64), ("n_runs", C.c_uint64), ("first_run", C.c_uint64),
+                ("status", C.c_uint64)]
+
+
 VCF_TILE_BYTES = 4096    # include/csvgpu.h CSV_VCF_TILE_BYTES
 VCF_HEADER_LINE = 1      # csv_vcf_counts::status reason
 VCF_NO_STOP = (1 << 64) - 1
@@ -242,6 +252,20 @@ ABI = {
     "csvgpu_genome_free": (None, [_P, _P]),
     "csvgpu_genome_describe": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(csv_genome_counts)]),
     "csvgpu_genome_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int, _P]),
+    "csvgpu_snp_builder_create": (_P, [_P, C.c_uint64]),
+    "csvgpu_snp_builder_append": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_snp_runs), C.POINTER(csv_snp_append_counts)]),
+    "csvgpu_snp_builder_append_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_snp_runs), C.POINTER(csv_snp_append_counts)]),
+    "csvgpu_snp_builder_append_host": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
+    "csvgpu_snp_builder_finish": (_P, [_P, _P, _P, C.c_uint64]),
+    "csvgpu_snp_builder_destroy": (None, [_P, _P]),
+    "csvgpu_snp_columns_describe": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "csvgpu_snp_columns_fetch": (C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    "csvgpu_snp_columns_af_parse": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(csv_vcf_out),
+                                              C.POINTER(csv_vcf_counts)]),
+    "csvgpu_snp_columns_af_parse_dev": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(csv_vcf_out),
+                                                  C.POINTER(csv_vcf_counts)]),
+    "csvgpu_snp_columns_table": (_P, [_P, _P, C.c_uint32, _P, _P, C.c_uint64]),
+    "csvgpu_snp_columns_free": (None, [_P, _P]),
     "csvgpu_window_log2_resident": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P, _P, _P]),
     "csvgpu_window_log2_resident_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "csvgpu_chr_fetch": (C.c_int, [_P, _P, C.POINTER(csv_chr_result), _P, _P]),

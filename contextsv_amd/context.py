@@ -880,6 +880,11 @@ class Context:
         (the file's size: the array never grows then)."""
         return GenomeBuilder(self, reserve_bytes)
 
+    def snp_builder(self, reserve: int = 0) -> "SnpBuilder":
+        """csvgpu_snp_builder_create: per-contig SNP columns that are built on the device from VCF text batches. reserve: records
+        allocated now."""
+        return SnpBuilder(self, reserve)
+
     def alt_bases(self, shard: "Shard", read, qpos, lengths):
         """csvgpu_alt_bases_resident: for item i the `lengths[i]` bases from query offset qpos[i] of record read[i], cut from the packed
         sequences a built shard holds (ambiguity codes as N; all N where the bases leave the stored sequence) -> list of str."""
@@ -905,6 +910,190 @@ class SnpTable:
         if self.h:
             self.ctx.lib.csvgpu_snp_table_free(self.ctx.h, self.h)
             self.h = None
+
+
+class SnpBuilder:
+    """csv_snp_builder: the kept SNP records of VCF text batches in device arrays that grow, cut into CHROM runs on the device; finish()
+    orders them by (contig id, order key) and gives SnpColumns."""
+
+    _RUN_KEYS = ("run_first", "run_line_off", "run_chrom_len")
+
+    def __init__(self, ctx: Context, reserve: int = 0):
+        self.ctx = ctx
+        self.h = ctx.lib.csvgpu_snp_builder_create(ctx.h, int(reserve))
+        if not self.h:
+            raise ctx._error(_lib.CSV_ENOMEM)
+
+    def _live(self):
+        if not self.h:
+            raise ValueError("SnpBuilder: already finished or destroyed")
+
+    def _append(self, dev, text_ptr, length, text_base, out, dp_int, ad_int):
+        self._live()
+        o = _lib.csv_snp_runs()
+        for k in self._RUN_KEYS + ("defer_off",):
+            a = out.get(k)
+            if a is None or a.dtype != np.uint32 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise ValueError(f"snp_builder.append: '{k}' must be a writeable contiguous uint32 array")
+            setattr(o, k, a.ctypes.data)
+        o.cap_runs = min(len(out[k]) for k in self._RUN_KEYS)
+        o.cap_defer = len(out["defer_off"])
+        c = _lib.csv_snp_append_counts()
+        fn = self.ctx.lib.csvgpu_snp_builder_append_dev if dev else self.ctx.lib.csvgpu_snp_builder_append
+        rc = fn(self.ctx.h, self.h, text_ptr, int(length), int(text_base), int(bool(dp_int)), int(bool(ad_int)), C.byref(o), C.byref(c))
+        d = {k: int(getattr(c, k)) for k in ("n_lines", "n_kept", "n_deferred", "n_runs", "first_run", "status")}
+        d["reason"], d["offset"] = d["status"] & 0xFF, d["status"] >> 8
+        return rc, d
+
+    def append_into(self, text, out: dict, text_base: int = 0, dp_int: bool = True, ad_int: bool = True):
+        """csvgpu_snp_builder_append: whole VCF data lines (bytes or a uint8 array) whose first byte is byte `text_base` of the file. out:
+        uint32 numpy arrays run_first / run_line_off / run_chrom_len (the call's CHROM runs) and defer_off; the capacities are their
+        lengths. -> (rc, counts): rc 0 appended, 1 declined, or a negative CSV_E* (CSV_ECAPACITY with the exact counts, CSV_ENOMEM with
+        the builder unchanged)."""
+        data = _as_u8(text)
+        return self._append(False, ptr(data) if len(data) else None, len(data), text_base, out, dp_int, ad_int)
+
+    def append_dev_into(self, d_text, out: dict, text_base: int = 0, dp_int: bool = True, ad_int: bool = True):
+        """csvgpu_snp_builder_append_dev: the same for a uint8 torch tensor on the context's device, at any alignment."""
+        if not _is_dev(d_text, 1):
+            raise ValueError("append_dev: contiguous uint8 device tensor expected")
+        return self.append_ptr_into(d_text.data_ptr(), int(d_text.numel()), out, text_base, dp_int, ad_int)
+
+    def append_ptr_into(self, dev_ptr: int, length: int, out: dict, text_base: int = 0, dp_int: bool = True, ad_int: bool = True):
+        """The same for `length` bytes at a device address."""
+        return self._append(True, dev_ptr if length else None, length, text_base, out, dp_int, ad_int)
+
+    def _sized(self, into):
+        def alloc(r, d):
+            a = {k: np.zeros(max(r, 1), np.uint32)[:r] for k in self._RUN_KEYS}
+            a["defer_off"] = np.zeros(max(d, 1), np.uint32)[:d]
+            return a
+        arrays = alloc(0, 0)
+        rc, c = into(arrays)
+        if rc == _lib.CSV_ECAPACITY:
+            arrays = alloc(c["n_runs"], c["n_deferred"])
+            rc, c = into(arrays)
+        if rc < 0:
+            self.ctx._check(rc)
+        c["declined"] = rc == 1
+        if rc == 0:
+            c.update(arrays)
+        return c
+
+    def append(self, text, text_base: int = 0, dp_int: bool = True, ad_int: bool = True) -> dict:
+        """The same into arrays of exactly the run and deferred counts (a sizing call first) -> dict of the counts, 'declined', and
+        (unless declined) the arrays."""
+        return self._sized(lambda a: self.append_into(text, a, text_base, dp_int, ad_int))
+
+    def append_dev(self, d_text, text_base: int = 0, dp_int: bool = True, ad_int: bool = True) -> dict:
+        return self._sized(lambda a: self.append_dev_into(d_text, a, text_base, dp_int, ad_int))
+
+    def append_host_raw(self, contig_id, order_key, pos, baf) -> int:
+        """csvgpu_snp_builder_append_host -> status."""
+        self._live()
+        cid, key = np.ascontiguousarray(contig_id, np.uint32), np.ascontiguousarray(order_key, np.uint64)
+        pos, baf = np.ascontiguousarray(pos, np.uint32), np.ascontiguousarray(baf, np.float64)
+        if not len(cid) == len(key) == len(pos) == len(baf):
+            raise ValueError("append_host: array lengths disagree")
+        return self.ctx.lib.csvgpu_snp_builder_append_host(self.ctx.h, self.h, len(cid), ptr(cid), ptr(key), ptr(pos), ptr(baf))
+
+    def append_host(self, contig_id, order_key, pos, baf):
+        """Records the host parser kept (deferred lines, declined batches), each with its contig id (< 2^16) and its line's file offset."""
+        self.ctx._check(self.append_host_raw(contig_id, order_key, pos, baf))
+
+    def finish(self, run_contig) -> "SnpColumns":
+        """csvgpu_snp_builder_finish: run_contig[r] = the contig id of global run r. The builder is consumed, also on failure."""
+        self._live()
+        rc_ = np.ascontiguousarray(run_contig, np.uint32)
+        h, self.h = self.ctx.lib.csvgpu_snp_builder_finish(self.ctx.h, self.h, ptr(rc_) if len(rc_) else None, len(rc_)), None
+        if not h:
+            raise self.ctx._error(_lib.CSV_EINVAL)
+        return SnpColumns(self.ctx, h)
+
+    def destroy(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.csvgpu_snp_builder_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    __del__ = destroy
+
+
+class SnpColumns:
+    """csv_snp_columns: per-contig pos / baf columns resident on the device, in file order inside each contig."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx, self.h = ctx, handle
+
+    def free(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.ctx.lib.csvgpu_snp_columns_free(self.ctx.h, self.h)
+        self.h = None
+
+    __del__ = free
+
+    def describe(self) -> dict:
+        """-> dict(contig_id uint32, count uint64, ascending bool) of the contigs that hold a record, by ascending id."""
+        n = C.c_uint64(0)
+        self.ctx.lib.csvgpu_snp_columns_describe(self.h, 0, None, None, None, C.byref(n))
+        k = int(n.value)
+        cid, cnt, asc = np.zeros(max(k, 1), np.uint32)[:k], np.zeros(max(k, 1), np.uint64)[:k], np.zeros(max(k, 1), np.uint8)[:k]
+        self.ctx._check(self.ctx.lib.csvgpu_snp_columns_describe(self.h, k, ptr(cid), ptr(cnt), ptr(asc), C.byref(n)))
+        return dict(contig_id=cid, count=cnt, ascending=asc.astype(bool))
+
+    def fetch(self, contig_id: int, want_pos: bool = True, want_baf: bool = True):
+        """csvgpu_snp_columns_fetch -> (pos uint32 or None, baf float64 or None) of one contig."""
+        d = self.describe()
+        at = np.nonzero(d["contig_id"] == contig_id)[0]
+        k = int(d["count"][at[0]]) if len(at) else 0
+        pos = np.zeros(max(k, 1), np.uint32)[:k] if want_pos else None
+        baf = np.zeros(max(k, 1), np.float64)[:k] if want_baf else None
+        self.ctx._check(self.ctx.lib.csvgpu_snp_columns_fetch(self.ctx.h, self.h, int(contig_id), ptr(pos), ptr(baf)))
+        return pos, baf
+
+    def _af_call(self, dev, contig_id, text_ptr, length, contig, needle, o):
+        c = _lib.csv_vcf_counts()
+        contig, needle = (x.encode() if isinstance(x, str) else bytes(x) for x in (contig, needle))
+        fn = self.ctx.lib.csvgpu_snp_columns_af_parse_dev if dev else self.ctx.lib.csvgpu_snp_columns_af_parse
+        rc = fn(self.ctx.h, self.h, int(contig_id), text_ptr, int(length), contig, len(contig), needle, len(needle), C.byref(o), C.byref(c))
+        if rc < 0 and rc != _lib.CSV_ECAPACITY:
+            self.ctx._check(rc)
+        return rc, Context._vcf_counts(c)
+
+    def af_parse_into(self, contig_id: int, text, contig, needle, out: dict):
+        """csvgpu_snp_columns_af_parse: Context.vcf_af_parse_into with sorted_pos = the contig's resident positions. -> (rc, counts)."""
+        text = _as_u8(text)
+
+        def address(a, k):
+            if a.dtype != Context._VCF_DTYPES[k] or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise ValueError(f"af_parse: '{k}' must be a writeable contiguous {np.dtype(Context._VCF_DTYPES[k]).name} array")
+            return a.ctypes.data
+        o = Context._vcf_out(out, address, len, True, "af_parse")
+        return self._af_call(False, contig_id, ptr(text), len(text), contig, needle, o)
+
+    def af_parse(self, contig_id: int, text, contig, needle) -> dict:
+        """The same into arrays of exactly the kept and deferred counts, as Context.vcf_af_parse."""
+        return self.ctx._vcf_sized(lambda a: self.af_parse_into(contig_id, text, contig, needle, a), True)
+
+    def af_parse_dev(self, contig_id: int, d_text, contig, needle, out: dict):
+        """csvgpu_snp_columns_af_parse_dev: the text and the outputs as torch tensors on the context's device. -> (rc, counts)."""
+        def address(t, k):
+            if not _is_dev(t, np.dtype(Context._VCF_DTYPES[k]).itemsize):
+                raise ValueError(f"af_parse_dev: '{k}' must be a contiguous device tensor of {np.dtype(Context._VCF_DTYPES[k]).itemsize}-byte elements")
+            return t.data_ptr()
+        if not _is_dev(d_text, 1):
+            raise ValueError("af_parse_dev: contiguous uint8 device tensor expected")
+        o = Context._vcf_out(out, address, lambda t: int(t.numel()), True, "af_parse_dev")
+        return self._af_call(True, contig_id, d_text.data_ptr(), int(d_text.numel()), contig, needle, o)
+
+    def table(self, contig_id: int, af_pos, af) -> "SnpTable":
+        """csvgpu_snp_columns_table: the first-hit table of one ascending contig, its records copied on the device; af_pos / af numpy."""
+        af_pos, af = np.ascontiguousarray(af_pos, np.uint32), np.ascontiguousarray(af, np.float64)
+        if len(af_pos) != len(af):
+            raise ValueError("table: af_pos and af differ in length")
+        h = self.ctx.lib.csvgpu_snp_columns_table(self.ctx.h, self.h, int(contig_id), ptr(af_pos), ptr(af), len(af))
+        if not h:
+            raise self.ctx._error(_lib.CSV_EINVAL)
+        return SnpTable(self.ctx, h)
 
 
 class GenomeBuilder:

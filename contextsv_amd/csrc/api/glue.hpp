@@ -150,6 +150,15 @@ int devbuf_ensure(csv_ctx *ctx, DevBuf &b, uint64_t used, uint64_t need, const c
 // arena has grown: it runs a second time then). w: the count's slices, as the carve set them. n_slots: the lines, a last open one included.
 int count_lines(csv_ctx *ctx, Transfer &t, const char *what, const char *too_many, const uint8_t *d_text, uint32_t len, const VcfWs &w,
                 const std::function<bool(Arena &, uint64_t)> &carve, const std::function<int()> &first_pass, uint32_t &n_slots);
+// The SNP form of the parse with its outputs staged in the context's workspace (w.out: a record per kept line, in file order; every
+// deferred line's offset), whatever their counts: for csvgpu_snp_builder_append, which reads them on the device. CSV_OK (the last kernel
+// queued, not waited for; cnt filled) / 1 (declined) / CSV_E*.
+int vcf_snp_stage(csv_ctx *ctx, Transfer &t, const uint8_t *d_text, uint32_t len, int dp_int, int ad_int, csv_vcf_counts &cnt, VcfWs &w);
+// csvgpu_vcf_af_parse (dev_text: _dev) with sorted_pos on the device in both forms: a contig's resident column (csvgpu_snp_columns_af_parse).
+// PRECONDITION: d_sorted_pos ascending. Nothing here checks it (the host form's loop over sorted_pos is skipped): the caller must hold the
+// `ascending` flag that csvgpu_snp_builder_finish computed on the device, as af_parse of snp_build.hip does.
+int vcf_af_parse_sorted_dev(csv_ctx *ctx, bool dev_text, const uint8_t *text, uint64_t len, const char *contig, uint32_t contig_len, const char *needle,
+                            uint32_t needle_len, const uint32_t *d_sorted_pos, uint64_t n, const csv_vcf_out *out, csv_vcf_counts *counts);
 // reads.hip
 int check_reads(csv_ctx *ctx, const csv_reads *r);           // host arrays
 int check_reads_dev(csv_ctx *ctx, const csv_reads *r);       // arrays in HBM: one small kernel
@@ -169,6 +178,9 @@ static inline ReadsView shard_view(const csv_shard *sh)
 void shard_release(csv_shard *sh);                            // frees what the shard owns, and the shard
 csv_shard *shard_common(csv_ctx *ctx, csv_shard *sh);         // the side arrays and the scan's split of a shard whose reads are in place; releases it on failure
 // snp_table.hip
+// the first-hit kind from a contig's columns on the device and the population arrays of the host (csvgpu_snp_columns_table)
+csv_snp_table *snp_table_hits_mixed(csv_ctx *ctx, const char *what, const uint32_t *d_pos, const double *d_baf, const uint32_t *af_pos, const double *af, uint64_t n,
+                                    uint64_t n_af);
 SnpTabDev snp_table_dev(const csv_snp_table *t);              // the table as the kernels see it (NULL or no records: all zero)
 // cluster.hip
 int check_dbscan_args(csv_ctx *ctx, double eps, int32_t min_pts, bool interval);

@@ -10,8 +10,9 @@ namespace {
 
 struct BuildWs { uint64_t *baf = nullptr, *pfb = nullptr; uint8_t *has = nullptr; int32_t *marks = nullptr, *pm = nullptr; void *pm_tmp = nullptr; unsigned int *flag = nullptr; };
 
-// dev: the inputs are device arrays (copied device to device); else host arrays (through the page-locked block, in pieces)
-csv_snp_table *table_create(csv_ctx *ctx, const char *what, bool dev, bool hits, const uint32_t *pos, const double *baf, const double *pfb, const uint8_t *has_pfb,
+// dev: the records are device arrays (copied device to device); else host arrays (through the page-locked block, in pieces). dev_af: the
+// same for the population arrays of the first-hit kind.
+csv_snp_table *table_create(csv_ctx *ctx, const char *what, bool dev, bool dev_af, bool hits, const uint32_t *pos, const double *baf, const double *pfb, const uint8_t *has_pfb,
                             const uint32_t *af_pos, const double *af, uint64_t n, uint64_t n_af)
 {
     if (!ctx) return nullptr;
@@ -38,16 +39,16 @@ csv_snp_table *table_create(csv_ctx *ctx, const char *what, bool dev, bool hits,
     hipStream_t s = ctx->stream;
     Transfer tr(ctx);
     if (tr.open(what)) { (void)hipFree(blk); return nullptr; }
-    auto put = [&](void *dst, const void *src, size_t b) -> bool {
+    auto put = [&](void *dst, const void *src, size_t b, bool on_dev) -> bool {
         if (!b) return true;
-        if (!dev) return tr.up(dst, src, b) == CSV_OK;
+        if (!on_dev) return tr.up(dst, src, b) == CSV_OK;
         if (hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToDevice, s) == hipSuccess) return true;
         ctx->err = std::string(what) + ": device copy failed"; (void)hipGetLastError();
         return false;
     };
     if (hipMemsetAsync(w.flag, 0, 256, s) != hipSuccess) return release("memset failed");
-    if (!put(d_pos, pos, n * 4) || !put(w.baf, baf, n * 8) || !put(d_afp, af_pos, n_af * 4) || !put(d_af, af, n_af * 8) ||
-        (flagged && (!put(w.has, has_pfb, n) || (pfb && !put(w.pfb, pfb, n * 8))))) {
+    if (!put(d_pos, pos, n * 4, dev) || !put(w.baf, baf, n * 8, dev) || !put(d_afp, af_pos, n_af * 4, dev_af) || !put(d_af, af, n_af * 8, dev_af) ||
+        (flagged && (!put(w.has, has_pfb, n, dev) || (pfb && !put(w.pfb, pfb, n * 8, dev))))) {
         const std::string why = ctx->err;                                       // (the copy's own text)
         release("");
         ctx->err = why;
@@ -73,20 +74,20 @@ csv_snp_table *table_create(csv_ctx *ctx, const char *what, bool dev, bool hits,
 
 csv_snp_table *csvgpu_snp_table_create(csv_ctx *ctx, const uint32_t *pos, const double *baf, const double *pfb, const uint8_t *has_pfb, uint64_t n)
 {
-    return table_create(ctx, "snp_table_create", false, false, pos, baf, pfb, has_pfb, nullptr, nullptr, n, 0);
+    return table_create(ctx, "snp_table_create", false, false, false, pos, baf, pfb, has_pfb, nullptr, nullptr, n, 0);
 }
 csv_snp_table *csvgpu_snp_table_create_hits(csv_ctx *ctx, const uint32_t *pos, const double *baf, const uint32_t *af_pos, const double *af, uint64_t n, uint64_t n_af)
 {
-    return table_create(ctx, "snp_table_create_hits", false, true, pos, baf, nullptr, nullptr, af_pos, af, n, n_af);
+    return table_create(ctx, "snp_table_create_hits", false, false, true, pos, baf, nullptr, nullptr, af_pos, af, n, n_af);
 }
 csv_snp_table *csvgpu_snp_table_create_dev(csv_ctx *ctx, const uint32_t *d_pos, const double *d_baf, const double *d_pfb, const uint8_t *d_has_pfb, uint64_t n)
 {
-    return table_create(ctx, "snp_table_create_dev", true, false, d_pos, d_baf, d_pfb, d_has_pfb, nullptr, nullptr, n, 0);
+    return table_create(ctx, "snp_table_create_dev", true, true, false, d_pos, d_baf, d_pfb, d_has_pfb, nullptr, nullptr, n, 0);
 }
 csv_snp_table *csvgpu_snp_table_create_hits_dev(csv_ctx *ctx, const uint32_t *d_pos, const double *d_baf, const uint32_t *d_af_pos, const double *d_af, uint64_t n,
                                                 uint64_t n_af)
 {
-    return table_create(ctx, "snp_table_create_hits_dev", true, true, d_pos, d_baf, nullptr, nullptr, d_af_pos, d_af, n, n_af);
+    return table_create(ctx, "snp_table_create_hits_dev", true, true, true, d_pos, d_baf, nullptr, nullptr, d_af_pos, d_af, n, n_af);
 }
 
 void csvgpu_snp_table_free(csv_ctx *ctx, csv_snp_table *table)
@@ -101,6 +102,11 @@ void csvgpu_snp_table_free(csv_ctx *ctx, csv_snp_table *table)
 uint64_t csvgpu_snp_table_size(const csv_snp_table *table) { return table ? table->n : 0; }
 
 namespace csv {
+csv_snp_table *snp_table_hits_mixed(csv_ctx *ctx, const char *what, const uint32_t *d_pos, const double *d_baf, const uint32_t *af_pos, const double *af, uint64_t n,
+                                    uint64_t n_af)
+{
+    return table_create(ctx, what, true, false, true, d_pos, d_baf, nullptr, nullptr, af_pos, af, n, n_af);
+}
 SnpTabDev snp_table_dev(const csv_snp_table *t)
 {
     SnpTabDev d{};

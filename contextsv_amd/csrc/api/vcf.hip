@@ -16,6 +16,7 @@ struct Call {                                             // one call's argument
     int dp_int = 0, ad_int = 0;
     const char *contig = nullptr, *needle = nullptr; uint32_t contig_len = 0, needle_len = 0;
     const uint32_t *sorted_pos = nullptr; uint64_t n = 0;   // io: host array, else device
+    bool sorted_dev = false;                              // io with sorted_pos on the device all the same (a contig's resident column)
 };
 
 int check_args(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, const csv_vcf_out *out, csv_vcf_counts *counts)
@@ -30,7 +31,7 @@ int check_args(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, c
         for (uint32_t i = 0; i < c.needle_len; i++)
             if (c.needle[i] == '\t' || c.needle[i] == '\n' || c.needle[i] == '\r') return bad(ctx, "a needle with a tab or a line end in it");
         if (c.n >= (1ull << 32)) return bad(ctx, "2^32 positions or more");
-        if (c.io) for (uint64_t i = 1; i < c.n; i++) if (c.sorted_pos[i] < c.sorted_pos[i - 1]) return bad(ctx, "sorted_pos not ascending");
+        if (c.io && !c.sorted_dev) for (uint64_t i = 1; i < c.n; i++) if (c.sorted_pos[i] < c.sorted_pos[i - 1]) return bad(ctx, "sorted_pos not ascending");
     }
     return CSV_OK;
 }
@@ -135,13 +136,13 @@ int parse_host(csv_ctx *ctx, const uint8_t *text, uint64_t len, const Call &c, c
     if (len == 0) return CSV_OK;
     (void)hipSetDevice(ctx->device);
     VcfTextWs tw;
-    if ((rc = arena_reserve_for(ctx, ctx->arena, "vcf_parse", [&](Arena &a) { return carve_vcf_text(a, len, c.n, tw); }))) return rc;
+    if ((rc = arena_reserve_for(ctx, ctx->arena, "vcf_parse", [&](Arena &a) { return carve_vcf_text(a, len, c.sorted_dev ? 0 : c.n, tw); }))) return rc;
     Transfer t(ctx);
     if ((rc = t.open("vcf_parse"))) return rc;
     if ((rc = t.up(tw.text, text, len))) return rc;
-    if (c.n && (rc = t.up(tw.sorted_pos, c.sorted_pos, c.n * 4))) return rc;
+    if (c.n && !c.sorted_dev && (rc = t.up(tw.sorted_pos, c.sorted_pos, c.n * 4))) return rc;
     VcfWs w;
-    if ((rc = run_parse(ctx, t, tw.text, (uint32_t)len, c, tw.sorted_pos, nullptr, *out, *counts, w))) return rc;
+    if ((rc = run_parse(ctx, t, tw.text, (uint32_t)len, c, c.sorted_dev ? c.sorted_pos : tw.sorted_pos, nullptr, *out, *counts, w))) return rc;
     const uint64_t k = counts->n_kept, d = counts->n_deferred;
     if ((rc = t.down(out->line_off, w.out.line_off, k * 4)) || (rc = t.down(out->pos, w.out.pos, k * 4)) || (rc = t.down(out->value, w.out.value, k * 8)) ||
         (rc = t.down(out->defer_off, w.out.defer_off, d * 4))) return rc;
@@ -180,3 +181,22 @@ int csvgpu_vcf_af_parse_dev(csv_ctx *ctx, const uint8_t *d_text, uint64_t len, c
 {
     return parse_dev(ctx, d_text, len, af_call(contig, contig_len, needle, needle_len, d_sorted_pos, n, false), d_out, counts);
 }
+
+namespace csv {
+
+int vcf_snp_stage(csv_ctx *ctx, Transfer &t, const uint8_t *d_text, uint32_t len, int dp_int, int ad_int, csv_vcf_counts &cnt, VcfWs &w)
+{
+    csv_vcf_out caps{};
+    caps.cap = caps.cap_defer = UINT64_MAX;                 // (the staged arrays hold a record per line at the most)
+    return run_parse(ctx, t, d_text, len, snp_call(dp_int, ad_int, true), nullptr, nullptr, caps, cnt, w);
+}
+
+int vcf_af_parse_sorted_dev(csv_ctx *ctx, bool dev_text, const uint8_t *text, uint64_t len, const char *contig, uint32_t contig_len, const char *needle,
+                            uint32_t needle_len, const uint32_t *d_sorted_pos, uint64_t n, const csv_vcf_out *out, csv_vcf_counts *counts)
+{
+    Call c = af_call(contig, contig_len, needle, needle_len, d_sorted_pos, n, !dev_text);
+    c.sorted_dev = true;
+    return dev_text ? parse_dev(ctx, text, len, c, out, counts) : parse_host(ctx, text, len, c, out, counts);
+}
+
+}  // namespace csv

@@ -593,6 +593,25 @@ void launch_fasta_lines(hipStream_t s, const uint8_t *text, uint32_t len, uint32
 void launch_fasta_compact(hipStream_t s, const uint8_t *text, uint32_t len, const FastaWs &w, uint8_t *dst);
 // item i: out[out_off[i] .. out_off[i + 1]) = seq[src[i] ..), ambiguity codes as N if mask; out_off[0] = 0, out_off[n] = total; out 16-byte aligned
 void launch_fasta_cut(hipStream_t s, const uint8_t *seq, const uint64_t *src, const uint64_t *out_off, uint64_t n, uint64_t total, bool mask, uint8_t *out);
+// snpbuild.hip — the kept records of VCF batches cut by contig on the device (csvgpu_snp_builder_*; the rules in snp_build_core.hpp)
+constexpr uint32_t SB_MAX_BLOCKS = 256;      // of 256 threads; larger calls stride
+struct SnpAppendArgs {                       // passed to the kernel by value
+    uint32_t n;                              // the call's kept records
+    const uint32_t *ridx;                    // [n + 1] the exclusive sums of the run flags
+    const uint32_t *line_off, *chrom_len, *rec_pos; const uint64_t *rec_baf;      // [n] what launch_vcf_emit left
+    uint64_t tail, text_base; uint32_t run_base;                                  // the builder's records and runs before the call
+    uint32_t *pos; uint64_t *baf; uint32_t *run; uint64_t *key;                   // the builder's arrays
+    uint32_t *run_first, *run_line_off, *run_chrom_len;                           // [ridx[n]] the call's run table
+};
+// flags[0 .. n]: 1 where kept record k starts a CHROM run, then their exclusive sums in place: flags[n] = the call's runs
+void launch_snp_run_flags(hipStream_t s, const uint8_t *text, const uint32_t *line_off, const uint32_t *chrom_len, uint32_t n, uint32_t *flags, void *es_tmp);
+void launch_snp_append(hipStream_t s, const SnpAppendArgs &a);
+// keys[i] = contig id << shift | order key, vals[i] = i (run_contig[]: the contig of every run; host-appended records carry their own)
+void launch_snp_keys(hipStream_t s, const uint32_t *run, const uint64_t *key, const uint32_t *run_contig, uint32_t n, int shift, uint64_t *keys, uint32_t *vals);
+// behind the sort: pos / baf in the order; per contig id first / end slot and desc (a pos below its predecessor's); *dup: two equal keys.
+// first / end / desc / dup zeroed by the caller.
+void launch_snp_columns(hipStream_t s, const uint64_t *keys, const uint32_t *vals, const uint32_t *pos_in, const uint64_t *baf_in, uint32_t n, int shift,
+                        uint32_t *pos_out, uint64_t *baf_out, uint32_t *first, uint32_t *end, uint32_t *desc, uint32_t *dup);
 // shardbuild.hip — a resident shard built on the device (csvgpu_shard_builder_*), and the ALT strings cut from its sequences
 // *unsorted |= pos[i] < pos[i - 1] for the records [first, first + n) (the first one against its predecessor, if there is one)
 void launch_sb_unsorted(hipStream_t s, const int32_t *pos, uint64_t first, uint64_t n, uint32_t *unsorted);

@@ -1,5 +1,6 @@
 // run.cpp — whole runs: SVCaller::run over host arrays, runResident over a staged genome, runBam from a file. What the caller may set of a
 // run arrives as one csvhost_run_options (csvhost_abi.h), decoded by run_params_from and passed on as it is.
+#include <atomic>
 #include <mutex>
 
 #include "abi.hpp"
@@ -241,6 +242,14 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
     })
 }
 
+// The switches of the SVCaller behind csvhost_run_bam (process-wide, off by default, like csvhost_set_merge_on_device):
+// SVCaller::snp_parse_on_device, snp_tables_on_device. csvhost_run_options is untouched.
+static std::atomic<int> g_snp_parse_on_device{0}, g_snp_tables_on_device{0};
+void csvhost_set_snp_on_device(int parse, int tables) { g_snp_parse_on_device = parse != 0; g_snp_tables_on_device = tables != 0; }
+// out[2]: copy-number decode calls that took the table route (every job's SNPs resident: "cn: decode on resident tables") / that ran the
+// host's SNP queries, since the process began or the last reset
+void csvhost_cn_route_stats(uint64_t *out, int reset) { cnRouteStats(out, reset != 0); }
+
 // SVCaller::runBam: chrs = '\n'-separated contig names or null (all). snp_vcf / pfb_table / ethnicity: RunParams' fields of those names (null: none —
 // every window then gets the dummy observation). Calls come back grouped by contig in header order, with their contig index in out_tid.
 int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int threads, const csv_hmm *hmm, const csvhost_run_options *opt,
@@ -253,6 +262,7 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         P.snp_vcf = snp_vcf ? snp_vcf : ""; P.pfb_table = pfb_table ? pfb_table : ""; P.ethnicity = ethnicity ? ethnicity : "";
         set_vcf_output(P, fasta, vcf_dir, gap_path, file_date);
         SVCaller caller(ctx);
+        caller.snp_parse_on_device = g_snp_parse_on_device.load() != 0; caller.snp_tables_on_device = g_snp_tables_on_device.load() != 0;
         std::unordered_map<std::string, std::vector<SVCall>> calls;
         BamRunStats bs;
         caller.runBam(bam_path, split_lines(chrs), threads, chmm_from_pod(hmm), P, calls, &bs);

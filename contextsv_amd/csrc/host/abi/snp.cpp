@@ -28,7 +28,24 @@ csvhost_snp *csvhost_snp_open_device(const char *snp_vcf, int threads, csv_ctx *
     if (!h->f.load(snp_vcf ? snp_vcf : "", threads, &e, h->device())) { set_error(e); delete h; return nullptr; }
     return h;
 }
+// The same with the tables built on the device (SNPDeviceOptions::tables_on_device: csvgpu_snp_builder_* per chunk, the contigs' columns
+// fetched once, csvhost_snp_table / csvhost_snp_query making each ascending contig's resident table from the columns). ctx must outlive h.
+csvhost_snp *csvhost_snp_open_device_tables(const char *snp_vcf, int threads, csv_ctx *ctx, uint32_t window_blocks)
+{
+    if (!ctx) { set_error("csvhost_snp_open_device_tables: no context"); return nullptr; }
+    csvhost_snp *h = new csvhost_snp();
+    h->dev.ctx = ctx; h->dev.window_blocks = window_blocks; h->dev.tables_on_device = true;
+    std::string e;
+    if (!h->f.load(snp_vcf ? snp_vcf : "", threads, &e, h->device())) { set_error(e); delete h; return nullptr; }
+    return h;
+}
 void csvhost_snp_free(csvhost_snp *h) { delete h; }
+// out[3]: CHROM runs the builder reported, records appended through the host, contigs whose resident table was made from the columns
+void csvhost_snp_build_stats(const csvhost_snp *h, uint64_t *out)
+{
+    const SNPDeviceStats &s = h->f.device_stats();
+    out[0] = s.runs; out[1] = s.appended_host; out[2] = s.tables_resident;
+}
 // out[4]: lines the device examined, records it kept, lines it deferred to the host parser, batches it declined
 void csvhost_snp_device_stats(const csvhost_snp *h, uint64_t *out)
 {

@@ -328,6 +328,14 @@ void CNVCaller::filterRegions(RegionBatch &B, bool log) const
     }
 }
 
+// which route observeAndDecode took, process-wide (csvhost_cn_route_stats)
+static std::atomic<uint64_t> g_cn_table_route{0}, g_cn_query_route{0};
+void cnRouteStats(uint64_t *out, bool reset)
+{
+    out[0] = g_cn_table_route.load(); out[1] = g_cn_query_route.load();
+    if (reset) { g_cn_table_route = 0; g_cn_query_route = 0; }
+}
+
 bool CNVCaller::allResident(const std::vector<ContigJob> &jobs, const std::vector<RegionBatch> &batches)
 {
     bool any = false;
@@ -514,6 +522,7 @@ void CNVCaller::observeAndDecode(std::vector<RegionBatch> &batches, const std::v
             for (size_t j = 0; j < jobs.size(); j++) if (!batches[j].regions.empty()) filterRegions(batches[j], true);
             G.chunks.assign((nq + kChunk - 1) / kChunk, ObsChunk());
             G.on_device = true;
+            g_cn_table_route++;
             G.seq_off = std::move(T.out.obs_off); G.dev_pos = std::move(T.out.pos); G.ll = std::move(T.out.ll);
             G.states.assign(T.out.states.begin(), T.out.states.begin() + (std::ptrdiff_t)G.seq_off[nq]);
             for (size_t q = 0; q < nq; q++)
@@ -522,6 +531,7 @@ void CNVCaller::observeAndDecode(std::vector<RegionBatch> &batches, const std::v
         }
         for (RegionBatch &B : batches) { B.r_start.clear(); B.r_end.clear(); B.slot.clear(); }      // declined: the whole batch takes the route below
     }
+    g_cn_query_route++;
     {
         csvhost::TraceScope tr("cn: snp queries");
         // the chunks of ALL contigs as one parallel section (24 sections of a few chunks each left most of the pool idle)

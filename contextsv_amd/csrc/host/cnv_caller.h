@@ -62,6 +62,9 @@ struct SNPTable : SNPSource {
     csv_ctx *resident_ctx = nullptr;
 };
 
+// out[0]: observeAndDecode calls that decoded on resident tables, out[1]: those that ran the host's SNP queries (process-wide counters)
+void cnRouteStats(uint64_t *out, bool reset);
+
 class CNVCaller {
 public:
     explicit CNVCaller(csv_ctx *ctx) : ctx(ctx) {}

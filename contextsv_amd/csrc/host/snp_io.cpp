@@ -451,6 +451,11 @@ bool SNPFile::load(const std::string &snp_vcf, int threads, std::string *err, co
         return true;
     };
     if (dev == nullptr || dev->ctx == nullptr) return tf.forEachChunk(threads, [&](sv chunk) { return for_lines(chunk, on_line); }, err);
+    if (dev->tables_on_device) {
+        std::string why;
+        if (loadTables(snp_vcf, threads, &why, *dev)) return true;
+        printError("WARNING: SNP tables are not built on the device (" + why + "): the records of " + snp_vcf + " are merged on the host");
+    }
 
     DeviceLines d;
     bool failed = false;
@@ -496,6 +501,134 @@ bool SNPFile::load(const std::string &snp_vcf, int threads, std::string *err, co
     return ok && !failed;
 }
 
+// ---- the tables built on the device (SNPDeviceOptions::tables_on_device) ----------------------------------------------------------
+// Replaces, per chunk, the parse call and the per-record loop above by one csvgpu_snp_builder_append: the kept records stay on the device,
+// a run table comes back, and every run's name is looked up once. Deferred lines, declined batches and batches of 2^32 bytes or more go
+// through snp_record_of_line and csvgpu_snp_builder_append_host with their offsets in the text as keys.
+bool SNPFile::loadTables(const std::string &snp_vcf, int threads, std::string *err, const SNPDeviceOptions &dev)
+{
+    csv_ctx *ctx = dev.ctx;
+    TextFile tf;
+    if (!tf.open(snp_vcf, err)) return false;
+    csv_snp_builder *b = csvgpu_snp_builder_create(ctx, 0);
+    if (!b) { *err = csvgpu_last_error(ctx); return false; }
+    bool dp_int = false, ad_int = false;
+    auto on_header = [&](sv line) {
+        std::string id, type;
+        if (header_decl(line, "FORMAT", id, type)) {
+            if (id == "DP") dp_int = type == "Integer";
+            if (id == "AD") ad_int = type == "Integer";
+        }
+    };
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<std::string> names;
+    auto id_of = [&](sv name) {
+        auto it = ids.find(std::string(name));
+        if (it != ids.end()) return it->second;
+        names.emplace_back(name);
+        return ids.emplace(names.back(), (uint32_t)names.size() - 1).first->second;
+    };
+    std::vector<uint32_t> run_contig, run_first, run_line_off, run_chrom_len, defer_off(4096), h_id, h_pos;
+    std::vector<uint64_t> h_key;
+    std::vector<double> h_baf;
+    SNPDeviceStats st;
+    uint64_t base = 0;                                    // the chunk's offset in the text: the order keys' base
+    bool failed = false;
+    auto fail = [&](const std::string &what) { *err = what; failed = true; return false; };
+    auto host_line = [&](sv line, uint64_t key) {
+        SnpLineRecord rec;
+        if (!snp_record_of_line(line, dp_int, ad_int, rec)) return;
+        h_id.push_back(id_of(rec.chrom)); h_key.push_back(key); h_pos.push_back(rec.pos); h_baf.push_back(rec.baf);
+    };
+    auto flush_host = [&]() {
+        if (h_id.empty()) return true;
+        const int rc = csvgpu_snp_builder_append_host(ctx, b, h_id.size(), h_id.data(), h_key.data(), h_pos.data(), h_baf.data());
+        st.appended_host += h_id.size();
+        h_id.clear(); h_key.clear(); h_pos.clear(); h_baf.clear();
+        return rc == CSV_OK;
+    };
+    const bool ok = tf.forEachChunk(threads, [&](sv chunk) {
+        const uint64_t chunk_base = base;
+        base += chunk.size();
+        const size_t a = leading_header(chunk, on_header);
+        const sv rest = chunk.substr(a);
+        if (rest.empty()) return true;
+        const uint64_t rest_base = chunk_base + a;
+        // the whole batch through the host parser (a header line behind data may change dp_int / ad_int)
+        auto host_batch = [&]() {
+            for_lines(rest, [&](sv line) {
+                if (line[0] == '#') on_header(line);
+                else host_line(line, rest_base + (uint64_t)(line.data() - rest.data()));
+                return true;
+            });
+            return flush_host() ? true : fail(csvgpu_last_error(ctx));
+        };
+        if (rest.size() >= (1ull << 32)) return host_batch();
+        csv_snp_append_counts c{};
+        int rc = CSV_OK;
+        for (int pass = 0; pass < 2; pass++) {
+            csv_snp_runs o{};
+            o.run_first = run_first.data(); o.run_line_off = run_line_off.data(); o.run_chrom_len = run_chrom_len.data(); o.defer_off = defer_off.data();
+            o.cap_runs = run_first.size(); o.cap_defer = defer_off.size();
+            rc = csvgpu_snp_builder_append(ctx, b, (const uint8_t *)rest.data(), rest.size(), rest_base, dp_int, ad_int, &o, &c);
+            if (rc != CSV_ECAPACITY) break;
+            if (c.n_runs > run_first.size()) { const size_t n = c.n_runs + c.n_runs / 4 + 16; run_first.resize(n); run_line_off.resize(n); run_chrom_len.resize(n); }
+            if (c.n_deferred > defer_off.size()) defer_off.resize(c.n_deferred + c.n_deferred / 4);
+        }
+        if (rc < 0) return fail(csvgpu_last_error(ctx));
+        if (rc == 1) { st.declined_batches++; return host_batch(); }
+        st.lines += c.n_lines; st.kept += c.n_kept; st.deferred += c.n_deferred; st.runs += c.n_runs;
+        if (run_contig.size() != c.first_run) return fail("the builder's run count is not the caller's");
+        for (uint64_t r = 0; r < c.n_runs; r++) run_contig.push_back(id_of(rest.substr(run_line_off[r], run_chrom_len[r])));      // one string per run
+        for (uint64_t q = 0; q < c.n_deferred; q++) host_line(line_at(rest, defer_off[q]), rest_base + defer_off[q]);
+        return flush_host() ? true : fail(csvgpu_last_error(ctx));
+    }, err, dev.window_blocks ? dev.window_blocks : 1024);
+    if (!ok || failed) { csvgpu_snp_builder_destroy(ctx, b); return false; }
+    csv_snp_columns *cols = csvgpu_snp_builder_finish(ctx, b, run_contig.data(), run_contig.size());       // (consumes b)
+    if (!cols) { *err = csvgpu_last_error(ctx); return false; }
+    // every contig's columns ONCE to the host vectors: query, queryFlat, declined copy-number batches and csvhost_snp_table work unchanged
+    uint64_t n_contigs = 0;
+    csvgpu_snp_columns_describe(cols, 0, nullptr, nullptr, nullptr, &n_contigs);
+    std::vector<uint32_t> cid(n_contigs);
+    std::vector<uint64_t> count(n_contigs);
+    std::vector<uint8_t> asc(n_contigs);
+    bool good = csvgpu_snp_columns_describe(cols, n_contigs, cid.data(), count.data(), asc.data(), &n_contigs) == CSV_OK;
+    std::unordered_map<std::string, SNPFileTable> built;
+    std::unordered_map<std::string, std::pair<uint32_t, bool>> where;
+    uint64_t total = 0;
+    for (uint64_t k = 0; good && k < n_contigs; k++) {
+        good = cid[k] < names.size();
+        if (!good) break;
+        SNPFileTable &t = built[names[cid[k]]];
+        t.pos.resize(count[k]); t.baf.resize(count[k]);
+        good = csvgpu_snp_columns_fetch(ctx, cols, cid[k], t.pos.data(), t.baf.data()) == CSV_OK;
+        where[names[cid[k]]] = {cid[k], asc[k] != 0};
+        total += count[k];
+    }
+    if (!good) { *err = std::string("the columns' fetch: ") + csvgpu_last_error(ctx); csvgpu_snp_columns_free(ctx, cols); return false; }
+    tables = std::move(built);
+    column_of = std::move(where);
+    columns = cols; columns_ctx = ctx;
+    n_kept = total;
+    dev_stats.lines += st.lines; dev_stats.kept += st.kept; dev_stats.deferred += st.deferred; dev_stats.declined_batches += st.declined_batches;
+    dev_stats.runs += st.runs; dev_stats.appended_host += st.appended_host;
+    return true;
+}
+
+void SNPFile::dropColumns()
+{
+    if (columns) csvgpu_snp_columns_free(columns_ctx, columns);
+    columns = nullptr; columns_ctx = nullptr;
+    column_of.clear();
+}
+
+SNPFile::~SNPFile()
+{
+    for (auto &kv : tables)
+        if (kv.second.resident) { csvgpu_snp_table_free(kv.second.resident_ctx, kv.second.resident); kv.second.resident = nullptr; }      // (dropResident)
+    dropColumns();
+}
+
 const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev)
 {
     auto it = tables.find(chr);
@@ -503,12 +636,31 @@ const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pf
     SNPFileTable &t = it->second;
     if (af_done[chr]) return t;
     af_done[chr] = true;
-    if (pfb_vcf.empty() || !file_exists(pfb_vcf) || t.pos.empty()) return t;        // use_pfb = false (:596-611)
+    // the contig's columns are resident and ascending: the population file is read against them, and the table is made from them
+    int64_t column_id = -1;
+    if (dev && dev->ctx && dev->tables_on_device && columns && dev->ctx == columns_ctx) {
+        auto c = column_of.find(chr);
+        if (c != column_of.end() && c->second.second) column_id = c->second.first;
+    }
+    attachAf(t, chr, pfb_vcf, ethnicity, threads, dev, column_id);
+    if (column_id >= 0 && !t.resident) {
+        // (a table the device refuses keeps the host arrays only: the host route serves the contig, with the same results)
+        t.resident = csvgpu_snp_columns_table(columns_ctx, columns, (uint32_t)column_id, t.af_pos.data(), t.af.data(), t.af_pos.size());
+        if (t.resident) { t.resident_ctx = columns_ctx; dev_stats.tables_resident++; }
+        else printError(std::string("WARNING: no resident SNP table for ") + chr + ": " + csvgpu_last_error(columns_ctx));
+    }
+    return t;
+}
+
+void SNPFile::attachAf(SNPFileTable &t, const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev,
+                       int64_t column_id)
+{
+    if (pfb_vcf.empty() || !file_exists(pfb_vcf) || t.pos.empty()) return;        // use_pfb = false (:596-611)
     TextFile tf;
     std::string err;
     if (!tf.open(pfb_vcf, &err) || (tf.compressed() && !file_exists(pfb_vcf + ".tbi") && !file_exists(pfb_vcf + ".csi"))) {
         printError("ERROR: Could not add population allele frequency file to reader: " + pfb_vcf);
-        return t;
+        return;
     }
     const std::string key = ethnicity.empty() ? std::string("AF") : "AF_" + ethnicity;       // :616-623
     const std::string contig = gnomadContigName(chr, pfb_vcf);
@@ -535,7 +687,7 @@ const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pf
     };
     if (dev == nullptr || dev->ctx == nullptr) {
         tf.forEachChunk(threads, [&](sv chunk) { return for_lines(chunk, on_line); }, &err);
-        return t;
+        return;
     }
     // table() has no way to report a failure (an unreadable population file is logged and leaves the table without hits): a device call that
     // fails (CSV_E*: out of memory, a HIP error) is logged ONCE and the host parser reads that chunk and the rest of the file — the table is
@@ -550,6 +702,10 @@ const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pf
         if (device_failed || rest.size() >= (1ull << 32)) return for_lines(rest, on_line);
         d.expect(std::min(rest.size() / 64, 2 * sorted.size()) + 16);
         const int rc = d.run(dev->ctx, true, [&](const csv_vcf_out *o, csv_vcf_counts *c) {
+            // (resident columns: the contig's positions are on the device already, and ascending, so they are the sorted ones — none goes up)
+            if (column_id >= 0)
+                return csvgpu_snp_columns_af_parse(dev->ctx, columns, (uint32_t)column_id, (const uint8_t *)rest.data(), rest.size(), contig.data(),
+                                                   (uint32_t)contig.size(), needle.data(), (uint32_t)needle.size(), o, c);
             return csvgpu_vcf_af_parse(dev->ctx, (const uint8_t *)rest.data(), rest.size(), contig.data(), (uint32_t)contig.size(), needle.data(),
                                        (uint32_t)needle.size(), sorted.data(), sorted.size(), o, c);
         }, &err);
@@ -570,5 +726,4 @@ const SNPFileTable &SNPFile::table(const std::string &chr, const std::string &pf
         }
         return d.counts.stop_off == UINT64_MAX;
     }, &err, dev->window_blocks);
-    return t;
 }

@@ -45,10 +45,19 @@ private:
 // Opt-in: the data lines of every chunk decided on the device (csvgpu_vcf_snp_parse / csvgpu_vcf_af_parse on `ctx`); the lines it defers and
 // the batches it declines run through the two functions below, so the tables are the same byte for byte.
 struct csv_ctx;
+struct csv_snp_columns;
 // A device call that fails outright (CSV_E*): load() fails with the message in `err`; table(), which has no error channel, logs it once and
 // lets the host parser read the rest of that population file.
-struct SNPDeviceOptions { csv_ctx *ctx = nullptr; size_t window_blocks = 0; };          // window_blocks 0: forEachChunk's default
-struct SNPDeviceStats { uint64_t lines = 0, kept = 0, deferred = 0, declined_batches = 0; };
+// tables_on_device (needs ctx): load() hands every chunk to a csv_snp_builder, which cuts the kept records by contig on the device, and fetches
+// each contig's columns once; table() reads the population file against the resident positions and makes the contig's resident table from
+// the columns. Any CSV_E* from the builder makes load() start over on the parse_on_device path, with nothing kept from the builder.
+struct SNPDeviceOptions { csv_ctx *ctx = nullptr; size_t window_blocks = 0; bool tables_on_device = false; };   // window_blocks 0: forEachChunk's default
+struct SNPDeviceStats {
+    uint64_t lines = 0, kept = 0, deferred = 0, declined_batches = 0;
+    uint64_t runs = 0;                 // CHROM runs the builder reported (one name string each)
+    uint64_t appended_host = 0;        // records that went through csvgpu_snp_builder_append_host (deferred lines, declined or oversized batches)
+    uint64_t tables_resident = 0;      // contigs whose resident table was made from the columns
+};
 
 // One data line's decision, as SNPFile::load and SNPFile::table take it (the device parser's deferred lines and the stand-alone check of
 // vcf_record_core.hpp call the same two functions).
@@ -68,7 +77,8 @@ struct SNPFileTable : SNPSource {
     std::vector<double> af;
     void query(uint32_t start_pos, uint32_t end_pos, std::vector<uint32_t> &snp_pos, std::unordered_map<uint32_t, double> &snp_baf,
                std::unordered_map<uint32_t, double> &snp_pfb) const override;
-    // Opt-in: the table on ctx's device (the first-hit kind), as SNPTable::makeResident. Nothing in runBam creates one yet.
+    // Opt-in: the table on ctx's device (the first-hit kind) from the host arrays, as SNPTable::makeResident. SNPFile::table sets `resident`
+    // itself, from the device columns, when the file was loaded with SNPDeviceOptions::tables_on_device (runBam: SVCaller::snp_tables_on_device).
     bool makeResident(csv_ctx *ctx);
     void dropResident();
     const csv_snp_table *residentTable() const override { return resident; }
@@ -88,7 +98,19 @@ public:
     const SNPFileTable &table(const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev = nullptr);
     uint64_t records_kept() const { return n_kept; }
     const SNPDeviceStats &device_stats() const { return dev_stats; }       // summed over load() and every table() that parsed on the device
+    SNPFile() = default;
+    SNPFile(const SNPFile &) = delete;
+    SNPFile &operator=(const SNPFile &) = delete;
+    ~SNPFile();                                                              // frees the resident tables table() made, and the columns
 private:
+    // load() through a csv_snp_builder; false (err set, nothing kept) when the builder refused anything
+    bool loadTables(const std::string &snp_vcf, int threads, std::string *err, const SNPDeviceOptions &dev);
+    void attachAf(SNPFileTable &t, const std::string &chr, const std::string &pfb_vcf, const std::string &ethnicity, int threads, const SNPDeviceOptions *dev,
+                  int64_t column_id);
+    void dropColumns();
+    csv_snp_columns *columns = nullptr;                                      // tables_on_device: the contigs' columns, and whose they are
+    csv_ctx *columns_ctx = nullptr;
+    std::unordered_map<std::string, std::pair<uint32_t, bool>> column_of;    // contig -> (id in `columns`, ascending)
     std::unordered_map<std::string, SNPFileTable> tables;
     std::unordered_map<std::string, bool> af_done;
     SNPFileTable none;

@@ -1297,6 +1297,7 @@ struct BamSource : ContigSource {
     size_t i = 0;
     BamRunStats st;
     SNPFile *snp_file = nullptr;                                  // loaded SNP VCF, or nullptr
+    SNPDeviceOptions snp_dev;                                     // how it was loaded (ctx null: the host parser); table() takes the same
     const AlleleFreqFiles *af_files = nullptr;
     std::string ethnicity;
 
@@ -1336,7 +1337,7 @@ struct BamSource : ContigSource {
         out.seq = opt.want_seq ? &seq : nullptr;
         out.depth_len = cur.target_len + 1;                       // cnv_caller.cpp:482
         out.qnames = opt.want_qnames ? &cur.qnames : nullptr;
-        if (snp_file) out.snps = &snp_file->table(cur.name, af_files ? af_files->get(cur.name) : std::string(), ethnicity, opt.threads);
+        if (snp_file) out.snps = &snp_file->table(cur.name, af_files ? af_files->get(cur.name) : std::string(), ethnicity, opt.threads, snp_dev.ctx ? &snp_dev : nullptr);
         st.n_contigs++; st.n_reads += cur.n_reads(); st.n_cigar += n_cigar;
         i++;
         return true;
@@ -1352,7 +1353,9 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
     // With RunParams::inflate_on_device the reader inflates one contig ahead on a thread of its own, beside this run on the device: its context is
     // its own (two threads must not share one), on the same device, for the length of the run — declared in front of the source, so that it
     // outlives a read that is still in flight when the source goes.
-    struct OwnCtx { csv_ctx *c = nullptr; ~OwnCtx() { if (c) csvgpu_destroy(c); } } inflate_ctx;
+    struct OwnCtx { csv_ctx *c = nullptr; ~OwnCtx() { if (c) csvgpu_destroy(c); } } inflate_ctx, snp_ctx;
+    // (snp_file in front of the source and behind its context: the source's tables point into it, and its resident tables are freed on snp_ctx)
+    SNPFile snp_file;
     BamSource src;
     if (!src.reader.open(bam_path)) throw std::runtime_error("ERROR failed to open BAM file " + bam_path + ": " + src.reader.error());
     if (!src.reader.loadIndex()) throw std::runtime_error("ERROR failed to load index for " + bam_path);
@@ -1372,12 +1375,18 @@ void SVCaller::runBam(const std::string &bam_path, const std::vector<std::string
         if (P.unpack_on_device || P.shard_on_device) src.opt.device_unpack = inflate_ctx.c;         // (one context for both: the reader's thread is its only user)
         src.opt.device_shard = P.shard_on_device;
     }
-    SNPFile snp_file;
     AlleleFreqFiles af_files;
     if (!P.snp_vcf.empty()) {
         std::string e;
         if (!af_files.load(P.pfb_table, &e)) throw std::runtime_error(e);          // the reference exits (input_data.cpp:221-225, :278-283)
-        if (snp_file.load(P.snp_vcf, src.opt.threads, &e)) {
+        if (snp_parse_on_device || snp_tables_on_device) {
+            // a context of the file's own on the run's device, for the length of the run: load() and every table() of the source use it from
+            // the thread that feeds the run, never beside a lane's
+            snp_ctx.c = csvgpu_create(P.inflate_device, nullptr);
+            if (!snp_ctx.c) throw std::runtime_error(std::string("ERROR: no device context for the SNP reader: ") + csvgpu_last_error(nullptr));
+            src.snp_dev.ctx = snp_ctx.c; src.snp_dev.tables_on_device = snp_tables_on_device;
+        }
+        if (snp_file.load(P.snp_vcf, src.opt.threads, &e, src.snp_dev.ctx ? &src.snp_dev : nullptr)) {
             src.snp_file = &snp_file; src.af_files = &af_files; src.ethnicity = P.ethnicity;
         } else {
             printError(e);                                                         // as there: every region then has no SNPs (cnv_caller.cpp:586-591)

@@ -169,6 +169,10 @@ public:
     // the host route (csvgpu_chr_fetch + mergeOrdered): the call set is the same either way. merge_max_partitions: the device's bound on the
     // partitions per bucket (0: the library's own depth limit).
     bool merge_on_device = false;
+    // Opt-in, runBam: the SNP VCF (and the population files) parsed on the device (SNPDeviceOptions of host/snp_io.h, on a context of the
+    // run's own); with snp_tables_on_device the contigs' SNP tables are built there and stay resident, so that the copy-number pass takes
+    // the table route by itself. Beside merge_on_device, not in RunParams: csvhost_run_options is pinned.
+    bool snp_parse_on_device = false, snp_tables_on_device = false;
     uint32_t merge_max_partitions = 0;
     // which route the contigs of this process took since the last reset (all callers, all lanes), and the buckets the device declined
     struct MergeRouteStats { uint64_t contigs_device = 0, contigs_host_declined = 0, contigs_host_overflow = 0, buckets_declined = 0; };

@@ -158,6 +158,14 @@ def load() -> C.CDLL:
     lib.csvhost_snp_free.argtypes = [_P]
     lib.csvhost_snp_open_device.restype = _P
     lib.csvhost_snp_open_device.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32]
+    lib.csvhost_snp_open_device_tables.restype = _P
+    lib.csvhost_snp_open_device_tables.argtypes = [C.c_char_p, C.c_int, _P, C.c_uint32]
+    lib.csvhost_snp_build_stats.restype = None
+    lib.csvhost_snp_build_stats.argtypes = [_P, _P]
+    lib.csvhost_set_snp_on_device.restype = None
+    lib.csvhost_set_snp_on_device.argtypes = [C.c_int, C.c_int]
+    lib.csvhost_cn_route_stats.restype = None
+    lib.csvhost_cn_route_stats.argtypes = [_P, C.c_int]
     lib.csvhost_snp_device_stats.restype = None
     lib.csvhost_snp_device_stats.argtypes = [_P, _P]
     lib.csvhost_snp_table.restype = C.c_int
@@ -1051,8 +1059,12 @@ def write_bam(path: str, ref_names, ref_lens, tid, reads: Reads, qnames, seq_off
 def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0.1, min_pts_pct=0.1, sample_size=20, min_cnv=2000, split_svs=True, cigar_cn=True, save_cnv=False,
             genome: ReferenceGenome | None = None, vcf_dir=None, gap_path=None, file_date=None, capacity: int = 1 << 20,
             snp_vcf=None, pfb_table=None, ethnicity="", inflate_on_device: bool = False, split_groups_on_device: bool = False, split_fits_on_device: bool = False,
-            split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False, shard_on_device: bool = False):
+            split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False, shard_on_device: bool = False,
+            snp_parse_on_device: bool = False, snp_tables_on_device: bool = False):
     """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict).
+    snp_parse_on_device / snp_tables_on_device: SVCaller's fields of those names (the SNP VCF parsed on ctx's device, on a context of the
+    run's own; with the second the contigs' SNP tables are built and stay there, and the copy-number pass looks its SNPs up on the device:
+    cn_route_stats() counts it). Process-wide switches, set for the length of this call and restored. Neither changes the calls.
     shard_on_device (implies unpack_on_device): every contig's resident shard is built on the device from the unpacked batches and handed to
     the run — no host arrays, no upload; the 50-base ALT strings are cut from the shard's own sequences on the device.
     unpack_on_device: the records of every batch are unpacked on ctx's device (csvgpu_bam_unpack, on the reader's own context) instead of
@@ -1067,25 +1079,46 @@ def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0
     tid = np.zeros(capacity, np.int32)
     n = C.c_uint64(0)
     st = bam_stats()
-    _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm),
-                                  C.byref(opt), genome.h if genome is not None and vcf_dir else None,
-                                  os.fsencode(vcf_dir) if vcf_dir else None, os.fsencode(gap_path) if gap_path else None,
-                                  file_date.encode() if file_date else None, out.ctypes.data, tid.ctypes.data, capacity, C.byref(n), C.byref(st),
-                                  os.fsencode(snp_vcf) if snp_vcf else None, os.fsencode(pfb_table) if pfb_table else None, ethnicity.encode()))
+    load().csvhost_set_snp_on_device(int(bool(snp_parse_on_device)), int(bool(snp_tables_on_device)))
+    try:
+        _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm),
+                                      C.byref(opt), genome.h if genome is not None and vcf_dir else None,
+                                      os.fsencode(vcf_dir) if vcf_dir else None, os.fsencode(gap_path) if gap_path else None,
+                                      file_date.encode() if file_date else None, out.ctypes.data, tid.ctypes.data, capacity, C.byref(n), C.byref(st),
+                                      os.fsencode(snp_vcf) if snp_vcf else None, os.fsencode(pfb_table) if pfb_table else None, ethnicity.encode()))
+    finally:
+        load().csvhost_set_snp_on_device(0, 0)
     if n.value > capacity:
         raise RuntimeError("run_bam: capacity too small")
     return out[: n.value].copy(), tid[: n.value].copy(), {f: getattr(st, f) for f, _ in bam_stats._fields_}
+
+
+def cn_route_stats(reset: bool = False) -> dict:
+    """Which route the copy-number pass's decode calls took so far in this process: 'tables' (every contig's SNPs looked up in resident
+    tables on the device) or 'queries' (the host's SNP queries)."""
+    out = np.zeros(2, np.uint64)
+    load().csvhost_cn_route_stats(out.ctypes.data, int(bool(reset)))
+    return dict(tables=int(out[0]), queries=int(out[1]))
 
 
 class SNPFile:
     """The sample's SNP VCF (.vcf or bgzipped + indexed .vcf.gz) parsed once with the reference's filters; query() gives what
     readSNPAlleleFrequencies returns for a region: (positions in file order, BAF at those positions, (pfb_pos, pfb) or None)."""
 
-    def __init__(self, snp_vcf: str, threads: int = 4, parse_on_device: bool = False, ctx: Context | None = None, window_blocks: int = 0):
+    def __init__(self, snp_vcf: str, threads: int = 4, parse_on_device: bool = False, ctx: Context | None = None, window_blocks: int = 0,
+                 tables_on_device: bool = False):
         """parse_on_device (opt-in): the data lines of the file, and of the population files of later queries, are decided on `ctx`'s device
-        (Context.vcf_snp_parse / vcf_af_parse); the tables are the same. window_blocks: BGZF members per batch (0: the default)."""
+        (Context.vcf_snp_parse / vcf_af_parse); the tables are the same. window_blocks: BGZF members per batch (0: the default).
+        tables_on_device (opt-in, needs ctx): the kept records are cut by contig on the device too (Context.snp_builder) and each contig's
+        columns come down once; table() / query() read the population file against the resident positions and leave every ascending
+        contig's first-hit table resident on the device. The tables are the same; build_stats says what the device did."""
         self.h, self.ctx = None, None
-        if parse_on_device:
+        if tables_on_device:
+            if ctx is None:
+                raise ValueError("SNPFile: tables_on_device needs a context")
+            self.ctx = ctx
+            self.h = load().csvhost_snp_open_device_tables(os.fsencode(snp_vcf), threads, ctx.h, window_blocks)
+        elif parse_on_device:
             if ctx is None:
                 raise ValueError("SNPFile: parse_on_device needs a context")
             self.ctx = ctx                               # kept alive as long as the file may parse on it
@@ -1113,6 +1146,14 @@ class SNPFile:
         out = np.zeros(4, np.uint64)
         load().csvhost_snp_device_stats(self.h, out.ctypes.data)
         return dict(zip(("lines", "kept", "deferred", "declined_batches"), (int(x) for x in out)))
+
+    @property
+    def build_stats(self) -> dict:
+        """tables_on_device: CHROM runs the builder reported, records appended through the host (deferred lines, declined batches), contigs
+        whose resident table was made from the device columns so far."""
+        out = np.zeros(3, np.uint64)
+        load().csvhost_snp_build_stats(self.h, out.ctypes.data)
+        return dict(zip(("runs", "appended_host", "tables_resident"), (int(x) for x in out)))
 
     def table(self, chr: str, pfb_vcf: str | None = None, ethnicity: str = "", threads: int = 4):
         """The contig's whole tables, file order: (pos, baf, af_pos, af) — the kept SNP records and the population records that can become

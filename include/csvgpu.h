@@ -888,6 +888,80 @@ int  csvgpu_genome_describe(csv_ctx *ctx, const csv_genome *g, uint64_t cap_reco
 int  csvgpu_genome_fetch(csv_ctx *ctx, const csv_genome *g, const uint32_t *record, const uint32_t *pos_start, const uint32_t *pos_end, const uint64_t *out_off,
                          uint64_t n, int mask, char *out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Resident SNP columns built on the device from VCF text (opt-in: the host reader merges the parsed records per contig by default) */
+/* A builder takes batches of whole VCF data lines, decides them as csvgpu_vcf_snp_parse does and keeps the records in device arrays that
+ * grow as csvgpu_shard_builder's do. The parsed records of a batch interleave contigs: the builder cuts them into CHROM RUNS on the device
+ * (a kept record starts a run when it is the call's first kept record or its CHROM — the chrom_len bytes at line_off — differs in length
+ * or in a byte from the previous KEPT record's; skipped and deferred lines between two kept records break nothing) and hands back one
+ * small table of runs, whose names the caller maps to contig ids below 2^16. _finish orders every record by (contig id, order key), the
+ * key of a device record being text_base + line_off, and leaves per-contig pos / baf columns in device memory, from which tables and the
+ * population parse are made without the host arrays going up again. Replaces the `keep` lambda and the merge loop of SNPFile::load and
+ * the `sorted` copy of SNPFile::table (host/snp_io.cpp); rules in csrc/snp_build_core.hpp, kernels in kernels/snpbuild.hip. One builder is
+ * used from one host thread at a time, on contexts of one device. Launches are timed under CSV_K_MISC. */
+typedef struct csv_snp_builder csv_snp_builder;
+typedef struct csv_snp_columns csv_snp_columns;
+typedef struct csv_snp_runs {            /* the caller's HOST arrays */
+    uint32_t *run_first;                 /* [cap_runs] the run's first kept record, counted inside the call */
+    uint32_t *run_line_off;              /* [cap_runs] that record's line offset: the run's CHROM starts there */
+    uint32_t *run_chrom_len;             /* [cap_runs] */
+    uint32_t *defer_off;                 /* [cap_defer] offsets of the lines the caller parses itself, ascending */
+    uint64_t  cap_runs, cap_defer;
+} csv_snp_runs;
+typedef struct csv_snp_append_counts {
+    uint64_t n_lines, n_kept, n_deferred;        /* as csv_vcf_counts */
+    uint64_t n_runs;                             /* the call's runs */
+    uint64_t first_run;                          /* the builder's run count before the call: run r of the call is global run first_run + r */
+    uint64_t status;                             /* 0, or (offset << 8) | reason when declined, as csv_vcf_counts */
+} csv_snp_append_counts;
+
+/* reserve_records: room allocated now (0: the arrays grow from nothing). NULL on failure. */
+csv_snp_builder *csvgpu_snp_builder_create(csv_ctx *ctx, uint64_t reserve_records);
+/* One batch (text, dp_int, ad_int as csvgpu_vcf_snp_parse). Returns CSV_OK: the kept records are behind the builder's tail, the run table
+ * and the deferred offsets in *out; 1 = declined (a '#' line behind data; counts->status as csv_vcf_counts), nothing appended, the run
+ * count unchanged: the caller parses the batch and uses _append_host; CSV_ECAPACITY: cap_runs or cap_defer too small, the exact counts
+ * filled in, nothing appended or written; CSV_ENOMEM: a growth failed, the builder keeps its contents and the same append may be
+ * repeated; CSV_EINVAL, nothing reaching the device: a null pointer, len >= 2^32, text_base + len > 2^48. A call that would bring the
+ * builder to 2^31 runs or more is CSV_EINVAL too, but only the device can count the runs: the batch has been parsed by then, and nothing
+ * is appended.
+ * len == 0: CSV_OK with zero counts. Calls may come in any order of text_base: the key orders the records. Waits for its kernels.
+ * _dev: text is a device pointer at any alignment (what csvgpu_bgzf_inflate_dev left); out and counts are the host's. */
+int  csvgpu_snp_builder_append(csv_ctx *ctx, csv_snp_builder *b, const uint8_t *text, uint64_t len, uint64_t text_base, int dp_int, int ad_int,
+                               const csv_snp_runs *out, csv_snp_append_counts *counts);
+int  csvgpu_snp_builder_append_dev(csv_ctx *ctx, csv_snp_builder *b, const uint8_t *d_text, uint64_t len, uint64_t text_base, int dp_int, int ad_int,
+                                   const csv_snp_runs *out, csv_snp_append_counts *counts);
+/* Records the host parser kept (snp_record_of_line on a deferred line; a declined batch): HOST arrays, each record with its own contig id
+ * and order key (its line's offset in the file). CSV_EINVAL, nothing changed: an id at or above 2^16, a key at or above 2^48, a null array
+ * with a count. CSV_ENOMEM as above. */
+int  csvgpu_snp_builder_append_host(csv_ctx *ctx, csv_snp_builder *b, uint64_t n, const uint32_t *contig_id, const uint64_t *order_key, const uint32_t *pos,
+                                    const double *baf);
+/* run_contig[r]: the contig id of global run r (HOST array, n_runs == the builder's run count). One stable order by (contig id, order
+ * key): one radix sort of the packed key over the bits that vary, a gather of pos / baf; then per contig its count, its offset and whether
+ * it is ascending (pos[i] >= pos[i - 1] inside the contig), all on the device. Consumes the builder, also on failure. NULL with a message:
+ * n_runs is not the builder's run count, a run_contig at or above 2^16, two records of a contig with one order key (found on the device
+ * behind the sort: the caller broke the contract), 2^32 - 1 records or more, no memory. A contig that is not ascending is no error: it is
+ * flagged and can be fetched; csvgpu_snp_columns_table and _af_parse refuse it, and the host route serves it. */
+csv_snp_columns *csvgpu_snp_builder_finish(csv_ctx *ctx, csv_snp_builder *b, const uint32_t *run_contig, uint64_t n_runs);
+void csvgpu_snp_builder_destroy(csv_ctx *ctx, csv_snp_builder *b);
+
+/* The contigs that hold a record, by ascending id: *n_contigs is always set; CSV_ECAPACITY, nothing written, when cap is below it. Any
+ * array may be NULL. */
+int  csvgpu_snp_columns_describe(const csv_snp_columns *cols, uint64_t cap, uint32_t *contig_id, uint64_t *count, uint8_t *ascending, uint64_t *n_contigs);
+/* One contig's columns to the host, in file order (count entries each; either may be NULL). CSV_EINVAL: an id that holds no record. */
+int  csvgpu_snp_columns_fetch(csv_ctx *ctx, const csv_snp_columns *cols, uint32_t contig_id, uint32_t *pos, double *baf);
+/* csvgpu_vcf_af_parse / _dev with sorted_pos = the contig's resident pos (an ascending contig's file order is its sorted order), nothing
+ * going up but the text: counts, decline, capacity and deferral are that function's. CSV_EINVAL also for an id that holds no record, a
+ * contig that is not ascending, columns of another device. */
+int  csvgpu_snp_columns_af_parse(csv_ctx *ctx, const csv_snp_columns *cols, uint32_t contig_id, const uint8_t *text, uint64_t len, const char *contig,
+                                 uint32_t contig_len, const char *needle, uint32_t needle_len, const csv_vcf_out *out, csv_vcf_counts *counts);
+int  csvgpu_snp_columns_af_parse_dev(csv_ctx *ctx, const csv_snp_columns *cols, uint32_t contig_id, const uint8_t *d_text, uint64_t len, const char *contig,
+                                     uint32_t contig_len, const char *needle, uint32_t needle_len, const csv_vcf_out *d_out, csv_vcf_counts *counts);
+/* csvgpu_snp_table_create_hits of the contig's columns (copied device to device) and the caller's HOST af arrays. NULL with a message as
+ * there, and for an id that holds no record or a contig that is not ascending. The table does not depend on the columns afterwards. */
+csv_snp_table *csvgpu_snp_columns_table(csv_ctx *ctx, const csv_snp_columns *cols, uint32_t contig_id, const uint32_t *af_pos, const double *af, uint64_t n_af);
+/* Plain device memory: any context of the device may read the columns. Waits for ctx's stream, then frees. */
+void csvgpu_snp_columns_free(csv_ctx *ctx, csv_snp_columns *cols);
+
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
  * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster and of the

@@ -28,6 +28,19 @@ int csvgpu_vcf_snp_parse(csv_ctx *, const uint8_t *, uint64_t, int, int, const c
 int csvgpu_vcf_af_parse(csv_ctx *, const uint8_t *, uint64_t, const char *, uint32_t, const char *, uint32_t, const uint32_t *, uint64_t, const csv_vcf_out *,
                         csv_vcf_counts *) { abort(); }
 const char *csvgpu_last_error(const csv_ctx *) { abort(); }
+// ... and its tables_on_device path these (csvgpu_snp_builder_* / csvgpu_snp_columns_*); never taken here either
+csv_snp_builder *csvgpu_snp_builder_create(csv_ctx *, uint64_t) { abort(); }
+int csvgpu_snp_builder_append(csv_ctx *, csv_snp_builder *, const uint8_t *, uint64_t, uint64_t, int, int, const csv_snp_runs *, csv_snp_append_counts *) { abort(); }
+int csvgpu_snp_builder_append_host(csv_ctx *, csv_snp_builder *, uint64_t, const uint32_t *, const uint64_t *, const uint32_t *, const double *) { abort(); }
+csv_snp_columns *csvgpu_snp_builder_finish(csv_ctx *, csv_snp_builder *, const uint32_t *, uint64_t) { abort(); }
+void csvgpu_snp_builder_destroy(csv_ctx *, csv_snp_builder *) { abort(); }
+int csvgpu_snp_columns_describe(const csv_snp_columns *, uint64_t, uint32_t *, uint64_t *, uint8_t *, uint64_t *) { abort(); }
+int csvgpu_snp_columns_fetch(csv_ctx *, const csv_snp_columns *, uint32_t, uint32_t *, double *) { abort(); }
+int csvgpu_snp_columns_af_parse(csv_ctx *, const csv_snp_columns *, uint32_t, const uint8_t *, uint64_t, const char *, uint32_t, const char *, uint32_t,
+                                const csv_vcf_out *, csv_vcf_counts *) { abort(); }
+csv_snp_table *csvgpu_snp_columns_table(csv_ctx *, const csv_snp_columns *, uint32_t, const uint32_t *, const double *, uint64_t) { abort(); }
+void csvgpu_snp_columns_free(csv_ctx *, csv_snp_columns *) { abort(); }
+void csvgpu_snp_table_free(csv_ctx *, csv_snp_table *) { abort(); }
 }
 
 // SNPFileTable's base class keeps this one function (and with it its vtable) in host/cnv_caller.cpp, which is not linked; no table is queried here
