@@ -131,6 +131,24 @@ class csv_shard_sizes(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq", C.c_uint64), ("n_name", C.c_uint64)]
 
 
+# csv_vcf_call: csvhost_call's layout (host.CALL_DTYPE is the same dtype)
+VCF_CALL_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("sv_type", "<i4"), ("cluster_size", "<i4"), ("hmm_likelihood", "<f8"),
+                           ("id", "<i8"), ("aln_flags", "<u4"), ("genotype", "<i4"), ("cn_state", "<i4"), ("aln_offset", "<i4")])
+# the status byte of a call (csrc/vcf_format_core.hpp): disposition in the low two bits, flags above; why a batch is declined
+VCF_WRITTEN, VCF_SKIP_UNCLASSIFIED, VCF_SKIP_FIRST_POSITION, VCF_DISPOSITION, VCF_EMPTY_REF, VCF_GAP_FILTERED, VCF_DEPTH_OUT_OF_RANGE = 0, 1, 2, 3, 4, 8, 16
+VCF_WHY_LIKELIHOOD, VCF_WHY_DEL_LENGTH, VCF_WHY_ENUM, VCF_WHY_NO_RECORD, VCF_WHY_DEL_START, VCF_WHY_TEXT_BYTES = 1, 2, 3, 4, 5, 6
+
+
+class csv_vcf_contig(C.Structure):
+    _fields_ = [("name", C.c_void_p), ("name_len", C.c_uint32), ("genome_record", C.c_int64), ("shard", C.c_void_p),
+                ("gap_start", C.c_void_p), ("gap_end", C.c_void_p), ("n_gaps", C.c_uint32)]
+
+
+class csv_vcf_format_counts(C.Structure):
+    _fields_ = [("text_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("total", C.c_uint32), ("unclassified", C.c_uint32),
+                ("gap_filtered", C.c_uint32), ("declined_why", C.c_uint32)]
+
+
 class csv_genome_counts(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("n_name_bytes", C.c_uint64), ("total_bases", C.c_uint64), ("n_text_bytes", C.c_uint64), ("n_lines", C.c_uint64)]
 
@@ -252,6 +270,8 @@ ABI = {
     "csvgpu_genome_free": (None, [_P, _P]),
     "csvgpu_genome_describe": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(csv_genome_counts)]),
     "csvgpu_genome_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_int, _P]),
+    "csvgpu_vcf_format": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P, C.POINTER(csv_vcf_format_counts)]),
+    "csvgpu_vcf_format_dev": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P, C.POINTER(csv_vcf_format_counts)]),
     "csvgpu_snp_builder_create": (_P, [_P, C.c_uint64]),
     "csvgpu_snp_builder_append": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_snp_runs), C.POINTER(csv_snp_append_counts)]),
     "csvgpu_snp_builder_append_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(csv_snp_runs), C.POINTER(csv_snp_append_counts)]),

@@ -885,6 +885,64 @@ class Context:
         allocated now."""
         return SnpBuilder(self, reserve)
 
+    # -------------------------------------------------------------------------------- VCF records formatted on the device
+    def vcf_format_raw(self, genome: "Genome", contigs, calls, alts, method: bytes, cap: int, text_ptr, dev: bool = False):
+        """One csvgpu_vcf_format (dev: _dev) call. contigs: [(name, n_calls, shard or None, gaps or None[, record])] — gaps = (gap_start,
+        gap_end) BED rows in file order, record = the genome record's index (-1: none; left out: the last record of that name, -1 when there
+        is none); calls: all contigs' calls in order (_lib.VCF_CALL_DTYPE); alts: one bytes per call; text_ptr: `cap` writeable bytes (an
+        address; the device's with dev). -> (rc, line_status uint8[n], counts dict)."""
+        calls = np.ascontiguousarray(calls, _lib.VCF_CALL_DTYPE)
+        alts = [a.encode("latin-1") if isinstance(a, str) else bytes(a) for a in alts]
+        if len(alts) != len(calls) or sum(int(c[1]) for c in contigs) != len(calls):
+            raise ValueError("vcf_format: array lengths disagree")
+        n_contigs = len(contigs)
+        call_off, alt_off = np.zeros(n_contigs + 1, np.uint64), np.zeros(len(calls) + 1, np.uint64)
+        call_off[1:] = np.cumsum([int(c[1]) for c in contigs], dtype=np.uint64)
+        alt_off[1:] = np.cumsum([len(a) for a in alts], dtype=np.uint64)
+        alt_bytes = np.frombuffer(b"".join(alts) + b"\0", np.uint8)
+        tab = (_lib.csv_vcf_contig * max(n_contigs, 1))()
+        keep = []                                          # what the table points into
+        for t, c in enumerate(contigs):
+            name = c[0].encode("latin-1") if isinstance(c[0], str) else bytes(c[0])
+            name_arr = np.frombuffer(name + b"\0", np.uint8)
+            shard, gaps = c[2], c[3] if len(c) > 3 else None
+            if len(c) > 4:
+                record = int(c[4])
+            else:
+                try:
+                    record = genome.record_of(name)
+                except KeyError:
+                    record = -1
+            gs, ge = (np.ascontiguousarray(g, np.uint32) for g in gaps) if gaps is not None else (np.zeros(0, np.uint32),) * 2
+            if len(gs) != len(ge):
+                raise ValueError("vcf_format: gap arrays disagree")
+            keep += [name_arr, gs, ge]
+            tab[t] = _lib.csv_vcf_contig(ptr(name_arr), len(name), record, shard.h if shard is not None else None, ptr(gs) if len(gs) else None,
+                                         ptr(ge) if len(ge) else None, len(gs))
+        status = np.zeros(max(len(calls), 1), np.uint8)
+        cnt = _lib.csv_vcf_format_counts()
+        method = np.frombuffer(bytes(method) + b"\0", np.uint8)
+        fn = self.lib.csvgpu_vcf_format_dev if dev else self.lib.csvgpu_vcf_format
+        rc = fn(self.h, genome.h, tab, n_contigs, ptr(call_off), ptr(calls) if len(calls) else None, ptr(alt_off), ptr(alt_bytes), ptr(method), len(method) - 1,
+                int(cap), text_ptr, ptr(status), C.byref(cnt))
+        counts = {k: int(getattr(cnt, k)) for k in ("text_bytes", "n_lines", "total", "unclassified", "gap_filtered", "declined_why")}
+        return rc, status[: len(calls)], counts
+
+    def vcf_format(self, genome: "Genome", contigs, calls, alts, method: bytes = b"ContextSV v1.0.0"):
+        """csvgpu_vcf_format: the record lines of the VCF writer for `calls`, assembled on the device from the resident genome and the
+        shards' depth maps -> (text: bytes, line_status: uint8[n], counts: dict). Arguments as vcf_format_raw. Two calls: the first sizes the
+        second. A declined batch returns text=None with counts["declined_why"] set; CSV_E* raises."""
+        rc, status, counts = self.vcf_format_raw(genome, contigs, calls, alts, method, 0, None)
+        if rc == _lib.CSV_ECAPACITY:
+            out = np.zeros(counts["text_bytes"], np.uint8)
+            rc, status, counts = self.vcf_format_raw(genome, contigs, calls, alts, method, len(out), ptr(out))
+            if rc == _lib.CSV_OK:
+                return out.tobytes(), status, counts
+        if rc == 1:
+            return None, status, counts
+        self._check(rc)
+        return b"", status, counts
+
     def alt_bases(self, shard: "Shard", read, qpos, lengths):
         """csvgpu_alt_bases_resident: for item i the `lengths[i]` bases from query offset qpos[i] of record read[i], cut from the packed
         sequences a built shard holds (ambiguity codes as N; all N where the bases leave the stored sequence) -> list of str."""

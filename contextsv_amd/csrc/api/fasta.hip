@@ -16,8 +16,6 @@ namespace {
 
 constexpr uint64_t kSlack = 16;                      // bytes kept behind the array's last base
 
-struct Rec { uint64_t start; uint32_t len; uint64_t name_off; uint32_t name_len; };
-
 }  // namespace
 
 struct csv_genome_builder {
@@ -26,15 +24,6 @@ struct csv_genome_builder {
     uint64_t n_kept = 0;
     uint64_t n_text = 0, n_lines = 0;                // what was appended: bytes, line ends
     Assembler a;                                     // the records so far, and what crosses the cut between two appends
-};
-
-struct csv_genome {
-    int device = 0;
-    char *seq = nullptr;
-    uint64_t total = 0;                              // bases that belong to a record: seq[0 .. total)
-    std::vector<Rec> rec;                            // file order, one per named header
-    std::string names;
-    uint64_t n_text = 0, n_lines = 0;
 };
 
 namespace {
@@ -175,7 +164,7 @@ csv_genome *csvgpu_genome_builder_finish(csv_ctx *ctx, csv_genome_builder *b)
     }
     g->device = b->device; g->total = total; g->n_text = b->n_text; g->n_lines = b->n_lines;
     for (const fastacore::Record &r : b->a.rec) {
-        g->rec.push_back(Rec{r.start, (uint32_t)(r.end - r.start), g->names.size(), (uint32_t)r.name.size()});
+        g->rec.push_back(csv_genome_rec{r.start, (uint32_t)(r.end - r.start), g->names.size(), (uint32_t)r.name.size()});
         g->names += r.name;
     }
     g->seq = b->seq.p;                                   // the array changes hands
@@ -218,7 +207,7 @@ int csvgpu_genome_fetch(csv_ctx *ctx, const csv_genome *g, const uint32_t *recor
     for (uint64_t i = 0; i < n; i++) {
         if (record[i] >= g->rec.size()) return bad(ctx, "genome_fetch: record index beyond the genome");
         if (out_off[i + 1] < out_off[i]) return bad(ctx, "genome_fetch: out_off decreases");
-        const Rec &r = g->rec[record[i]];
+        const csv_genome_rec &r = g->rec[record[i]];
         uint32_t first = 0;
         const uint32_t len = fastacore::cut_len(r.len, pos_start[i], pos_end[i], first);
         if (out_off[i + 1] - out_off[i] != len) return bad(ctx, "genome_fetch: an item's room is not its cut's length");

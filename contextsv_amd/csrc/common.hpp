@@ -121,6 +121,18 @@ struct csv_snp_table {
     const uint64_t *baf = nullptr, *pfb = nullptr, *af = nullptr;      // values as their bits
 };
 
+// a reference genome's bases in device memory (csvgpu_genome_*, api/fasta.hip; read by csvgpu_vcf_format, api/vcf_format.hip): immutable once
+// built, readable from every context of its device. 16 spare bytes lie behind seq[total).
+struct csv_genome_rec { uint64_t start; uint32_t len; uint64_t name_off; uint32_t name_len; };
+struct csv_genome {
+    int device = 0;
+    char *seq = nullptr;
+    uint64_t total = 0;                              // bases that belong to a record: seq[0 .. total)
+    std::vector<csv_genome_rec> rec;                 // file order, one per named header
+    std::string names;
+    uint64_t n_text = 0, n_lines = 0;
+};
+
 namespace csv {
 
 // device scalars written by the scan / depth kernels, read back once per chromosome
@@ -593,6 +605,37 @@ void launch_fasta_lines(hipStream_t s, const uint8_t *text, uint32_t len, uint32
 void launch_fasta_compact(hipStream_t s, const uint8_t *text, uint32_t len, const FastaWs &w, uint8_t *dst);
 // item i: out[out_off[i] .. out_off[i + 1]) = seq[src[i] ..), ambiguity codes as N if mask; out_off[0] = 0, out_off[n] = total; out 16-byte aligned
 void launch_fasta_cut(hipStream_t s, const uint8_t *seq, const uint64_t *src, const uint64_t *out_off, uint64_t n, uint64_t total, bool mask, uint8_t *out);
+// vcfformat.hip — the VCF writer's record lines assembled on the device (csvgpu_vcf_format; the rules in vcf_format_core.hpp)
+struct VfContig {                            // one contig of the batch, as the kernels see it
+    uint64_t call_first;                     // its first call (call_off[t]); the table has one more entry, whose call_first is the call count
+    uint64_t name_off; uint32_t name_len;    // its name in names[]
+    uint32_t n_gaps; uint64_t gap_first;     // its BED rows in gap_start / gap_end
+    int64_t  contig_len;                     // its length in the genome, -1: the genome has no such record
+    uint64_t rec_start;                      // its first base in the genome's array
+    const uint32_t *depth; uint32_t depth_len, pad;      // its resident depth map (null: no call asks for a depth)
+};
+struct VfHead {                              // one slice, zeroed per call (first_refused to all ones), copied back whole
+    unsigned long long text_bytes, n_lines;
+    unsigned long long first_refused;        // min over the refused calls of (call index << 8 | why); all ones: none
+    uint32_t total, unclassified, gap_filtered, pad;
+};
+struct VfArgs {                              // passed to the kernels by value
+    const VfContig *contig; uint32_t n_contigs;
+    const void *calls; uint64_t n_calls;     // [n_calls] csv_vcf_call
+    const uint64_t *alt_off; const uint8_t *alts;
+    const uint8_t *names, *method; uint32_t method_len;
+    const uint32_t *gap_start, *gap_end;
+    const uint8_t *seq;                      // the genome's base array (16 spare bytes behind its last base)
+    uint32_t *len;                           // [n_calls + 1] the lines' lengths, then their exclusive sums
+    int32_t *depth;                          // [n_calls] the value at POS
+    uint8_t *status;                         // [n_calls]
+    VfHead *head;
+    void *es_tmp;                            // exclusive_sum_tmp_bytes(n_calls + 1)
+};
+// a lane per call: disposition, depth, gap search, the line's length; the sums of the head; then the exclusive sum of the lengths
+void launch_vcf_format_size(hipStream_t s, const VfArgs &a);
+// text[0 .. total): every 16-byte piece by one lane (total = len[n_calls] < 2^32, after the caller has read the head)
+void launch_vcf_format_write(hipStream_t s, const VfArgs &a, uint64_t total, uint8_t *text);
 // snpbuild.hip — the kept records of VCF batches cut by contig on the device (csvgpu_snp_builder_*; the rules in snp_build_core.hpp)
 constexpr uint32_t SB_MAX_BLOCKS = 256;      // of 256 threads; larger calls stride
 struct SnpAppendArgs {                       // passed to the kernel by value

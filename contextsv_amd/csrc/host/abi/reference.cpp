@@ -3,6 +3,13 @@
 
 #include "abi.hpp"
 
+// csvgpu_vcf_format takes the mirror's calls as they are: csv_vcf_call (include/csvgpu.h) and csvhost_call (csvhost_abi.h) are one layout
+#define SAME_FIELD(f) (offsetof(csv_vcf_call, f) == offsetof(csvhost_call, f) && sizeof(((csv_vcf_call *)0)->f) == sizeof(((csvhost_call *)0)->f))
+static_assert(sizeof(csv_vcf_call) == sizeof(csvhost_call) && sizeof(csvhost_call) == 48 && SAME_FIELD(start) && SAME_FIELD(end) && SAME_FIELD(sv_type) &&
+              SAME_FIELD(cluster_size) && SAME_FIELD(hmm_likelihood) && SAME_FIELD(id) && SAME_FIELD(aln_flags) && SAME_FIELD(genotype) && SAME_FIELD(cn_state) &&
+              SAME_FIELD(aln_offset), "csv_vcf_call and csvhost_call are one layout");
+#undef SAME_FIELD
+
 extern "C" {
 
 csvhost_fasta *csvhost_fasta_open(const char *path)
@@ -58,13 +65,10 @@ int64_t csvhost_fasta_chromosomes(const csvhost_fasta *h, char *buf, uint64_t ca
     return (int64_t)copy_text(s, buf, cap);
 }
 
-// Calls of contig t = calls[call_off[t] .. call_off[t+1]) with ALT strings alts[i]. Depth comes from resident shards
-// (shards != nullptr, ShardDepthSource) or from host arrays depth[t][0..depth_len[t]) (a null depth[t] = contig without a map).
-// map_order != 0 goes through saveToVCF's unordered_map iteration; otherwise contigs are written in the order given.
-// counts = {total, unclassified, assembly-gap filtered}.
-int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fasta, const char *gap_path, const char *file_date, int n_contigs,
-                     const char *const *chr_names, const uint64_t *call_off, const csvhost_call *calls, const char *const *alts,
-                     csv_shard *const *shards, const uint32_t *const *depth, const uint64_t *depth_len, int map_order, int32_t *counts)
+// csvhost_save_vcf and csvhost_save_vcf_device: one body
+static int save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fasta, const char *gap_path, const char *file_date, int n_contigs,
+                    const char *const *chr_names, const uint64_t *call_off, const csvhost_call *calls, const char *const *alts,
+                    csv_shard *const *shards, const uint32_t *const *depth, const uint64_t *depth_len, int map_order, int32_t *counts, bool format_on_device)
 {
     GUARD({
         std::vector<std::pair<std::string, std::vector<SVCall>>> per((size_t)n_contigs);
@@ -86,6 +90,7 @@ int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fas
         opt.assembly_gaps = gap_path ? gap_path : "";
         opt.output_dir = out_dir;
         opt.file_date = file_date ? file_date : "";
+        opt.format_on_device = format_on_device; opt.ctx = ctx;
         VCFCounts c;
         if (map_order) {
             std::unordered_map<std::string, std::vector<SVCall>> m;
@@ -103,5 +108,29 @@ int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fas
         if (counts) { counts[0] = c.total; counts[1] = c.unclassified; counts[2] = c.assembly_gap_filtered; }
     })
 }
+
+// Calls of contig t = calls[call_off[t] .. call_off[t+1]) with ALT strings alts[i]. Depth comes from resident shards
+// (shards != nullptr, ShardDepthSource) or from host arrays depth[t][0..depth_len[t]) (a null depth[t] = contig without a map).
+// map_order != 0 goes through saveToVCF's unordered_map iteration; otherwise contigs are written in the order given.
+// counts = {total, unclassified, assembly-gap filtered}.
+int csvhost_save_vcf(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fasta, const char *gap_path, const char *file_date, int n_contigs,
+                     const char *const *chr_names, const uint64_t *call_off, const csvhost_call *calls, const char *const *alts,
+                     csv_shard *const *shards, const uint32_t *const *depth, const uint64_t *depth_len, int map_order, int32_t *counts)
+{
+    return save_vcf(ctx, out_dir, fasta, gap_path, file_date, n_contigs, chr_names, call_off, calls, alts, shards, depth, depth_len, map_order, counts, false);
+}
+// The same with VCFOptions::format_on_device: the record lines from one csvgpu_vcf_format call on ctx where the genome is on the device and
+// the depth comes from shards; the host loop otherwise, and for a batch the device declines. The file is the same either way.
+int csvhost_save_vcf_device(csv_ctx *ctx, const char *out_dir, const csvhost_fasta *fasta, const char *gap_path, const char *file_date, int n_contigs,
+                            const char *const *chr_names, const uint64_t *call_off, const csvhost_call *calls, const char *const *alts,
+                            csv_shard *const *shards, const uint32_t *const *depth, const uint64_t *depth_len, int map_order, int32_t *counts,
+                            int format_on_device)
+{
+    return save_vcf(ctx, out_dir, fasta, gap_path, file_date, n_contigs, chr_names, call_off, calls, alts, shards, depth, depth_len, map_order, counts,
+                    format_on_device != 0);
+}
+// out[3]: batches of writeVCF formatted on the device / that ran the host loop with the option on / of those, declined by the device; since
+// the process began or the last reset
+void csvhost_vcf_route_stats(uint64_t *out, int reset) { vcfRouteStats(out, reset != 0); }
 
 }  // extern "C"

@@ -246,6 +246,9 @@ int csvhost_genome_run(csvhost_genome *g, csv_ctx *ctx, int n_lanes, csv_ctx *co
 // SVCaller::snp_parse_on_device, snp_tables_on_device. csvhost_run_options is untouched.
 static std::atomic<int> g_snp_parse_on_device{0}, g_snp_tables_on_device{0};
 void csvhost_set_snp_on_device(int parse, int tables) { g_snp_parse_on_device = parse != 0; g_snp_tables_on_device = tables != 0; }
+// SVCaller::vcf_format_on_device of the same caller: the run's output.vcf through csvgpu_vcf_format where the genome is on the device
+static std::atomic<int> g_vcf_on_device{0};
+void csvhost_set_vcf_on_device(int on) { g_vcf_on_device = on != 0; }
 // out[2]: copy-number decode calls that took the table route (every job's SNPs resident: "cn: decode on resident tables") / that ran the
 // host's SNP queries, since the process began or the last reset
 void csvhost_cn_route_stats(uint64_t *out, int reset) { cnRouteStats(out, reset != 0); }
@@ -263,6 +266,7 @@ int csvhost_run_bam(csv_ctx *ctx, const char *bam_path, const char *chrs, int th
         set_vcf_output(P, fasta, vcf_dir, gap_path, file_date);
         SVCaller caller(ctx);
         caller.snp_parse_on_device = g_snp_parse_on_device.load() != 0; caller.snp_tables_on_device = g_snp_tables_on_device.load() != 0;
+        caller.vcf_format_on_device = g_vcf_on_device.load() != 0;
         std::unordered_map<std::string, std::vector<SVCall>> calls;
         BamRunStats bs;
         caller.runBam(bam_path, split_lines(chrs), threads, chmm_from_pod(hmm), P, calls, &bs);

@@ -73,6 +73,19 @@ FastaDeviceStats ReferenceGenome::deviceStats() const
     return dev->stats;
 }
 
+const csv_genome *ReferenceGenome::deviceGenome(csv_ctx **ctx) const
+{
+    if (ctx) *ctx = dev ? dev->ctx : nullptr;
+    return dev ? dev->g : nullptr;
+}
+
+int64_t ReferenceGenome::deviceRecord(const std::string &chr) const
+{
+    if (!dev) return -1;
+    const auto it = dev->record.find(chr);
+    return it == dev->record.end() ? -1 : (int64_t)it->second;
+}
+
 void ReferenceGenome::addContig(const std::string &name, std::string sequence)
 {
     chromosomes.push_back(name);

@@ -12,6 +12,7 @@
 #include <vector>
 
 struct csv_ctx;
+struct csv_genome;
 
 struct FastaDeviceOptions {
     csv_ctx *ctx = nullptr;           // the context the genome is built on and fetched through
@@ -60,6 +61,10 @@ public:
     void addContig(const std::string &name, std::string sequence);
 
     bool onDevice() const { return dev != nullptr; }
+    // The device genome and the context it was built on (both null with a host backing), and a name's record in it: the LAST record of a
+    // duplicated name, as the loader's map decides; -1 when the genome has none. For csvgpu_vcf_format (host/vcf_writer.cpp).
+    const csv_genome *deviceGenome(csv_ctx **ctx = nullptr) const;
+    int64_t deviceRecord(const std::string &chr) const;
     FastaDeviceStats deviceStats() const;
 
 private:

@@ -1274,7 +1274,9 @@ void SVCaller::finishRun(std::vector<ResidentContig> &contigs, const std::vector
         printMessage("Saving SVs to VCF...");
         ShardDepthSource depth(ctx);
         for (const ResidentContig &c : contigs) if (c.shard) depth.add(c.name, c.shard);
-        saveToVCF(whole_genome_sv_calls, P.vcf, *P.ref_genome, depth);
+        VCFOptions vcf = P.vcf;
+        vcf.format_on_device = vcf_format_on_device; vcf.ctx = ctx;
+        saveToVCF(whole_genome_sv_calls, vcf, *P.ref_genome, depth);
         T.ms_vcf = now_ms() - t0;
     }
 }

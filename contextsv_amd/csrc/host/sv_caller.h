@@ -173,6 +173,9 @@ public:
     // run's own); with snp_tables_on_device the contigs' SNP tables are built there and stay resident, so that the copy-number pass takes
     // the table route by itself. Beside merge_on_device, not in RunParams: csvhost_run_options is pinned.
     bool snp_parse_on_device = false, snp_tables_on_device = false;
+    // The run's output.vcf with its record lines assembled on the device (VCFOptions::format_on_device; host/vcf_writer.h): one
+    // csvgpu_vcf_format call where the reference genome is on the device, the host loop otherwise. Same file. Beside the switches above.
+    bool vcf_format_on_device = false;
     uint32_t merge_max_partitions = 0;
     // which route the contigs of this process took since the last reset (all callers, all lanes), and the buckets the device declined
     struct MergeRouteStats { uint64_t contigs_device = 0, contigs_host_declined = 0, contigs_host_overflow = 0, buckets_declined = 0; };

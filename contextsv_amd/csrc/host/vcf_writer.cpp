@@ -1,6 +1,7 @@
 #include "vcf_writer.h"
 
 #include <algorithm>
+#include <atomic>
 #include <ctime>
 #include <fstream>
 #include <iostream>
@@ -54,6 +55,110 @@ const char *const kHeaderLines[] = {
     "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Read depth at the variant site (sum of start and end positions)\">",
 };
 }  // namespace
+
+namespace {
+std::atomic<uint64_t> g_vcf_device_batches{0}, g_vcf_host_batches{0}, g_vcf_declined{0};
+
+// status bits of csvgpu_vcf_format's line_status (csrc/vcf_format_core.hpp)
+enum : uint8_t { ST_DISPOSITION = 3, ST_SKIP_UNCLASSIFIED = 1, ST_SKIP_FIRST_POSITION = 2, ST_EMPTY_REF = 4, ST_DEPTH_OUT_OF_RANGE = 16 };
+
+// The record lines of all contigs from ONE csvgpu_vcf_format call, written to `out` with the host loop's messages replayed from the status
+// bytes. false: nothing was written and the caller runs the host loop (the genome or the depth maps are not on the device, the device
+// declined the batch, or the call failed).
+bool formatOnDevice(std::ostream &out, const std::vector<std::pair<std::string, const std::vector<SVCall> *>> &contigs, const VCFOptions &opt,
+                    const std::unordered_map<std::string, std::vector<std::pair<uint32_t, uint32_t>>> &gaps, const ReferenceGenome &ref_genome,
+                    const DepthSource &depth, const std::string &sv_method, VCFCounts &counts)
+{
+    const ShardDepthSource *shards = dynamic_cast<const ShardDepthSource *>(&depth);
+    const csv_genome *genome = ref_genome.deviceGenome();
+    csv_ctx *ctx = opt.ctx ? opt.ctx : (shards ? shards->ctx : nullptr);
+    if (!shards || !genome || !ctx) { g_vcf_host_batches++; return false; }
+
+    const size_t n_contigs = contigs.size();
+    std::vector<csv_vcf_contig> tab(n_contigs);
+    std::vector<uint64_t> call_off(n_contigs + 1, 0);
+    std::vector<std::vector<uint32_t>> gap_start(n_contigs), gap_end(n_contigs);
+    std::vector<csv_vcf_call> calls;
+    std::vector<uint64_t> alt_off(1, 0);
+    std::string alts;
+    uint64_t bound = 0;                                   // of the text: the cuts' lengths are the contigs' lengths at most
+    for (size_t t = 0; t < n_contigs; t++) {
+        const std::string &chr = contigs[t].first;
+        csv_vcf_contig &c = tab[t];
+        c.name = chr.data(); c.name_len = (uint32_t)chr.size();
+        c.genome_record = ref_genome.deviceRecord(chr);
+        const auto sh = shards->shards.find(chr);
+        c.shard = sh == shards->shards.end() ? nullptr : sh->second;
+        const auto gap_it = gaps.find(chr);
+        if (gap_it != gaps.end())
+            for (const auto &row : gap_it->second) { gap_start[t].push_back(row.first); gap_end[t].push_back(row.second); }
+        c.gap_start = gap_start[t].data(); c.gap_end = gap_end[t].data(); c.n_gaps = (uint32_t)gap_start[t].size();
+        const uint64_t contig_len = c.genome_record < 0 ? 0 : ref_genome.getChromosomeLength(chr);
+        for (const SVCall &sv : *contigs[t].second) {
+            csv_vcf_call p;
+            p.start = sv.start; p.end = sv.end; p.sv_type = (int32_t)sv.sv_type; p.cluster_size = sv.cluster_size; p.hmm_likelihood = sv.hmm_likelihood; p.id = -1;
+            p.aln_flags = (uint32_t)sv.aln_type.to_ulong(); p.genotype = (int32_t)sv.genotype; p.cn_state = sv.cn_state; p.aln_offset = sv.aln_offset;
+            calls.push_back(p);
+            alts += sv.alt_allele;
+            alt_off.push_back(alts.size());
+            uint64_t ref = 1;                             // a DEL's cut [preceding, end], the contig's length at most
+            if (sv.sv_type == SVType::DEL) {
+                const uint64_t preceding = sv.start >= 2 && sv.start < 0x80000000u ? sv.start - 1 : 1;
+                ref = sv.end >= preceding ? std::min<uint64_t>(contig_len, sv.end - preceding + 1) : 1;
+            }
+            bound += chr.size() + ref + sv.alt_allele.size() + sv_method.size() + 400;
+        }
+        call_off[t + 1] = calls.size();
+    }
+    std::vector<uint8_t> status(calls.size() + 1);
+    std::string text((size_t)bound, '\0');
+    csv_vcf_format_counts fc{};
+    int rc = csvgpu_vcf_format(ctx, genome, tab.data(), (uint32_t)n_contigs, call_off.data(), calls.data(), alt_off.data(), alts.data(), sv_method.data(),
+                               (uint32_t)sv_method.size(), text.size(), &text[0], status.data(), &fc);
+    if (rc == CSV_ECAPACITY) {                            // (the bound holds; handled all the same)
+        text.assign((size_t)fc.text_bytes, '\0');
+        rc = csvgpu_vcf_format(ctx, genome, tab.data(), (uint32_t)n_contigs, call_off.data(), calls.data(), alt_off.data(), alts.data(), sv_method.data(),
+                               (uint32_t)sv_method.size(), text.size(), &text[0], status.data(), &fc);
+    }
+    if (rc != CSV_OK) {
+        g_vcf_host_batches++;
+        if (rc == 1) g_vcf_declined++;
+        return false;
+    }
+    g_vcf_device_batches++;
+    // the host loop's messages, contig by contig: the REF warnings in record order, then the depth warnings (the gather follows the records)
+    for (size_t t = 0; t < n_contigs; t++) {
+        const std::string &chr = contigs[t].first;
+        printMessage("Saving SV calls for " + chr + "...");
+        const std::vector<SVCall> &v = *contigs[t].second;
+        for (size_t i = 0; i < v.size(); i++) {
+            const uint8_t st = status[(size_t)call_off[t] + i];
+            const SVCall &sv = v[i];
+            if ((st & ST_DISPOSITION) == ST_SKIP_FIRST_POSITION)
+                std::cerr << "Error: Insertion at the first position " << chr << ":" << sv.start << "-" << sv.end << std::endl;
+            else if ((st & ST_EMPTY_REF) && sv.sv_type == SVType::DEL)
+                std::cerr << "Warning: Reference allele is empty for deletion at " << chr << ":" << sv.start << "-" << sv.end << std::endl;
+            else if (st & ST_EMPTY_REF)
+                std::cerr << "Warning: Reference allele is empty for insertion at " << chr << ":" << sv.start - 1 << "-" << sv.end << std::endl;
+        }
+        for (size_t i = 0; i < v.size(); i++) {
+            if (!(status[(size_t)call_off[t] + i] & ST_DEPTH_OUT_OF_RANGE)) continue;
+            const SVCall &sv = v[i];
+            const uint32_t pos = sv.sv_type == SVType::DEL ? (uint32_t)std::max(1, (int)sv.start - 1) : sv.sv_type == SVType::INS ? sv.start - 1 : sv.start;
+            printError("Warning: Read depth for position " + std::to_string(pos) + " is out of range of the depth map");
+        }
+    }
+    out.write(text.data(), (std::streamsize)fc.text_bytes);
+    counts.total = (int)fc.total; counts.unclassified = (int)fc.unclassified; counts.assembly_gap_filtered = (int)fc.gap_filtered;
+    return true;
+}
+}  // namespace
+
+void vcfRouteStats(uint64_t *out, bool reset)
+{
+    out[0] = g_vcf_device_batches.load(); out[1] = g_vcf_host_batches.load(); out[2] = g_vcf_declined.load();
+    if (reset) { g_vcf_device_batches = 0; g_vcf_host_batches = 0; g_vcf_declined = 0; }
+}
 
 std::string svMethodString()
 {
@@ -119,6 +224,11 @@ VCFCounts writeVCF(std::ostream &out, const std::vector<std::pair<std::string, c
     for (const char *line : kHeaderLines) { text += line; text += '\n'; }
     text += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE\n";
     out << text;
+
+    if (opt.format_on_device && formatOnDevice(out, contigs, opt, gaps, ref_genome, depth, sv_method, counts)) {
+        out.flush();
+        return counts;
+    }
 
     std::vector<Record> recs;
     std::vector<uint32_t> positions;

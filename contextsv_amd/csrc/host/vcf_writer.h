@@ -42,7 +42,15 @@ struct VCFOptions {
     std::string assembly_gaps;       // --assembly-gaps BED path, "" = none (input_data.getAssemblyGaps())
     std::string output_dir;          // the file is <output_dir>/output.vcf (:1103-1104)
     std::string file_date;           // "" = today, strftime("%Y%m%d") of local time (:1153-1160); settable so tests are reproducible
+    // Opt-in: the record lines assembled on the device by ONE csvgpu_vcf_format call for all contigs, where the genome is on the device and
+    // the depth source is a ShardDepthSource. ctx: the context of that call (null: the depth source's). Byte-identical to the host loop; any
+    // return but CSV_OK (a declined batch, another device, no memory) runs the host loop for the whole batch.
+    bool format_on_device = false;
+    csv_ctx *ctx = nullptr;
 };
+// which route writeVCF's batches took, process-wide (csvhost_vcf_route_stats). out[3]: batches formatted on the device / batches that ran
+// the host loop with the option on (declined and failed ones included) / of those, the batches the device declined
+void vcfRouteStats(uint64_t *out, bool reset);
 
 struct VCFCounts { int total = 0, unclassified = 0, assembly_gap_filtered = 0; };
 

@@ -124,6 +124,11 @@ def load() -> C.CDLL:
     lib.csvhost_fasta_chromosomes.restype = C.c_int64
     lib.csvhost_fasta_chromosomes.argtypes = [_P, _P, C.c_uint64]
     lib.csvhost_save_vcf.argtypes = [_P, C.c_char_p, _P, C.c_char_p, C.c_char_p, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]
+    lib.csvhost_save_vcf_device.argtypes = lib.csvhost_save_vcf.argtypes + [C.c_int]
+    lib.csvhost_vcf_route_stats.restype = None
+    lib.csvhost_vcf_route_stats.argtypes = [_P, C.c_int]
+    lib.csvhost_set_vcf_on_device.restype = None
+    lib.csvhost_set_vcf_on_device.argtypes = [C.c_int]
     lib.csvhost_bam_open.restype = _P
     lib.csvhost_bam_open.argtypes = [C.c_char_p, C.c_int]
     lib.csvhost_bam_close.argtypes = [_P]
@@ -881,9 +886,12 @@ class ReferenceGenome:
 
 
 def save_vcf(out_dir: str, genome: ReferenceGenome, contigs, gap_path: str | None = None, file_date: str | None = None,
-             ctx: Context | None = None, map_order: bool = False):
+             ctx: Context | None = None, map_order: bool = False, format_on_device: bool = False):
     """saveToVCF (host mirror) -> <out_dir>/output.vcf. `contigs` = [(name, calls[CALL_DTYPE], alts[list of bytes], depth)] where depth is a
-    resident Shard (SUPPORT/DP gathered on the device; needs ctx), a uint32 numpy array, or None. Returns (total, unclassified, gap_filtered)."""
+    resident Shard (SUPPORT/DP gathered on the device; needs ctx), a uint32 numpy array, or None. Returns (total, unclassified, gap_filtered).
+    format_on_device (opt-in): with a genome opened with load_on_device and depth from shards, the record lines of all contigs come from ONE
+    csvgpu_vcf_format call on ctx (Context.vcf_format's entry point); otherwise, and for a batch the device declines, the host loop writes
+    them. The file is the same either way; vcf_route_stats() says which route ran."""
     lib = load()
     n = len(contigs)
     names = (C.c_char_p * n)(*[c[0].encode() for c in contigs])
@@ -905,10 +913,18 @@ def save_vcf(out_dir: str, genome: ReferenceGenome, contigs, gap_path: str | Non
         dlen = np.array([(len(a) if a is not None else 0) for a in arrs] + [0], np.uint64)
         depth_p, len_p, shard_p = dptr, dlen.ctypes.data, None
     counts = np.zeros(3, np.int32)
-    _check(lib.csvhost_save_vcf(ctx.h if ctx is not None else None, os.fsencode(out_dir), genome.h, os.fsencode(gap_path) if gap_path else None,
-                                file_date.encode() if file_date else None, n, names, off.ctypes.data, calls.ctypes.data, alts,
-                                shard_p, depth_p, len_p, int(map_order), counts.ctypes.data))
+    args = (ctx.h if ctx is not None else None, os.fsencode(out_dir), genome.h, os.fsencode(gap_path) if gap_path else None,
+            file_date.encode() if file_date else None, n, names, off.ctypes.data, calls.ctypes.data, alts, shard_p, depth_p, len_p, int(map_order), counts.ctypes.data)
+    _check(lib.csvhost_save_vcf_device(*args, 1) if format_on_device else lib.csvhost_save_vcf(*args))
     return tuple(int(x) for x in counts)
+
+
+def vcf_route_stats(reset: bool = False) -> dict:
+    """Which route the VCF writer's batches took so far in this process with format_on_device / vcf_on_device set: 'device' (formatted by
+    csvgpu_vcf_format), 'host' (the host loop), and of the latter 'declined' (the device refused a value of the batch)."""
+    out = np.zeros(3, np.uint64)
+    load().csvhost_vcf_route_stats(out.ctypes.data, int(bool(reset)))
+    return dict(device=int(out[0]), host=int(out[1]), declined=int(out[2]))
 
 
 def _np_from(ptr_, count, dtype):
@@ -1060,8 +1076,10 @@ def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0
             genome: ReferenceGenome | None = None, vcf_dir=None, gap_path=None, file_date=None, capacity: int = 1 << 20,
             snp_vcf=None, pfb_table=None, ethnicity="", inflate_on_device: bool = False, split_groups_on_device: bool = False, split_fits_on_device: bool = False,
             split_tables_on_device: bool = False, cn_observations_on_device: bool = False, unpack_on_device: bool = False, shard_on_device: bool = False,
-            snp_parse_on_device: bool = False, snp_tables_on_device: bool = False):
+            snp_parse_on_device: bool = False, snp_tables_on_device: bool = False, vcf_on_device: bool = False):
     """SVCaller::runBam: the whole run fed from a coordinate-sorted, indexed BAM. -> (calls, contig index per call, stats dict).
+    vcf_on_device: SVCaller::vcf_format_on_device — with a genome opened with load_on_device, the record lines of <vcf_dir>/output.vcf come
+    from one csvgpu_vcf_format call (vcf_route_stats() counts it); the same file. A process-wide switch like the two below.
     snp_parse_on_device / snp_tables_on_device: SVCaller's fields of those names (the SNP VCF parsed on ctx's device, on a context of the
     run's own; with the second the contigs' SNP tables are built and stay there, and the copy-number pass looks its SNPs up on the device:
     cn_route_stats() counts it). Process-wide switches, set for the length of this call and restored. Neither changes the calls.
@@ -1080,6 +1098,7 @@ def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0
     n = C.c_uint64(0)
     st = bam_stats()
     load().csvhost_set_snp_on_device(int(bool(snp_parse_on_device)), int(bool(snp_tables_on_device)))
+    load().csvhost_set_vcf_on_device(int(bool(vcf_on_device)))
     try:
         _check(load().csvhost_run_bam(ctx.h, os.fsencode(bam_path), "\n".join(chromosomes).encode() if chromosomes else None, threads, C.byref(hmm),
                                       C.byref(opt), genome.h if genome is not None and vcf_dir else None,
@@ -1088,6 +1107,7 @@ def run_bam(ctx: Context, bam_path: str, hmm, chromosomes=None, threads=8, eps=0
                                       os.fsencode(snp_vcf) if snp_vcf else None, os.fsencode(pfb_table) if pfb_table else None, ethnicity.encode()))
     finally:
         load().csvhost_set_snp_on_device(0, 0)
+        load().csvhost_set_vcf_on_device(0)
     if n.value > capacity:
         raise RuntimeError("run_bam: capacity too small")
     return out[: n.value].copy(), tid[: n.value].copy(), {f: getattr(st, f) for f, _ in bam_stats._fields_}

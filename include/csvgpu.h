@@ -962,6 +962,41 @@ csv_snp_table *csvgpu_snp_columns_table(csv_ctx *ctx, const csv_snp_columns *col
 /* Plain device memory: any context of the device may read the columns. Waits for ctx's stream, then frees. */
 void csvgpu_snp_columns_free(csv_ctx *ctx, csv_snp_columns *cols);
 
+/* ------------------------------------------------------------------------------------------ */
+/* VCF records formatted on the device (opt-in: the host writer assembles them by default) */
+/* The record lines of the reference's SVCaller::saveToVCF (sv_caller.cpp:1067-1330) with the SUPPORT / DP values of ::getReadDepth
+ * (:1332-1344), assembled where their inputs lie: REF from the genome's base array, the depth from the contigs' resident depth maps
+ * (csvgpu_depth_lookup_resident's value at POS), ALT from the caller's bytes. Replaces the record loop of writeVCF (host/vcf_writer.cpp);
+ * the header stays the host's. Rules in csrc/vcf_format_core.hpp, kernels in kernels/vcfformat.hip: a lane per call sizes its line, an
+ * exclusive sum places the lines, and every 16-byte piece of the text has one owning lane, so a REF of 1 MB costs what 1 MB of short lines
+ * costs. The text is the concatenation of the contigs' lines in the order given, byte for byte the host writer's.
+ *   calls       contig t's are calls[call_off[t] .. call_off[t + 1]); call i's ALT string is alts[alt_off[i] .. alt_off[i + 1]).
+ *   line_status [call_off[n_contigs]] the core's status byte of every call (disposition in bits 0-1: 0 written, 1 skipped as UNKNOWN /
+ *               NEUTRAL, 2 an INS at the first position: counted, no line; 4 REF was empty: N and <DEL> / <INS>; 8 assembly-gap filtered;
+ *               16 POS outside the depth map: 0 printed), from which the caller replays the host's warnings. May be NULL.
+ *   counts      always filled on CSV_OK, 1 and CSV_ECAPACITY.
+ * Returns CSV_OK; 1 = declined, nothing written to text, counts->declined_why names the rule (vcffmt::Why: a likelihood of 2^63 or more,
+ * a DEL whose length does not fit a positive int or that starts at 2^31, an enum outside its table, a REF asked of a contig the genome has
+ * not — for these the host throws or is undefined — or a text of 2^32 bytes or more): the caller runs the host writer;
+ * CSV_ECAPACITY = cap < text_bytes, nothing written, call again with room; CSV_EINVAL, nothing launched: a null array, offsets that
+ * decrease or do not start at 0, a record index beyond the genome, a method string above 64 bytes, a genome of another device, a contig
+ * with a call to write and no shard or no depth map in it. Nothing outside [0, text_bytes) is written, and nothing outside the genome's
+ * array, the ALT bytes and the depth maps is read. Launches are timed under CSV_K_MISC; one readback sizes the text, one brings it down.
+ * _dev: text is a device pointer (the seam a device BGZF writer starts from); every other array is the host's. */
+typedef struct csv_vcf_call { uint32_t start, end; int32_t sv_type, cluster_size; double hmm_likelihood; int64_t id;
+                              uint32_t aln_flags; int32_t genotype, cn_state, aln_offset; } csv_vcf_call;      /* 48 bytes: csvhost_call's layout */
+typedef struct csv_vcf_contig { const char *name; uint32_t name_len; int64_t genome_record;  /* -1: the genome has none */
+                                csv_shard *shard;                                             /* its depth map; NULL only with no call to write */
+                                const uint32_t *gap_start, *gap_end; uint32_t n_gaps; } csv_vcf_contig;  /* BED rows as loaded, file order */
+typedef struct csv_vcf_format_counts { uint64_t text_bytes, n_lines; uint32_t total, unclassified, gap_filtered, declined_why; } csv_vcf_format_counts;
+
+int  csvgpu_vcf_format(csv_ctx *ctx, const csv_genome *g, const csv_vcf_contig *contigs, uint32_t n_contigs, const uint64_t *call_off, const csv_vcf_call *calls,
+                       const uint64_t *alt_off, const char *alts, const char *method, uint32_t method_len, uint64_t cap, char *text, uint8_t *line_status,
+                       csv_vcf_format_counts *counts);
+int  csvgpu_vcf_format_dev(csv_ctx *ctx, const csv_genome *g, const csv_vcf_contig *contigs, uint32_t n_contigs, const uint64_t *call_off, const csv_vcf_call *calls,
+                           const uint64_t *alt_off, const char *alts, const char *method, uint32_t method_len, uint64_t cap, char *d_text, uint8_t *line_status,
+                           csv_vcf_format_counts *counts);
+
 #ifdef CSV_TEST_HOOKS
 /* Test build only (libcsvgpu_testhooks.so, -DCSV_TEST_HOOKS; libcsvgpu.so does not export it): the next n guarded device allocations
  * inside the library fail as if HBM were exhausted (error-path tests of the signature-buffer growth in csvgpu_chr_job_cluster and of the
